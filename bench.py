@@ -5,7 +5,16 @@ Metric (BASELINE.json): kNN queries/s (+ |dlnE|) at N = 1M, D = 27, kmax = 10 (c
 chain, `mcevidence_amd.synth.CONFIGS['C3']`), inputs resident in HBM when the timed region starts.  One "step" = one full
 pass of the hot path (pack -> kNN search -> merge -> volume/weight reduction -> dotp[kmax]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1000000] [--d 27] [--kmax 10] [--mode 0|1] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1000000] [--d 27] [--kmax 10] [--mode 0|1] [--dump-outputs DIR]
+                    [--full [--no-extras] [--cpu-sample Q] [--extras-scale F]]
+
+A plain run sets up, warms up, times EXACTLY K steps and prints the line: `value`, `ms_per_step` (one timed step), `lnE` of the
+last step and the headline's `roofline` (its HIP-event bracket of the timed steps + committed profiles; no run of its own).
+`--full` adds everything else described below, each section as before: ln E against the reference's golden output, the run-time
+certificate's cost, the CPU baseline, evidence() from host arrays, the fp64 mode, C2 / C4 / C5 and `beyond_baseline_shapes`;
+sections not run are null in the line.  `--dump-outputs DIR` writes what the timed path returned in its last step: DIR/dotp.npy
+(the kmax reduced sums, float64) and DIR/lnE.npy (ln E from them, float64).  The inputs are seeded: the same arguments give the
+same inputs in every run.
 
 `--gpus N` with N > 1 works both ways: started by a launcher (`python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N ...`: WORLD_SIZE is set, this process is one rank) or plainly (`python bench.py --gpus N`: the parent
@@ -14,7 +23,7 @@ included, goes to the parent's stdout -- and exits with the job's code).  One pr
 kmax doubles (RCCL): strong scaling.  What a rank computes is the library's choice: auto evidence -- the
 symmetric partition (a contiguous range of the sorted query blocks) or every N-th wave of the pruned walk's dispatch order
 (`mce_knn_dotp_part_f64_dev`); cross evidence -- contiguous query rows of s1 against the replicated s2.  Under N > 1 the
-line carries C3 (headline) AND, unless --no-extras, `configs.C2 / C4 / C5` timed the same way (barrier + synchronize
+line carries C3 (headline) AND, with --full unless --no-extras, `configs.C2 / C4 / C5` timed the same way (barrier + synchronize
 on both sides, max over ranks), `ranks_seen`, and per rank its device ordinal and its own HIP-event search time.
 
 Prints ONE JSON line on rank 0.
@@ -34,7 +43,7 @@ loaded library (profiles/<round>/meta.json: source_hash == mce_source_hash()); o
 `cpu_baseline` = the reference's own CPU path -- scikit-learn NearestNeighbors exactly as MCEvidence.py:1093-1104 calls it
 + the NumPy volume/weight sum -- on a bounded query sample, rank 0, with the host it ran on.
 
-`configs` (unless --no-extras): the other BASELINE.json GPU configs C2, C4, C5 through the same entry points (resident
+`configs` (--full, unless --no-extras): the other BASELINE.json GPU configs C2, C4, C5 through the same entry points (resident
 data), each with ln E against the reference's own golden output and (N = 1) a CPU baseline on a query sample;
 `fp64_mode` (N = 1): C3 through the fp64 sweep -- the reference-precision arithmetic end to end.
 """
@@ -426,11 +435,12 @@ class Ctx(object):
         self.torch.cuda.synchronize()
 
 
-def time_config(ctx, cfg, steps, warmup, mode=0, nsample=0, orc=None):
+def time_config(ctx, cfg, steps, warmup, mode=0, nsample=0, orc=None, checks=True):
     """One config through the device-pointer entry points on resident data.  world = 1: mce_knn_dotp_f64_dev over the whole
     set.  world > 1: this rank's share + ONE all-reduce of kmax doubles per step -- auto evidence through
     mce_knn_dotp_part_f64_dev (the library's partition), cross evidence on the contiguous query rows [S r / W, S (r+1) / W)
-    of s1 against the replicated s2.  EXACTLY `steps` timed steps between barrier + synchronize; ms = max over ranks."""
+    of s1 against the replicated s2.  EXACTLY `steps` timed steps between barrier + synchronize; ms = max over ranks.
+    `checks`: after the timed region, ln E against the reference's golden output and the certificate's cost (--full)."""
     torch, dist, _capi, world, rank, dev = ctx.torch, ctx.dist, ctx.capi, ctx.world, ctx.rank, ctx.dev
     dist_on = ctx.dist_on
     progress("config %s: %d steps + %d warm-up" % (cfg["name"], steps, warmup))
@@ -509,7 +519,7 @@ def time_config(ctx, cfg, steps, warmup, mode=0, nsample=0, orc=None):
         res["executed_tflops"] = round(stats["flops_main"] / (stats["kernel_ms"] * 1e-3) / 1e12, 1)
     lnE = lnE_from_dotp(dotp, cfg)
     res["lnE"] = [float(x) for x in lnE]
-    g = golden_lnE(cfg["name"], cfg)
+    g = golden_lnE(cfg["name"], cfg) if checks else None
     if g is not None:
         res["max_abs_dlnE_vs_reference"] = float(np.max(np.abs(lnE - np.array(g["lnE"]))))
         res["reference_wall_s"] = round(g.get("ref_wall_s", 0.0), 1)
@@ -525,7 +535,7 @@ def time_config(ctx, cfg, steps, warmup, mode=0, nsample=0, orc=None):
         res["sampled_rows"] = len(rows)
         res["max_rel_dist_err_sampled_rows_vs_exact_cpu_search"] = float(np.max(np.abs(got - od) / od))
         del dd
-    if not dist_on and K <= 32 and d <= 128:
+    if checks and not dist_on and K <= 32 and d <= 128:
         # what the default run-time certificate costs a host-pointer call of this shape (round 6: it is ON by default behind the fp16
         # filter): the step once more WITH the distances written out (what the check reads) + the re-check of 256 rows by an exact fp64
         # scan (mce_verify_knn_f64_dev), against the plain step -- resident data, after the timed region, best of 3
@@ -673,9 +683,14 @@ def main():
     ap.add_argument("--kmax", type=int, default=10)
     ap.add_argument("--cpu-sample", type=int, default=100000, help="queries timed on the CPU baseline (0 = skip): ~12 s of the reference's sklearn call on a 256-thread host")
     ap.add_argument("--mode", type=int, default=0, help="0 auto (fp16 filter + fp64 refine), 1 fp64 MFMA sweep")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip the C2/C4/C5 and fp64-mode sections")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: golden ln E, certificate, CPU baseline, evidence() from host arrays, fp64 mode, C2/C4/C5, beyond-baseline shapes")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the C2/C4/C5 and fp64-mode sections")
     ap.add_argument("--extras-scale", type=float, default=1.0, help="rows of the C2/C4/C5 sections x this factor (functional checks; 1 = BASELINE.json sizes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed path's outputs of its last step: DIR/dotp.npy, DIR/lnE.npy (float64)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become one (before torch is imported -- this process never initialises the GPU)
@@ -738,12 +753,12 @@ def main():
     c3 = dict(name="C3", X=Xh, Y=None, weight=weight, fs=fsh, kmax=kmax, k0=1, S=n, SumW=float(np.sum(weight)), J=cov["J"], logLmax=logLmax)
     K = kmax - 1
 
-    head, stats, dp = time_config(ctx, c3, a.steps, a.warmup, mode=a.mode)
+    head, stats, dp = time_config(ctx, c3, a.steps, a.warmup, mode=a.mode, checks=a.full)
     ms_step, kern_ms = head["ms_per_step"], stats["kernel_ms"]
     lnE = np.array(head["lnE"])
 
     e2e_ranks = None
-    if dist_on:
+    if dist_on and a.full:
         progress("evidence() from host arrays under the process group")
         # the whole MCEvidence(...).evidence() call from host arrays under the process group: each rank uploads the chain once,
         # whitens on its device, searches its share (mce_evidence_feed_part_f64), ONE all-reduce -- the PCIe-inclusive figure
@@ -817,10 +832,10 @@ def main():
         torch.cuda.empty_cache()
 
     orc = None
-    if rank == 0:
+    if rank == 0 and a.full:
         from oracle import oracle_np as orc                 # checker / CPU baseline only; never inside a timed region
     extras = None
-    want_extras = not a.no_extras and a.mode == 0 and ((n, d, kmax) == (1_000_000, 27, 10) or a.extras_scale != 1.0)
+    want_extras = a.full and not a.no_extras and a.mode == 0 and ((n, d, kmax) == (1_000_000, 27, 10) or a.extras_scale != 1.0)
     if want_extras and dist_on:
         extras = extra_configs(ctx, orc, pkg, a.extras_scale)   # every rank takes part
 
@@ -841,10 +856,10 @@ def main():
         if (pairs_once["ms_per_step"] < ms_step and pairs_once["max_abs_dlnE_vs_default_partition"] < 1e-9 and po_stats is not None
                 and po_stats["kernel_ms"] > 0 and os.environ.get("MCE_BENCH_HEADLINE", "") != "default"):
             partition = "pairs_once"
-            ms_step, kern_ms, stats, lnE = pairs_once["ms_per_step"], po_stats["kernel_ms"], po_stats, lnE1
+            ms_step, kern_ms, stats, lnE, dp = pairs_once["ms_per_step"], po_stats["kernel_ms"], po_stats, lnE1, dp1
             head = dict(head, kernel=pairs_once["kernel"])
             head_per_rank = pairs_once["per_rank"]
-            g = golden_lnE("C3", c3)
+            g = golden_lnE("C3", c3) if a.full else None
             dlnE_ref = float(np.max(np.abs(lnE1 - np.array(g["lnE"])))) if g is not None else None
         partitions["value_is_of"] = partition
 
@@ -890,7 +905,7 @@ def main():
         fp64_mode = None
         e2e = None
         shapes = None
-        if not dist_on:
+        if not dist_on and a.full:
             if a.cpu_sample > 0:
                 rng = np.random.default_rng(0)
                 rows = np.sort(rng.choice(n, size=min(a.cpu_sample, n), replace=False))
@@ -952,6 +967,11 @@ def main():
                    beyond_baseline_shapes=shapes)
         if pairs_once is not None:
             out["pairs_once"] = pairs_once
+        if a.dump_outputs:
+            # what the timed path handed back in its last step (the sums `value` is of), and ln E from them
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, "dotp.npy"), np.asarray(dp, dtype=np.float64))
+            np.save(os.path.join(a.dump_outputs, "lnE.npy"), np.asarray(lnE, dtype=np.float64))
         print(json.dumps(out), flush=True)
     if dist_on:
         progress("done")

@@ -158,12 +158,41 @@ def _bench_line(args, env_extra, timeout=900):
     return json.loads(lines[0])
 
 
+def test_steps_must_be_at_least_one():
+    """`--steps` is the number of timed steps and ms_per_step divides by it: 0 is refused before anything is set up"""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120, cwd=REPO)
+    assert r.returncode == 2 and "--steps" in r.stderr, (r.returncode, r.stderr[-1000:])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: K timed steps and the headline only (every section of
+    --full null); DIR holds what the timed path returned in its last step -- the kmax sums and ln E from them, float64 -- the
+    line's ln E, and a second run with the same arguments (the same seeded inputs) writes the same outputs."""
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--n", "150000", "--d", "27", "--kmax", "10"]
+    line = _bench_line(args + ["--dump-outputs", str(tmp_path / "a")], {})
+    again = _bench_line(args + ["--dump-outputs", str(tmp_path / "b")], {})
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["n_gpus"] == 1
+    assert abs(line["value"] - 150000 / (line["ms_per_step"] * 1e-3)) < 1.0
+    assert line["metric"] == "knn_queries_per_sec" and line["unit"] == "queries/s" and line["higher_is_better"] is True
+    for key in ("max_abs_dlnE_vs_reference", "cpu_baseline", "evidence_call_from_host", "certificate", "configs", "fp64_mode", "beyond_baseline_shapes"):
+        assert line[key] is None, key
+    assert line["roofline"]["kernel_ms"] > 0
+    out = {}
+    for run in ("a", "b"):
+        dotp, lnE = np.load(str(tmp_path / run / "dotp.npy")), np.load(str(tmp_path / run / "lnE.npy"))
+        assert dotp.dtype == np.float64 and dotp.shape == (10,) and lnE.dtype == np.float64 and lnE.shape == (9,)
+        out[run] = (dotp, lnE)
+    assert np.max(np.abs(out["a"][1] - np.array(line["lnE"]))) < 1e-9
+    assert np.allclose(out["a"][0], out["b"][0], rtol=1e-12, atol=0) and np.max(np.abs(out["b"][1] - np.array(again["lnE"]))) < 1e-9
+
+
 @pytest.mark.gpu
 def test_bench_gpus_2_from_a_plain_shell():
     """`python bench.py --gpus 2` with no launcher around it (what the driver's SCALE run does): the parent starts two ranks,
     every config is timed under N = 2 with one all-reduce per step, and the sums equal the single-rank run's.  Both ranks
     share this box's one GPU (MCE_BENCH_ONE_DEVICE=1) over gloo; sizes scaled down."""
-    common = ["--steps", "2", "--warmup", "1", "--n", "150000", "--d", "27", "--kmax", "10", "--cpu-sample", "0", "--extras-scale", "0.05"]
+    common = ["--steps", "2", "--warmup", "1", "--n", "150000", "--d", "27", "--kmax", "10", "--full", "--cpu-sample", "0", "--extras-scale", "0.05"]
     two = _bench_line(["--gpus", "2"] + common, dict(MCE_BENCH_BACKEND="gloo", MCE_BENCH_ONE_DEVICE="1"))
     one = _bench_line(["--gpus", "1"] + common, {})
     assert two["n_gpus"] == 2 and two["ranks_seen"] == 2 and two["backend"] == "gloo" and one["n_gpus"] == 1
@@ -200,7 +229,7 @@ def test_bench_gpus_2_under_the_launcher():
     env.update(MCE_BENCH_BACKEND="gloo", MCE_BENCH_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--cpu-sample", "0", "--no-extras"], capture_output=True, text=True, env=env, timeout=900, cwd=REPO)
+                        "--full", "--cpu-sample", "0", "--no-extras"], capture_output=True, text=True, env=env, timeout=900, cwd=REPO)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1

@@ -2,7 +2,9 @@
 (reference MCEvidence.py:564) -- bit for bit.  CPU only."""
 import ctypes
 import os
+import platform
 import re
+import shutil
 
 import numpy as np
 import pytest
@@ -194,5 +196,12 @@ def test_reader_under_address_and_ub_sanitizers(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread"] + src + ["-o", exe_t])
     work_t = tmp_path / "files_t"
     work_t.mkdir()
-    out = subprocess.run([exe_t, str(work_t)], capture_output=True, text=True, timeout=900)
+    # GCC's ThreadSanitizer refuses to start ("FATAL: ThreadSanitizer: unexpected memory mapping") where the kernel's address-space
+    # randomisation places the program outside the ranges it shadows (high mmap entropy): the binary runs with randomisation off
+    # for itself (a personality flag of that one process) wherever setarch can set it
+    cmd_t = [exe_t, str(work_t)]
+    setarch = shutil.which("setarch")
+    if setarch and subprocess.run([setarch, platform.machine(), "-R", "true"], capture_output=True).returncode == 0:
+        cmd_t = [setarch, platform.machine(), "-R"] + cmd_t
+    out = subprocess.run(cmd_t, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and "OK" in out.stdout and "WARNING: ThreadSanitizer" not in out.stderr, out.stdout + out.stderr[-3000:]

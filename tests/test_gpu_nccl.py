@@ -142,7 +142,7 @@ def test_bench_timed_loop_over_nccl_with_one_rank():
     """`MCE_BENCH_FORCE_DIST=1 python bench.py --gpus 1`: the `world > 1` code path of bench.py -- nccl group, the library's
     partition entry point, one all-reduce per timed step, the per-rank gather, the class's evidence() under the group, the
     C2 / C4 / C5 sections timed the same way -- with ONE rank; every ln E equals the plain one-GPU run's to the last bit."""
-    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--n", "150000", "--d", "27", "--kmax", "10", "--cpu-sample", "0", "--extras-scale", "0.05"]
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--n", "150000", "--d", "27", "--kmax", "10", "--full", "--cpu-sample", "0", "--extras-scale", "0.05"]
     forced, err = _bench_line(common, dict(MCE_BENCH_FORCE_DIST="1"))
     plain, _ = _bench_line(common, {})
     assert forced["backend"] == "nccl" and forced["ranks_seen"] == 1 and forced["n_gpus"] == 1 and plain["backend"] is None

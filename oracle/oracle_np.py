@@ -49,6 +49,188 @@ def whiten(samples, evec, eval_):
 
 
 # --------------------------------------------------------------------------
+# high-precision feeders: the truth the device feeders are measured against
+# (not the reference's arithmetic -- that is covariance_eig / whiten above)
+# --------------------------------------------------------------------------
+_LD = np.longdouble
+_HP_CHUNK = 1 << 16
+
+
+def covariance_hp(rows):
+    """Unweighted covariance of ``rows`` [n, d] (two passes, divided by n - 1) accumulated in
+    ``np.longdouble``: the matrix the device covariance kernels round.  Returns [d, d] longdouble."""
+    rows = np.asarray(rows, dtype=np.float64)
+    n, d = rows.shape
+    mean = np.zeros(d, dtype=_LD)
+    for s in range(0, n, _HP_CHUNK):
+        mean += rows[s:s + _HP_CHUNK].astype(_LD).sum(axis=0)
+    mean /= n
+    cov = np.zeros((d, d), dtype=_LD)
+    for s in range(0, n, _HP_CHUNK):
+        c = rows[s:s + _HP_CHUNK].astype(_LD) - mean
+        cov += c.T @ c
+    return cov / (n - 1)
+
+
+def canonical_eig(lam, U):
+    """The library's canonical form (include/mcevidence_hip.h): eigenvalues descending, each
+    eigenvector's largest component positive."""
+    order = np.argsort(-np.asarray(lam, dtype=np.float64), kind="stable")
+    lam, U = np.asarray(lam)[order], np.asarray(U)[:, order]
+    big = np.argmax(np.abs(U.astype(np.float64)), axis=0)
+    sgn = np.where(U[big, np.arange(U.shape[1])] < 0, -1, 1).astype(U.dtype)
+    return lam, U * sgn
+
+
+def jacobi_eig_ld(cov, tol=1e-19, max_sweeps=60):
+    """Cyclic Jacobi in ``np.longdouble`` with the per-element rule (a rotation is skipped when
+    |a_pq| <= tol sqrt(a_pp a_qq); stop after a sweep without one), so every eigenvalue carries a
+    relative error of about eps_ld * cond of the diagonally scaled matrix.  The fallback of
+    :func:`eig_hp` when mpmath is not installed.  Returns (lam, U) in canonical form."""
+    A = np.array(cov, dtype=_LD)
+    d = A.shape[0]
+    V = np.eye(d, dtype=_LD)
+    for _ in range(max_sweeps):
+        rotated = False
+        for p in range(d - 1):
+            for q in range(p + 1, d):
+                apq = A[p, q]
+                if abs(apq) <= tol * np.sqrt(abs(A[p, p] * A[q, q])):
+                    continue
+                rotated = True
+                theta = (A[q, q] - A[p, p]) / (2 * apq)
+                t = (1 if theta >= 0 else -1) / (abs(theta) + np.sqrt(theta * theta + 1))
+                c = 1 / np.sqrt(t * t + 1)
+                s = t * c
+                ap, aq = A[:, p].copy(), A[:, q].copy()
+                A[:, p], A[:, q] = c * ap - s * aq, s * ap + c * aq
+                ap, aq = A[p, :].copy(), A[q, :].copy()
+                A[p, :], A[q, :] = c * ap - s * aq, s * ap + c * aq
+                vp, vq = V[:, p].copy(), V[:, q].copy()
+                V[:, p], V[:, q] = c * vp - s * vq, s * vp + c * vq
+        if not rotated:
+            break
+    return canonical_eig(np.diag(A).copy(), V)
+
+
+def eig_hp(cov, dps=34, return_mp=False):
+    """Eigen-system of the symmetric ``cov`` (converted exactly from its binary entries) by
+    ``mpmath.eigsy`` at ``dps`` digits, in canonical form, rounded to ``np.longdouble``:
+    (lam[d] descending, U[d, d] with the eigenvectors in its columns).  ``return_mp``: also
+    the mpmath (E, Q) in the same order and signs.  Without mpmath: :func:`jacobi_eig_ld`."""
+    cov = np.asarray(cov, dtype=_LD)
+    try:
+        import mpmath
+    except ImportError:                                   # pragma: no cover - mpmath ships with this image
+        if return_mp:
+            raise
+        return jacobi_eig_ld(cov)
+    d = cov.shape[0]
+    with mpmath.workdps(dps):
+        A = mpmath.matrix(d, d)
+        for i in range(d):
+            for j in range(d):
+                A[i, j] = _mpf_of(mpmath, cov[i, j])
+        E, Q = mpmath.eigsy(A)
+        lam = np.array([_ld_of(E[i]) for i in range(d)])
+        U = np.array([[_ld_of(Q[i, j]) for j in range(d)] for i in range(d)])
+    order = np.argsort(-lam.astype(np.float64), kind="stable")
+    sgn = np.sign(U[np.argmax(np.abs(U.astype(np.float64)), axis=0), np.arange(d)]).astype(int)
+    lam_c, U_c = canonical_eig(lam, U)
+    if not return_mp:
+        return lam_c, U_c
+    with mpmath.workdps(dps):
+        E_c = [E[int(k)] for k in order]
+        Q_c = mpmath.matrix(d, d)
+        for c, k in enumerate(order):
+            for i in range(d):
+                Q_c[i, c] = Q[i, int(k)] * sgn[k]
+    return lam_c, U_c, (E_c, Q_c)
+
+
+def _mpf_of(mpmath, x):
+    """a longdouble as an mpf, exactly (its 64-bit significand is the sum of two doubles)"""
+    hi = float(x)
+    return mpmath.mpf(hi) + mpmath.mpf(float(_LD(x) - _LD(hi)))
+
+
+def _ld_of(v):
+    """an mpf rounded to longdouble (through a pair of doubles: 106 bits)"""
+    hi = float(v)
+    return _LD(hi) + _LD(float(v - hi))
+
+
+def whiten_hp(rows, U, lam):
+    """``diagonalise_chain`` in ``np.longdouble``: rows @ U / sqrt(lam).  Returns [n, d] longdouble."""
+    rows = np.asarray(rows, dtype=np.float64)
+    U = np.asarray(U, dtype=_LD)
+    scale = 1 / np.sqrt(np.asarray(lam, dtype=_LD))
+    out = np.empty(rows.shape, dtype=_LD)
+    for s in range(0, rows.shape[0], _HP_CHUNK):
+        out[s:s + _HP_CHUNK] = (rows[s:s + _HP_CHUNK].astype(_LD) @ U) * scale
+    return out
+
+
+def feed_hp(rows):
+    """covariance_hp -> eig_hp of ``rows``: dict(cov, lam, U, J, condC, condCn) (longdouble where it matters).
+    cond(Cn) is the condition number of the correlation matrix diag(C)^-1/2 C diag(C)^-1/2."""
+    cov = covariance_hp(rows)
+    lam, U = eig_hp(cov)
+    dg = np.sqrt(np.diag(cov))
+    cn = (cov / np.outer(dg, dg)).astype(np.float64)
+    ev_n = np.linalg.eigvalsh(cn)
+    J = float(np.exp(0.5 * np.sum(np.log(lam)))) if np.all(lam > 0) else math.nan
+    return dict(cov=cov, lam=lam, U=U, J=J, condC=float(lam[0] / lam[-1]),
+                condCn=float(ev_n[-1] / ev_n[0]) if ev_n[0] > 0 else math.inf)
+
+
+def evidence_truth(chain, ndim=None, kmax=5, priorvolume=1.0, pos_lnp=False, covtype="all",
+                   s1_idx=None, s2_idx=None):
+    """:func:`evidence_from_chain` with high-precision feeders: covariance_hp + eig_hp + whiten_hp, the
+    whitened rows rounded to fp64, then the exact search (knn_brute), the log-domain sums and the MLE
+    assembly.  ``covtype='single'`` with a split whitens s2 with its OWN eigen-system (J stays s1's).
+    Returns dict(lnE, dotp, DkNN, X, Y, J, lam, lam2, feed, feed2, ...)."""
+    kmax = max(2, kmax)
+    w_all, nll_all, th_all = chain[:, 0], chain[:, 1], chain[:, 2:]
+    if ndim is None:
+        ndim = th_all.shape[1]
+    split = s1_idx is not None
+    if split:
+        s1, s2 = th_all[s1_idx][:, :ndim], th_all[s2_idx][:, :ndim]
+        w, lnp = w_all[s1_idx], -nll_all[s1_idx]
+        allrows = np.concatenate((s1, s2))
+    else:
+        s1, s2 = th_all[:, :ndim], None
+        w, lnp = w_all, -nll_all
+        allrows = s1
+    if covtype == "all":
+        f1 = feed_hp(allrows)
+        f2 = f1
+    else:
+        f1 = feed_hp(s1)
+        f2 = feed_hp(s2) if split else f1
+    X = whiten_hp(s1, f1["U"], f1["lam"]).astype(np.float64)
+    logL = -lnp if pos_lnp else lnp
+    logLmax = float(np.amax(logL))
+    fs = logL - logLmax
+    if split:
+        Y = whiten_hp(s2, f2["U"], f2["lam"]).astype(np.float64)
+        k0 = 0
+        DkNN, _ = knn_brute(X, Y, kmax)
+    else:
+        Y = X
+        k0 = 1
+        DkNN = np.zeros((X.shape[0], kmax))
+        DkNN[:, 1:], _ = knn_brute(X, X, kmax - 1, self_mode=2)
+    S = X.shape[0]
+    dotp = dotp_logdomain(DkNN, w, fs, ndim, k0, kmax)
+    SumW = float(np.sum(w))
+    lnE = mle_from_dotp(dotp, S, k0, kmax, SumW, f1["J"], logLmax, math.log(priorvolume))
+    return dict(lnE=lnE, dotp=dotp, DkNN=DkNN, X=X, Y=Y, J=f1["J"], lam=f1["lam"], lam2=f2["lam"], feed=f1, feed2=f2,
+                SumW=SumW, logLmax=logLmax, S=S, k0=k0, w=w, fs=fs, ndim=ndim, kmax=kmax)
+
+
+# --------------------------------------------------------------------------
 # a1/a2: the neighbour search
 # --------------------------------------------------------------------------
 def knn_sklearn(X, Y, K, n_jobs=-1, algorithm="auto"):

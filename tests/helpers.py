@@ -137,3 +137,119 @@ def build_mce(case, **kw):
     if split is not None:
         mce.set_split(*split)
     return mce
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# ill-conditioned chain families for the device feeders (tests/test_gpu_feeders.py, tests/test_oracle_feeders.py).
+# Every family returns a chain in the reference's column layout (weight, -ln L, params...), seeded.  C is the covariance,
+# Cn = diag(C)^-1/2 C diag(C)^-1/2 its correlation matrix; the eigenvalues of C are fixed to about eps * cond(Cn)
+# relative by C itself (Demmel & Veselic 1992), whatever cond(C) is.
+# --------------------------------------------------------------------------------------------------------------------
+def _chain_from_rows(rows, z, rng):
+    """weights 1..5, -ln L = z.z / 2 (the Gaussian the rows were drawn from, up to a constant)"""
+    w = rng.integers(1, 6, rows.shape[0]).astype(np.float64)
+    nll = 0.5 * np.einsum("ij,ij->i", z, z) + 0.5 * z.shape[1] * math.log(2.0 * math.pi)
+    return np.column_stack([w, nll, rows])
+
+
+def graded_cov(c):
+    """Graded covariance number ``c`` (0..5, d = 6, 12, 27, 27, 40, 64) of one seeded recipe: C = diag(s) Cn diag(s) with
+    s spanning 1e-4..1e2 (even c) or a permuted 1e-5..1e1 (odd c), and for c >= 2 a near-dependence 50 v v^T in Cn.
+    c = 4 (d = 40, cond(C) 7.7e13, cond(Cn) 3.8e4) is the matrix on which a stopping rule relative to the LARGEST
+    eigenvalues leaves the small ones wrong by 2e-9."""
+    rng = np.random.default_rng(1)
+    for k in range(c + 1):
+        d = [6, 12, 27, 27, 40, 64][k]
+        sig = np.logspace(-4, 2, d) if k % 2 == 0 else np.logspace(-5, 1, d)[rng.permutation(d)]
+        L = np.eye(d) + 0.8 * rng.standard_normal((d, d)) / math.sqrt(d)
+        Cn = L @ L.T
+        if k >= 2:
+            v = rng.standard_normal(d)
+            Cn += 50 * np.outer(v, v)
+        Cn = Cn / np.outer(np.sqrt(np.diag(Cn)), np.sqrt(np.diag(Cn)))
+    return Cn * np.outer(sig, sig)
+
+
+def sampled_chain(C, n, seed, mean=None):
+    """n rows drawn from N(mean, C)"""
+    rng = np.random.default_rng(seed)
+    d = C.shape[0]
+    z = rng.standard_normal((n, d))
+    rows = z @ np.linalg.cholesky(C).T
+    if mean is not None:
+        rows += mean
+    return _chain_from_rows(rows, z, rng)
+
+
+def graded_chain(seed, n, d, lo=1e-5, hi=1e2, dep=50.0):
+    """graded Gaussian: spreads log-spaced over [lo, hi] in random column order, random correlations plus one
+    near-dependence of weight ``dep``"""
+    rng = np.random.default_rng(seed)
+    sig = np.logspace(math.log10(lo), math.log10(hi), d)[rng.permutation(d)]
+    L = np.eye(d) + 0.8 * rng.standard_normal((d, d)) / math.sqrt(max(d, 1))
+    Cn = L @ L.T
+    if d > 1 and dep:
+        v = rng.standard_normal(d)
+        Cn += dep * np.outer(v, v)
+    Cn = Cn / np.outer(np.sqrt(np.diag(Cn)), np.sqrt(np.diag(Cn)))
+    return sampled_chain(Cn * np.outer(sig, sig), n, seed + 1000)
+
+
+def planck_allparams_chain(seed, n, nderived=6, nnuis=15):
+    """A Planck '--allparams' stand-in: the 6 base parameters of synth.PLANCK_PARAMS (their means and spreads, mildly
+    correlated), ``nderived`` derived columns that are smooth non-linear functions of them plus noise of 1e-3 of their
+    spread (near-functions), and ``nnuis`` nuisance amplitudes with spreads of ~10."""
+    from mcevidence_amd.synth import PLANCK_PARAMS
+    rng = np.random.default_rng(seed)
+    mu = np.array([p[1] for p in PLANCK_PARAMS])
+    sg = np.array([p[2] for p in PLANCK_PARAMS])
+    mix = np.eye(6) + 0.3 * rng.standard_normal((6, 6))
+    z = rng.standard_normal((n, 6))
+    zz = z @ mix
+    zz /= zz.std(axis=0)
+    ob, oc, th, tau, logA, ns = (mu + zz * sg).T
+    h = 0.6736 + 50.0 * (th - 1.04085) - 1.5 * (oc - 0.1197)               # H0 / 100 from theta and the densities
+    derived = [100.0 * h, (ob + oc) / h ** 2, 0.811 * np.exp(0.5 * (logA - 3.089)) * (oc / 0.1197) ** 0.6,
+               13.8 - 8.0 * (h - 0.6736), 0.1 * np.exp(logA) * np.exp(-2.0 * tau), 1090.0 + 300.0 * (ob - 0.02222) - 20.0 * (ns - 0.9655)]
+    cols = [ob, oc, th, tau, logA, ns]
+    for k in range(nderived):
+        f = derived[k % len(derived)] * (1.0 + 0.01 * (k // len(derived)))
+        cols.append(f + 1e-3 * f.std() * rng.standard_normal(n))
+    nuis = 10.0 * rng.uniform(0.5, 2.0, nnuis) * rng.standard_normal((n, nnuis)) + rng.uniform(50, 500, nnuis)
+    rows = np.column_stack(cols + [nuis])
+    return _chain_from_rows(rows, np.column_stack([z, (nuis - nuis.mean(0)) / nuis.std(0)]), rng)
+
+
+def offset_chain(seed, n, d, ratio=1e5):
+    """offset-dominated: column means up to ``ratio`` times the column spread (theta: 1.04 +- 4.7e-4 in Planck)"""
+    rng = np.random.default_rng(seed)
+    sig = np.logspace(-3, 1, d)[rng.permutation(d)]
+    A = np.eye(d) + 0.5 * rng.standard_normal((d, d)) / math.sqrt(d)
+    Cn = A @ A.T
+    Cn = Cn / np.outer(np.sqrt(np.diag(Cn)), np.sqrt(np.diag(Cn)))
+    mean = sig * ratio * rng.uniform(-1.0, 1.0, d)
+    mean[0] = sig[0] * ratio
+    return sampled_chain(Cn * np.outer(sig, sig), n, seed + 1000, mean=mean)
+
+
+def isotropic_chain(seed, n, blocks=(4, 5, 3, 6)):
+    """near-repeated eigenvalues: the rows are recoloured so that their sample covariance is Q diag(lam) Q^T, with lam
+    constant over blocks of the given sizes (10, 1, 0.1, ...) up to rounding -- isotropic eigen-spaces in which the
+    eigenvectors are fixed by rounding alone, so only rotation-invariant quantities can be compared there."""
+    rng = np.random.default_rng(seed)
+    d = int(sum(blocks))
+    lam = np.concatenate([np.full(b, 10.0 ** (1 - i)) for i, b in enumerate(blocks)])
+    Q, _ = np.linalg.qr(rng.standard_normal((d, d)))
+    z = rng.standard_normal((n, d))
+    z -= z.mean(axis=0)
+    z = z @ np.linalg.inv(np.linalg.cholesky(np.cov(z.T))).T
+    rows = (z * np.sqrt(lam)) @ Q.T + rng.standard_normal(d)
+    return _chain_from_rows(rows, z, rng)
+
+
+def singular_chain(seed, n, d=5):
+    """a column that is the sum of two others: singular by construction (rounding leaves it merely near-singular)"""
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal((n, d - 1))
+    rows = np.column_stack([z, z[:, 0] + z[:, 1]])
+    return _chain_from_rows(rows, z, rng)

@@ -47,10 +47,9 @@ PairsOnceShape pairs_once_shape(const Plan& p, int64_t nr, int32_t kmax, int32_t
 {
     PairsOnceShape sh;
     const int nown = (p.nqblk + nparts - 1) / std::max(nparts, 1);
-    // (the two overrides are read ONCE per process: the five entry points below derive the workspace layout from them again and
-    //  again, and an environment that changes between the calls on one workspace would misplace the list sets -- ADVICE round 5)
-    static const int env_split = [] { const char* e = getenv("MCE_PAIRS_ONCE_SPLIT"); const int v = e ? atoi(e) : 0; return (v >= 1 && v <= 8) ? v : 0; }();
-    static const int env_panel = [] { const char* e = getenv("MCE_PAIRS_ONCE_PANEL"); const int v = e ? atoi(e) : 0; return v >= 1 ? v : 0; }();
+    // (the two overrides are read ONCE per process: the five entry points below derive the workspace layout from them again and again)
+    const int env_split = env_pairs_once_split();
+    const int env_panel = env_pairs_once_panel();
     int S = std::min(8, std::max(1, (1536 + nown - 1) / std::max(nown, 1)));
     if (env_split) S = env_split;
     const int def_panel = kSymPanelChunks[p.KST];
@@ -100,14 +99,28 @@ int apo_step(const void* ws, int64_t nr, int d, int kmax, int part, int nparts, 
     else g_apo_calls[ws] = ApoCall{nr, d, kmax, part, nparts, sh.nsplit, sh.panel, phase_set};
     return MCE_OK;
 }
-// (the plan's list offsets point at the shape's list sets from here on)
-void pairs_once_apply(Plan& p, const PairsOnceShape& sh)
+// The preamble of the four calls: the plan, the rank count against the blocks, the shape of the rank's share, the workspace, the
+// step's place in the sequence (apo_step); then the plan as the rank's share, whose list offsets point at the shape's list sets.
+// (export reports a bad rank count as "part r of W"; export and finish report a small workspace without the sizes)
+enum PairsOnceStep { kApoPrepare, kApoSweep, kApoExport, kApoFinish };
+int pairs_once_begin(PairsOnceStep step, const void* ws, size_t ws_bytes, int64_t nr, int32_t d, int32_t kmax, int32_t part, int32_t nparts, Plan& p,
+                     PairsOnceShape& sh)
 {
-    p.apo = true;
-    p.apo_nsplit = sh.nsplit;
-    p.apo_panel = sh.panel;
-    p.off_pd = sh.off_d;
-    p.off_pi = sh.off_i;
+    static const struct { int from, to, set; const char* what; } kSteps[4] = {{0, 0, 1, "prepare"}, {1, 1, 2, "sweep"}, {2, 3, 3, "export"},
+                                                                               {2, 3, -1, "finish"}};      // (export may be skipped by a rank with nothing to ship)
+    int rc = pairs_once_plan(nr, d, kmax, p, false);
+    if (rc != MCE_OK) return rc;
+    if (nparts > p.nqblk || (step == kApoExport && nparts < 2))        // (the other three calls have refused nparts < 2 already)
+        return step == kApoExport ? fail(MCE_ERR_INVALID, "part %d of %d", part, nparts)
+                                  : fail(MCE_ERR_INVALID, "pairs-once partition: %d ranks for %d blocks", nparts, p.nqblk);
+    sh = pairs_once_shape(p, nr, kmax, nparts);
+    if (ws_bytes < sh.total)
+        return step >= kApoExport ? fail(MCE_ERR_WORKSPACE, "workspace too small") : fail(MCE_ERR_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, sh.total);
+    rc = apo_step(ws, nr, d, kmax, part, nparts, sh, kSteps[step].from, kSteps[step].to, kSteps[step].set, kSteps[step].what);
+    if (rc != MCE_OK) return rc;
+    p.apo = true; p.apo_nsplit = sh.nsplit; p.apo_panel = sh.panel; p.off_pd = sh.off_d; p.off_pi = sh.off_i;
+    p.part = part; p.nparts = nparts;
+    return MCE_OK;
 }
 
 __global__ __launch_bounds__(256) void pairs_once_fill_kernel(unsigned long long* __restrict__ p, int64_t n, unsigned long long v)
@@ -132,31 +145,6 @@ __global__ __launch_bounds__(256) void pairs_once_row_gates_kernel(unsigned long
 #pragma unroll
     for (int o = 16; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     if ((threadIdx.x & 31) == 0) rtile[q >> 5] = m;
-}
-
-// the argument block of the symmetric sweep's launches from a plan and its workspace (after run_search has filled it)
-void pairs_once_args(const Plan& p, char* ws, int64_t nr, int32_t d, int32_t K, mce::KnnF16Args& a)
-{
-    char* const sw = ws + p.off_sym;
-    a.Yh = reinterpret_cast<_Float16*>(ws + p.off_yh); a.nchunk_total = p.nchunk; a.rsplit = 1;
-    a.Xh = reinterpret_cast<_Float16*>(ws + p.off_xh);
-    a.qinfo = reinterpret_cast<double*>(ws + p.off_qinfo); a.params = reinterpret_cast<double*>(ws + p.off_params);
-    a.X = a.Y = reinterpret_cast<const double*>(sw + p.sl.Ys);
-    a.nq = a.nr = nr; a.D = d; a.nq_pad = p.nq_pad; a.nqblk = p.nqblk;
-    a.self_exclude = 1; a.self_offset = 0; a.ksel = K;
-    a.part_d = reinterpret_cast<double*>(ws + p.off_pd); a.part_i = reinterpret_cast<int*>(ws + p.off_pi);
-    a.rperm = reinterpret_cast<const int*>(sw + p.sl.perm);
-    a.sym.thr = reinterpret_cast<unsigned long long*>(sw + p.sl.thr);
-    a.sym.rrow = reinterpret_cast<unsigned*>(sw + p.sl.rrow);
-    a.sym.rtile = reinterpret_cast<float*>(sw + p.sl.rtile);
-    a.sym.slots = reinterpret_cast<unsigned long long*>(sw + p.sl.slots);
-    a.sym.bucket_cnt = reinterpret_cast<int*>(sw + p.sl.bucket_cnt);
-    a.sym.bucket_flag = reinterpret_cast<int*>(sw + p.sl.bucket_flag);
-    a.sym.bucket = reinterpret_cast<mce::SymEntry*>(sw + p.sl.bucket);
-    a.sym.cap = p.sl.cap;
-    a.sym.done = reinterpret_cast<int*>(sw + p.sl.done);
-    const Tuning tun = read_tuning();
-    a.sym.panel = tun.sym_panel > 0 ? tun.sym_panel : kSymPanelChunks[p.KST];
 }
 
 // a result that must not be used: an entry arrived for a row this rank does not own (ranks that disagree about the partition)
@@ -197,18 +185,11 @@ int mce_pairs_once_prepare_dev(const double* dY, int64_t nr, int32_t d, int32_t 
     if (!dY || !ws || !bounds_offset || !bounds_count) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (nparts < 2 || part < 0 || part >= nparts) return fail(MCE_ERR_INVALID, "part %d of %d (the pairs-once partition needs two ranks or more)", part, nparts);
     Plan p;
-    int rc = pairs_once_plan(nr, d, kmax, p, false);
+    PairsOnceShape sh;
+    int rc = pairs_once_begin(kApoPrepare, ws, ws_bytes, nr, d, kmax, part, nparts, p, sh);
     if (rc != MCE_OK) return rc;
-    if (nparts > p.nqblk) return fail(MCE_ERR_INVALID, "pairs-once partition: %d ranks for %d blocks", nparts, p.nqblk);
-    const PairsOnceShape sh = pairs_once_shape(p, nr, kmax, nparts);
-    if (ws_bytes < sh.total) return fail(MCE_ERR_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, sh.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* wsc = static_cast<char*>(ws);
-    rc = apo_step(ws, nr, d, kmax, part, nparts, sh, 0, 0, 1, "prepare");
-    if (rc != MCE_OK) return rc;
-    p.part = part;
-    p.nparts = nparts;
-    pairs_once_apply(p, sh);
     p.apo_phase = 1;
     // every row's bound starts at +inf, every slot empty; the prepass below fills in the rows of this rank's blocks
     const unsigned long long inf_bits = 0x7FF0000000000000ull;
@@ -237,21 +218,13 @@ int mce_pairs_once_sweep_dev(const double* dY, int64_t nr, int32_t d, int32_t km
     if (!dY || !d_counts || !d_flags || !ws) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (nparts < 2 || part < 0 || part >= nparts) return fail(MCE_ERR_INVALID, "part %d of %d (the pairs-once partition needs two ranks or more)", part, nparts);
     Plan p;
-    int rc = pairs_once_plan(nr, d, kmax, p, false);
+    PairsOnceShape sh;
+    int rc = pairs_once_begin(kApoSweep, ws, ws_bytes, nr, d, kmax, part, nparts, p, sh);
     if (rc != MCE_OK) return rc;
-    if (nparts > p.nqblk) return fail(MCE_ERR_INVALID, "pairs-once partition: %d ranks for %d blocks", nparts, p.nqblk);
-    const PairsOnceShape sh = pairs_once_shape(p, nr, kmax, nparts);
-    if (ws_bytes < sh.total) return fail(MCE_ERR_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, sh.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* wsc = static_cast<char*>(ws);
-    rc = apo_step(ws, nr, d, kmax, part, nparts, sh, 1, 1, 2, "sweep");
-    if (rc != MCE_OK) return rc;
-    p.part = part;
-    p.nparts = nparts;
-    pairs_once_apply(p, sh);
     p.apo_phase = 2;
-    mce::KnnF16Args a;
-    pairs_once_args(p, wsc, nr, d, kmax - 1, a);
+    const mce::KnnF16Args a = sym_args(p, wsc, nr, d, kmax - 1, 1);
     // the bounds are everybody's now (MIN over the ranks): the row-side gate constants follow from them
     hipLaunchKernelGGL(pairs_once_row_gates_kernel, dim3((unsigned)(p.nq_pad / 256)), dim3(256), 0, st, a.sym.thr, a.sym.rrow, a.sym.rtile, a.qinfo, a.params, nr, p.KST);
     MCE_HIP(hipGetLastError());
@@ -271,18 +244,13 @@ int mce_pairs_once_export_dev(int64_t nr, int32_t d, int32_t kmax, int32_t part,
 {
     if (!ws) return fail(MCE_ERR_INVALID, "null pointer argument");
     Plan p;
-    int rc = pairs_once_plan(nr, d, kmax, p, false);
-    if (rc != MCE_OK) return rc;
-    if (nparts < 2 || nparts > p.nqblk) return fail(MCE_ERR_INVALID, "part %d of %d", part, nparts);
-    const PairsOnceShape sh = pairs_once_shape(p, nr, kmax, nparts);
-    if (ws_bytes < sh.total) return fail(MCE_ERR_WORKSPACE, "workspace too small");
-    rc = apo_step(ws, nr, d, kmax, part, nparts, sh, 2, 3, 3, "export");
+    PairsOnceShape sh;
+    const int rc = pairs_once_begin(kApoExport, ws, ws_bytes, nr, d, kmax, part, nparts, p, sh);
     if (rc != MCE_OK) return rc;
     if (!d_send) return MCE_OK;           // (nothing to ship)
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* wsc = static_cast<char*>(ws);
-    mce::KnnF16Args a;
-    pairs_once_args(p, wsc, nr, d, kmax - 1, a);
+    const mce::KnnF16Args a = sym_args(p, wsc, nr, d, kmax - 1, 1);
     const int* offs = reinterpret_cast<const int*>(wsc + p.off_sym + p.sl.keys_a);
     hipLaunchKernelGGL(mce::apo_export_kernel, dim3((unsigned)p.nqblk), dim3(256), 0, st, a.sym.bucket, offs, a.sym.cap, p.nqblk, (int)nparts,
                        static_cast<mce::SymEntry*>(d_send));
@@ -297,19 +265,13 @@ int mce_pairs_once_finish_dev(const double* dY, int64_t nr, int32_t d, int32_t k
     if (!dY || !d_w || !d_fs || !d_dotp || !d_flags || !ws || (nrecv > 0 && !d_recv)) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (nparts < 2 || part < 0 || part >= nparts || nrecv < 0) return fail(MCE_ERR_INVALID, "part %d of %d, %lld entries", part, nparts, (long long)nrecv);
     Plan p;
-    int rc = pairs_once_plan(nr, d, kmax, p, false);
+    PairsOnceShape sh;
+    int rc = pairs_once_begin(kApoFinish, ws, ws_bytes, nr, d, kmax, part, nparts, p, sh);
     if (rc != MCE_OK) return rc;
-    if (nparts > p.nqblk) return fail(MCE_ERR_INVALID, "pairs-once partition: %d ranks for %d blocks", nparts, p.nqblk);
-    const PairsOnceShape sh = pairs_once_shape(p, nr, kmax, nparts);
-    if (ws_bytes < sh.total) return fail(MCE_ERR_WORKSPACE, "workspace too small");
-    rc = apo_step(ws, nr, d, kmax, part, nparts, sh, 2, 3, -1, "finish");      // (export may be skipped by a rank with nothing to ship)
-    if (rc != MCE_OK) return rc;
-    pairs_once_apply(p, sh);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* wsc = static_cast<char*>(ws);
     const int K = kmax - 1;
-    mce::KnnF16Args a;
-    pairs_once_args(p, wsc, nr, d, K, a);
+    mce::KnnF16Args a = sym_args(p, wsc, nr, d, K, 1);
     const int nown = mce::apo_rank_count(p.nqblk, part, nparts);          // this rank's blocks: part, part + nparts, ...
     int* err = reinterpret_cast<int*>(wsc + p.off_sym + p.sl.keys_a) + p.nqblk + 1;
     MCE_HIP(mce::zero_async(err, sizeof(int), st));
@@ -334,14 +296,12 @@ int mce_pairs_once_finish_dev(const double* dY, int64_t nr, int32_t d, int32_t k
     // the reduction enumerates every nparts-th block of list columns through a block table (reduce_kernels.hpp: border): the identity
     hipLaunchKernelGGL(mce::apo_iota_kernel, dim3((unsigned)((p.nqblk + 255) / 256)), dim3(256), 0, st, a.sym.done, p.nqblk);
     MCE_HIP(hipGetLastError());
-    p.part = part; p.nparts = nparts; p.sym_qb_lo = 0; p.sym_qb_hi = p.nqblk; p.sym_active = true; p.L = sh.nsplit;
+    p.sym_qb_lo = 0; p.sym_qb_hi = p.nqblk; p.sym_active = true; p.L = sh.nsplit;
     double* partial = reinterpret_cast<double*>(wsc + p.total);
     rc = launch_merge(p, false, true, dY, dY, nr, d, K, MCE_SELF_EXCLUDE, 0, nullptr, nullptr, 1, (int)kmax, d_w, d_fs, partial, wsc, st);
     if (rc != MCE_OK) return rc;
-    const int64_t ncol = (int64_t)nown * qpb;
-    const unsigned blocks = (unsigned)std::max<int64_t>((ncol + mce::kRedThreads - 1) / mce::kRedThreads, 1);
-    hipLaunchKernelGGL(mce::dotp_final_kernel, dim3((unsigned)kmax), dim3(mce::kRedThreads), 0, st, partial, (int64_t)blocks, 1, (int)kmax, d_dotp);
-    MCE_HIP(hipGetLastError());
+    rc = finish_dotp(partial, (int64_t)nown * qpb, 1, kmax, d_dotp, st);
+    if (rc != MCE_OK) return rc;
     hipLaunchKernelGGL(pairs_once_poison_kernel, dim3(1), dim3(64), 0, st, err, d_dotp, (int)kmax);
     MCE_HIP(hipGetLastError());
     return MCE_OK;

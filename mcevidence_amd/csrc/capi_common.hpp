@@ -44,22 +44,30 @@ std::atomic<int> g_prune_mode{0};
 // Tuning and test knobs.  This is the ONE place where the library reads the environment; every knob is result-neutral
 // (the tests run the same searches under different settings and compare bit for bit) and exists for tests, bisecting and
 // tuning -- production callers set none of them.  Read at every call (a dozen getenv per search), so tests can change
-// them between calls; the workspace LAYOUT depends on sym / sym_bucket / rsplit / the seed knobs, which must therefore not
-// change between a workspace query and the call that uses the workspace.
+// them between calls, unless marked "read once"; the workspace LAYOUT depends on sym / sym_bucket / rsplit / the seed knobs,
+// which must therefore not change between a workspace query and the call that uses the workspace.
 //   MCE_SYM=0|1|2                initial value of mce_set_sym_mode (read once)
 //   MCE_SYM_KERNEL=f16           the symmetric sweep on knn_f16_kernel<.., SYM = 2> (round 2) instead of knn_panel_kernel
 //   MCE_SYM_SPIN_LIMIT=n         ~microseconds a unit waits for its block's previous unit before it gives up (2^21)
 //   MCE_SYM_BUCKET=n             row-side candidates per row the buckets hold (6K + 24)
 //   MCE_SYM_PANEL=n              chunks per panel of reference rows (256; 96 with one k-step)
+//   MCE_SYM_CHAINS=S             symmetric sweep on one GPU: chains of units (list sets) per block (1: off)
 //   MCE_SYM_SEED_ROWS / _SHARE / _MODE   prepass: rows (32768; 65536), at most 1/share of the chunks (2), where (by k-steps)
 //   MCE_F16_SEED_ROWS / _SHARE / _TG     seed phase of the exhaustive sweep: rows (24576), share (4), tiles per group (8)
 //   MCE_RSPLIT=n                 reference splits of the exhaustive sweep (the model's choice)
 //   MCE_TAIL_SPLIT=0             keep a search with a nearly empty last round of workgroups in one launch
 //   MCE_WIDE=0                   exhaustive one-k-step sweep: two query tiles per wave also where four would be taken (A/B)
 //   MCE_PANEL_DEBUG=bits         knn_panel.hpp test hooks (8: every candidate through the redo list, 16: waves give up waiting)
+//   MCE_PRUNE_HEAVY="<waves>,<S>"|auto|0   pruned walk over one set: the first waves served by S workgroups each (off)
+//   MCE_PRUNE_LISTS=long         pruned walk, K <= 10: the full-length list kernel instead of the short-list one (A/B)
+//   MCE_PRUNE_TIMES=<file>       pruned walk: every workgroup's duration written to <file> (diagnostic)
+//   MCE_PRUNE_PROF=1             print the pruned walk's per-wave cycle breakdown (builds with -DMCE_PRUNE_PROF)
+//   MCE_LONG=0                   128 <= d <= 1024 on the generic kernel instead of the long-row sweep (read once)
+//   MCE_DEEP=0                   64 <= d <= 127 on the fp64 sweep instead of the deep fp16 filter (read once)
+//   MCE_PAIRS_ONCE_SPLIT / _PANEL        all-pairs-once partition: chains per block (1..8), chunks per panel (read once)
 //   MCE_FEED_WAVE_BYTES=n        batched feed: bytes of host data per upload wave (tests: force several waves)
 //   MCE_FEED_UPLOAD=async        batched feed: uploads on the job's stream (read once)
-//   MCE_PRUNE_PROF=1             print the pruned walk's per-wave cycle breakdown (builds with -DMCE_PRUNE_PROF)
+//   MCE_VERIFY=n                 rows of the default run-time certificate (256; 0 = off; read once)
 // ---------------------------------------------------------------------------------------------------------------------
 struct Tuning {
     bool sym_kernel_f16 = false, tail_split = true, prune_prof = false, wide = true;
@@ -105,11 +113,18 @@ int sym_mode()
     }
     return m;
 }
-// which kernel sweeps: knn_panel_kernel (default) or the SYM = 2 instantiation of knn_f16_kernel (MCE_SYM_KERNEL=f16: kept
-// for comparisons).  A unit of the panel kernel waits for its block's previous unit at most this many ~1 us sleeps
-// (MCE_SYM_SPIN_LIMIT; 0 in the tests: every wait that is not already satisfied gives up, and the repair launch takes over)
-bool sym_use_panel_kernel() { return !read_tuning().sym_kernel_f16; }
-int sym_spin_limit() { return read_tuning().spin_limit; }
+// the pruned walk's knobs, read at every call (null: unset)
+const char* env_prune_heavy() { return getenv("MCE_PRUNE_HEAVY"); }
+const char* env_prune_lists() { return getenv("MCE_PRUNE_LISTS"); }
+const char* env_prune_times() { return getenv("MCE_PRUNE_TIMES"); }
+// read once per process
+bool env_long_on() { static const bool v = [] { const char* e = getenv("MCE_LONG"); return !(e && e[0] == '0'); }(); return v; }
+bool env_deep_on() { static const bool v = [] { const char* e = getenv("MCE_DEEP"); return !(e && e[0] == '0'); }(); return v; }
+bool env_feed_upload_async() { static const bool v = [] { const char* e = getenv("MCE_FEED_UPLOAD"); return e && !strcmp(e, "async"); }(); return v; }
+// (the all-pairs-once partition's workspace layout depends on these two: an environment that changed between the calls on one
+//  workspace would misplace the list sets -- ADVICE round 5)
+int env_pairs_once_split() { static const int v = [] { const char* e = getenv("MCE_PAIRS_ONCE_SPLIT"); const int n = e ? atoi(e) : 0; return (n >= 1 && n <= 8) ? n : 0; }(); return v; }
+int env_pairs_once_panel() { static const int v = [] { const char* e = getenv("MCE_PAIRS_ONCE_PANEL"); const int n = e ? atoi(e) : 0; return n >= 1 ? n : 0; }(); return v; }
 // Per-call options (mce_options, include/mcevidence_hip.h): the *_opt entry points and mce_options_push / _pop set them for
 // the calls the CURRENT THREAD makes; -1 = the process-wide default of the setters above.  Threads the library starts
 // itself (one per device) inherit the caller's.  The planner reads the modes through these three functions only.

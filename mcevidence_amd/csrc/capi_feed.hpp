@@ -102,19 +102,16 @@ int fused_on_device(int device, const double* X, int64_t q_lo, int64_t q_hi, con
     rc = make_plan(nq, nr, d, K, k0 == 1 ? MCE_SELF_EXCLUDE : MCE_SELF_NONE, p);
     if (rc != MCE_OK) return rc;
     const size_t wsb = p.total + dotp_ws_bytes(nq, kmax);
-    const bool inside = Xs >= Y && Xs + (size_t)nq * d <= Y + (size_t)nr * d && (Xs - Y) % d == 0;     // as in mce_knn_f64
     DevBuf dX, dY, dW, dF, dO, dD, ws;
-    if (!inside) MCE_HIP(dX.alloc((size_t)nq * d * sizeof(double)));
-    MCE_HIP(dY.alloc((size_t)nr * d * sizeof(double)));
+    const double* dXp = nullptr;
+    rc = upload_rows(Xs, nq, Y, nr, d, dX, dY, dXp);
+    if (rc != MCE_OK) return rc;
     MCE_HIP(dW.alloc((size_t)nq * sizeof(double)));
     MCE_HIP(dF.alloc((size_t)nq * sizeof(double)));
     MCE_HIP(dO.alloc((size_t)kmax * sizeof(double)));
     const int nverify = (d <= mce::kVerifyMaxDim && K <= mce::kVerifyMaxK) ? eff_verify(p.filter(), nq) : 0;     // mce_options.verify (default: on behind the fp16 filter)
     if (dist_out || nverify) MCE_HIP(dD.alloc((size_t)nq * K * sizeof(double)));
     MCE_HIP(ws.alloc(wsb));
-    if (!inside) MCE_HIP(hipMemcpy(dX.p, Xs, (size_t)nq * d * sizeof(double), hipMemcpyHostToDevice));
-    MCE_HIP(hipMemcpy(dY.p, Y, (size_t)nr * d * sizeof(double), hipMemcpyHostToDevice));
-    const double* dXp = inside ? dY.as<double>() + (Xs - Y) : dX.as<double>();
     MCE_HIP(hipMemcpy(dW.p, w + q_lo, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
     MCE_HIP(hipMemcpy(dF.p, fs + q_lo, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
     rc = mce_knn_dotp_f64_dev(dXp, nq, dY.as<double>(), nr, d, kmax, k0, self_offset + q_lo,
@@ -266,7 +263,7 @@ int feed_stage_a(FeedJob& j, hipStream_t st)
     // (a blocking hipMemcpy from pageable memory only promises that the SOURCE has been consumed on return, and
     // hipStreamNonBlocking streams do not synchronise with the legacy default stream).  MCE_FEED_UPLOAD=async: the
     // copies themselves on the job's stream.
-    static const bool async_upload = [] { const char* e = getenv("MCE_FEED_UPLOAD"); return e && !strcmp(e, "async"); }();
+    const bool async_upload = env_feed_upload_async();
     if (j.src_device) {
         // the rows are on this device already (the caller has synchronised the stream that produced them)
         MCE_HIP(hipMemcpy2DAsync(j.dS1(), row, q.S1, (size_t)q.ld1 * sizeof(double), row, (size_t)q.n1, hipMemcpyDeviceToDevice, st));

@@ -33,7 +33,7 @@ constexpr int kWideMinBlocks = 480;                    // query blocks from whic
 bool prune_heavy_enabled()
 {
     if (t_no_heavy) return false;
-    const char* e = getenv("MCE_PRUNE_HEAVY");
+    const char* e = env_prune_heavy();
     return kPruneHeavyDefault || (e && *e && strcmp(e, "0") != 0);
 }
 static_assert(mce::kPruneWavesPerBlock == mce::kHWaves, "prune.hip orders kHWaves waves per query block");
@@ -117,6 +117,26 @@ int sweep_seed_cfg(int64_t cps, int CT, int kneed)
     return 0;
 }
 
+// the fp16 filter's variant table (fp16 or deep) for list capacity index ki: KCAP 4, 8, 12, 16
+template <class V> const V* by_kcap(int ki, const V* t4, const V* t8, const V* t12, const V* t16) { return ki == 0 ? t4 : ki == 1 ? t8 : ki == 2 ? t12 : t16; }
+
+// reference split r: more workgroups fill the chip and trim the last partial round
+// (one 512-thread workgroup per CU), but every split re-pays the list warm-up: a query
+// accepts ~K(1+ln(n/K)) candidates while streaming n references, each a serialised
+// whole-wave insertion.  Model (cycles per SIMD, fitted on MI355X):
+//   fp64 sweep : block(r) = 256*KS*tiles16(r)      + 1000 * 32   * K (1 + ln(n_r/K))
+//   fp16 filter: block(r) = 64*QT*KST*tiles32(r)   +  300 * 32QT * K (1 + ln(n_r/K))
+//   total(r)   = ceil(nqblk*r / CUs) * block(r),   n_r = nr/r
+double split_cost(const Plan& p, bool filt, int64_t nr, int32_t K, int r)
+{
+    const double n_r = (double)nr / r;
+    const double lnf = 1.0 + std::log(std::max(1.0, n_r / K));
+    const double block = filt ? 64.0 * p.QT * p.KST * (n_r / 32.0) + 300.0 * 32.0 * p.QT * K * lnf
+                              : 256.0 * p.KS * (n_r / 16.0) + 1000.0 * 32.0 * K * lnf;
+    const double rounds = std::ceil((double)p.nqblk * r / kAssumedCUs);
+    return rounds * block;
+}
+
 int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, Plan& p)
 {
     if (nq < 0 || nr < 1 || d < 1 || K < 1) return fail(MCE_ERR_INVALID, "invalid sizes nq=%lld nr=%lld d=%d K=%d", (long long)nq, (long long)nr, d, K);
@@ -133,8 +153,7 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
     const bool wide_f64 = d > MCE_MAX_DIM && d <= mce::kWideMaxDim && K <= MCE_MAX_K;
     // 128 <= d <= 1024 (round 6): the fp64 MFMA sweep with the k dimension in blocks (knn_long.hpp) -- the vector-FMA kernel below ran
     // these at 0.12 of the fp64 vector peak; it keeps K > 32.  (MCE_LONG=0: comparisons.)
-    static const bool long_on = [] { const char* e = getenv("MCE_LONG"); return !(e && e[0] == '0'); }();
-    if (long_on && d >= mce::kLongMinDim && d <= mce::kLongMaxDim && K <= MCE_MAX_K) {
+    if (env_long_on() && d >= mce::kLongMinDim && d <= mce::kLongMaxDim && K <= MCE_MAX_K) {
         p.ksel = std::min<int>(K + kRefineMargin, MCE_MAX_K);          // (GEMM-form keys: the merge picks the K on exact distances)
         p.vl = &mce::g_knn_long[p.ksel <= 8 ? 0 : (p.ksel <= 16 ? 1 : 2)];
         p.v = nullptr;
@@ -207,39 +226,29 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
     const bool f16 = !wide_f64 && (eff_search_mode() != 1) && mce::f16_supported(d, K);
     // 64 <= d <= 127 (round 6): the fp16 filter with 5, 6 or 8 k-steps (knn_deep.hpp), K <= 32 (beyond 16 in two passes); search mode 1
     // keeps the fp64 sweep's wide form.  (MCE_DEEP=0: comparisons.)
-    static const bool deep_on = [] { const char* e = getenv("MCE_DEEP"); return !(e && e[0] == '0'); }();
-    const bool deep = wide_f64 && (eff_search_mode() != 1) && mce::deep_supported(d, K) && deep_on;
+    const bool deep = wide_f64 && (eff_search_mode() != 1) && mce::deep_supported(d, K) && env_deep_on();
     const bool filt = f16 || deep;          // fp16 operands in the workspace, 32-row tiles, 512-query blocks
     p.vd = nullptr;
     int qpb, rows_per_tile;
-    if (deep) {
-        if (K > 16) {                          // 16 nearest per reference split first, then the next K - 16 beyond them (knn_deep.hpp, LOWER)
+    if (filt) {
+        if (K > 16) {                          // 16 nearest per reference split first, then the next K - 16 beyond them (LOWER)
             p.twopass = true;
             ki = 3;
             p.KCAP = 16;
         }
-        p.KST = mce::deep_ksteps(d);
-        const mce::KnnDeepVariant* tab = ki == 0 ? mce::g_knn_deep_kcap4 : ki == 1 ? mce::g_knn_deep_kcap8 : ki == 2 ? mce::g_knn_deep_kcap12 : mce::g_knn_deep_kcap16;
-        p.vd = &tab[p.KST == 5 ? 0 : (p.KST == 6 ? 1 : 2)];
-        p.v = nullptr;
-        p.vh = nullptr;
-        p.QT = mce::kHQT;
-        p.CT = p.vd->ct;
-        qpb = mce::f16_qpb(p.KCAP);
-        rows_per_tile = 32;
-    } else if (f16) {
-        if (K > 16) {                          // 16 nearest per reference split first, then the next K - 16 beyond them
-            p.twopass = true;
-            ki = 3;
-            p.KCAP = 16;
+        if (deep) {
+            p.KST = mce::deep_ksteps(d);
+            p.vd = &by_kcap(ki, mce::g_knn_deep_kcap4, mce::g_knn_deep_kcap8, mce::g_knn_deep_kcap12, mce::g_knn_deep_kcap16)[p.KST == 5 ? 0 : (p.KST == 6 ? 1 : 2)];
+            p.vh = nullptr;
+            p.QT = mce::kHQT;
+            p.CT = p.vd->ct;
+        } else {
+            p.KST = mce::f16_ksteps(d);
+            p.vh = &by_kcap(ki, mce::g_knn_f16_kcap4, mce::g_knn_f16_kcap8, mce::g_knn_f16_kcap12, mce::g_knn_f16_kcap16)[p.KST - 1];
+            p.QT = p.vh->qt;
+            p.CT = p.vh->ct;
         }
-        p.KST = mce::f16_ksteps(d);
-        const mce::KnnF16Variant* tab = ki == 0 ? mce::g_knn_f16_kcap4 : ki == 1 ? mce::g_knn_f16_kcap8
-                                        : ki == 2 ? mce::g_knn_f16_kcap12 : mce::g_knn_f16_kcap16;
-        p.vh = &tab[p.KST - 1];
         p.v = nullptr;
-        p.QT = p.vh->qt;
-        p.CT = p.vh->ct;
         qpb = mce::f16_qpb(p.KCAP);
         rows_per_tile = 32;
     } else {
@@ -292,13 +301,7 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
             p.nrow_pad = p.nchunk * rows_per_chunk;
         }
     }
-    // reference split r: more workgroups fill the chip and trim the last partial round
-    // (one 512-thread workgroup per CU), but every split re-pays the list warm-up: a query
-    // accepts ~K(1+ln(n/K)) candidates while streaming n references, each a serialised
-    // whole-wave insertion.  Model (cycles per SIMD, fitted on MI355X):
-    //   fp64 sweep : block(r) = 256*KS*tiles16(r)      + 1000 * 32   * K (1 + ln(n_r/K))
-    //   fp16 filter: block(r) = 64*QT*KST*tiles32(r)   +  300 * 32QT * K (1 + ln(n_r/K))
-    //   total(r)   = ceil(nqblk*r / CUs) * block(r),   n_r = nr/r
+    // reference splits: the model's cheapest count (split_cost)
     int best_r = 1;
     double best_c = 1e300;
     const int rmax = (int)std::min<int64_t>(p.twopass ? mce::kMaxLists / 2 : mce::kMaxLists, p.nchunk);
@@ -307,12 +310,7 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
         return fail(MCE_ERR_INVALID, "reference set too large for the fp16-filter path at d = %d (nr=%lld): use search mode 1", d, (long long)nr);
     if (rmin > rmax) return fail(MCE_ERR_INVALID, "reference set too large for the fp16-filter path (nr=%lld)", (long long)nr);
     for (int r = std::max(1, rmin); r <= rmax; ++r) {
-        const double n_r = (double)nr / r;
-        const double lnf = 1.0 + std::log(std::max(1.0, n_r / K));
-        const double block = filt ? 64.0 * p.QT * p.KST * (n_r / 32.0) + 300.0 * 32.0 * p.QT * K * lnf
-                                  : 256.0 * p.KS * (n_r / 16.0) + 1000.0 * 32.0 * K * lnf;
-        const double rounds = std::ceil((double)p.nqblk * r / kAssumedCUs);
-        const double c = rounds * block;
+        const double c = split_cost(p, filt, nr, K, r);
         if (c < best_c * 0.98) { best_c = c; best_r = r; }   // need >2% gain to take a bigger split
     }
     // Searches of at most one round of workgroups (up to ~130 k queries): the sweep of such a set is mostly candidate
@@ -336,13 +334,7 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
     }
     if (p.prune) best_r = 1;                  // every workgroup walks its own chunk list
     p.rsplit = best_r;
-    {   // the model's cost of the split count actually taken (the overrides above may have left its minimum)
-        const double n_r = (double)nr / best_r;
-        const double lnf = 1.0 + std::log(std::max(1.0, n_r / K));
-        const double block = filt ? 64.0 * p.QT * p.KST * (n_r / 32.0) + 300.0 * 32.0 * p.QT * K * lnf : 256.0 * p.KS * (n_r / 16.0) + 1000.0 * 32.0 * K * lnf;
-        best_c = std::ceil((double)p.nqblk * best_r / kAssumedCUs) * block;
-    }
-    p.cost = best_c;
+    p.cost = split_cost(p, filt, nr, K, best_r);        // (the overrides above may have left the model's minimum)
     // the workspace layout for the split count taken; a part of a search that was handed the WHOLE search's workspace
     // (mce_knn_dotp_part_f64_dev: a row shard plans more reference splits than the whole set would, and every split has its
     // own lists) takes fewer splits until it fits (t_plan_cap)
@@ -424,6 +416,29 @@ size_t dotp_ws_bytes(int64_t nq, int32_t kmax)
 {
     const int64_t nb = (nq + mce::kRedThreads - 1) / mce::kRedThreads;
     return align_up((size_t)std::max<int64_t>(nb, 1) * (size_t)kmax * sizeof(double), 256);
+}
+
+// The plan of a *_dev entry point for the caller's workspace of ws_bytes, of which it needs `extra` bytes behind the plan's own
+// (the reduction's partial sums).  A workspace sized with same_set = 0 takes the exhaustive plan (same_set_fallback: the caller
+// holds a SameSetHint), one sized before MCE_PRUNE_HEAVY was set the walk without the heavy waves' side lists: `nh` is then
+// engaged, and the caller keeps it for every make_plan that follows (a tail split's).
+int plan_for_workspace(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, size_t ws_bytes, size_t extra, bool same_set_fallback,
+                       Plan& p, std::optional<NoHeavy>& nh)
+{
+    int rc = make_plan(nq, nr, d, K, self_mode, p);
+    if (rc != MCE_OK) return rc;
+    if (same_set_fallback && ws_bytes < p.total + extra && p.sym) {
+        g_same_set_hint = 0;
+        rc = make_plan(nq, nr, d, K, self_mode, p);
+        if (rc != MCE_OK) return rc;
+    }
+    if (ws_bytes < p.total + extra && p.heavy_max > 0) {        // the walk runs unsplit
+        nh.emplace();
+        rc = make_plan(nq, nr, d, K, self_mode, p);
+        if (rc != MCE_OK) return rc;
+    }
+    if (ws_bytes < p.total + extra) return fail(MCE_ERR_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, p.total + extra);
+    return MCE_OK;
 }
 
 }  // namespace

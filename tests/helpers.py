@@ -253,3 +253,277 @@ def singular_chain(seed, n, d=5):
     z = rng.standard_normal((n, d - 1))
     rows = np.column_stack([z, z[:, 0] + z[:, 1]])
     return _chain_from_rows(rows, z, rng)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# inputs chosen to stress the fp16 filter's bound (tests/test_gpu_parity.py, tests/test_gpu_adversarial.py): dynamic
+# range, clustering far below the fp16 resolution of the extent, offsets, fp16 over/underflow before scaling
+# --------------------------------------------------------------------------------------------------------------------
+ADVERSARIAL = {            # name -> f(rng, n, d) -> rows
+    "heavy_tails": lambda r, n, d: r.standard_t(1.5, size=(n, d)),
+    "tight_clusters": lambda r, n, d: r.integers(0, 3, size=(n, 1)) * 1000.0 + 1e-3 * r.standard_normal((n, d)),
+    "tiny_scale": lambda r, n, d: 1e-9 * r.standard_normal((n, d)),
+    "huge_scale_offset": lambda r, n, d: 1e7 + 3e4 * r.standard_normal((n, d)),
+    "anisotropic": lambda r, n, d: r.standard_normal((n, d)) * np.logspace(-4, 2, d)[None, :],
+    "one_outlier": lambda r, n, d: np.vstack([r.standard_normal((n - 1, d)), np.full((1, d), 1e4)]),
+    "lattice_ties": lambda r, n, d: r.integers(-3, 4, size=(n, d)).astype(float),
+    "subnormal_fp16_coords": lambda r, n, d: np.hstack([r.standard_normal((n, 1)), 1e-6 * r.standard_normal((n, d - 1))]),
+    "all_identical": lambda r, n, d: np.full((n, d), 3.25),
+    "constant_column": lambda r, n, d: np.hstack([np.full((n, 1), -7.0), r.standard_normal((n, d - 1))]),
+    "few_distinct": lambda r, n, d: r.standard_normal((5, d))[r.integers(0, 5, n)],
+}
+
+
+def _fp16_cell_straddlers(r, n, d):
+    """64 clusters with centres of order 1 in the first three columns (1e-3 of that in the others), each 2^-14 of its centre
+    wide: an eighth of the fp16 spacing there, so most clusters lie across a rounding boundary in some column and rows a
+    small fraction of a cell apart differ by a whole cell once converted"""
+    c = r.uniform(0.5, 1.0, size=(64, d)) * r.choice([-1.0, 1.0], size=(64, d))
+    c[:, 3:] *= 1e-3
+    lab = r.integers(0, 64, n)
+    return c[lab] + 2.0 ** -14 * np.abs(c[lab]) * r.standard_normal((n, d))
+
+
+#: kinds added with the every-row matrix (tests/test_gpu_adversarial.py); kept apart so that the older tests keep their cases
+ADVERSARIAL_EXTRA = {
+    "fp16_cell_straddlers": _fp16_cell_straddlers,
+    # a lattice whose ties are broken by a jitter of 1e-4 of its spacing, below the fp16 resolution of the (mean-centred) coordinates:
+    # nearly every row has its K-th and (K + 1)-th neighbours within 1e-4 relative -- a neighbour arriving when the threshold is
+    # already tight passes the gate on its error terms alone -- and the order is the distances', not the row numbers'
+    "jittered_lattice": lambda r, n, d: r.integers(-3, 4, size=(n, d)) + 1e-4 * r.standard_normal((n, d)),
+}
+#: kinds that need at least two columns
+ADVERSARIAL_MIN2 = ("anisotropic", "subnormal_fp16_coords", "constant_column")
+
+
+def _rows_cycled(A, n, rng=None):
+    """n rows of A: a random choice without replacement while A has enough rows, cycled otherwise"""
+    if rng is not None and n <= len(A):
+        return A[rng.permutation(len(A))[:n]].copy()
+    return A[np.arange(n) % len(A)].copy()
+
+
+def _far_queries(r, nq, nr, d):
+    Y = r.standard_normal((nr, d))
+    X = _rows_cycled(Y, nq)
+    X[:, 0] += 50.0
+    return X, Y
+
+
+def _query_outlier(r, nq, nr, d):
+    Y = r.standard_normal((nr, d))
+    X = r.standard_normal((nq, d))
+    X[nq // 2] = 1e6
+    return X, Y
+
+
+def _queries_on_refs(r, nq, nr, d):
+    Y = r.standard_normal((nr, d))
+    return _rows_cycled(Y, nq, r), Y
+
+
+#: separate query and reference sets (X != Y): name -> f(rng, nq, nr, d) -> (X, Y)
+CROSS = {
+    # every query outside the reference box, every K-th distance large
+    "far_queries": _far_queries,
+    # one query row at 1e6: the power-of-two scale puts every reference coordinate into fp16 subnormals
+    "query_outlier_sets_scale": _query_outlier,
+    # all references nearly equidistant from a query at fp16 resolution
+    "refs_in_a_speck": lambda r, nq, nr, d: (10.0 * r.standard_normal((nq, d)), 5.0 + 1e-3 * r.standard_normal((nr, d))),
+    # queries are copies of reference rows: the first distance is exactly 0 and the threshold reaches 0
+    "queries_on_refs": _queries_on_refs,
+    "lattice_queries": lambda r, nq, nr, d: (r.integers(-3, 4, size=(nq, d)).astype(float), r.standard_normal((nr, d))),
+    "lattice_refs": lambda r, nq, nr, d: (r.standard_normal((nq, d)), r.integers(-3, 4, size=(nr, d)).astype(float)),
+}
+#: scale of the Gaussian partner of a one-set kind where a unit Gaussian makes neighbours that no fp64 reference can order: from
+#: unit-Gaussian queries all rows of a 1e-9 cloud are equidistant to 1e-13 relative, and so are unit-Gaussian references from queries
+#: at 1e7 (one row in a hundred / in a few thousand would be ambiguous) -- there the partner takes the kind's own spread
+PARTNER_SCALE = {("tiny_scale", "refs"): 3e-9, ("huge_scale_offset", "queries"): 3e4}
+for _kind, _gen in sorted({**ADVERSARIAL, **ADVERSARIAL_EXTRA}.items()):
+    # every one-set kind as the queries of a Gaussian reference set, and as the references of Gaussian queries
+    CROSS[_kind + "_as_queries"] = lambda r, nq, nr, d, _g=_gen, _s=PARTNER_SCALE.get((_kind, "queries"), 1.0): (
+        _g(r, nq, d), _s * r.standard_normal((nr, d)))
+    CROSS[_kind + "_as_refs"] = lambda r, nq, nr, d, _g=_gen, _s=PARTNER_SCALE.get((_kind, "refs"), 1.0): (
+        _s * r.standard_normal((nq, d)), _g(r, nr, d))
+del _kind, _gen
+# the same two against a UNIT Gaussian partner, as the other kinds: only few queries and K = 1 stay under the cap of ambiguous rows
+CROSS["tiny_scale_unit_refs"] = lambda r, nq, nr, d: (r.standard_normal((nq, d)), ADVERSARIAL["tiny_scale"](r, nr, d))
+CROSS["huge_scale_offset_unit_queries"] = lambda r, nq, nr, d: (ADVERSARIAL["huge_scale_offset"](r, nq, d), r.standard_normal((nr, d)))
+
+
+def needs_two_columns(kind):
+    """a kind (one-set or cross) that is undefined at d = 1"""
+    return kind in ADVERSARIAL_MIN2 or any(kind == k + s for k in ADVERSARIAL_MIN2 for s in ("_as_queries", "_as_refs"))
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# kNN certificate: plain NumPy on the host, nothing shared with the library.
+#   C1 rows        indices in [0, nr), distinct; the own row never reported (SELF_EXCLUDE) / first at distance 0 (SELF_INCLUDE)
+#   C2 distances   dist[q, k] == the np.longdouble distance to row idx[q, k] within relative B; a true 0 is exactly 0;
+#                  ascending, equal distances by ascending row
+#   C3 complete    |dist[q, k] - od[q, k]| <= 2 B od[q, k] against the brute-force oracle asked for K + 1 neighbours
+#   C4 same rows   idx[q] == oi[q, :K] on every row that is not ambiguous
+# B = (D/2 + 2) 2^-53 is derived, not measured: each of the D differences carries a relative error u = 2^-53, its square
+# 2u; a sum of D positive terms, in any order and with or without fma, adds at most D u; the square root halves the total
+# ((3 + D) u / 2 < (D/2 + 1.5) u) and adds u of its own -- rounded up to (D/2 + 2) u.
+# With C1 and C2, C3 proves the list a valid K-nearest set up to ties of relative width 3B.  A row is AMBIGUOUS when the
+# oracle's own K + 1 distances hold an adjacent pair with 0 < gap <= 4B od[q, k + 1]: there two correct fp64 evaluations
+# may order the pair differently, and the row is judged by C1 - C3 only.  Exact ties (gap == 0) are not ambiguous: both
+# sides break them by row number.  At most AMBIGUOUS_CAP of the rows of a case may be ambiguous, which is checked on the
+# oracle's output before the result under test is looked at.
+# --------------------------------------------------------------------------------------------------------------------
+SELF_NONE, SELF_INCLUDE, SELF_EXCLUDE = 0, 1, 2
+AMBIGUOUS_CAP = 1e-5
+
+
+def cert_bound(D):
+    return (0.5 * D + 2.0) * 2.0 ** -53
+
+
+class CertificateError(AssertionError):
+    """raised by knn_certificate; ``report`` is the per-row report"""
+
+    def __init__(self, msg, report):
+        super().__init__(msg)
+        self.report = report
+
+
+def oracle_lists(X, Y, K, self_mode, self_offset=0):
+    """The oracle's side of the certificate: (od, oi, ambiguous) -- its K + 1 nearest (fewer where the reference set
+    ends), in the order the library documents for ``self_mode``, and the mask of ambiguous rows.  Raises when more than
+    AMBIGUOUS_CAP of the rows are ambiguous: such a case cannot judge anybody."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    nq, D = X.shape
+    nr = Y.shape[0]
+    if self_mode == SELF_NONE:
+        od, oi = orc.knn_brute(X, Y, min(K + 1, nr), self_mode=0)
+    elif self_mode == SELF_EXCLUDE:
+        od, oi = orc.knn_brute(X, Y, min(K + 1, nr - 1), self_mode=2, self_offset=self_offset)
+    elif self_mode == SELF_INCLUDE:           # the own row first, at distance 0, whatever duplicates it has; then the others
+        own = self_offset + np.arange(nq, dtype=np.int64)
+        kk = min(K, nr - 1)
+        if kk > 0:
+            od, oi = orc.knn_brute(X, Y, kk, self_mode=2, self_offset=self_offset)
+        else:
+            od, oi = np.empty((nq, 0)), np.empty((nq, 0), dtype=np.int64)
+        od = np.column_stack([np.zeros(nq), od])
+        oi = np.column_stack([own, oi])
+    else:
+        raise ValueError("self_mode %r" % (self_mode,))
+    if od.shape[1] < K:
+        raise ValueError("K = %d exceeds the usable reference rows" % K)
+    gap = np.diff(od, axis=1)
+    ambiguous = np.any((gap > 0) & (gap <= 4.0 * cert_bound(D) * od[:, 1:]), axis=1)
+    namb = int(ambiguous.sum())
+    if namb > AMBIGUOUS_CAP * nq:
+        raise ValueError("%d of %d rows are ambiguous on the oracle alone (cap %g of the rows): first rows %s -- change the seed "
+                         "or the input" % (namb, nq, AMBIGUOUS_CAP, np.flatnonzero(ambiguous)[:5].tolist()))
+    return od, oi, ambiguous
+
+
+_LONGDOUBLE_OK = np.finfo(np.longdouble).eps < 2.0 ** -52
+
+
+def _dist_within_bound(X, Y, idx, dist, B):
+    """(ok, zero): per entry, whether dist[q, k] lies within relative B of the true distance from X[q] to Y[idx[q, k]],
+    and whether that true distance is 0.  np.longdouble where it is wider than double (64-bit significand: its own
+    error, (D + 2) 2^-64, is 2^-11 of B); exact rational arithmetic otherwise."""
+    nq, K = idx.shape
+    D = X.shape[1]
+    ok = np.zeros((nq, K), dtype=bool)
+    zero = np.zeros((nq, K), dtype=bool)
+    if _LONGDOUBLE_OK:
+        step = max(1, (1 << 21) // max(1, K * D))
+        Bl = np.longdouble(B)
+        for s in range(0, nq, step):
+            e = min(nq, s + step)
+            diff = X[s:e, None, :].astype(np.longdouble) - Y[idx[s:e]].astype(np.longdouble)
+            t = np.sqrt((diff * diff).sum(-1))
+            ok[s:e] = np.abs(dist[s:e].astype(np.longdouble) - t) <= Bl * t
+            zero[s:e] = t == 0
+        return ok, zero
+    from fractions import Fraction
+    lo, hi = (1 - Fraction(B)) ** 2, (1 + Fraction(B)) ** 2
+    for q in range(nq):
+        xq = [Fraction(v) for v in X[q].tolist()]
+        for k in range(K):
+            s2 = sum((a - Fraction(v)) ** 2 for a, v in zip(xq, Y[idx[q, k]].tolist()))
+            g = dist[q, k]
+            zero[q, k] = s2 == 0
+            ok[q, k] = bool(np.isfinite(g)) and g >= 0 and lo * s2 <= Fraction(float(g)) ** 2 <= hi * s2
+    return ok, zero
+
+
+def knn_certificate(X, Y, K, dist, idx, self_mode, self_offset=0, kernel=None, oracle=None, max_report=8):
+    """Certify a finished K-nearest search ``(dist, idx)`` of the queries X in the references Y, EVERY row (C1 - C4 above).
+    Returns the report (dict: rows, K, B, ambiguous, ambiguous_rows, failures = []) or raises CertificateError whose message
+    names the first failing rows, the check each failed and ``kernel`` (the caller's ``last_kernel()``); its ``report``
+    lists every failure as (row, column, check, detail).  ``oracle``: a precomputed ``oracle_lists(...)`` of the same
+    arguments (several searches of one input)."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    nq, D = X.shape
+    nr = Y.shape[0]
+    B = cert_bound(D)
+    # the reference first, and alone: how many rows it cannot judge
+    od, oi, ambiguous = oracle if oracle is not None else oracle_lists(X, Y, K, self_mode, self_offset)
+    assert od.shape[0] == nq and od.shape[1] >= K
+    dist = np.asarray(dist)
+    idx = np.asarray(idx)
+    assert dist.shape == (nq, K) and idx.shape == (nq, K), (dist.shape, idx.shape, (nq, K))
+    assert dist.dtype == np.float64 and idx.dtype.kind in "iu"
+    idx = idx.astype(np.int64)
+    own = self_offset + np.arange(nq, dtype=np.int64)
+    fails = {}              # (row, check) -> (column, detail): the first column of a row a check fails at
+
+    def note(mask, check, detail):
+        for q, k in zip(*np.nonzero(mask)):
+            fails.setdefault((int(q), check), (int(k), detail(int(q), int(k))))
+
+    # ---- C1
+    inrange = (idx >= 0) & (idx < nr)
+    note(~inrange, "C1 row out of range", lambda q, k: "idx=%d" % idx[q, k])
+    safe = np.where(inrange, idx, 0)
+    order = np.argsort(safe, axis=1, kind="stable")
+    srt = np.take_along_axis(safe, order, axis=1)
+    dup = np.zeros((nq, K), dtype=bool)                     # (marked at the list column of the later of two equal entries)
+    np.put_along_axis(dup, order[:, 1:], srt[:, 1:] == srt[:, :-1], axis=1)
+    note(dup, "C1 duplicate row", lambda q, k: "idx=%s" % idx[q].tolist())
+    if self_mode == SELF_EXCLUDE:
+        note(idx == own[:, None], "C1 own row reported", lambda q, k: "idx=%s" % idx[q].tolist())
+    elif self_mode == SELF_INCLUDE:
+        first = np.zeros((nq, K), dtype=bool)
+        first[:, 0] = (idx[:, 0] != own) | (dist[:, 0] != 0.0)
+        note(first, "C1 own row not first at distance 0", lambda q, k: "idx=%d dist=%r" % (idx[q, 0], dist[q, 0]))
+    # ---- C2
+    finite = np.isfinite(dist) & (dist >= 0)
+    note(~finite, "C2 distance not finite", lambda q, k: "dist=%r" % dist[q, k])
+    ok, zero = _dist_within_bound(X, Y, safe, np.where(finite, dist, 0.0), B)
+    note(inrange & finite & ~ok, "C2 distance off its row's", lambda q, k: "dist=%r to row %d" % (dist[q, k], idx[q, k]))
+    note(inrange & zero & (dist != 0.0), "C2 zero distance not exact", lambda q, k: "dist=%r to row %d" % (dist[q, k], idx[q, k]))
+    desc = np.zeros((nq, K), dtype=bool)
+    desc[:, 1:] = dist[:, 1:] < dist[:, :-1]
+    note(desc, "C2 not ascending", lambda q, k: "dist=%r after %r" % (dist[q, k], dist[q, k - 1]))
+    tie = np.zeros((nq, K), dtype=bool)
+    tie[:, 1:] = (dist[:, 1:] == dist[:, :-1]) & (idx[:, 1:] < idx[:, :-1])
+    if self_mode == SELF_INCLUDE and K > 1:
+        tie[:, 1] = False                                      # (the own row leads whatever duplicates it has)
+    note(tie, "C2 tie not by ascending row", lambda q, k: "rows %d, %d at %r" % (idx[q, k - 1], idx[q, k], dist[q, k]))
+    # ---- C3
+    odk = od[:, :K]
+    note(~(np.abs(np.where(finite, dist, np.inf) - odk) <= 2.0 * B * odk), "C3 not the K nearest",
+         lambda q, k: "dist=%r oracle=%r (row %d, oracle row %d)" % (dist[q, k], od[q, k], idx[q, k], oi[q, k]))
+    # ---- C4
+    note((idx != oi[:, :K]) & ~ambiguous[:, None], "C4 rows differ from the oracle's",
+         lambda q, k: "row %d, oracle row %d at %r / %r" % (idx[q, k], oi[q, k], dist[q, k], od[q, k]))
+
+    failures = sorted((q, k, c, t) for (q, c), (k, t) in fails.items())
+    report = dict(rows=nq, K=K, B=B, ambiguous=int(ambiguous.sum()), ambiguous_rows=np.flatnonzero(ambiguous), failures=failures,
+                  failed_rows=sorted({f[0] for f in failures}), kernel=kernel)
+    if failures:
+        lines = ["row %d column %d: %s (%s)" % f for f in failures[:max_report]]
+        raise CertificateError("kNN certificate failed on %d of %d rows (nq=%d nr=%d d=%d K=%d self_mode=%d self_offset=%d, "
+                               "%d ambiguous rows); kernel: %s\n  %s" % (len(report["failed_rows"]), nq, nq, nr, D, K, self_mode, self_offset,
+                                                                     report["ambiguous"], kernel, "\n  ".join(lines)), report)
+    return report

@@ -6,7 +6,7 @@ import math
 import numpy as np
 import pytest
 
-from helpers import DIST_RTOL, LNE_TOL, OracleBackend, build_mce, chain_of, load_golden, orc
+from helpers import ADVERSARIAL, DIST_RTOL, LNE_TOL, OracleBackend, build_mce, chain_of, load_golden, orc
 
 pytestmark = pytest.mark.gpu
 logging.disable(logging.CRITICAL)
@@ -270,23 +270,6 @@ def test_knn_large_offsets_are_stable(capi):
     d, i = capi.knn(Y, Y, 5, self_mode=capi.SELF_EXCLUDE)
     od, oi = orc.knn_brute(Y, Y, 5, self_mode=2)
     assert _rel(d, od) < 1e-8 and np.mean(i == oi) > 0.999
-
-
-ADVERSARIAL = {
-    # name: (generator, n, d) -- inputs chosen to stress the fp16 filter's bound: dynamic range,
-    # clustering far below the fp16 resolution of the extent, offsets, fp16 over/underflow before scaling
-    "heavy_tails": lambda r, n, d: r.standard_t(1.5, size=(n, d)),
-    "tight_clusters": lambda r, n, d: r.integers(0, 3, size=(n, 1)) * 1000.0 + 1e-3 * r.standard_normal((n, d)),
-    "tiny_scale": lambda r, n, d: 1e-9 * r.standard_normal((n, d)),
-    "huge_scale_offset": lambda r, n, d: 1e7 + 3e4 * r.standard_normal((n, d)),
-    "anisotropic": lambda r, n, d: r.standard_normal((n, d)) * np.logspace(-4, 2, d)[None, :],
-    "one_outlier": lambda r, n, d: np.vstack([r.standard_normal((n - 1, d)), np.full((1, d), 1e4)]),
-    "lattice_ties": lambda r, n, d: r.integers(-3, 4, size=(n, d)).astype(float),
-    "subnormal_fp16_coords": lambda r, n, d: np.hstack([r.standard_normal((n, 1)), 1e-6 * r.standard_normal((n, d - 1))]),
-    "all_identical": lambda r, n, d: np.full((n, d), 3.25),
-    "constant_column": lambda r, n, d: np.hstack([np.full((n, 1), -7.0), r.standard_normal((n, d - 1))]),
-    "few_distinct": lambda r, n, d: r.standard_normal((5, d))[r.integers(0, 5, n)],
-}
 
 
 @pytest.mark.parametrize("kind", sorted(ADVERSARIAL))

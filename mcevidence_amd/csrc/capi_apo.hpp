@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void pairs_once_row_gates_kernel(unsigned long
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;         // (nq_pad rows: a whole number of workgroups)
     float R = 0.0f;
     if (q < nq) {
-        R = mce::sym_row_gate(__longlong_as_double((long long)thr[q]), qinfo[2 * q], params, KST);
+        R = mce::f16_row_gate_of(__longlong_as_double((long long)thr[q]), qinfo[2 * q], params, KST);
         rrow[q] = __float_as_uint(R);
     } else {
         thr[q] = 0x7FF0000000000000ull;

@@ -10,7 +10,8 @@
 // its chain is done, and the SIMD's other wave fills the pipe meanwhile.  Budget at KST = 8, K <= 12: 64 (B) + 32 (acc) +
 // ~24 (A in flight) + 36 (lists) + constants.  The candidate path -- wave-uniform resolution of a tile that passed the gate,
 // per-wave LDS queue, redo list, ONE collective drain per chunk with exact fp64 evaluation (8 lanes per pair, 16 elements
-// each) and the register lists' insertion network -- is knn_panel.hpp's, column side only.
+// each) and the register lists' insertion network -- is knn_panel.hpp's, column side only; what the two share with the
+// exhaustive kernel, the bound first of all, is written once in f16_filter.hpp.
 //
 // Cold start.  A block meets its references with empty lists; with no bound every pair of the first chunks would be a
 // candidate (tens of thousands of exact evaluations per wave).  So every (block, reference split) first SEEDS its bounds
@@ -137,14 +138,13 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
             G[qt] = -__builtin_huge_valf();
         }
     }
-    // gate of query (qt, lane & 31): gq_a = e_x + max e_y (+ slack), gq_c = eps_q - |x^|^2 (-inf: padding query); see knn_f16.hpp
+    // gate of query (qt, lane & 31): gq_a = e_x + max e_y (+ slack), gq_c = eps_q - |x^|^2 (-inf: padding query); see f16_filter.hpp
     double gq_a[QT], gq_c[QT], gq_xn[QT], gq_eps[QT], s2c;
     {
         const auto params = gptr(a.params);
         const auto qinfo = gptr(a.qinfo);
         const double p_scale = params[HP_SCALE], p_ey = params[HP_EY], p_ym = params[HP_YHATMAX], p_rho = params[HP_RHO];
         s2c = p_scale * p_scale;
-        const double slack = 2.0 * sqrt(16.0 * KST) * 0x1p-14;
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const int64_t q = qwave0 + qt * 32 + (lane & 31);
@@ -153,22 +153,16 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
             gq_xn[qt] = 0.0;
             gq_eps[qt] = 0.0;
             if (q < a.nq) {
-                const double ex = qinfo[2 * q], xn = qinfo[2 * q + 1];
-                const double r = sqrt(xn) + p_ym;
-                const double eps = (32.0 * KST) * 0x1p-24 * r * r * (1.0 + 0x1p-9) + p_rho + 1e-30;
-                gq_a[qt] = (ex + p_ey) * (1.0 + 1e-9) + slack;
-                gq_c[qt] = eps - xn;
+                const double xn = qinfo[2 * q + 1];
+                const F16GateTerms t = f16_gate_terms(qinfo[2 * q], xn, p_ey, p_ym, p_rho, KST);
+                gq_a[qt] = t.a;
+                gq_c[qt] = t.c;
                 gq_xn[qt] = xn;
-                gq_eps[qt] = eps;
+                gq_eps[qt] = t.eps;
             }
         }
     }
-    auto gate_of = [&](double thr, int qt) __attribute__((always_inline)) -> float {
-        if (!(gq_c[qt] > -INF)) return -__builtin_huge_valf();
-        if (!(thr < INF)) return __builtin_huge_valf();
-        const double rr = sqrt(thr * s2c) * (1.0 + 1e-12) + gq_a[qt];
-        return __double2float_ru(rr * rr * (1.0 + 1e-12) + gq_c[qt]);
-    };
+    auto gate_of = [&](double thr, int qt) __attribute__((always_inline)) -> float { return f16_gate(thr, s2c, gq_a[qt], gq_c[qt]); };
 
     const int qlimit_gate = (a.debug & 8) ? -1 : QN - 64;
     int qcount = 0;
@@ -237,17 +231,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
                 if constexpr (LOWER) {      // only what lies beyond the first pass's 16th neighbour of this split
                     if (!(d2 > lo_own_d || (d2 == lo_own_d && j > lo_own_i))) d2 = INF;
                 }
-                // ascending list, ties by row; d2 = +inf (idle lane) changes nothing
-                bool c_hi = (d2 < own_d[KCAP - 1]) || (d2 == own_d[KCAP - 1] && j < own_i[KCAP - 1] && d2 < INF);
-#pragma unroll
-                for (int k = KCAP - 1; k >= 1; --k) {
-                    const bool c_lo = (d2 < own_d[k - 1]) || (d2 == own_d[k - 1] && j < own_i[k - 1] && d2 < INF);
-                    own_d[k] = c_lo ? own_d[k - 1] : (c_hi ? d2 : own_d[k]);
-                    own_i[k] = c_lo ? own_i[k - 1] : (c_hi ? j : own_i[k]);
-                    c_hi = c_lo;
-                }
-                own_d[0] = c_hi ? d2 : own_d[0];
-                own_i[0] = c_hi ? j : own_i[0];
+                list_insert<KCAP>(own_d, own_i, d2, j);
             }
         }
         qcount = 0;
@@ -261,51 +245,14 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
         for (int qt = 0; qt < QT; ++qt) G[qt] = gate_of(__shfl(thr_own, qt * 32 + (lane & 31), 64), qt);
     };
 
-    // ---- a tile with a candidate: wave-wide compares, scalar branches over the empty ones (knn_panel.hpp) --------------
+    // ---- a tile with a candidate: f16_event (f16_filter.hpp), column side only ----------------------------------------------
     auto event = [&](const v16f& c, const float (&l1)[5], const int qt, const float g, const int jb0, const unsigned todo, const int qlimit) __attribute__((always_inline)) -> unsigned {
-        const unsigned wbase = lanew[qt] + (unsigned)jb0;
-        unsigned rem = 0;
-#define MCE_HIT(R_, P_, S_)                                                                                               \
-        if ((S_) != 0 && (todo & (1u << (R_)))) {                                                                         \
-            if (qcount > qlimit) rem |= 1u << (R_);                                                                       \
-            else {                                                                                                        \
-                if (P_) wq[__builtin_amdgcn_mbcnt_hi((unsigned)((S_) >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)(S_), (unsigned)qcount))] = \
-                            (int)(wbase + (unsigned)(((R_) & 3) + 8 * ((R_) >> 2)));                                      \
-                qcount += __builtin_popcountll(S_);                                                                       \
-            }                                                                                                             \
-        }
-        {
-            const bool q0 = l1[0] <= g, q1 = l1[1] <= g, q2 = l1[2] <= g, q3 = l1[3] <= g, q4 = l1[4] <= g, p15 = c[15] <= g;
-            const unsigned long long u0 = __ballot(q0), u1 = __ballot(q1), u2 = __ballot(q2), u3 = __ballot(q3), u4 = __ballot(q4), s15 = __ballot(p15);
-#define MCE_TRIPLE(I_, U_)                                                                                                \
-            if ((U_) != 0) {                                                                                              \
-                const bool p0 = c[3 * (I_) + 0] <= g, p1 = c[3 * (I_) + 1] <= g, p2 = c[3 * (I_) + 2] <= g;             \
-                const unsigned long long s0 = __ballot(p0), s1 = __ballot(p1), s2 = __ballot(p2);                        \
-                MCE_HIT(3 * (I_) + 0, p0, s0)                                                                             \
-                MCE_HIT(3 * (I_) + 1, p1, s1)                                                                             \
-                MCE_HIT(3 * (I_) + 2, p2, s2)                                                                             \
-            }
-            MCE_TRIPLE(0, u0) MCE_TRIPLE(1, u1) MCE_TRIPLE(2, u2) MCE_TRIPLE(3, u3) MCE_TRIPLE(4, u4)
-#undef MCE_TRIPLE
-            MCE_HIT(15, p15, s15)
-        }
-#undef MCE_HIT
-        return rem;
+        return f16_event<false>(c, l1, lanew[qt], g, false, jb0, todo, qlimit, wq, qcount);
     };
 
     // ---- staging (global_load_lds DMA, linear image) + MFMA ------------------------------------------------------------
     const auto Yh_bytes = (const __attribute__((address_space(1))) char*)a.Yh;
-    auto stage_async = [&](int64_t c, int buf) {
-        const auto src = Yh_bytes + c * (int64_t)CHUNK_BYTES;
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int e = tid + i * kHThreads;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)(src + (size_t)e * 16),
-                (__attribute__((address_space(3))) void*)(stage0 + buf * CHUNK_BYTES + (size_t)(wave * 64 + i * kHThreads) * 16),
-                16, 0, 0);
-        }
-    };
+    auto stage_async = [&](int64_t c, int buf) { f16_stage_chunk<VPT>(Yh_bytes + c * (int64_t)CHUNK_BYTES, stage0 + buf * CHUNK_BYTES, tid, wave); };
     // one 32-row tile for both query tiles (or one of them): KST MFMAs per chain; the A fragments are read as the chain goes.
     // The statement after the chain spells out the wait states before the accumulators may be read through inline asm
     // (v_min3_f32: invisible to the compiler's hazard recogniser; 11 wait states are needed after an 8-pass MFMA).
@@ -326,16 +273,6 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]));
 #endif
-    };
-    auto min16 = [&](const v16f& c, float (&l1)[5]) __attribute__((always_inline)) -> float {
-        l1[0] = min3f(c[0], c[1], c[2]);
-        l1[1] = min3f(c[3], c[4], c[5]);
-        l1[2] = min3f(c[6], c[7], c[8]);
-        l1[3] = min3f(c[9], c[10], c[11]);
-        l1[4] = min3f(c[12], c[13], c[14]);
-        const float m0 = min3f(l1[0], l1[1], l1[2]);
-        const float m3 = min3f(l1[3], l1[4], c[15]);
-        return min3f(m0, m3, m3);
     };
 
     stage_async(c_lo, 0);
@@ -362,7 +299,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
                     float l1[5];
-                    gmin[qt] = fminf(gmin[qt], min16(acc[qt], l1));
+                    gmin[qt] = fminf(gmin[qt], f16_min16(acc[qt], l1));
                 }
                 if (++in_group == a.seed_tg) {
 #pragma unroll
@@ -381,12 +318,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             thr_q[qt] = INF;
-            if (gq_c[qt] > -INF && gmax[qt] < __builtin_huge_valf()) {
-                const double A = (double)gmax[qt] * (1.0 + 0x1p-22) + 0x1p-100;                       // (the float holds the accumulator exactly; margin for the sum below)
-                const double up = fmax(A + gq_xn[qt] + gq_eps[qt], 0.0);
-                const double rr = (sqrt(up) * (1.0 + 1e-12) + gq_a[qt]) * (1.0 + 1e-12);
-                thr_q[qt] = rr * rr * (1.0 + 1e-12) / s2c * (1.0 + 1e-12);
-            }
+            if (gq_c[qt] > -INF && gmax[qt] < __builtin_huge_valf()) thr_q[qt] = f16_seed_bound((double)gmax[qt], gq_xn[qt], gq_eps[qt], gq_a[qt], s2c);
         }
         const double t_lo = __shfl(thr_q[0], lane & 31, 64), t_hi = __shfl(thr_q[1], lane & 31, 64);
         seed_thr = lane < 32 ? t_lo : t_hi;
@@ -418,7 +350,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
             bool pq[QT];
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
-                mm[qt] = min16(acc[qt], l1[qt]);
+                mm[qt] = f16_min16(acc[qt], l1[qt]);
                 pq[qt] = mm[qt] <= G[qt];
             }
             if (__any(pq[0] || pq[1])) {
@@ -449,10 +381,10 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_deep_kernel(DeepArgs a)
                 // (wave-uniform choice of the query tile)
                 unsigned rem = 0;
                 if (qt == 0) {
-                    const float mm = min16(acc[0], l1);
+                    const float mm = f16_min16(acc[0], l1);
                     if (__any(mm <= G[0])) rem = event(acc[0], l1, 0, G[0], jchunk + t * 32, todo, QN - 64);
                 } else {
-                    const float mm = min16(acc[1], l1);
+                    const float mm = f16_min16(acc[1], l1);
                     if (__any(mm <= G[1])) rem = event(acc[1], l1, 1, G[1], jchunk + t * 32, todo, QN - 64);
                 }
                 if (rem) {

@@ -25,12 +25,17 @@
 // lane l -- which OWNS wave-local query l and keeps its sorted top-K list in registers --
 // walks its chain and applies a static compare/select insertion network.  Then the gates
 // G_q are refreshed from the owners' K-th best.
+//
+// The bound's arithmetic and what this kernel shares with knn_panel.hpp and knn_deep.hpp (list insertion, the 16-accumulator
+// minimum, the row side's slots, chunk staging) are in f16_filter.hpp; process() below -- the per-lane bit-mask event path --
+// is this kernel's own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
 #include "sym_types.hpp"
+#include "f16_filter.hpp"   // the gate's bound and everything else the filter kernel families share
 #include "prune.hpp"        // prune_band_floor: the order of the pruned walk's chunk lists
 
 #ifndef MCE_ABLATE
@@ -41,7 +46,6 @@
 
 namespace mce {
 
-// v_min3_f32 without the NaN-canonicalising v_max the compiler adds around fminf()
 // Barrier that publishes a chunk staged by LDS-DMA (global_load_lds).  The landing of a DMA is ordered for OTHER waves only
 // by the issuing wave's vmcnt wait FOLLOWED by the workgroup barrier -- and __syncthreads() by itself waits for LDS
 // traffic (lgkmcnt) only: the compiler emits vmcnt(0) before a barrier just when other code around it happens to need it.
@@ -54,24 +58,13 @@ __device__ __forceinline__ void dma_barrier()
     __syncthreads();
 }
 
-__device__ __forceinline__ float min3f(float a, float b, float c)
-{
-    float r;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 // Workgroup geometry: 8 waves (2 per SIMD) x 2 query tiles.  Measured and dropped (the builds are gone from this file, the
 // numbers are in DESIGN.md / profiles/): 4 waves x 4 tiles, one wave per SIMD (83 vs 56 ms at C3, round 1); 16 waves, four per
 // SIMD (spills); 12 waves, three per SIMD, at one k-step and K <= 4 (42.7 vs 41.3 ms at C4, round 5).  What did pay at one
 // k-step and K <= 4 is 8 waves x FOUR tiles: the kernel's QTT parameter.
-constexpr int kHWaves = 8;      // waves per workgroup (two per SIMD)
+// (kHWaves = 8 waves per workgroup, kHThreads: f16_filter.hpp)
 constexpr int kHQT = 2;         // 32-query tiles per wave (the wide exhaustive sweep: four -- template parameter QTT of the kernel)
 constexpr int kHNL = kHQT / 2;                     // top-K lists per owner lane (64 queries per list set)
-constexpr int kHThreads = kHWaves * 64;
 #ifndef MCE_H_QUEUE
 #define MCE_H_QUEUE 448
 #endif
@@ -121,13 +114,8 @@ __host__ __device__ constexpr int f16_prune_trigger(int KCAP) { return KCAP <= 8
 #endif
 constexpr int kHQueue = MCE_H_QUEUE;          // candidate queue entries per wave (16 B each in LDS)
 constexpr int kHDrainTrigger = MCE_H_TRIGGER;    // a wave with this many queued candidates asks the workgroup to drain
-constexpr int kHRelBits = 26;   // queue entry = query-local (6|7 bits) << kHRelBits | row - first row of the split
-constexpr int kHSymRowBits = kHRelBits - 1;            // symmetric sweep: the row field's top bit says "this lane passed the ROW gate"
 constexpr double kHTargetRadius = 200.0;
 constexpr int kPruneDims = 15;                // pruned walk: largest d (KST = 1)
-
-// device-side scalars shared by the f16 kernels (doubles; maxima kept as bit patterns)
-enum { HP_RMAX = 0, HP_SCALE = 1, HP_EY = 2, HP_YHATMAX = 3, HP_RHO = 4, HP_STAT_CHUNKS = 5, HP_STAT_TILES = 6, HP_COUNT = 16 };   // STAT_*: pruned walk, totals over the launch
 
 // |y^|^2 rides in the k dimension as 1..3 fp16 pieces (x' carries matching ones): three pieces (33 bits) when
 // they fit the padding of the last 16-wide k-step, fewer when that saves a whole k-step -- d = 14, 15, 30, 31,
@@ -190,19 +178,8 @@ __host__ __device__ constexpr size_t f16_lds_bytes(int KST, int KCAP, bool sym =
 // Everything published is a valid upper bound at all times and only ever shrinks, so stale reads merely let more
 // candidates through.  Lists carry the caller's row numbers and ties break on them: results are bit-identical to
 // the exhaustive sweep's.
+// (R_j, c_i and the slots: f16_row_gate, f16_gate_terms and sym_slot_insert of f16_filter.hpp)
 // ---------------------------------------------------------------------------
-// R_j from the bound thr on row j's K-th squared distance and its conversion error ex (same error terms as the
-// column gate, see gate_of); inflated by what the gate's fp32 addition R + c can lose
-__device__ __forceinline__ float sym_row_gate(double thr, double ex, const double* __restrict__ params, int KST)
-{
-    if (!(thr < __builtin_huge_val())) return __builtin_huge_valf();
-    const double s2 = params[HP_SCALE] * params[HP_SCALE];
-    const double ga = (ex + params[HP_EY]) * (1.0 + 1e-9) + 2.0 * sqrt(16.0 * KST) * 0x1p-14;
-    const double rr = sqrt(thr * s2) * (1.0 + 1e-12) + ga;
-    const double g = rr * rr * (1.0 + 1e-12);
-    const double ym = params[HP_YHATMAX];
-    return __double2float_ru(g * (1.0 + 0x1p-22) + 0x1p-22 * (ym * ym + 1.0) + 1e-30);
-}
 
 __host__ __device__ constexpr int f16_prune_slice_bytes(int KST, int KCAP) { return f16_prune_batch(KCAP) * KST * 1024 + 256; }   // kBatch tiles + pending ids
 #ifndef MCE_H_PRUNE_BOOT
@@ -401,12 +378,7 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const int64_t q = qwave0 + qt * 32 + (lane & 31);
-            if (q < nq) {
-                const double xn = qinfo[2 * q + 1];
-                const double r = sqrt(xn) + params[HP_YHATMAX];
-                const double eps = (32.0 * KST) * 0x1p-24 * r * r * (1.0 + 0x1p-9) + params[HP_RHO] + 1e-30;
-                cR[qt] = __double2float_ru(eps - xn);
-            }
+            if (q < nq) cR[qt] = f16_round_up(f16_gate_terms(0.0, qinfo[2 * q + 1], params[HP_EY], params[HP_YHATMAX], params[HP_RHO], KST).c);
         }
     }
     const int k_last = ksel - 1;
@@ -415,38 +387,18 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
     // and keeping them in registers would cost 6 VGPRs per query tile in the sweep.
     auto gate_of = [&](double thr, int qt) __attribute__((always_inline)) -> float {
         const int64_t q = qwave0 + qt * 32 + (lane & 31);
-        if (!(q < nq) || MCE_ABLATE == 1) return -__builtin_huge_valf();
+        if (!(q < nq) || MCE_ABLATE == 1) return -__builtin_huge_valf();      // padding queries never pass
         if (!(thr < INF)) return __builtin_huge_valf();
-        const double ex = qinfo[2 * q], xn = qinfo[2 * q + 1];
-        const double r = sqrt(xn) + params[HP_YHATMAX];
-        // + 2*sqrt(16 KST)*2^-14: even if the matrix unit flushed fp16 subnormal inputs (it does not
-        // on gfx950) the bound would hold
-        const double ga = (ex + params[HP_EY]) * (1.0 + 1e-9) + 2.0 * sqrt(16.0 * KST) * 0x1p-14;
-        const double eps = (32.0 * KST) * 0x1p-24 * r * r * (1.0 + 0x1p-9) + params[HP_RHO] + 1e-30;
-        const double rr = sqrt(thr * s2) * (1.0 + 1e-12) + ga;
-        const double g = rr * rr * (1.0 + 1e-12) - xn + eps;
-        return __double2float_ru(g);
+        const F16GateTerms t = f16_gate_terms(qinfo[2 * q], qinfo[2 * q + 1], params[HP_EY], params[HP_YHATMAX], params[HP_RHO], KST);
+        return f16_gate_finite(thr, s2, t.a, t.c);
     };
 
     // ---- staging (global_load_lds DMA, linear image) -----------------------------
-    auto stage_async = [&](int64_t c, int buf) {
-        const char* src = reinterpret_cast<const char*>(Yh) + c * (int64_t)CHUNK_BYTES;
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int e = tid + i * kHThreads;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)(src + (size_t)e * 16),
-                (__attribute__((address_space(3))) void*)(stage0 + buf * CHUNK_BYTES + (size_t)(wave * 64 + i * kHThreads) * 16),
-                16, 0, 0);
-        }
-    };
+    auto stage_async = [&](int64_t c, int buf) { f16_stage_chunk<VPT>(reinterpret_cast<const char*>(Yh) + c * (int64_t)CHUNK_BYTES, stage0 + buf * CHUNK_BYTES, tid, wave); };
 
     // A fragments of one 32-row tile: KST 16-byte LDS reads per lane.  They are fetched one
     // tile AHEAD of the MFMAs that consume them, so the LDS latency is never exposed.
-    auto load_a = [&](const char* lp, v8h (&a)[KST]) {
-#pragma unroll
-        for (int ks = 0; ks < KST; ++ks) a[ks] = *reinterpret_cast<const v8h*>(lp + ks * 1024);
-    };
+    auto load_a = [&](const char* lp, v8h (&a)[KST]) { f16_load_a<KST>(lp, a); };
     // one 32-row tile: QT chains of KST MFMAs
     auto mfma_tile = [&](const v8h (&a)[KST], v16f (&acc)[QT]) {
 #pragma unroll
@@ -555,50 +507,7 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
             // on j's K-th distance, published for everybody -- and into the bucket of j's block.  Then the entry's
             // packed word is replaced by the caller's row number of j, which is what the lists carry.
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            // one candidate distance d2 for sorted row `row`: replace the largest of the row's K slots if d2 is
-            // smaller (compare-and-swap; lock-free, any number of writers) and publish the new K-th as the row's
-            // bound.  Returns false if K slots hold strictly smaller distances (the candidate cannot be among the K).
-            auto slot_insert = [&](int row, double d2) __attribute__((always_inline)) -> bool {
-                unsigned long long* const sl = sym.slots + (int64_t)row * KCAP;
-                for (;;) {
-                    double vmax = -1.0, v2 = -1.0;
-                    int imax = 0;
-#pragma unroll
-                    for (int k = 0; k < KCAP; ++k) {
-                        if (k < ksel) {
-                            const double v = __longlong_as_double((long long)__hip_atomic_load(sl + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                            if (v > vmax) { v2 = vmax; vmax = v; imax = k; }
-                            else if (v > v2) v2 = v;
-                        }
-                    }
-                    if (d2 > vmax) return false;
-                    if (d2 == vmax) return true;                     // a tie: the merge decides by row number
-                    unsigned long long expect = (unsigned long long)__double_as_longlong(vmax);
-                    if (__hip_atomic_compare_exchange_strong(sl + imax, &expect, (unsigned long long)__double_as_longlong(d2), __ATOMIC_RELAXED,
-                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        const double nk = fmax(v2, d2);              // the K-th smallest after the replacement, from a snapshot: an upper bound
-                        if (nk < INF) {
-                            const unsigned long long nb = (unsigned long long)__double_as_longlong(nk);
-                            const unsigned long long ob = __hip_atomic_fetch_min(sym.thr + row, nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if (nb < ob) {
-                                const unsigned rb = __float_as_uint(sym_row_gate(nk, qinfo[2 * (int64_t)row], params, KST));
-                                const unsigned orb = __hip_atomic_fetch_min(sym.rrow + row, rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                if (rb < orb) {
-                                    // the tile's largest R_j, from a snapshot (each value >= its current one): safe to store
-                                    const unsigned* const rt = sym.rrow + (int64_t)(row >> 5) * 32;
-                                    unsigned m = 0;
-                                    for (int k = 0; k < 32; ++k) {
-                                        const unsigned v = __hip_atomic_load(rt + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                        m = v > m ? v : m;
-                                    }
-                                    __hip_atomic_store(sym.rtile + (row >> 5), __uint_as_float(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                }
-                            }
-                        }
-                        return true;
-                    }
-                }
-            };
+            auto row_gate = [&](double thr, int row) { return f16_row_gate_of(thr, qinfo[2 * (int64_t)row], params, KST); };
             for (int e0 = 0; e0 < qcount; e0 += 64) {
                 const int e = e0 + lane;
                 const bool valid = e < qcount;
@@ -612,7 +521,7 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
                 const int jb = j / QPB;
                 bool rs = ok && SYM == 2 && jb != qblk && rowflag;
                 if (rs) rs = d2 <= __longlong_as_double((long long)__hip_atomic_load(sym.thr + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                if (rs) rs = slot_insert(j, d2);
+                if (rs) rs = sym_slot_insert<KCAP>(sym.slots, sym.thr, sym.rrow, sym.rtile, ksel, j, d2, row_gate);
                 if (rs) {
                     const int slot = atomicAdd(sym.bucket_cnt + jb, 1);
                     if ((unsigned)slot < (unsigned)sym.cap) {      // (unsigned: a count that is not a count ends in the repair pass, not in a wild store)
@@ -643,17 +552,7 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
                 const double d2 = on ? wqd[ce] : INF;
                 const int j = (PRUNE || SYM >= 2) ? wq[ce] : jsplit0 + (int)((unsigned)wq[ce] & ((1u << RELB) - 1u));
                 cur = on ? wnx[ce] : -1;
-                // ascending list, ties by row; d2 = +inf (idle lane) changes nothing
-                bool c_hi = (d2 < own_d[nl][LC - 1]) || (d2 == own_d[nl][LC - 1] && j < own_i[nl][LC - 1] && d2 < INF);
-#pragma unroll
-                for (int k = LC - 1; k >= 1; --k) {
-                    const bool c_lo = (d2 < own_d[nl][k - 1]) || (d2 == own_d[nl][k - 1] && j < own_i[nl][k - 1] && d2 < INF);
-                    own_d[nl][k] = c_lo ? own_d[nl][k - 1] : (c_hi ? d2 : own_d[nl][k]);
-                    own_i[nl][k] = c_lo ? own_i[nl][k - 1] : (c_hi ? j : own_i[nl][k]);
-                    c_hi = c_lo;
-                }
-                own_d[nl][0] = c_hi ? d2 : own_d[nl][0];
-                own_i[nl][0] = c_hi ? j : own_i[nl][0];
+                list_insert<LC>(&own_d[nl][0], &own_i[nl][0], d2, j);
             }
         }
         qcount = 0;
@@ -681,7 +580,7 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
                 } else {
                     t = __longlong_as_double((long long)__hip_atomic_load(sym.thr + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                 }
-                const unsigned rb = __float_as_uint(sym_row_gate(t, qinfo[2 * q], params, KST));
+                const unsigned rb = __float_as_uint(f16_row_gate_of(t, qinfo[2 * q], params, KST));
                 const unsigned orb = __hip_atomic_fetch_min(sym.rrow + q, rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 R = __uint_as_float(rb < orb ? rb : orb);
             }
@@ -727,15 +626,8 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
         float mm[QT];                          // the lane's smallest accumulator (SYM: read again in the event path)
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-            const v16f& c = acc[qt];
-            float m0 = min3f(c[0], c[1], c[2]);
-            float m1 = min3f(c[3], c[4], c[5]);
-            float m2 = min3f(c[6], c[7], c[8]);
-            float m3 = min3f(c[9], c[10], c[11]);
-            float m4 = min3f(c[12], c[13], c[14]);
-            m0 = min3f(m0, m1, m2);
-            m3 = min3f(m3, m4, c[15]);
-            mm[qt] = min3f(m0, m3, m3);
+            float l1[5];
+            mm[qt] = f16_min16(acc[qt], l1);
             if constexpr (SYM == 2) passq[qt] = mm[qt] <= fmaxf(G[qt], Rt + cR[qt]);      // either side
             else passq[qt] = mm[qt] <= G[qt];
             pass |= passq[qt];
@@ -828,15 +720,8 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
         bool pass = false;
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-            const v16f& c = acc[qt];
-            float m0 = min3f(c[0], c[1], c[2]);
-            float m1 = min3f(c[3], c[4], c[5]);
-            float m2 = min3f(c[6], c[7], c[8]);
-            float m3 = min3f(c[9], c[10], c[11]);
-            float m4 = min3f(c[12], c[13], c[14]);
-            m0 = min3f(m0, m1, m2);
-            m3 = min3f(m3, m4, c[15]);
-            passq[qt] = min3f(m0, m3, m3) <= G[qt];
+            float l1[5];
+            passq[qt] = f16_min16(acc[qt], l1) <= G[qt];
             pass |= passq[qt];
         }
         if (!__any(pass)) return;
@@ -1057,15 +942,8 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
                     MCE_SEED_WAIT(ACC);                                                                    \
                     _Pragma("unroll") for (int qt = 0; qt < QT; ++qt)                                      \
                     {                                                                                      \
-                        const v16f& c_ = ACC[qt];                                                          \
-                        float m0 = min3f(c_[0], c_[1], c_[2]);                                             \
-                        float m1 = min3f(c_[3], c_[4], c_[5]);                                             \
-                        float m2 = min3f(c_[6], c_[7], c_[8]);                                             \
-                        float m3 = min3f(c_[9], c_[10], c_[11]);                                           \
-                        float m4 = min3f(c_[12], c_[13], c_[14]);                                          \
-                        m0 = min3f(m0, m1, m2);                                                            \
-                        m3 = min3f(m3, m4, c_[15]);                                                        \
-                        gm[qt] = min3f(gm[qt], m0, m3);                                                    \
+                        float l1_[5];                                                                      \
+                        gm[qt] = f16_min16(ACC[qt], l1_, gm[qt]);                                          \
                     }                                                                                      \
                     if (++tcnt == tg) MCE_SEED_GROUP_END();                                                \
                 } while (0)
@@ -1117,13 +995,9 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
                     const float a_up = (lane >> 5) ? u1 : u0;
                     const int64_t q = qwave0 + nl * 64 + lane;
                     if (q < nq && a_up < FINF) {
-                        const double ex = qinfo[2 * q], xn = qinfo[2 * q + 1];
-                        const double r = sqrt(xn) + params[HP_YHATMAX];
-                        const double ga = (ex + params[HP_EY]) * (1.0 + 1e-9) + 2.0 * sqrt(16.0 * KST) * 0x1p-14;
-                        const double eps = (32.0 * KST) * 0x1p-24 * r * r * (1.0 + 0x1p-9) + params[HP_RHO] + 1e-30;
-                        const double h2 = fmax((double)a_up + xn + eps, 0.0);
-                        const double dd = sqrt(h2) * (1.0 + 1e-12) + ga;
-                        seed_thr[nl] = dd * dd * (1.0 + 1e-12) / s2 * (1.0 + 1e-12);
+                        const double xn = qinfo[2 * q + 1];
+                        const F16GateTerms t = f16_gate_terms(qinfo[2 * q], xn, params[HP_EY], params[HP_YHATMAX], params[HP_RHO], KST);
+                        seed_thr[nl] = f16_seed_bound((double)a_up, xn, t.eps, t.a, s2);
                     }
                 }
 #pragma unroll
@@ -1138,7 +1012,7 @@ __global__ __launch_bounds__(PRUNE ? 64 : kHThreads, PRUNE ? (LC <= MCE_H_PRUNE_
             float R = 0.0f;
             if (q < nq) {
                 sym.thr[q] = (unsigned long long)__double_as_longlong(seed_thr[0]);
-                R = sym_row_gate(seed_thr[0], qinfo[2 * q], params, KST);
+                R = f16_row_gate_of(seed_thr[0], qinfo[2 * q], params, KST);
                 sym.rrow[q] = __float_as_uint(R);
                 const int sstride = sym.slot_stride ? sym.slot_stride : KCAP;
                 for (int k = 0; k < sstride; ++k) sym.slots[q * sstride + k] = 0x7FF0000000000000ull;

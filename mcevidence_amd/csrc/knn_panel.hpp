@@ -5,7 +5,8 @@
 // of blocks symmetrically, everybody else's column side only), with the work cut into UNITS (panel of reference rows x
 // query block) that hand a block's register lists on.  (geom.sym_on = 0 -- every tile column side only, i.e. the exhaustive
 // sweep of cross evidence in units -- works and was measured: no faster than knn_f16_kernel's seeded sweep, so the library
-// does not take it)
+// does not take it)  The bound and the pieces shared with the other filter kernels -- gate, 16-accumulator
+// minimum, list insertion, the row side's slots, the candidate-tile event, chunk staging -- are f16_filter.hpp's.
 //
 // Why a second kernel.  knn_f16_kernel<.., SYM = 2> carries the pruned walk, the two-pass search and the seed phase in one
 // body: 256 VGPRs, 104 SGPRs with scalars spilled to VGPR lanes INSIDE the tile loop, six inlined copies of the drain, and a
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
     // Per-query constants of the gates, computed once and kept in registers (the drains re-read them from L2 before:
     // a round trip per refresh): for the lane's two gated queries gq_a = e_x + max e_y (+ slack) and gq_c = eps - |x^|^2
     // (-inf: padding query), for the query the lane OWNS own_a = the same sum; and the launch's scale^2 and the row gate's
-    // additive term.  See knn_f16.hpp (gate_of, sym_row_gate) for the bound.
+    // additive term.  See f16_filter.hpp for the bound.
     double gq_a[QT], gq_c[QT], own_a = 0.0, s2c, rowc;
     {
         const ArgsPtr a = MCE_ARGS();
@@ -279,39 +280,27 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         const auto qinfo = gptr(a->qinfo);
         const double p_scale = params[HP_SCALE], p_ey = params[HP_EY], p_ym = params[HP_YHATMAX], p_rho = params[HP_RHO];
         s2c = p_scale * p_scale;
-        rowc = 0x1p-22 * (p_ym * p_ym + 1.0) + 1e-30;
-        const double slack = 2.0 * sqrt(16.0 * KST) * 0x1p-14;
+        rowc = f16_row_const(p_ym);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const int64_t q = qwave0 + qt * 32 + (lane & 31);
             gq_a[qt] = 0.0;
             gq_c[qt] = -INF;
             if (q < a->nq && MCE_PANEL_ABL != 1) {
-                const double ex = qinfo[2 * q], xn = qinfo[2 * q + 1];
-                const double r = sqrt(xn) + p_ym;
-                const double eps = (32.0 * KST) * 0x1p-24 * r * r * (1.0 + 0x1p-9) + p_rho + 1e-30;
-                gq_a[qt] = (ex + p_ey) * (1.0 + 1e-9) + slack;
-                gq_c[qt] = eps - xn;
+                const F16GateTerms t = f16_gate_terms(qinfo[2 * q], qinfo[2 * q + 1], p_ey, p_ym, p_rho, KST);
+                gq_a[qt] = t.a;
+                gq_c[qt] = t.c;
             }
         }
         {
             const int64_t q = qwave0 + lane;
-            if (q < a->nq) own_a = (qinfo[2 * q] + p_ey) * (1.0 + 1e-9) + slack;
+            if (q < a->nq) own_a = f16_gate_a(qinfo[2 * q], p_ey, KST);
         }
     }
     // gate of query (qt, lane & 31) from a bound `thr` on its K-th squared distance (input units)
-    auto gate_of = [&](double thr, int qt) __attribute__((always_inline)) -> float {
-        if (!(gq_c[qt] > -INF)) return -__builtin_huge_valf();
-        if (!(thr < INF)) return __builtin_huge_valf();
-        const double rr = sqrt(thr * s2c) * (1.0 + 1e-12) + gq_a[qt];
-        return __double2float_ru(rr * rr * (1.0 + 1e-12) + gq_c[qt]);
-    };
-    // row-side gate constant R of the OWNED query from the bound on its K-th squared distance (sym_row_gate, knn_f16.hpp)
-    auto own_row_gate = [&](double thr) __attribute__((always_inline)) -> float {
-        if (!(thr < INF)) return __builtin_huge_valf();
-        const double rr = sqrt(thr * s2c) * (1.0 + 1e-12) + own_a;
-        return __double2float_ru(rr * rr * (1.0 + 1e-12) * (1.0 + 0x1p-22) + rowc);
-    };
+    auto gate_of = [&](double thr, int qt) __attribute__((always_inline)) -> float { return f16_gate(thr, s2c, gq_a[qt], gq_c[qt]); };
+    // row-side gate constant R of the OWNED query from the bound on its K-th squared distance
+    auto own_row_gate = [&](double thr) __attribute__((always_inline)) -> float { return f16_row_gate(thr, s2c, own_a, rowc); };
     {
         const ArgsPtr a = MCE_ARGS();
         const int64_t q = qwave0 + lane;
@@ -329,7 +318,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         for (int qt = 0; qt < QT; ++qt) G[qt] = gate_of(__shfl(t0, qt * 32 + (lane & 31), 64), qt);
         if (sym_on) {
 #pragma unroll
-            for (int qt = 0; qt < QT; ++qt) cR[qt] = gq_c[qt] > -INF ? __double2float_ru(gq_c[qt]) : -__builtin_huge_valf();
+            for (int qt = 0; qt < QT; ++qt) cR[qt] = gq_c[qt] > -INF ? f16_round_up(gq_c[qt]) : -__builtin_huge_valf();
         }
     }
 
@@ -441,47 +430,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
             const auto sp_bucket = gptr_w(a->sym.bucket);
             const int sp_cap = a->sym.cap;
             const int ksel = a->ksel;
-            auto slot_insert = [&](int row, double d2) __attribute__((always_inline)) -> bool {
-                const auto sl = sp_slots + (int64_t)row * KCAP;
-                for (;;) {
-                    double vmax = -1.0, v2 = -1.0;
-                    int imax = 0;
-#pragma unroll
-                    for (int k = 0; k < KCAP; ++k) {
-                        if (k < ksel) {
-                            const double v = __longlong_as_double((long long)__hip_atomic_load(sl + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                            if (v > vmax) { v2 = vmax; vmax = v; imax = k; }
-                            else if (v > v2) v2 = v;
-                        }
-                    }
-                    if (d2 > vmax) return false;
-                    if (d2 == vmax) return true;                     // a tie: the merge decides by row number
-                    unsigned long long expect = (unsigned long long)__double_as_longlong(vmax);
-                    if (__hip_atomic_compare_exchange_strong(sl + imax, &expect, (unsigned long long)__double_as_longlong(d2), __ATOMIC_RELAXED,
-                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        const double nk = fmax(v2, d2);              // the K-th smallest after the replacement, from a snapshot: an upper bound
-                        if (nk < INF) {
-                            const unsigned long long nb = (unsigned long long)__double_as_longlong(nk);
-                            const unsigned long long ob = __hip_atomic_fetch_min(sp_thr + row, nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if (nb < ob) {
-                                const unsigned rb = __float_as_uint(sym_row_gate(nk, gptr(a->qinfo)[2 * (int64_t)row], a->params, KST));
-                                const unsigned orb = __hip_atomic_fetch_min(sp_rrow + row, rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                if (rb < orb) {
-                                    // the tile's largest R_j, from a snapshot (each value >= its current one): safe to store
-                                    const auto rt = sp_rrow + (int64_t)(row >> 5) * 32;
-                                    unsigned m = 0;
-                                    for (int k = 0; k < 32; ++k) {
-                                        const unsigned v = __hip_atomic_load(rt + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                        m = v > m ? v : m;
-                                    }
-                                    __hip_atomic_store(sp_rtile + (row >> 5), __uint_as_float(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                }
-                            }
-                        }
-                        return true;
-                    }
-                }
-            };
+            auto row_gate = [&](double thr, int row) { return f16_row_gate_of(thr, gptr(a->qinfo)[2 * (int64_t)row], a->params, KST); };
             for (int e0 = 0; e0 < qcount; e0 += 64) {
                 const int e = e0 + lane;
                 const bool valid = e < qcount;
@@ -505,7 +454,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
                             rs = d2 > ld || (d2 == ld && sc > li);
                         }
                     }
-                    if (rs) rs = slot_insert(j, d2);
+                    if (rs) rs = sym_slot_insert<KCAP>(sp_slots, sp_thr, sp_rrow, sp_rtile, ksel, j, d2, row_gate);
                     if (rs) {
                         const int slot = __hip_atomic_fetch_add(sp_bucket_cnt + jb, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if ((unsigned)slot < (unsigned)sp_cap) {      // (unsigned: a count that is not a count ends in the repair pass, not in a wild store)
@@ -536,17 +485,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
                 const double d2 = on ? wqd[ce] : INF;
                 const int j = wq[ce];
                 cur = on ? wnx[ce] : -1;
-                // ascending list, ties by row; d2 = +inf (idle lane) changes nothing
-                bool c_hi = (d2 < own_d[KCAP - 1]) || (d2 == own_d[KCAP - 1] && j < own_i[KCAP - 1] && d2 < INF);
-#pragma unroll
-                for (int k = KCAP - 1; k >= 1; --k) {
-                    const bool c_lo = (d2 < own_d[k - 1]) || (d2 == own_d[k - 1] && j < own_i[k - 1] && d2 < INF);
-                    own_d[k] = c_lo ? own_d[k - 1] : (c_hi ? d2 : own_d[k]);
-                    own_i[k] = c_lo ? own_i[k - 1] : (c_hi ? j : own_i[k]);
-                    c_hi = c_lo;
-                }
-                own_d[0] = c_hi ? d2 : own_d[0];
-                own_i[0] = c_hi ? j : own_i[0];
+                list_insert<KCAP>(own_d, own_i, d2, j);
             }
         }
         qcount = 0;
@@ -595,66 +534,19 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
     };
 
     // ---- a tile with a candidate ------------------------------------------------------------------------------------
-    // c: the 16 accumulators of query tile qt (C layout of 32x32 f32: lane l -> query column l & 31, rows
-    // (r & 3) + 8 (r >> 2) + 4 (l >> 5)); gq: the lane's gate; rowflag: the lane passed the ROW gate; jb0: first reference
-    // row of the tile; todo: the accumulators still to be looked at (a redo passes what is left).  Wave-wide compares, scalar
-    // branches over the empty ones; the lanes under the gate append (query, row) to the wave's queue.  Returns the accumulators
-    // NOT handled because the queue was full.  (Static s_setprio for either half of the workgroup -- MI355X_MICROARCH.md, two
+    // (f16_event, f16_filter.hpp: the lanes under the gate append (query, row) to the wave's queue; it returns the accumulators NOT
+    // handled because the queue was full.  Static s_setprio for either half of the workgroup -- MI355X_MICROARCH.md, two
     // waves per SIMD, item 4 -- was measured in round 5: 36.9-37.1 ms either way against 36.7-37.3, nothing.  DYNAMIC priority, round 6 --
     // raised while a wave sweeps and dropped inside its candidate tiles and drains, or the other way round: +1.0 % / +0.15 %,
     // profiles/r06_mid/panel_dynamic_priority_ab.txt.)
     auto event = [&](const v16f& c, const float (&l1)[5], const int qt, const float gq, const bool rowflag, const int jb0, const unsigned todo, const int qlimit) __attribute__((always_inline)) -> unsigned {
-        (void)l1;
-        const unsigned wbase = (lanew[qt] + (unsigned)jb0) | (rowflag ? (1u << kHSymRowBits) : 0u);
-        unsigned rem = 0;
-        float g = gq;
-#define MCE_HIT(R_, P_, S_)                                                                                               \
-        if ((S_) != 0 && (todo & (1u << (R_)))) {                                                                         \
-            if (qcount > qlimit) rem |= 1u << (R_);                                                                       \
-            else {                                                                                                        \
-                if (P_) wq[__builtin_amdgcn_mbcnt_hi((unsigned)((S_) >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)(S_), (unsigned)qcount))] = \
-                            (int)(wbase + (unsigned)(((R_) & 3) + 8 * ((R_) >> 2)));                                      \
-                qcount += __builtin_popcountll(S_);                                                                       \
-            }                                                                                                             \
-        }
-        // the gate's own first-level minima say which triples of accumulators hold something: 6 wave-wide compares, then 3
-        // for each triple that does (usually one) -- 9 instead of 16
-        {
-            const bool q0 = l1[0] <= g, q1 = l1[1] <= g, q2 = l1[2] <= g, q3 = l1[3] <= g, q4 = l1[4] <= g, p15 = c[15] <= g;
-            const unsigned long long u0 = __ballot(q0), u1 = __ballot(q1), u2 = __ballot(q2), u3 = __ballot(q3), u4 = __ballot(q4), s15 = __ballot(p15);
-#define MCE_TRIPLE(I_, U_)                                                                                                \
-            if ((U_) != 0) {                                                                                              \
-                const bool p0 = c[3 * (I_) + 0] <= g, p1 = c[3 * (I_) + 1] <= g, p2 = c[3 * (I_) + 2] <= g;             \
-                const unsigned long long s0 = __ballot(p0), s1 = __ballot(p1), s2 = __ballot(p2);                        \
-                MCE_HIT(3 * (I_) + 0, p0, s0)                                                                             \
-                MCE_HIT(3 * (I_) + 1, p1, s1)                                                                             \
-                MCE_HIT(3 * (I_) + 2, p2, s2)                                                                             \
-            }
-            MCE_TRIPLE(0, u0) MCE_TRIPLE(1, u1) MCE_TRIPLE(2, u2) MCE_TRIPLE(3, u3) MCE_TRIPLE(4, u4)
-#undef MCE_TRIPLE
-            MCE_HIT(15, p15, s15)
-        }
-#undef MCE_HIT
-        return rem;
+        return f16_event<true>(c, l1, lanew[qt], gq, rowflag, jb0, todo, qlimit, wq, qcount);
     };
 
     // ---- staging (global_load_lds DMA, linear image) + A fragments + MFMA -----------------------------------------
     const auto Yh_bytes = (const __attribute__((address_space(1))) char*)MCE_ARGS()->Yh;
-    auto stage_async = [&](int64_t c, int buf) {
-        const auto src = Yh_bytes + c * (int64_t)CHUNK_BYTES;
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int e = tid + i * kHThreads;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)(src + (size_t)e * 16),
-                (__attribute__((address_space(3))) void*)(stage0 + buf * CHUNK_BYTES + (size_t)(wave * 64 + i * kHThreads) * 16),
-                16, 0, 0);
-        }
-    };
-    auto load_a = [&](const char* lp, v8h (&a)[KST]) {
-#pragma unroll
-        for (int ks = 0; ks < KST; ++ks) a[ks] = *reinterpret_cast<const v8h*>(lp + ks * 1024);
-    };
+    auto stage_async = [&](int64_t c, int buf) { f16_stage_chunk<VPT>(Yh_bytes + c * (int64_t)CHUNK_BYTES, stage0 + buf * CHUNK_BYTES, tid, wave); };
+    auto load_a = [&](const char* lp, v8h (&a)[KST]) { f16_load_a<KST>(lp, a); };
     // one 32-row tile = QT chains of KST MFMAs, issued k-step by k-step (the dependent ones one apart)
     auto mfma_first = [&](const v8h (&a)[KST], v16f (&acc)[QT]) __attribute__((always_inline)) {
 #pragma unroll
@@ -679,18 +571,6 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
 #else
 #define MCE_ORDER(GATED_, NEXT_) do {} while (0)
 #endif
-    // min of the lane's 16 accumulators (8 v_min3_f32); l1: the five first-level minima -- of the accumulators 3i .. 3i + 2 --
-    // which the event path looks at first
-    auto min16 = [&](const v16f& c, float (&l1)[5]) __attribute__((always_inline)) -> float {
-        l1[0] = min3f(c[0], c[1], c[2]);
-        l1[1] = min3f(c[3], c[4], c[5]);
-        l1[2] = min3f(c[6], c[7], c[8]);
-        l1[3] = min3f(c[9], c[10], c[11]);
-        l1[4] = min3f(c[12], c[13], c[14]);
-        const float m0 = min3f(l1[0], l1[1], l1[2]);
-        const float m3 = min3f(l1[3], l1[4], c[15]);
-        return min3f(m0, m3, m3);
-    };
     // gate of one finished tile (both query tiles): ONE branch per tile, so that the tile's MFMAs and the gate's VALU work
     // share a basic block and interleave; tix: the tile's index in its chunk (for a redo); gq / rg: the lane's gates for
     // the PAIR of tiles this one belongs to (either side / row side)
@@ -705,7 +585,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         bool pq[QT];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-            mm[qt] = min16(acc[qt], l1[qt]);
+            mm[qt] = f16_min16(acc[qt], l1[qt]);
             pq[qt] = mm[qt] <= gq[qt];
         }
         if (__any(pq[0] || pq[1])) {
@@ -845,7 +725,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
                 asm volatile("s_nop 15\n\ts_nop 3" : "+v"(r_));
 #endif
                 float l1[5];
-                const float mm = min16(r_, l1);
+                const float mm = f16_min16(r_, l1);
                 const float rg = Rt + (qt ? cR[1] : cR[0]);
                 const float gq = vmaxf(qt ? G[1] : G[0], rg);
                 unsigned rem = 0;

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "sym_types.hpp"
+#include "f16_filter.hpp"   // list_insert
 
 namespace mce {
 
@@ -261,7 +262,6 @@ __global__ __launch_bounds__(kSymMergeThreads) void sym_merge_kernel(double* __r
     int n = bucket_cnt[b];
     if (n <= 0) return;
     if (n > cap) n = cap;
-    const double INF = __builtin_huge_val();
     const int64_t q = (int64_t)b * kSymMergeThreads + t;
     double own_d[KCAP];
     int own_i[KCAP];
@@ -283,18 +283,7 @@ __global__ __launch_bounds__(kSymMergeThreads) void sym_merge_kernel(double* __r
         }
         __syncthreads();
         for (int cur = head[t]; cur >= 0; cur = e_nx[cur]) {
-            const double d2 = e_d[cur];
-            const int j = e_i[cur];
-            bool c_hi = (d2 < own_d[KCAP - 1]) || (d2 == own_d[KCAP - 1] && j < own_i[KCAP - 1] && d2 < INF);
-#pragma unroll
-            for (int k = KCAP - 1; k >= 1; --k) {
-                const bool c_lo = (d2 < own_d[k - 1]) || (d2 == own_d[k - 1] && j < own_i[k - 1] && d2 < INF);
-                own_d[k] = c_lo ? own_d[k - 1] : (c_hi ? d2 : own_d[k]);
-                own_i[k] = c_lo ? own_i[k - 1] : (c_hi ? j : own_i[k]);
-                c_hi = c_lo;
-            }
-            own_d[0] = c_hi ? d2 : own_d[0];
-            own_i[0] = c_hi ? j : own_i[0];
+            list_insert<KCAP>(own_d, own_i, e_d[cur], e_i[cur]);
         }
         __syncthreads();
     }

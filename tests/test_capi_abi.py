@@ -131,6 +131,19 @@ def test_symmetric_sweep_unit_enumeration(tmp_path):
     assert out.startswith("ok ")
 
 
+def test_f16_gate_bound_on_the_cpu(tmp_path):
+    """the fp16 filter's bound as the kernels call it (mcevidence_amd/csrc/f16_filter.hpp): never below its long-double
+    value, monotone in the threshold, closed for padding queries, open without a bound, consistent with the seed bound and
+    the row-side gate -- inequalities only, checked on the CPU over seeded draws, with UBSan"""
+    import subprocess
+    exe = str(tmp_path / "f16_gate_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(REPO, "mcevidence_amd", "csrc"),
+                           os.path.join(REPO, "tests", "native", "f16_gate_check.cpp"), "-o", exe])
+    out = subprocess.check_output([exe]).decode()
+    assert out.startswith("ok ")
+
+
 def test_workspace_query_with_the_same_set_hint():
     """mce_knn_workspace_bytes_opt: a caller who knows that queries and references are two buffers (cross evidence with
     equal halves) says so and is not charged the symmetric sweep's scratch (~1.7 GB at 1M rows, K = 9); sizes only, no

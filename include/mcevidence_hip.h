@@ -334,6 +334,20 @@ int mce_verify_knn_f64(const double* X, int64_t nq, const double* Y, int64_t nr,
                        int64_t self_offset, const double* dist, int32_t ld, int32_t nsample, uint64_t seed, int32_t* failed,
                        int32_t device);
 
+/* Chain text -> fp64 on the device: what mce_chain_open / _read of libmcechains.so (include/mcechains.h) return for the same bytes,
+ * bit for bit (replaces np.loadtxt at reference MCEvidence.py:564).  Fields separated by ' ', \t, \v, \f; '#' starts a comment that
+ * runs to the end of the line; \n and \r both end a line; blank and comment-only lines are skipped; every data line must hold the
+ * fields of the first one.  open uploads `text` (host memory, e.g. a mapping of the file; it must stay valid until close) and finds
+ * rows and columns; read converts every field on the device -- one correctly rounded IEEE operation for up to 15 digits, the
+ * Eisel-Lemire scheme for up to 19 -- and patches what the device cannot decide (inf, nan, longer tails, subnormals, junk) with the
+ * host's strtod.  A ragged file (open) or a field that is not a number (read) -> MCE_ERR_INVALID; no visible device ->
+ * MCE_ERR_NO_DEVICE; a failed device allocation -> MCE_ERR_HIP.  A handle belongs to one thread; several may be open on one device.
+ *   out: host, [nrows * ncols] row-major.  stats (may be NULL, nstats >= 6): {tokens, tokens patched on the host, ms upload,
+ *   ms structure, ms parse, ms download} */
+int mce_chain_dev_open(const char* text, int64_t nbytes, int32_t device, void** handle, int64_t* nrows, int64_t* ncols);
+int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats);
+void mce_chain_dev_close(void* handle);
+
 /* Spatial pruning of the fp16-filter search for low-dimensional, large reference sets (d <= 13):
  * both point sets are put in k-d order on the device (cells of 32 rows) and every wave of 64 queries
  * visits the reference chunks nearest-box-first, multiplies only the 32-row tiles whose box is within

@@ -94,6 +94,9 @@ SIGNATURES = {
                                           _c.c_uint64, _P, _P, _c.c_size_t, _P]),
     "mce_verify_knn_f64": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64, _P, _c.c_int32, _c.c_int32,
                                       _c.c_uint64, _P, _c.c_int32]),
+    "mce_chain_dev_open": (_c.c_int, [_P, _c.c_int64, _c.c_int32, _c.POINTER(_P), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    "mce_chain_dev_read": (_c.c_int, [_P, _P, _P, _c.c_int32]),
+    "mce_chain_dev_close": (None, [_P]),
     "mce_knn_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32]),
     "mce_dotp_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int32]),
     "mce_knn_f64_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
@@ -286,6 +289,23 @@ def _f64_fs(a, name="fs"):
     if np.isnan(a).any() or (a == np.inf).any():
         raise ValueError("%s contains NaN or +infinity" % name)
     return a
+
+
+def chain_dev_parse(text_ptr, nbytes, device=0):
+    """Chain text at host address ``text_ptr`` (``nbytes`` bytes, valid for the duration of the call) -> (fp64 array
+    [rows, columns], stats) through mce_chain_dev_open / _read / _close.  stats: dict(tokens, patched, ms_upload, ms_structure,
+    ms_parse, ms_download).  ValueError: ragged lines or a field that is not a number; RuntimeError: no device, HIP failure."""
+    lib = load()
+    handle = _P()
+    nrows, ncols = _c.c_int64(), _c.c_int64()
+    check(lib.mce_chain_dev_open(text_ptr, int(nbytes), int(device), _c.byref(handle), _c.byref(nrows), _c.byref(ncols)))
+    try:
+        out = np.empty((nrows.value, ncols.value), dtype=np.float64)
+        st = (_c.c_double * 6)()
+        check(lib.mce_chain_dev_read(handle, out.ctypes.data, _c.cast(st, _P), 6))
+    finally:
+        lib.mce_chain_dev_close(handle)
+    return out, dict(tokens=int(st[0]), patched=int(st[1]), ms_upload=st[2], ms_structure=st[3], ms_parse=st[4], ms_download=st[5])
 
 
 # ---------------------------------------------------------------------------

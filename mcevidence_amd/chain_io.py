@@ -5,6 +5,10 @@ mmap-based reader for chain text files.
 MontePython chains (whitespace-separated numbers, ``#`` comments): same array, bit for bit
 (every field is the correctly rounded fp64 value, like Python's ``float()``), ~100x faster.
 Host-only native code; no GPU involved.
+
+``loadtxt_device(path)`` is the same array parsed on the GPU (``mce_chain_dev_*`` of ``libmcevidence_hip.so``; opt-in,
+``MCE_CHAIN_READER=hip``): the file's bytes are uploaded, split into fields and converted there, and only what the device cannot
+decide (inf, nan, more than 19 digits, subnormals) is patched by the host's strtod.
 """
 from __future__ import annotations
 
@@ -73,6 +77,10 @@ def loadtxt(path, ndmin=2, nthreads=0):
             _raise(rc, lib)
     finally:
         lib.mce_chain_close(handle)
+    return _shape_like_numpy(out, ndmin)
+
+
+def _shape_like_numpy(out, ndmin):
     if out.shape[0] == 0:                       # np.loadtxt: empty input -> shape (0,), (0, 1) with ndmin=2
         out = np.empty((0, 1) if ndmin == 2 else (0,))
     elif ndmin < 2:
@@ -80,6 +88,33 @@ def loadtxt(path, ndmin=2, nthreads=0):
         if ndmin == 1 and out.ndim == 0:
             out = out.reshape(1)
     return out
+
+
+def loadtxt_device(path, ndmin=2, device=0, return_stats=False):
+    """``loadtxt(path, ndmin)`` computed on GPU ``device``: same array, bit for bit.  Always the device -- ``RuntimeError`` without
+    one, never a quiet host read.  A ragged line or a field that is not a number raises what ``loadtxt`` raises for the file,
+    with its message (row, column and line numbers): the host reader is run on the failing file to word it.  An unreadable path
+    raises ``OSError``.  ``return_stats``: also dict(tokens, patched, ms_upload, ms_structure, ms_parse, ms_download)."""
+    import mmap
+    from . import _capi
+    with open(path, "rb") as f:
+        size = os.fstat(f.fileno()).st_size
+        _capi.require_device()
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size > 0 else None
+        try:
+            view = np.frombuffer(mm, dtype=np.uint8) if mm is not None else None
+            try:
+                out, stats = _capi.chain_dev_parse(view.ctypes.data if view is not None else None, size, device)
+            except ValueError as dev_err:
+                loadtxt(path, ndmin)            # raises ValueError with the row, column and line of the first bad field
+                raise RuntimeError("mcevidence_amd: the device chain reader refused %s (%s) but the host reader accepts it" % (path, dev_err))
+            finally:
+                del view
+        finally:
+            if mm is not None:
+                mm.close()
+    out = _shape_like_numpy(out, ndmin)
+    return (out, stats) if return_stats else out
 
 
 def parse_token(text):

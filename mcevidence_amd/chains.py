@@ -49,8 +49,13 @@ def rank0_draw(draw):
 def read_chain_file(path):
     """One chain text file -> fp64 array [rows, columns]: what ``np.loadtxt(f)`` gives the reference
     (:564), read by the native multi-threaded reader (``chain_io`` / ``libmcechains.so``).
-    ``MCE_CHAIN_READER=numpy`` selects NumPy's reader instead."""
-    if os.environ.get("MCE_CHAIN_READER", "native") == "numpy" or not _native_reader():
+    ``MCE_CHAIN_READER=numpy`` selects NumPy's reader instead, ``MCE_CHAIN_READER=hip`` the device reader
+    (``chain_io.loadtxt_device``: same array, parsed on the GPU; RuntimeError without one)."""
+    mode = os.environ.get("MCE_CHAIN_READER", "native")
+    if mode == "hip":
+        from . import chain_io
+        return chain_io.loadtxt_device(path)
+    if mode == "numpy" or not _native_reader():
         return np.loadtxt(path, ndmin=2)
     from . import chain_io
     return chain_io.loadtxt(path)
@@ -78,7 +83,8 @@ def read_chain_files(paths):
     """The chain files of one root, in order.  Small files (a Planck chain is ~3 MB: one reader thread
     each) are parsed concurrently -- the native reader runs outside the GIL."""
     paths = list(paths)
-    if len(paths) < 2 or os.environ.get("MCE_CHAIN_READER", "native") == "numpy" or not _native_reader():
+    mode = os.environ.get("MCE_CHAIN_READER", "native")
+    if len(paths) < 2 or mode == "numpy" or (mode != "hip" and not _native_reader()):
         return [read_chain_file(f) for f in paths]
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=min(len(paths), 8)) as pool:

@@ -1,0 +1,225 @@
+// capi_chain.hpp -- part of capi.hip (one translation unit): mce_chain_dev_open / _read / _close, chain text -> fp64 on the device
+// (chain_kernels.hpp has the passes).  open uploads the bytes and runs the structure pass (rows, columns, ragged lines); read runs
+// the parse pass, downloads the values and patches the tokens the device left undecided with the host's strtod, reading their
+// text from the CALLER'S buffer -- which therefore must stay valid until close.  Each handle has its own stream and its own
+// scratch (the text, padded to whole tiles; 8 bytes per token of offsets; 8 bytes per token of line numbers during open, of
+// values during read; 26 bytes per 4 KB tile), freed in close.  A handle belongs to one thread.
+#pragma once
+
+#include <chrono>
+
+#include "chain_kernels.hpp"
+#include "chain_parse.hpp"
+
+namespace {
+
+struct ChainDev {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    const char* host_text = nullptr;
+    int64_t nbytes = 0, ntiles = 0, ntok = 0, nrows = 0, ncols = 0;
+    unsigned char* text = nullptr;
+    unsigned char *tile_kind = nullptr, *tile_in = nullptr;
+    unsigned *tile_ntok = nullptr, *tile_nterm = nullptr;
+    unsigned long long *tok_base = nullptr, *term_base = nullptr;
+    int64_t *tok_off = nullptr, *tok_line = nullptr;
+    uint64_t* pow5 = nullptr;
+    mce::ChainTotals* tot = nullptr;
+    double ms_upload = 0.0, ms_structure = 0.0;
+    ~ChainDev()
+    {
+        int cur = 0;
+        (void)hipGetDevice(&cur);
+        if (cur != device) (void)hipSetDevice(device);
+        for (void* p : {(void*)text, (void*)tile_kind, (void*)tile_in, (void*)tile_ntok, (void*)tile_nterm, (void*)tok_base, (void*)term_base, (void*)tok_off,
+                        (void*)tok_line, (void*)pow5, (void*)tot})
+            if (p) (void)hipFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (cur != device) (void)hipSetDevice(cur);
+    }
+};
+
+template <class T>
+int chain_alloc(T*& p, size_t count, const char* what)
+{
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) {
+        p = nullptr;
+        (void)hipGetLastError();
+        return fail(MCE_ERR_HIP, "chain reader: cannot allocate %zu bytes of device memory for %s: %s", count * sizeof(T), what, hipGetErrorString(e));
+    }
+    return MCE_OK;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+unsigned chain_grid(int64_t items, int per_block)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)kAssumedCUs * 64));
+}
+
+int chain_dev_structure(ChainDev& c)
+{
+    using namespace mce;
+    const auto t_up = std::chrono::steady_clock::now();
+    c.ntiles = (c.nbytes + kChainTileBytes - 1) / kChainTileBytes;
+    const size_t padded = (size_t)c.ntiles * (size_t)kChainTileBytes;
+    int rc;
+    if ((rc = chain_alloc(c.text, padded, "the text")) != MCE_OK) return rc;
+    if ((rc = chain_alloc(c.tot, 1, "the totals")) != MCE_OK) return rc;
+    if ((rc = chain_alloc(c.pow5, (size_t)mce_parse::kPow5Words, "the powers of five")) != MCE_OK) return rc;
+    MCE_HIP(hipMemcpyAsync(c.text, c.host_text, (size_t)c.nbytes, hipMemcpyHostToDevice, c.stream));
+    if (padded > (size_t)c.nbytes) MCE_HIP(hipMemsetAsync(c.text + c.nbytes, '\n', padded - (size_t)c.nbytes, c.stream));
+    MCE_HIP(hipMemsetAsync(c.tot, 0, sizeof(ChainTotals), c.stream));
+    MCE_HIP(hipMemcpyAsync(c.pow5, mce_parse::pow5_table(), (size_t)mce_parse::kPow5Words * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+    MCE_HIP(hipStreamSynchronize(c.stream));
+    c.ms_upload = ms_since(t_up);
+
+    const auto t_st = std::chrono::steady_clock::now();
+    const size_t nt = (size_t)c.ntiles;
+    if ((rc = chain_alloc(c.tile_kind, nt, "the tile states")) != MCE_OK) return rc;
+    if ((rc = chain_alloc(c.tile_in, nt, "the tile states")) != MCE_OK) return rc;
+    if ((rc = chain_alloc(c.tile_ntok, nt, "the tile counts")) != MCE_OK) return rc;
+    if ((rc = chain_alloc(c.tile_nterm, nt, "the tile counts")) != MCE_OK) return rc;
+    if ((rc = chain_alloc(c.tok_base, nt, "the tile offsets")) != MCE_OK) return rc;
+    if ((rc = chain_alloc(c.term_base, nt, "the tile offsets")) != MCE_OK) return rc;
+    const unsigned grid = chain_grid(c.ntiles, 1);
+    hipLaunchKernelGGL(chain_tile_kernel<0>, dim3(grid), dim3(kChainThreads), 0, c.stream, c.text, c.ntiles, c.tile_kind, c.tile_in, c.tile_ntok, c.tile_nterm,
+                       c.tok_base, c.term_base, (int64_t*)nullptr, (int64_t*)nullptr);
+    hipLaunchKernelGGL(chain_scan_state_kernel, dim3(1), dim3(kChainScanThreads), 0, c.stream, c.tile_kind, c.ntiles, c.tile_in);
+    hipLaunchKernelGGL(chain_tile_kernel<1>, dim3(grid), dim3(kChainThreads), 0, c.stream, c.text, c.ntiles, c.tile_kind, c.tile_in, c.tile_ntok, c.tile_nterm,
+                       c.tok_base, c.term_base, (int64_t*)nullptr, (int64_t*)nullptr);
+    hipLaunchKernelGGL(chain_scan_count_kernel, dim3(1), dim3(kChainScanThreads), 0, c.stream, c.tile_ntok, c.tile_nterm, c.ntiles, c.tok_base, c.term_base, c.tot);
+    MCE_HIP(hipGetLastError());
+    ChainTotals tot;
+    MCE_HIP(hipMemcpyAsync(&tot, c.tot, sizeof(tot), hipMemcpyDeviceToHost, c.stream));
+    MCE_HIP(hipStreamSynchronize(c.stream));
+    c.ntok = (int64_t)tot.ntok;
+    if (c.ntok > 0) {
+        if ((rc = chain_alloc(c.tok_off, (size_t)c.ntok, "the token offsets")) != MCE_OK) return rc;
+        if ((rc = chain_alloc(c.tok_line, (size_t)c.ntok, "the token lines")) != MCE_OK) return rc;
+        hipLaunchKernelGGL(chain_tile_kernel<2>, dim3(grid), dim3(kChainThreads), 0, c.stream, c.text, c.ntiles, c.tile_kind, c.tile_in, c.tile_ntok, c.tile_nterm,
+                           c.tok_base, c.term_base, c.tok_off, c.tok_line);
+        hipLaunchKernelGGL(chain_ncols_kernel, dim3(1), dim3(64), 0, c.stream, c.tok_line, c.tot);
+        hipLaunchKernelGGL(chain_rows_kernel, dim3(chain_grid(c.ntok, kChainThreads)), dim3(kChainThreads), 0, c.stream, c.tok_line, c.tot);
+        MCE_HIP(hipGetLastError());
+        MCE_HIP(hipMemcpyAsync(&tot, c.tot, sizeof(tot), hipMemcpyDeviceToHost, c.stream));
+        MCE_HIP(hipStreamSynchronize(c.stream));
+        MCE_HIP(hipFree(c.tok_line));          // (only the structure check reads the line numbers)
+        c.tok_line = nullptr;
+        c.ncols = (int64_t)tot.ncols;
+        if (tot.ragged || c.ncols < 1 || c.ntok % c.ncols != 0)
+            return fail(MCE_ERR_INVALID, "chain reader: the number of columns changed: not every data line holds the %lld fields of the first one", (long long)c.ncols);
+        c.nrows = c.ntok / c.ncols;
+    }
+    c.ms_structure = ms_since(t_st);
+    return MCE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mce_chain_dev_open(const char* text, int64_t nbytes, int32_t device, void** handle, int64_t* nrows, int64_t* ncols)
+{
+    if (!handle || !nrows || !ncols || nbytes < 0 || (!text && nbytes > 0)) return fail(MCE_ERR_INVALID, "chain reader: null pointer or negative size");
+    *handle = nullptr;
+    *nrows = *ncols = 0;
+    int rc = select_device(device);
+    if (rc != MCE_OK) return rc;
+    ChainDev* c = new ChainDev();
+    c->device = device;
+    c->host_text = text;
+    c->nbytes = nbytes;
+    if (nbytes > 0) {
+        const hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            c->stream = nullptr;
+            delete c;
+            return fail(MCE_ERR_HIP, "chain reader: hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
+        }
+        rc = chain_dev_structure(*c);
+        if (rc != MCE_OK) {
+            delete c;
+            return rc;
+        }
+    }
+    *nrows = c->nrows;
+    *ncols = c->ncols;
+    *handle = c;
+    return MCE_OK;
+}
+
+int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats)
+{
+    using namespace mce;
+    if (!handle) return fail(MCE_ERR_INVALID, "chain reader: null handle");
+    ChainDev& c = *static_cast<ChainDev*>(handle);
+    if (stats && nstats < 6) return fail(MCE_ERR_INVALID, "chain reader: stats[6] expected");
+    double ms_parse = 0.0, ms_down = 0.0;
+    int64_t npatched = 0;
+    if (c.ntok > 0) {
+        if (!out) return fail(MCE_ERR_INVALID, "chain reader: null output buffer");
+        int rc = select_device(c.device);
+        if (rc != MCE_OK) return rc;
+        const auto t_p = std::chrono::steady_clock::now();
+        struct Scratch {
+            double* vals = nullptr;
+            ChainPatch* list = nullptr;
+            ~Scratch() { if (vals) (void)hipFree(vals); if (list) (void)hipFree(list); }
+        } s;
+        if ((rc = chain_alloc(s.vals, (size_t)c.ntok, "the values")) != MCE_OK) return rc;
+        // the undecided tokens: room for one token in 32 at first; a file that needs more (nan columns, 25-digit fields) gets a list of the
+        // counted size and a second pass
+        int64_t cap = std::max<int64_t>(4096, c.ntok / 32);
+        int64_t nlist = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            if ((rc = chain_alloc(s.list, (size_t)cap, "the list of undecided tokens")) != MCE_OK) return rc;
+            MCE_HIP(hipMemsetAsync(&c.tot->nlist, 0, sizeof(unsigned long long), c.stream));
+            hipLaunchKernelGGL(chain_parse_kernel, dim3(chain_grid(c.ntok, kChainThreads)), dim3(kChainThreads), 0, c.stream, reinterpret_cast<const char*>(c.text),
+                               c.nbytes, c.tok_off, c.ntok, c.pow5, s.vals, s.list, cap, c.tot);
+            MCE_HIP(hipGetLastError());
+            ChainTotals tot;
+            MCE_HIP(hipMemcpyAsync(&tot, c.tot, sizeof(tot), hipMemcpyDeviceToHost, c.stream));
+            MCE_HIP(hipStreamSynchronize(c.stream));
+            nlist = (int64_t)tot.nlist;
+            if (nlist <= cap) break;
+            if (pass == 1) return fail(MCE_ERR_HIP, "chain reader: the list of undecided tokens changed between two passes (%lld > %lld)", (long long)nlist, (long long)cap);
+            MCE_HIP(hipFree(s.list));
+            s.list = nullptr;
+            cap = nlist;
+        }
+        ms_parse = ms_since(t_p);
+        const auto t_d = std::chrono::steady_clock::now();
+        std::vector<ChainPatch> patch((size_t)nlist);
+        MCE_HIP(hipMemcpyAsync(out, s.vals, (size_t)c.ntok * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        if (nlist > 0) MCE_HIP(hipMemcpyAsync(patch.data(), s.list, (size_t)nlist * sizeof(ChainPatch), hipMemcpyDeviceToHost, c.stream));
+        MCE_HIP(hipStreamSynchronize(c.stream));
+        ms_down = ms_since(t_d);
+        // host fix-up: strtod on the caller's own bytes
+        const ChainPatch* bad = nullptr;
+        for (const ChainPatch& p : patch) {
+            if (p.token < 0 || p.token >= c.ntok || p.offset < 0 || p.length < 0 || p.offset + p.length > c.nbytes)
+                return fail(MCE_ERR_HIP, "chain reader: a listed token lies outside the text (token %lld, offset %lld, length %lld)", (long long)p.token,
+                            (long long)p.offset, (long long)p.length);
+            if (!mce_parse::parse_slow(c.host_text + p.offset, c.host_text + p.offset + p.length, out + p.token) && (!bad || p.token < bad->token)) bad = &p;
+        }
+        npatched = nlist;
+        if (bad)
+            return fail(MCE_ERR_INVALID, "could not convert string '%.*s' to float64 at row %lld, column %lld", (int)std::min<int64_t>(bad->length, 60),
+                        c.host_text + bad->offset, (long long)(bad->token / c.ncols), (long long)(bad->token % c.ncols + 1));
+    }
+    if (stats) {
+        stats[0] = (double)c.ntok;
+        stats[1] = (double)npatched;
+        stats[2] = c.ms_upload;
+        stats[3] = c.ms_structure;
+        stats[4] = ms_parse;
+        stats[5] = ms_down;
+    }
+    return MCE_OK;
+}
+
+void mce_chain_dev_close(void* handle) { delete static_cast<ChainDev*>(handle); }
+
+}  // extern "C"

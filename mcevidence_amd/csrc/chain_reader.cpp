@@ -6,6 +6,7 @@
 // falls back to strtod (correctly rounded in glibc) otherwise, so the values are bit-identical to
 // Python's float() -- which is what np.loadtxt applies.  Host-only C++17; no GPU involved.
 #include "../../include/mcechains.h"
+#include "chain_parse.hpp"
 
 #include <fcntl.h>
 #include <locale.h>
@@ -36,102 +37,8 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
-const double kP10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
-                         1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-
-inline bool is_space(char c) { return c == ' ' || c == '\t' || c == '\v' || c == '\f'; }
-inline bool is_digit(char c) { return c >= '0' && c <= '9'; }
-
-locale_t c_locale()
-{
-    static locale_t loc = newlocale(LC_ALL_MASK, "C", (locale_t)0);
-    return loc;
-}
-
-// strtod on a copy of the token; accepts what Python's float() accepts for decimal text
-bool parse_slow(const char* p, const char* e, double* out)
-{
-    const size_t n = (size_t)(e - p);
-    if (n == 0 || n > 4096) return false;
-    for (const char* q = p; q < e; ++q) {
-        const char c = *q;
-        const bool ok = is_digit(c) || c == '+' || c == '-' || c == '.' || c == 'e' || c == 'E' ||
-                        ((c | 0x20) >= 'a' && (c | 0x20) <= 'z' && (c | 0x20) != 'x' && (c | 0x20) != 'p');
-        if (!ok) return false;
-    }
-    char buf[4100];
-    std::memcpy(buf, p, n);
-    buf[n] = '\0';
-    char* endp = nullptr;
-    errno = 0;
-    const double v = strtod_l(buf, &endp, c_locale());
-    if (endp != buf + n) return false;
-    *out = v;
-    return true;
-}
-
-// one numeric token [p, e) -> correctly rounded double
-bool parse_token(const char* p, const char* e, double* out)
-{
-    const char* const tok = p;
-    bool neg = false;
-    if (p < e && (*p == '+' || *p == '-')) {
-        neg = (*p == '-');
-        ++p;
-    }
-    uint64_t mant = 0;
-    int shift = 0;           // decimal exponent adjustment from the digits themselves
-    bool any = false, inexact = false;
-    constexpr uint64_t kMantMax = (UINT64_MAX - 9) / 10;
-    while (p < e && is_digit(*p)) {
-        any = true;
-        if (mant <= kMantMax) mant = mant * 10 + (uint64_t)(*p - '0');
-        else { ++shift; inexact |= (*p != '0'); }
-        ++p;
-    }
-    if (p < e && *p == '.') {
-        ++p;
-        while (p < e && is_digit(*p)) {
-            any = true;
-            if (mant <= kMantMax) { mant = mant * 10 + (uint64_t)(*p - '0'); --shift; }
-            else inexact |= (*p != '0');
-            ++p;
-        }
-    }
-    if (!any) return parse_slow(tok, e, out);          // inf / nan / junk
-    int e10 = 0;
-    if (p < e && (*p == 'e' || *p == 'E')) {
-        ++p;
-        bool eneg = false;
-        if (p < e && (*p == '+' || *p == '-')) { eneg = (*p == '-'); ++p; }
-        if (p == e || !is_digit(*p)) return false;
-        while (p < e && is_digit(*p)) {
-            if (e10 < 100000) e10 = e10 * 10 + (*p - '0');
-            ++p;
-        }
-        if (eneg) e10 = -e10;
-    }
-    if (p != e) return false;
-    e10 += shift;
-    if (!inexact && mant <= ((uint64_t)1 << 53)) {
-        if (mant == 0) { *out = neg ? -0.0 : 0.0; return true; }
-        double d = (double)mant;
-        if (e10 >= -22 && e10 <= 22) {
-            d = e10 < 0 ? d / kP10[-e10] : d * kP10[e10];
-            *out = neg ? -d : d;
-            return true;
-        }
-        if (e10 > 22 && e10 <= 22 + 15) {               // mant * 10^(e10-22) still exact below 2^53
-            d *= kP10[e10 - 22];
-            if (d <= 9007199254740992.0) {
-                d *= kP10[22];
-                *out = neg ? -d : d;
-                return true;
-            }
-        }
-    }
-    return parse_slow(tok, e, out);
-}
+using mce_parse::is_space;
+using mce_parse::parse_token;          // chain_parse.hpp: Clinger's exact fast path, then strtod
 
 struct Range {
     size_t b0 = 0, b1 = 0;       // bytes: lines starting in [b0, b1)

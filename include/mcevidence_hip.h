@@ -347,6 +347,51 @@ int mce_verify_knn_f64(const double* X, int64_t nq, const double* Y, int64_t nr,
 int mce_chain_dev_open(const char* text, int64_t nbytes, int32_t device, void** handle, int64_t* nrows, int64_t* ncols);
 int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats);
 void mce_chain_dev_close(void* handle);
+/* mce_chain_dev_read with the values left ON THE DEVICE: d_out is a device buffer of nrows * ncols doubles on the handle's device.
+ * The tokens the device leaves undecided are converted by the host's strtod from the caller's text, as in mce_chain_dev_read, and
+ * written to d_out in one small copy (stats[5], "ms download", is that copy); a field that is not a number fails with the same
+ * message.  The handle's stream is synchronised on return. */
+int mce_chain_dev_read_dev(void* handle, double* d_out, double* stats, int32_t nstats);
+
+/* Burn-in, concatenation, thinning, the s1 / s2 split, the column split and the fs / SumW reductions of chains that are on the device
+ * already (replaces the host passes of reference MCEvidence.py:350-391 removeBurn, :447-532 thinning, :221-249 the split, :394-405 the
+ * column split and :1062-1064 fs).  A chain is a list of parts -- device buffers [nrows, ncols] of doubles, one per file, the
+ * burn-in already skipped by the caller (pointer + start * ncols; the start is mce_prep::burn_start of csrc/chain_prep.hpp) -- whose
+ * rows are numbered consecutively ("burned, concatenated numbering").  All buffers and workspaces are the caller's, on the current
+ * device; everything runs on `stream`.  Argument errors: MCE_ERR_INVALID (no device needed); no visible device: MCE_ERR_NO_DEVICE.
+ *   weights       gathers the weight column and its int64 prefix sums into the workspace; totals[5] = {rows, sum of trunc(w), max of
+ *                 trunc(w), sum of w - trunc(w), weights that are negative / not finite / beyond 2^53}; *rule = 0 no thinning
+ *                 (thinlen 0 or 1), 1 integer-weight rule, 2 bin rule, < 0 the route must decline: -1 a refused weight, -2 the
+ *                 fractional sum lies within 1e-6 of the host's threshold 1e-4, -3 thinlen < 0 or 0 < thinlen < 1.
+ *   select_count  (same workspace) *n_out = rows the rule keeps; d_edges[nedges]: np.linspace(-1, n, nbins + 1) computed on the host
+ *                 (bin rule only; NULL otherwise).
+ *   select_fill   (same workspace) d_src[n_out]: the kept rows in the burned, concatenated numbering -- the host's `keep`, rows may
+ *                 repeat --, d_new_w[n_out]: their new weights.
+ *   gather        output row r is row (d_src ? d_src[k] : k), k = d_rows ? d_rows[r] : r (d_rows: an index list into the n_thin
+ *                 thinned rows, e.g. one side of a split).  Any of: d_params [n_out, ncols - itheta], d_w [n_out] (d_new_w[k] if
+ *                 given, else column iw), d_like [n_out] (column ilike), d_full [n_out, ncols] (the thinned rows, weight replaced).
+ *                 Synchronises the stream.
+ *   reduce        d_fs[n] = logL - max(logL), logL = pos_lnp ? d_like : -d_like; out[4] (host) = {max(logL) over the rows that are
+ *                 not NaN, SumW = sum of d_w, NaN likelihoods, weights that are not finite}.  Sums in a fixed order: two runs give
+ *                 the same bits.  Synchronises the stream. */
+typedef struct mce_chain_part {
+    const double* rows;
+    int64_t nrows;
+} mce_chain_part;
+size_t mce_chain_select_workspace_bytes(int64_t n, int32_t nparts);
+size_t mce_chain_gather_workspace_bytes(int32_t nparts);
+size_t mce_chain_reduce_workspace_bytes(int64_t n);
+int mce_chain_weights_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncols, int32_t iw, double thinlen, int32_t* rule,
+                          double* totals, void* ws, size_t ws_bytes, void* stream);
+int mce_chain_select_count_dev(int64_t n, int32_t nparts, int32_t rule, double thinlen, const double* d_edges, int64_t nedges,
+                               int64_t* n_out, void* ws, size_t ws_bytes, void* stream);
+int mce_chain_select_fill_dev(int64_t n, int32_t nparts, int32_t rule, double thinlen, int64_t nedges, int64_t n_out, int64_t* d_src,
+                              double* d_new_w, void* ws, size_t ws_bytes, void* stream);
+int mce_chain_gather_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncols, int32_t iw, int32_t ilike, int32_t itheta,
+                         const int64_t* d_src, const double* d_new_w, int64_t n_thin, const int64_t* d_rows, int64_t n_out,
+                         double* d_params, double* d_w, double* d_like, double* d_full, void* ws, size_t ws_bytes, void* stream);
+int mce_chain_reduce_dev(const double* d_like, const double* d_w, int64_t n, int32_t pos_lnp, double* d_fs, double* out, void* ws,
+                         size_t ws_bytes, void* stream);
 
 /* Spatial pruning of the fp16-filter search for low-dimensional, large reference sets (d <= 13):
  * both point sets are put in k-d order on the device (cells of 32 rows) and every wave of 64 queries

@@ -97,6 +97,16 @@ SIGNATURES = {
     "mce_chain_dev_open": (_c.c_int, [_P, _c.c_int64, _c.c_int32, _c.POINTER(_P), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     "mce_chain_dev_read": (_c.c_int, [_P, _P, _P, _c.c_int32]),
     "mce_chain_dev_close": (None, [_P]),
+    "mce_chain_dev_read_dev": (_c.c_int, [_P, _P, _P, _c.c_int32]),
+    "mce_chain_select_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int32]),
+    "mce_chain_gather_workspace_bytes": (_c.c_size_t, [_c.c_int32]),
+    "mce_chain_reduce_workspace_bytes": (_c.c_size_t, [_c.c_int64]),
+    "mce_chain_weights_dev": (_c.c_int, [_P, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_double, _c.POINTER(_c.c_int32), _P, _P, _c.c_size_t, _P]),
+    "mce_chain_select_count_dev": (_c.c_int, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_double, _P, _c.c_int64, _c.POINTER(_c.c_int64), _P, _c.c_size_t, _P]),
+    "mce_chain_select_fill_dev": (_c.c_int, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_double, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
+    "mce_chain_gather_dev": (_c.c_int, [_P, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P,
+                                        _P, _c.c_size_t, _P]),
+    "mce_chain_reduce_dev": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P, _P, _P, _c.c_size_t, _P]),
     "mce_knn_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32]),
     "mce_dotp_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int32]),
     "mce_knn_f64_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
@@ -306,6 +316,88 @@ def chain_dev_parse(text_ptr, nbytes, device=0):
     finally:
         lib.mce_chain_dev_close(handle)
     return out, dict(tokens=int(st[0]), patched=int(st[1]), ms_upload=st[2], ms_structure=st[3], ms_parse=st[4], ms_download=st[5])
+
+
+class ChainPart(ctypes.Structure):
+    """``mce_chain_part``: one burned chain on the device -- address of its first kept row, rows kept."""
+    _fields_ = [("rows", _P), ("nrows", _c.c_int64)]
+
+
+def chain_parts(parts):
+    """[(device address, rows)] -> the C array the ``mce_chain_*_dev`` calls take"""
+    arr = (ChainPart * max(len(parts), 1))()
+    for i, (ptr, nrows) in enumerate(parts):
+        arr[i].rows = ptr or None
+        arr[i].nrows = int(nrows)
+    return arr
+
+
+def chain_dev_open(text_ptr, nbytes, device=0):
+    """mce_chain_dev_open -> (handle, rows, columns); close it with ``chain_dev_close`` (the text must stay valid until then)"""
+    handle = _P()
+    nrows, ncols = _c.c_int64(), _c.c_int64()
+    check(load().mce_chain_dev_open(text_ptr, int(nbytes), int(device), _c.byref(handle), _c.byref(nrows), _c.byref(ncols)))
+    return handle, int(nrows.value), int(ncols.value)
+
+
+def chain_dev_read_dev(handle, d_out):
+    """mce_chain_dev_read_dev: the parsed values into the DEVICE buffer at address ``d_out``; returns the reader's stats"""
+    st = (_c.c_double * 6)()
+    check(load().mce_chain_dev_read_dev(handle, d_out or None, _c.cast(st, _P), 6))
+    return dict(tokens=int(st[0]), patched=int(st[1]), ms_upload=st[2], ms_structure=st[3], ms_parse=st[4], ms_download=st[5])
+
+
+def chain_dev_close(handle):
+    load().mce_chain_dev_close(handle)
+
+
+def chain_select_workspace_bytes(n, nparts):
+    return int(load().mce_chain_select_workspace_bytes(int(n), int(nparts)))
+
+
+def chain_gather_workspace_bytes(nparts):
+    return int(load().mce_chain_gather_workspace_bytes(int(nparts)))
+
+
+def chain_reduce_workspace_bytes(n):
+    return int(load().mce_chain_reduce_workspace_bytes(int(n)))
+
+
+def chain_weights_dev(parts, ncols, iw, thinlen, ws, ws_bytes, stream=0):
+    """mce_chain_weights_dev -> (rule, dict(rows, sum_int, max_int, frac, bad)); ``parts``: [(device address, rows)]"""
+    rule = _c.c_int32(0)
+    tot = (_c.c_double * 5)()
+    arr = chain_parts(parts)
+    check(load().mce_chain_weights_dev(_c.cast(arr, _P), len(parts), int(ncols), int(iw), float(thinlen), _c.byref(rule), _c.cast(tot, _P),
+                                       ws or None, int(ws_bytes), stream or None))
+    return int(rule.value), dict(rows=int(tot[0]), sum_int=int(tot[1]), max_int=int(tot[2]), frac=float(tot[3]), bad=int(tot[4]))
+
+
+def chain_select_count_dev(n, nparts, rule, thinlen, d_edges, nedges, ws, ws_bytes, stream=0):
+    n_out = _c.c_int64(0)
+    check(load().mce_chain_select_count_dev(int(n), int(nparts), int(rule), float(thinlen), d_edges or None, int(nedges), _c.byref(n_out), ws or None,
+                                            int(ws_bytes), stream or None))
+    return int(n_out.value)
+
+
+def chain_select_fill_dev(n, nparts, rule, thinlen, nedges, n_out, d_src, d_new_w, ws, ws_bytes, stream=0):
+    check(load().mce_chain_select_fill_dev(int(n), int(nparts), int(rule), float(thinlen), int(nedges), int(n_out), d_src or None, d_new_w or None,
+                                           ws or None, int(ws_bytes), stream or None))
+
+
+def chain_gather_dev(parts, ncols, iw, ilike, itheta, d_src, d_new_w, n_thin, d_rows, n_out, d_params, d_w, d_like, d_full, ws, ws_bytes, stream=0):
+    arr = chain_parts(parts)
+    check(load().mce_chain_gather_dev(_c.cast(arr, _P), len(parts), int(ncols), int(iw), int(ilike), int(itheta), d_src or None,
+                                      d_new_w or None, int(n_thin), d_rows or None, int(n_out), d_params or None, d_w or None, d_like or None,
+                                      d_full or None, ws or None, int(ws_bytes), stream or None))
+
+
+def chain_reduce_dev(d_like, d_w, n, pos_lnp, d_fs, ws, ws_bytes, stream=0):
+    """mce_chain_reduce_dev -> (max(logL), SumW, NaN likelihoods, weights that are not finite)"""
+    out = (_c.c_double * 4)()
+    check(load().mce_chain_reduce_dev(d_like or None, d_w or None, int(n), 1 if pos_lnp else 0, d_fs or None, _c.cast(out, _P), ws or None, int(ws_bytes),
+                                      stream or None))
+    return float(out[0]), float(out[1]), int(out[2]), int(out[3])
 
 
 # ---------------------------------------------------------------------------

@@ -38,6 +38,8 @@ def build_parser(prog=None):
     p.add_argument("--allparams", action="store_true", help="use all parameters, not only the cosmological ones")
     p.add_argument("--cross", action="store_true",
                    help="split the chain(s) in two and estimate the cross evidence (otherwise auto evidence)")
+    p.add_argument("--resident", action="store_true",
+                   help="keep the chain on the GPU from the text files to ln E (mcevidence_amd.resident); falls back to the host route where it does not apply")
     return p
 
 
@@ -55,6 +57,13 @@ def main(argv=None):
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
     print()
     print("Using file: ", args.root_name)
+    if args.resident:
+        from .resident import evidence_from_files
+        out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
+                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen)
+        print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
+        print("")
+        return out
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
                      thinlen=args.thinlen)

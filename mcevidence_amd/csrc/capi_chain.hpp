@@ -4,12 +4,15 @@
 // text from the CALLER'S buffer -- which therefore must stay valid until close.  Each handle has its own stream and its own
 // scratch (the text, padded to whole tiles; 8 bytes per token of offsets; 8 bytes per token of line numbers during open, of
 // values during read; 26 bytes per 4 KB tile), freed in close.  A handle belongs to one thread.
+// mce_chain_dev_read_dev is read with the values left on the device: the parse pass writes into the caller's device buffer, and the
+// host's patches go there in one small copy and one scatter launch (prep_patch_kernel).
 #pragma once
 
 #include <chrono>
 
 #include "chain_kernels.hpp"
 #include "chain_parse.hpp"
+#include "chain_prep_kernels.hpp"
 
 namespace {
 
@@ -150,7 +153,12 @@ int mce_chain_dev_open(const char* text, int64_t nbytes, int32_t device, void** 
     return MCE_OK;
 }
 
-int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats)
+}  // extern "C"
+
+namespace {
+
+// out: host memory (out_device false: the values are downloaded and patched there) or device memory on the handle's device
+int chain_dev_read_impl(void* handle, double* out, bool out_device, double* stats, int32_t nstats)
 {
     using namespace mce;
     if (!handle) return fail(MCE_ERR_INVALID, "chain reader: null handle");
@@ -164,11 +172,12 @@ int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats)
         if (rc != MCE_OK) return rc;
         const auto t_p = std::chrono::steady_clock::now();
         struct Scratch {
-            double* vals = nullptr;
+            double *vals = nullptr, *fix = nullptr;
             ChainPatch* list = nullptr;
-            ~Scratch() { if (vals) (void)hipFree(vals); if (list) (void)hipFree(list); }
+            ~Scratch() { if (vals) (void)hipFree(vals); if (fix) (void)hipFree(fix); if (list) (void)hipFree(list); }
         } s;
-        if ((rc = chain_alloc(s.vals, (size_t)c.ntok, "the values")) != MCE_OK) return rc;
+        if (!out_device && (rc = chain_alloc(s.vals, (size_t)c.ntok, "the values")) != MCE_OK) return rc;
+        double* const d_vals = out_device ? out : s.vals;
         // the undecided tokens: room for one token in 32 at first; a file that needs more (nan columns, 25-digit fields) gets a list of the
         // counted size and a second pass
         int64_t cap = std::max<int64_t>(4096, c.ntok / 32);
@@ -177,7 +186,7 @@ int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats)
             if ((rc = chain_alloc(s.list, (size_t)cap, "the list of undecided tokens")) != MCE_OK) return rc;
             MCE_HIP(hipMemsetAsync(&c.tot->nlist, 0, sizeof(unsigned long long), c.stream));
             hipLaunchKernelGGL(chain_parse_kernel, dim3(chain_grid(c.ntok, kChainThreads)), dim3(kChainThreads), 0, c.stream, reinterpret_cast<const char*>(c.text),
-                               c.nbytes, c.tok_off, c.ntok, c.pow5, s.vals, s.list, cap, c.tot);
+                               c.nbytes, c.tok_off, c.ntok, c.pow5, d_vals, s.list, cap, c.tot);
             MCE_HIP(hipGetLastError());
             ChainTotals tot;
             MCE_HIP(hipMemcpyAsync(&tot, c.tot, sizeof(tot), hipMemcpyDeviceToHost, c.stream));
@@ -192,22 +201,32 @@ int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats)
         ms_parse = ms_since(t_p);
         const auto t_d = std::chrono::steady_clock::now();
         std::vector<ChainPatch> patch((size_t)nlist);
-        MCE_HIP(hipMemcpyAsync(out, s.vals, (size_t)c.ntok * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        if (!out_device) MCE_HIP(hipMemcpyAsync(out, s.vals, (size_t)c.ntok * sizeof(double), hipMemcpyDeviceToHost, c.stream));
         if (nlist > 0) MCE_HIP(hipMemcpyAsync(patch.data(), s.list, (size_t)nlist * sizeof(ChainPatch), hipMemcpyDeviceToHost, c.stream));
         MCE_HIP(hipStreamSynchronize(c.stream));
         ms_down = ms_since(t_d);
         // host fix-up: strtod on the caller's own bytes
         const ChainPatch* bad = nullptr;
+        std::vector<double> fixed(out_device ? (size_t)nlist : 0);
         for (const ChainPatch& p : patch) {
             if (p.token < 0 || p.token >= c.ntok || p.offset < 0 || p.length < 0 || p.offset + p.length > c.nbytes)
                 return fail(MCE_ERR_HIP, "chain reader: a listed token lies outside the text (token %lld, offset %lld, length %lld)", (long long)p.token,
                             (long long)p.offset, (long long)p.length);
-            if (!mce_parse::parse_slow(c.host_text + p.offset, c.host_text + p.offset + p.length, out + p.token) && (!bad || p.token < bad->token)) bad = &p;
+            double* const dst = out_device ? &fixed[(size_t)(&p - patch.data())] : out + p.token;
+            if (!mce_parse::parse_slow(c.host_text + p.offset, c.host_text + p.offset + p.length, dst) && (!bad || p.token < bad->token)) bad = &p;
         }
         npatched = nlist;
         if (bad)
             return fail(MCE_ERR_INVALID, "could not convert string '%.*s' to float64 at row %lld, column %lld", (int)std::min<int64_t>(bad->length, 60),
                         c.host_text + bad->offset, (long long)(bad->token / c.ncols), (long long)(bad->token % c.ncols + 1));
+        if (out_device && nlist > 0) {
+            if ((rc = chain_alloc(s.fix, (size_t)nlist, "the patched values")) != MCE_OK) return rc;
+            MCE_HIP(hipMemcpyAsync(s.fix, fixed.data(), (size_t)nlist * sizeof(double), hipMemcpyHostToDevice, c.stream));
+            hipLaunchKernelGGL(prep_patch_kernel, dim3(chain_grid(nlist, kPrepThreads)), dim3(kPrepThreads), 0, c.stream, s.list, s.fix, nlist, c.ntok, d_vals);
+            MCE_HIP(hipGetLastError());
+            MCE_HIP(hipStreamSynchronize(c.stream));
+            ms_down = ms_since(t_d);
+        }
     }
     if (stats) {
         stats[0] = (double)c.ntok;
@@ -219,6 +238,14 @@ int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats)
     }
     return MCE_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int mce_chain_dev_read(void* handle, double* out, double* stats, int32_t nstats) { return chain_dev_read_impl(handle, out, false, stats, nstats); }
+
+int mce_chain_dev_read_dev(void* handle, double* d_out, double* stats, int32_t nstats) { return chain_dev_read_impl(handle, d_out, true, stats, nstats); }
 
 void mce_chain_dev_close(void* handle) { delete static_cast<ChainDev*>(handle); }
 

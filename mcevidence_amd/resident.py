@@ -1,0 +1,446 @@
+"""The resident route: chain files -> ln E without the chain ever coming back to the host.
+
+``MCEvidence(root, ...)`` reads the files into host arrays, burns, concatenates, thins and splits them in NumPy
+(``chains.py``) and uploads the parameter rows again for the search.  Here the files are parsed on the device
+(``mce_chain_dev_read_dev``), and burn-in, concatenation, thinning, the optional s1/s2 split, the column split and the
+``fs`` / ``SumW`` reductions run there too (``mce_chain_*_dev``: csrc/chain_prep_kernels.hpp, rules in
+csrc/chain_prep.hpp); the result goes to ``mce_evidence_feed_part_dev_f64`` (part 0 of 1) in place.  Only scalars come
+back.  Opt-in: nothing else in the package takes this route by itself.
+
+``ResidentChains.from_files`` / ``.from_arrays`` build the resident chain, ``.evidence(...)`` returns what
+``MCEvidence(root, ...).evidence(...)`` returns.  ``evidence_from_files`` takes the keywords of both, runs this route
+where ``plan`` says it applies and ``MCEvidence(root, ...).evidence(...)`` unchanged where it does not
+(``info["route"]``, ``info["declined"]``).  docs/design/chain_resident.md has the passes and the decline table.
+"""
+from __future__ import annotations
+
+import glob
+import logging
+import math
+import os
+import time
+
+import numpy as np
+
+from . import chains as _chains
+
+logger = logging.getLogger("mcevidence_amd")
+
+__all__ = ["ResidentChains", "ResidentDecline", "evidence_from_files", "plan", "REASONS"]
+
+RESIDENT = "resident"
+
+#: why the route declines (``plan``, and the weight cases found on the device)
+REASONS = {
+    "poisson": "0 < thinlen < 1 draws Poisson weights from the host's RNG",
+    "negative_thinlen": "thinlen < 0: the host route raises",
+    "isfunc": "importance sampling (isfunc) alters the weights on the host",
+    "batches": "batched runs (brange / nbatch > 1) slice the chain on the host",
+    "verbose": "verbose > 1 logs per-neighbour volumes from the distances",
+    "covtype": "covtype other than 'all' / 'single' is the host route's business",
+    "split_single": "split with covtype='single' whitens s1 and s2 with different eigen-systems",
+    "ndim": "ndim > 127: beyond the device feeders",
+    "distributed": "a process group is initialised: multi-rank chains are not resident",
+    "columns": "the files' column counts differ",
+    "rows": "fewer than 2 rows left",
+    "not_files": "not a chain file root or a list of file names",
+    "ischain": "ischain=False: the host route raises",
+    "ambiguous_weights": "the weights' fractional parts sum to within 1e-6 of the integer-weight threshold 1e-4",
+    "bad_weights": "a weight is negative, not finite or beyond 2^53",
+}
+
+
+#: mce_chain_weights_dev's verdicts (csrc/chain_prep.hpp: kRule*, kDecline*)
+RULE_NAME = {0: "none", 1: "integer", 2: "bin"}
+DECLINE_REASON = {-1: "bad_weights", -2: "ambiguous_weights", -3: "negative_thinlen"}
+
+
+class ResidentDecline(Exception):
+    """The resident route does not apply; ``reason`` says why (one of ``REASONS``' values)."""
+
+    def __init__(self, reason):
+        super().__init__(reason)
+        self.reason = reason
+
+
+def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all", split=False, ndim=None, nparam=None,
+         distributed=False, ncols=None, nrows=None, ischain=True):
+    """``"resident"`` or the reason why the route declines.  A pure function of the call's keywords and of what is known
+    about the data at the time (``ncols``: the files' column counts, ``nrows``: rows left after burn-in / thinning,
+    ``nparam``: parameter columns; None: not known yet)."""
+    if not ischain:
+        return REASONS["ischain"]
+    if thinlen < 0:
+        return REASONS["negative_thinlen"]
+    if 0 < thinlen < 1:
+        return REASONS["poisson"]
+    if isfunc:
+        return REASONS["isfunc"]
+    if brange is not None or nbatch > 1:
+        return REASONS["batches"]
+    if verbose is not None and verbose > 1:
+        return REASONS["verbose"]
+    if covtype not in ("all", "single"):
+        return REASONS["covtype"]
+    if split and covtype == "single":
+        return REASONS["split_single"]
+    eff = ndim if nparam is None else (nparam if ndim is None else min(int(ndim), nparam))
+    if eff is not None and eff > 127:
+        return REASONS["ndim"]
+    if distributed:
+        return REASONS["distributed"]
+    if ncols is not None and len(set(int(c) for c in ncols)) > 1:
+        return REASONS["columns"]
+    if nrows is not None and nrows < 2:
+        return REASONS["rows"]
+    return RESIDENT
+
+
+def _resolve_files(fname, idchain=0, idpattern="_?.txt"):
+    """the files ``MCSamples.load_from_file`` reads for ``fname``"""
+    if isinstance(fname, (list, tuple)):
+        flist = list(fname)
+    elif os.path.isfile(fname):
+        flist = [fname]
+    elif "*" in fname or "?" in fname:
+        flist = sorted(glob.glob(fname))
+    elif idchain > 0:
+        flist = ["%s_%d.txt" % (fname, idchain)]
+    else:
+        flist = sorted(glob.glob(fname + idpattern))
+    if not flist:
+        raise IOError("no chain files found for %r" % (fname,))
+    return flist
+
+
+def _is_file_root(method):
+    return isinstance(method, str) or (isinstance(method, (list, tuple)) and len(method) > 0 and all(isinstance(f, str) for f in method))
+
+
+def _distributed():
+    """is a process group initialised?  (multi-rank chains are not resident)"""
+    try:
+        import torch.distributed as dist
+    except Exception:
+        return False
+    return bool(dist.is_available() and dist.is_initialized())
+
+
+def _ms(t0):
+    return (time.perf_counter() - t0) * 1e3
+
+
+class ResidentChains(object):
+    """One or more chains on GPU ``device``, burned, concatenated and thinned there.
+
+    ``nrows`` / ``nparam``: the shape ``MCSamples(...).samples[:, itheta:]`` has; ``rule``: ``"none" | "integer" | "bin"``
+    (the thinning rule taken); ``keep()``: the kept rows in the burned, concatenated numbering (the host's ``keep``);
+    ``to_host()``: the array ``MCSamples(...).samples`` holds; ``stats``: reader statistics per file and milliseconds per
+    stage.  Raises ``ResidentDecline`` where the route does not apply, ``RuntimeError`` without a GPU."""
+
+    def __init__(self, tensors, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, device=0, reader_stats=None):
+        import torch
+        self._torch = torch
+        self.device = int(device)
+        self.iw, self.ilike, self.itheta = int(iw), int(ilike), int(itheta)
+        self.stats = {"files": list(reader_stats or []), "ms": {}}
+        self.nchains = len(tensors)
+        if not tensors:
+            raise ValueError("the chains array is empty")
+        reason = plan(thinlen=thinlen, ncols=[t.shape[1] for t in tensors], distributed=_distributed())
+        if reason != RESIDENT:
+            raise ResidentDecline(reason)
+        self.ncols = int(tensors[0].shape[1])
+        if self.ncols <= max(self.iw, self.ilike, self.itheta) or min(self.iw, self.ilike, self.itheta) < 0:
+            raise ValueError("columns iw=%d ilike=%d itheta=%d of a chain with %d" % (self.iw, self.ilike, self.itheta, self.ncols))
+        self.nparam = self.ncols - self.itheta
+        self._tensors = list(tensors)                     # (owners of the memory the parts point into)
+        self._parts = []
+        for t in self._tensors:
+            n = int(t.shape[0])
+            start = 0
+            if burnlen > 0:                               # (chains.MCSamples.removeBurn; csrc/chain_prep.hpp: burn_start)
+                start = min(n, int(n * burnlen) if burnlen < 1 else int(burnlen))
+                logger.info("Removing %s lines as burn in" % start)
+            self._parts.append((t.data_ptr() + start * self.ncols * 8, n - start))
+        self.nburned = sum(n for _, n in self._parts)
+        self._src = self._new_w = None
+        self.rule = "none"
+        self.totals = None
+        if self.nburned < 1:                              # (nothing to select from; fewer than 2 rows decline in evidence())
+            raise ResidentDecline(REASONS["rows"])
+        t0 = time.perf_counter()
+        if thinlen not in (0, 1):
+            self._select(float(thinlen))
+        self.stats["ms"]["select"] = _ms(t0)
+        self.nrows = self.nburned if self._src is None else int(self._src.shape[0])
+
+    # -- construction ------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_arrays(cls, arrays, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, device=0):
+        """Host arrays (one per chain) uploaded as they are.  Unlike ``MCSamples``, which ignores ``burnlen`` / ``thinlen``
+        for chains passed in memory (and keeps doing so), this entry HONOURS them, with the rules files get: it exists so
+        that the device preparation can be used and tested apart from the reader."""
+        from . import _capi
+        _capi.require_device()
+        import torch
+        seq = list(arrays.values()) if isinstance(arrays, dict) else list(arrays)
+        with torch.cuda.device(int(device)):
+            tensors = []
+            for a in seq:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.ndim != 2:
+                    raise ValueError("a chain must be a 2-D array, got shape %r" % (a.shape,))
+                tensors.append(torch.from_numpy(a).to("cuda:%d" % int(device)))
+            return cls(tensors, burnlen, thinlen, iw, ilike, itheta, device)
+
+    @classmethod
+    def from_files(cls, root_or_paths, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, idchain=0, idpattern="_?.txt", device=0):
+        """Chain text files parsed on the device and left there; the files are those ``MCSamples.load_from_file`` reads."""
+        import mmap
+        from . import _capi, chain_io
+        _capi.require_device()
+        import torch
+        flist = _resolve_files(root_or_paths, idchain, idpattern)
+        logger.debug("Reading from files: " + ", ".join(flist))
+        t0 = time.perf_counter()
+        tensors, stats = [], []
+        with torch.cuda.device(int(device)):
+            for path in flist:
+                with open(path, "rb") as f:
+                    size = os.fstat(f.fileno()).st_size
+                    mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size > 0 else None
+                    try:
+                        view = np.frombuffer(mm, dtype=np.uint8) if mm is not None else None
+                        try:
+                            handle, nrows, ncols = None, 0, 0
+                            try:
+                                handle, nrows, ncols = _capi.chain_dev_open(view.ctypes.data if view is not None else None, size, device)
+                                out = torch.empty((nrows, ncols), dtype=torch.float64, device="cuda:%d" % int(device))
+                                stats.append(dict(_capi.chain_dev_read_dev(handle, out.data_ptr() if nrows * ncols else 0), path=path))
+                            finally:
+                                if handle is not None:
+                                    _capi.chain_dev_close(handle)
+                        except ValueError as dev_err:
+                            chain_io.loadtxt(path)          # raises ValueError with the row, column and line of the first bad field
+                            raise RuntimeError("mcevidence_amd: the device chain reader refused %s (%s) but the host reader accepts it" % (path, dev_err))
+                        finally:
+                            del view
+                    finally:
+                        if mm is not None:
+                            mm.close()
+                if nrows == 0:                               # (np.loadtxt: an empty file is an array of shape (0, 1))
+                    out = torch.empty((0, 1), dtype=torch.float64, device="cuda:%d" % int(device))
+                tensors.append(out)
+            self = cls(tensors, burnlen, thinlen, iw, ilike, itheta, device, reader_stats=stats)
+        self.stats["ms"]["read"] = _ms(t0) - self.stats["ms"]["select"]
+        return self
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    def _ws(self, nbytes):
+        return self._torch.empty(max(int(nbytes), 1), dtype=self._torch.uint8, device="cuda:%d" % self.device)
+
+    def _select(self, thinlen):
+        from . import _capi
+        torch = self._torch
+        n, nparts = self.nburned, len(self._parts)
+        wsb = _capi.chain_select_workspace_bytes(n, nparts)
+        ws = self._ws(wsb)
+        st = self._stream()
+        rule, self.totals = _capi.chain_weights_dev(self._parts, self.ncols, self.iw, thinlen, ws.data_ptr(), wsb, st)
+        if rule < 0:
+            raise ResidentDecline(REASONS[DECLINE_REASON[rule]])
+        if rule == 0:
+            return
+        edges, nedges = None, 0
+        if RULE_NAME[rule] == "bin":
+            nbins = int(n * thinlen) if thinlen < 1 else int(n // thinlen)      # (chains.max_weight_bin_thin)
+            edges = torch.from_numpy(np.linspace(-1, n, nbins + 1)).to("cuda:%d" % self.device)
+            nedges = int(edges.shape[0])
+        n_out = _capi.chain_select_count_dev(n, nparts, rule, thinlen, edges.data_ptr() if edges is not None else 0, nedges, ws.data_ptr(), wsb, st)
+        src = torch.empty(n_out, dtype=torch.int64, device="cuda:%d" % self.device)
+        new_w = torch.empty(n_out, dtype=torch.float64, device="cuda:%d" % self.device)
+        _capi.chain_select_fill_dev(n, nparts, rule, thinlen, nedges, n_out, src.data_ptr(), new_w.data_ptr(), ws.data_ptr(), wsb, st)
+        torch.cuda.current_stream(self.device).synchronize()        # (the workspace and the edges go out of scope here)
+        self._src, self._new_w, self.rule = src, new_w, RULE_NAME[rule]
+        logger.info("Thinning with thin length=%s: #old_chain=%s, #new_chain=%s" % (thinlen, n, n_out))
+
+    # -- accessors -----------------------------------------------------------------------------------------------------
+    def keep(self):
+        """host copy of the kept rows (burned, concatenated numbering); every row when nothing was thinned"""
+        return np.arange(self.nburned, dtype=np.int64) if self._src is None else self._src.cpu().numpy()
+
+    def weights(self):
+        """host copy of the weight column after thinning"""
+        with self._torch.cuda.device(self.device):
+            return self._gather(None, want=("w",))["w"].cpu().numpy()
+
+    def _gather(self, rows, want):
+        """one gather pass -> dict of device tensors among params / w / like / full; ``rows``: int64 device tensor or None"""
+        from . import _capi
+        torch = self._torch
+        dev = "cuda:%d" % self.device
+        n_out = self.nrows if rows is None else int(rows.shape[0])
+        out = {}
+        if "params" in want:
+            out["params"] = torch.empty((n_out, self.nparam), dtype=torch.float64, device=dev)
+        if "w" in want:
+            out["w"] = torch.empty(n_out, dtype=torch.float64, device=dev)
+        if "like" in want:
+            out["like"] = torch.empty(n_out, dtype=torch.float64, device=dev)
+        if "full" in want:
+            out["full"] = torch.empty((n_out, self.ncols), dtype=torch.float64, device=dev)
+        wsb = _capi.chain_gather_workspace_bytes(len(self._parts))
+        ws = self._ws(wsb)
+        ptr = lambda k: out[k].data_ptr() if k in out else 0                    # noqa: E731
+        _capi.chain_gather_dev(self._parts, self.ncols, self.iw, self.ilike, self.itheta,
+                               self._src.data_ptr() if self._src is not None else 0, self._new_w.data_ptr() if self._new_w is not None else 0,
+                               self.nrows, rows.data_ptr() if rows is not None else 0, n_out, ptr("params"), ptr("w"), ptr("like"), ptr("full"),
+                               ws.data_ptr(), wsb, self._stream())
+        return out
+
+    def to_host(self):
+        """the array ``MCSamples(...).samples`` holds: the burned, concatenated, thinned rows, all columns"""
+        with self._torch.cuda.device(self.device):
+            return self._gather(None, want=("full",))["full"].cpu().numpy()
+
+    def _index_list(self, rows):
+        rows = np.asarray(rows)
+        if rows.dtype == bool:
+            rows = np.nonzero(rows)[0]
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if rows.size and (rows.min() < -self.nrows or rows.max() >= self.nrows):
+            raise IndexError("split row out of range for a chain of %d rows" % self.nrows)
+        rows = np.where(rows < 0, rows + self.nrows, rows)
+        return self._torch.from_numpy(rows).to("cuda:%d" % self.device)
+
+    # -- the estimator ---------------------------------------------------------------------------------------------------
+    def evidence(self, kmax=5, ndim=None, priorvolume=1, covtype="all", pos_lnp=False, split=False, s1frac=0.5, split_rows=None,
+                 info=False, backend=None):
+        """ln E as ``MCEvidence(...).evidence(...)`` returns it (``MLE[1:]``, and the info dict if ``info=True``; it
+        carries ``info["route"] = "resident"``).  ``split=True``: the reference's random split, drawn on the host with the
+        call ``MCSamples.chain_split`` makes (same RNG consumption); ``split_rows=(s1, s2)``: ``set_split``.
+        ``backend``: a ``HipBackend`` whose ``recheck_rows`` applies to the search."""
+        from . import _capi
+        from .evidence import HipBackend
+        backend = backend or HipBackend()
+        kmax = max(2, int(kmax))
+        nd = self.nparam if ndim is None else int(ndim)
+        if nd < 1:
+            raise ValueError("ndim must be >= 1 (got %r)" % (ndim,))
+        if nd > self.nparam:
+            logger.warning("ndim=%s exceeds the %s parameter columns of the chain; using all of them" % (ndim, self.nparam))
+            nd = self.nparam
+        cross = bool(split) or split_rows is not None
+        reason = plan(covtype=covtype, split=cross, ndim=nd, nparam=self.nparam, distributed=_distributed(), nrows=self.nrows)
+        if reason != RESIDENT:
+            raise ResidentDecline(reason)
+        torch = self._torch
+        ms = self.stats["ms"]
+        with torch.cuda.device(self.device):
+            rows1 = rows2 = None
+            if split_rows is not None:
+                rows1, rows2 = self._index_list(split_rows[0]), self._index_list(split_rows[1])
+            elif split:
+                nrow = self.nrows
+                pick = _chains.rank0_draw(lambda: np.random.choice(range(nrow), size=int(nrow * s1frac), replace=False))
+                rest = np.setxor1d(range(nrow), pick)
+                logger.info("%s chain with nrow=%s split to ns1=%s, ns2=%s" % (self.nchains, nrow, len(pick), len(rest)))
+                rows1, rows2 = self._index_list(pick), self._index_list(rest)
+            t0 = time.perf_counter()
+            s1 = self._gather(rows1, want=("params", "w", "like"))
+            s2 = self._gather(rows2, want=("params",)) if cross else None
+            n1 = int(s1["w"].shape[0])
+            n2 = int(s2["params"].shape[0]) if cross else 0
+            ms["gather"] = _ms(t0)
+            if n1 < 2 or (cross and n2 < 1):
+                raise ValueError("invalid sizes n1=%d n2=%d" % (n1, n2))
+            t0 = time.perf_counter()
+            fs = torch.empty(n1, dtype=torch.float64, device="cuda:%d" % self.device)
+            wsb = _capi.chain_reduce_workspace_bytes(n1)
+            ws = self._ws(wsb)
+            logLmax, SumW, nan_like, bad_w = _capi.chain_reduce_dev(s1["like"].data_ptr(), s1["w"].data_ptr(), n1, pos_lnp, fs.data_ptr(),
+                                                                    ws.data_ptr(), wsb, self._stream())
+            ms["reduce"] = _ms(t0)
+            if bad_w:
+                raise ValueError("weight contains NaN or infinity")
+            if nan_like or math.isinf(logLmax):
+                raise ValueError("fs contains NaN or +infinity")
+            t0 = time.perf_counter()
+            with backend._scoped():
+                dotp, jac, _, _ = _capi.evidence_feed_part_dev(s1["params"].data_ptr(), n1, self.nparam, s2["params"].data_ptr() if cross else 0, n2,
+                                                               self.nparam, nd, 0 if covtype == "all" else 1, kmax, s1["w"].data_ptr(), fs.data_ptr(),
+                                                               0, 1, device=self.device, want_checksum=False)
+            ms["feed"] = _ms(t0)
+        # ln E_k from the reduced sums (evidence.MCEvidence._feed_finish; reference :1120-1131)
+        logPriorVolume = math.log(priorvolume)
+        k0 = 0 if cross else 1
+        mle = np.zeros(kmax)
+        for k in range(k0, kmax):
+            k_nn = k if k0 == 1 else k + 1
+            mle[k] = math.log(SumW * (dotp[k] / (n1 * k_nn + 1.0)) * jac) + logLmax - logPriorVolume
+        out = mle[1:]
+        if not info:
+            return out
+        nsample = [n1, n2] if cross else [n1]
+        return out, {"NparamsMC": self.nparam, "Nsamples_read": self.nrows if split_rows is not None else n1, "Nparams_read": self.nparam, "NparamsCosmo": nd,
+                     "Nsamples": ", ".join(str(x) for x in nsample), "route": RESIDENT}
+
+
+_EVIDENCE_KEYS = ("rand", "info", "profile", "pvolume", "pos_lnp", "nproc", "prewhiten")
+
+
+def evidence_from_files(root, *, require_resident=False, **kwargs):
+    """``MCEvidence(root, **ctor).evidence(**call)`` with the keywords of both in ``kwargs``, through the resident route
+    where it applies (``plan``) and through that very expression where it does not.  With ``info=True`` the info dict
+    says which: ``info["route"]`` is ``"resident"`` or ``"host"``, and ``info["declined"]`` gives the reason.
+    ``require_resident=True`` turns a decline into ``ValueError(reason)``.  Without a GPU: ``RuntimeError``."""
+    from . import _capi
+    from .evidence import MCEvidence
+    _capi.require_device()
+    call = {k: kwargs.pop(k) for k in list(kwargs) if k in _EVIDENCE_KEYS}
+    ctor = dict(kwargs)
+    want_info = bool(call.get("info", False))
+    covtype = ctor.get("covtype", "all")               # (given: the call's covtype too; not given: evidence()'s default)
+    covtype = "single" if covtype is None else covtype
+    split = bool(ctor.get("split", False))
+    reason = RESIDENT if _is_file_root(root) else REASONS["not_files"]
+    if reason == RESIDENT:
+        reason = plan(thinlen=ctor.get("thinlen", 0.0), isfunc=ctor.get("isfunc"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1),
+                      verbose=max(ctor.get("verbose", 1), 2 if ctor.get("debug") else 0), covtype=covtype, split=split, ndim=None,
+                      distributed=_distributed(), ischain=ctor.get("ischain", True))
+    if reason == RESIDENT:
+        level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
+        if not logging.getLogger().handlers:
+            logging.basicConfig()
+        logger.setLevel(level)
+        rc = None
+        try:
+            rc = ResidentChains.from_files(root, burnlen=ctor.get("burnlen", 0.0), thinlen=ctor.get("thinlen", 0.0), iw=ctor.get("iw", 0),
+                                           ilike=ctor.get("ilike", 1), itheta=ctor.get("itheta", 2), idchain=ctor.get("idchain", 0),
+                                           idpattern=ctor.get("idpattern", "_?.txt"))
+            pv = call.get("pvolume")
+            got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
+                              covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,
+                              backend=ctor.get("backend"))
+            mle, inf = got
+            if ctor.get("verbose", 1) > 0:
+                for k in range(1, len(mle) + 1):
+                    logger.info("   ln(B)[k={}] = {}".format(k, mle[k - 1]))
+            return (mle, inf) if want_info else mle
+        except ResidentDecline as d:                     # (nothing half done is kept: the device buffers die with rc)
+            reason = d.reason
+        finally:
+            del rc
+    if require_resident:
+        raise ValueError(reason)
+    m = MCEvidence(root, **ctor)
+    if "covtype" in ctor:
+        call["covtype"] = ctor["covtype"]
+    out = m.evidence(**call)
+    if want_info:
+        out[1]["route"] = "host"
+        out[1]["declined"] = reason
+    return out

@@ -193,6 +193,11 @@ typedef struct mce_feed_problem {
 
 int mce_evidence_feed_batch_f64(mce_feed_problem *problems, int64_t nprob, const int32_t *devices, int32_t ndev);
 size_t mce_feed_problem_size(void);   /* sizeof(mce_feed_problem) as built: lets a binding check its struct layout */
+/* mce_evidence_feed_batch_f64 with S1, S2, w and fs of EVERY problem as device pointers on `device`, produced on a stream the caller
+ * has synchronised (as for mce_evidence_feed_part_dev_f64; the inputs are copied, not modified).  dotp, eigenvalues, jacobian and
+ * status stay host-side; streams, the wave limit, per-problem failures and the caller's mce_options (the run-time certificate
+ * included) as in the host-pointer call. */
+int mce_evidence_feed_batch_dev_f64(mce_feed_problem *problems, int64_t nprob, int32_t device);
 
 /* ---- device-pointer entry points (resident data, caller's stream) ------ */
 
@@ -392,6 +397,48 @@ int mce_chain_gather_dev(const mce_chain_part* parts, int32_t nparts, int64_t nc
                          double* d_params, double* d_w, double* d_like, double* d_full, void* ws, size_t ws_bytes, void* stream);
 int mce_chain_reduce_dev(const double* d_like, const double* d_w, int64_t n, int32_t pos_lnp, double* d_fs, double* out, void* ws,
                          size_t ws_bytes, void* stream);
+
+/* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
+ * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
+ * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an
+ * array a wave does not fit is grown once and counted in the stats).  A handle belongs to one thread.
+ * Layout of a wave: the caller writes file f's bytes into the staging buffer at file_off[f] -- a multiple of 4096, file_off[0] = 0 --
+ * with at least one byte behind every file: file_off[f + 1] >= file_off[f] + file_len[f] + 1, rounded up to 4096; wave_bytes (a
+ * multiple of 4096, <= capacity) ends the last file in the same way.  The library fills every gap with '\n' on the device, so a file
+ * boundary behaves like the end of a file.  TWO STEPS, as mce_chain_dev_open / _read_dev:
+ *   structure  uploads the wave (one copy) and finds, per file, its tokens, rows and columns: files[f] = {tok_base, ntok, nrows, ncols,
+ *              status}; *ntok_total = the tokens of the wave.  A ragged file (the rule of mce_chain_dev_open inside the file's tokens)
+ *              has status MCE_FARM_RAGGED and fails ALONE; a file with no token has 0 rows and 0 columns.
+ *   parse      the caller allocates d_out[ntok_total] on the handle's device in between; global token k is written to d_out[k], so file
+ *              f's array [nrows, ncols] starts at d_out + files[f].tok_base.  Undecided tokens are converted by the host's strtod from the
+ *              staging bytes (which must stay untouched until parse returns) and go up in one copy; a field that is not a number sets its
+ *              file's status to MCE_FARM_NOT_A_NUMBER and bad_row / bad_col (0-based row, 1-based column inside the file); the other
+ *              files are unaffected.  The handle's stream is synchronised on return of either step.
+ *   stats[12]  {waves, files, device allocations since creation, ... in the last wave, arrays grown, tokens of the last wave, tokens
+ *              patched, ms upload, ms structure, ms parse, ms patch, capacity}
+ * Argument errors: MCE_ERR_INVALID (no device needed); no visible device: MCE_ERR_NO_DEVICE. */
+#define MCE_FARM_OK 0
+#define MCE_FARM_RAGGED 1
+#define MCE_FARM_NOT_A_NUMBER 2
+typedef struct mce_farm_file {
+    int64_t tok_base, ntok, nrows, ncols, status, bad_row, bad_col;
+} mce_farm_file;
+int mce_chain_farm_create(int64_t capacity_bytes, int32_t device, void** handle, void** staging);
+void mce_chain_farm_destroy(void* handle);
+int mce_chain_farm_structure(void* handle, const int64_t* file_off, const int64_t* file_len, int32_t nfiles, int64_t wave_bytes,
+                             mce_farm_file* files, int64_t* ntok_total);
+int mce_chain_farm_parse(void* handle, double* d_out, mce_farm_file* files, int32_t nfiles);
+int mce_chain_farm_stats(void* handle, double* stats, int32_t nstats);
+/* mce_chain_gather_dev (parameters, weight, likelihood) and mce_chain_reduce_dev for EVERY unthinned root of a wave in one set of
+ * launches.  Root r owns the next root_nparts[r] entries of `parts` (its files after burn-in, as for mce_chain_gather_dev; empty parts
+ * allowed, a root needs one row) and has root_ncols[r] columns.  Outputs, roots one after the other: d_params (rows * (ncols - itheta)
+ * doubles per root), d_w / d_like / d_fs (one per row), out[4 * r ..] (host) = mce_chain_reduce_dev's out of root r.  The reductions
+ * run in the root's own row numbering, in mce_chain_reduce_dev's order: a root's bits do not depend on its neighbours.  Synchronises
+ * the stream. */
+size_t mce_chain_farm_prep_workspace_bytes(int32_t nroots, int32_t nparts, int64_t nrows);
+int mce_chain_farm_prep_dev(const int32_t* root_nparts, const int64_t* root_ncols, int32_t nroots, const mce_chain_part* parts, int32_t nparts,
+                            int32_t iw, int32_t ilike, int32_t itheta, int32_t pos_lnp, double* d_params, double* d_w, double* d_like,
+                            double* d_fs, double* out, void* ws, size_t ws_bytes, void* stream);
 
 /* Spatial pruning of the fp16-filter search for low-dimensional, large reference sets (d <= 13):
  * both point sets are put in k-d order on the device (cells of 32 rows) and every wave of 64 queries

@@ -8,8 +8,9 @@ reduction inside ``evidence()`` run as hand-written gfx950 HIP kernels behind a 
 from .chains import MCSamples
 from .evidence import HipBackend, MCEvidence, evidence_many
 from .resident import ResidentChains, evidence_from_files
+from .farm import evidence_many_from_files, farm_waves
 from .prior import cosmo_params_list, get_prior_volume, iscosmo_param, params_info
 
-__all__ = ["MCEvidence", "evidence_many", "MCSamples", "HipBackend", "ResidentChains", "evidence_from_files", "params_info", "get_prior_volume", "iscosmo_param",
+__all__ = ["MCEvidence", "evidence_many", "MCSamples", "HipBackend", "ResidentChains", "evidence_from_files", "evidence_many_from_files", "farm_waves", "params_info", "get_prior_volume", "iscosmo_param",
            "cosmo_params_list"]
 __version__ = "0.1.0"

@@ -126,6 +126,25 @@ class FeedProblem(ctypes.Structure):
 
 SIGNATURES["mce_evidence_feed_batch_f64"] = (_c.c_int, [_c.POINTER(FeedProblem), _c.c_int64, _P, _c.c_int32])
 SIGNATURES["mce_feed_problem_size"] = (_c.c_size_t, [])
+SIGNATURES["mce_evidence_feed_batch_dev_f64"] = (_c.c_int, [_c.POINTER(FeedProblem), _c.c_int64, _c.c_int32])
+
+
+class FarmFile(ctypes.Structure):
+    """``mce_farm_file``: one file of a wave -- its first global token, tokens, rows, columns, status (0 ok, 1 ragged, 2 a field
+    that is not a number, at ``bad_row`` / ``bad_col`` inside the file)."""
+    _fields_ = [("tok_base", _c.c_int64), ("ntok", _c.c_int64), ("nrows", _c.c_int64), ("ncols", _c.c_int64), ("status", _c.c_int64),
+                ("bad_row", _c.c_int64), ("bad_col", _c.c_int64)]
+
+
+FARM_OK, FARM_RAGGED, FARM_NOT_A_NUMBER = 0, 1, 2
+SIGNATURES["mce_chain_farm_create"] = (_c.c_int, [_c.c_int64, _c.c_int32, _c.POINTER(_P), _c.POINTER(_P)])
+SIGNATURES["mce_chain_farm_destroy"] = (None, [_P])
+SIGNATURES["mce_chain_farm_structure"] = (_c.c_int, [_P, _P, _P, _c.c_int32, _c.c_int64, _c.POINTER(FarmFile), _c.POINTER(_c.c_int64)])
+SIGNATURES["mce_chain_farm_parse"] = (_c.c_int, [_P, _P, _c.POINTER(FarmFile), _c.c_int32])
+SIGNATURES["mce_chain_farm_stats"] = (_c.c_int, [_P, _P, _c.c_int32])
+SIGNATURES["mce_chain_farm_prep_workspace_bytes"] = (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int64])
+SIGNATURES["mce_chain_farm_prep_dev"] = (_c.c_int, [_P, _P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _P, _P, _P,
+                                                     _P, _c.c_size_t, _P])
 
 _lib = None
 
@@ -349,6 +368,63 @@ def chain_dev_read_dev(handle, d_out):
 
 def chain_dev_close(handle):
     load().mce_chain_dev_close(handle)
+
+
+FARM_STATS = ("waves", "files", "allocs", "allocs_wave", "grows", "tokens", "patched", "ms_upload", "ms_structure", "ms_parse", "ms_patch", "capacity")
+
+
+def chain_farm_create(capacity_bytes, device=0):
+    """mce_chain_farm_create -> (handle, address of the pinned staging buffer of ``capacity_bytes``)"""
+    handle, staging = _P(), _P()
+    check(load().mce_chain_farm_create(int(capacity_bytes), int(device), _c.byref(handle), _c.byref(staging)))
+    return handle, int(staging.value)
+
+
+def chain_farm_destroy(handle):
+    load().mce_chain_farm_destroy(handle)
+
+
+def chain_farm_structure(handle, file_off, file_len, wave_bytes):
+    """mce_chain_farm_structure -> (the C array of ``FarmFile`` that ``chain_farm_parse`` takes, tokens of the wave)"""
+    off = np.ascontiguousarray(file_off, dtype=np.int64)
+    ln = np.ascontiguousarray(file_len, dtype=np.int64)
+    if off.ndim != 1 or off.shape != ln.shape:
+        raise ValueError("file_off and file_len must be 1-D of one length")
+    files = (FarmFile * max(len(off), 1))()
+    ntok = _c.c_int64(0)
+    check(load().mce_chain_farm_structure(handle, off.ctypes.data if len(off) else None, ln.ctypes.data if len(ln) else None, len(off), int(wave_bytes),
+                                          files, _c.byref(ntok)))
+    return files, int(ntok.value)
+
+
+def chain_farm_parse(handle, d_out, files, nfiles):
+    """mce_chain_farm_parse: global token k into the DEVICE buffer at address ``d_out``; updates ``files[f].status``"""
+    check(load().mce_chain_farm_parse(handle, d_out or None, files, int(nfiles)))
+
+
+def chain_farm_stats(handle):
+    st = (_c.c_double * 12)()
+    check(load().mce_chain_farm_stats(handle, _c.cast(st, _P), 12))
+    return {k: (float(st[i]) if k.startswith("ms_") else int(st[i])) for i, k in enumerate(FARM_STATS)}
+
+
+def chain_farm_prep_workspace_bytes(nroots, nparts, nrows):
+    return int(load().mce_chain_farm_prep_workspace_bytes(int(nroots), int(nparts), int(nrows)))
+
+
+def chain_farm_prep_dev(root_nparts, root_ncols, parts, iw, ilike, itheta, pos_lnp, d_params, d_w, d_like, d_fs, ws, ws_bytes, stream=0):
+    """mce_chain_farm_prep_dev -> float64 [nroots, 4]: (max(logL), SumW, NaN likelihoods, weights that are not finite) per root;
+    ``parts``: [(device address, rows)] of all roots, root after root"""
+    rn = np.ascontiguousarray(root_nparts, dtype=np.int32)
+    rc = np.ascontiguousarray(root_ncols, dtype=np.int64)
+    if rn.ndim != 1 or rn.shape != rc.shape:
+        raise ValueError("root_nparts and root_ncols must be 1-D of one length")
+    out = np.zeros((max(len(rn), 1), 4))
+    arr = chain_parts(parts)
+    check(load().mce_chain_farm_prep_dev(rn.ctypes.data if len(rn) else None, rc.ctypes.data if len(rc) else None, len(rn), _c.cast(arr, _P), len(parts),
+                                         int(iw), int(ilike), int(itheta), 1 if pos_lnp else 0, d_params or None, d_w or None, d_like or None, d_fs or None,
+                                         out.ctypes.data, ws or None, int(ws_bytes), stream or None))
+    return out[:len(rn)]
 
 
 def chain_select_workspace_bytes(n, nparts):
@@ -662,6 +738,42 @@ def evidence_feed_batch(problems, devices=None, return_exceptions=False):
             results.append((outs[i][0], float(arr[i].jacobian), outs[i][1]))
             continue
         # the library keeps only the first failure's text; later ones get a generic message
+        first = all(int(arr[j].status) == MCE_OK for j in range(i))
+        exc = _raise_for(st, last_error() if first else "problem %d failed with status %d" % (i, st))
+        if not return_exceptions:
+            raise exc
+        results.append(exc)
+    return results
+
+
+def evidence_feed_batch_dev(problems, device=0, return_exceptions=False):
+    """``evidence_feed_batch`` with the inputs on the device already (``mce_evidence_feed_batch_dev_f64``).  ``problems``: sequence
+    of ``(dS1, n1, ld1, dS2, n2, ld2, d, cov_mode, kmax, d_w, d_fs)`` -- device ADDRESSES on ``device`` (``dS2`` = 0: auto evidence),
+    produced on a stream the caller has synchronised.  Same returns and failure semantics."""
+    lib = load()
+    n = len(problems)
+    arr = (FeedProblem * max(n, 1))()
+    outs = []
+    for i, (dS1, n1, ld1, dS2, n2, ld2, d, cov_mode, kmax, d_w, d_fs) in enumerate(problems):
+        d, kmax = int(d), int(kmax)
+        out = np.zeros(max(kmax, 0))
+        ev = np.zeros(max(d, 0))
+        outs.append((out, ev))
+        q = arr[i]
+        q.S1, q.n1, q.ld1 = dS1 or None, int(n1), int(ld1)
+        if dS2:
+            q.S2, q.n2, q.ld2 = dS2, int(n2), int(ld2)
+        q.d, q.cov_mode, q.kmax = d, int(cov_mode), kmax
+        q.w, q.fs, q.dotp, q.eigenvalues = d_w or None, d_fs or None, out.ctypes.data, ev.ctypes.data
+    rc = lib.mce_evidence_feed_batch_dev_f64(arr, n, int(device))
+    if rc != MCE_OK and all(arr[i].status == MCE_OK for i in range(n)):
+        check(rc)                              # the machinery failed (allocation, device), not a problem
+    results = []
+    for i in range(n):
+        st = int(arr[i].status)
+        if st == MCE_OK:
+            results.append((outs[i][0], float(arr[i].jacobian), outs[i][1]))
+            continue
         first = all(int(arr[j].status) == MCE_OK for j in range(i))
         exc = _raise_for(st, last_error() if first else "problem %d failed with status %d" % (i, st))
         if not return_exceptions:

@@ -40,7 +40,37 @@ def build_parser(prog=None):
                    help="split the chain(s) in two and estimate the cross evidence (otherwise auto evidence)")
     p.add_argument("--resident", action="store_true",
                    help="keep the chain on the GPU from the text files to ln E (mcevidence_amd.resident); falls back to the host route where it does not apply")
+    p.add_argument("--farm", action="store_true",
+                   help="root_name is a text file with one chain root per line ('#' starts a comment): all roots in batched GPU passes "
+                        "(mcevidence_amd.farm); a root the farm does not cover takes the per-root route")
     return p
+
+
+def farm_main(args):
+    """``--farm``: every root of the list file, each with the ndim and the prior volume a single run would compute for it"""
+    import copy
+    from .farm import evidence_many_from_files
+    with open(args.root_name) as fh:
+        roots = [ln.split("#", 1)[0].strip() for ln in fh]
+    roots = [r for r in roots if r]
+    pvols, ndims = [], []
+    for r in roots:
+        a = copy.copy(args)
+        a.root_name = r
+        pvols.append(prior.get_prior_volume(a, cosmo=not args.allparams))      # (sets a.ndim, as for one root)
+        ndims.append(a.ndim)
+    logging.getLogger("mcevidence_amd").setLevel(
+        logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
+    outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
+                                    idchain=args.idchain, split=args.cross)
+    for r, mle in zip(roots, outs):
+        print()
+        print("Using file: ", r)
+        for k in range(1, len(mle) + 1):
+            print("   ln(B)[k={}] = {}".format(k, mle[k - 1]))
+    print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
+    print("")
+    return outs
 
 
 def main(argv=None):
@@ -52,6 +82,8 @@ def main(argv=None):
         for n in new:
             if n not in prior.cosmo_params_list:
                 prior.cosmo_params_list.append(n)
+    if args.farm:
+        return farm_main(args)
     prior_volume = prior.get_prior_volume(args, cosmo=not args.allparams)
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))

@@ -534,7 +534,7 @@ extern "C" {
 
 size_t mce_feed_problem_size(void) { return sizeof(mce_feed_problem); }
 
-int mce_evidence_feed_batch_f64(mce_feed_problem* problems, int64_t nprob, const int32_t* devices, int32_t ndev)
+static int feed_batch_impl(bool src_device, mce_feed_problem* problems, int64_t nprob, const int32_t* devices, int32_t ndev)
 {
     if (nprob < 0 || (nprob > 0 && !problems)) return fail(MCE_ERR_INVALID, "invalid problem list");
     if (nprob == 0) return MCE_OK;
@@ -542,6 +542,7 @@ int mce_evidence_feed_batch_f64(mce_feed_problem* problems, int64_t nprob, const
     for (int64_t i = 0; i < nprob; ++i) {
         jobs[i].q = &problems[i];
         jobs[i].index = i;
+        jobs[i].src_device = src_device;
         problems[i].status = MCE_OK;
         problems[i].jacobian = 0.0;
         const int r = feed_plan(jobs[i]);
@@ -596,6 +597,17 @@ int mce_evidence_feed_batch_f64(mce_feed_problem* problems, int64_t nprob, const
         }
     }
     return first;
+}
+
+int mce_evidence_feed_batch_f64(mce_feed_problem* problems, int64_t nprob, const int32_t* devices, int32_t ndev)
+{
+    return feed_batch_impl(false, problems, nprob, devices, ndev);
+}
+
+int mce_evidence_feed_batch_dev_f64(mce_feed_problem* problems, int64_t nprob, int32_t device)
+{
+    if (device < 0) return fail(MCE_ERR_INVALID, "device %d", device);
+    return feed_batch_impl(true, problems, nprob, &device, 1);
 }
 
 int mce_evidence_feed_f64(const double* S1, int64_t n1, int64_t ld1, const double* S2, int64_t n2, int64_t ld2,

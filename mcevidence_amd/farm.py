@@ -1,0 +1,432 @@
+"""The resident farm: many chain roots -> ln E in batched GPU passes.
+
+The reference's Planck driver runs ``MCEvidence(root).evidence()`` once per (data set, model, chain) over hundreds to thousands
+of small roots.  ``evidence_many_from_files(roots, ...)`` serves that pattern without the chains leaving the GPU: the files of
+many roots are read into ONE pinned staging buffer, go up in one copy per wave and are parsed in one pass
+(``mce_chain_farm_structure`` / ``_parse``: csrc/capi_farm.hpp), the roots that are not thinned are prepared in one set of
+launches (``mce_chain_farm_prep_dev``), thinned roots by the per-root calls of ``resident.ResidentChains`` on views of the wave's
+buffer, and all of them are fed by one ``mce_evidence_feed_batch_dev_f64`` call per wave.  Opt-in; a root the farm does not cover
+takes ``resident.evidence_from_files``.  docs/design/chain_farm.md has the layout, the passes and the error table.
+"""
+from __future__ import annotations
+
+import ctypes
+import logging
+import math
+import os
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from . import resident as _res
+
+logger = logging.getLogger("mcevidence_amd")
+
+__all__ = ["evidence_many_from_files", "farm_waves", "farm_layout", "read_files", "TILE", "DEFAULT_WAVE_BYTES"]
+
+TILE = 4096                                   # csrc/chain_farm.hpp: kTileBytes
+DEFAULT_WAVE_BYTES = 64 << 20                 # (docs/design/chain_farm.md: the sweep over 64 / 128 / 256 MiB)
+MAX_READERS = 16                              # file reader threads: a fixed bound, never the machine's core count
+FARM = "farm"
+
+#: milliseconds per stage of the last call (file read, upload, structure, parse, prep, feed) and its counts
+LAST_STATS = {}
+
+
+def next_offset(off, length):
+    """where the file after one of ``length`` bytes at ``off`` starts: at least one byte behind it, on a tile"""
+    return (off + length + 1 + TILE - 1) // TILE * TILE
+
+
+def farm_layout(file_lens):
+    """(offsets, wave_bytes) of files of these lengths laid out one after the other (csrc/chain_farm.hpp: next_offset)"""
+    offs, at = [], 0
+    for n in file_lens:
+        offs.append(at)
+        at = next_offset(at, int(n))
+    return offs, max(at, TILE)
+
+
+def farm_waves(sizes, wave_bytes):
+    """Pack roots of padded sizes ``sizes`` (bytes: ``farm_layout(lengths of the root's files)[1]``) into waves of at most
+    ``wave_bytes``: lists of root indices, every root exactly once and in order.  A root larger than a wave is a wave of its own (the
+    caller gives it to the per-root route).  A pure function."""
+    wave_bytes = int(wave_bytes)
+    if wave_bytes < TILE:
+        raise ValueError("wave_bytes=%d: at least one tile of %d bytes" % (wave_bytes, TILE))
+    waves, cur, used = [], [], 0
+    for i, s in enumerate(sizes):
+        s = int(s)
+        if s < 0:
+            raise ValueError("size %d of root %d" % (s, i))
+        if cur and used + s > wave_bytes:
+            waves.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += s
+        if used > wave_bytes:                 # (a single oversized root)
+            waves.append(cur)
+            cur, used = [], 0
+    if cur:
+        waves.append(cur)
+    return waves
+
+
+# one reader handle per device, reused by every call (the handle owns its stream, scratch and pinned staging buffer)
+_HANDLES = {}
+
+
+def _handle(device, need_bytes):
+    from . import _capi
+    got = _HANDLES.get(device)
+    if got is not None and got[2] >= need_bytes:
+        return got
+    if got is not None:
+        _capi.chain_farm_destroy(got[0])
+        del _HANDLES[device]
+    cap = (int(need_bytes) + TILE - 1) // TILE * TILE
+    handle, staging = _capi.chain_farm_create(cap, device)
+    _HANDLES[device] = (handle, staging, cap)
+    return _HANDLES[device]
+
+
+def release_handles():
+    """destroy the cached reader handles (their device scratch and pinned staging buffers)"""
+    from . import _capi
+    for dev in list(_HANDLES):
+        _capi.chain_farm_destroy(_HANDLES.pop(dev)[0])
+
+
+def handle_stats(device=0):
+    """the cached handle's statistics (``_capi.FARM_STATS``) or None"""
+    from . import _capi
+    got = _HANDLES.get(device)
+    return None if got is None else _capi.chain_farm_stats(got[0])
+
+
+def _read_into(path, view):
+    with open(path, "rb", buffering=0) as f:
+        at = 0
+        while at < len(view):
+            n = f.readinto(view[at:])
+            if not n:
+                break
+            at += n
+        if at != len(view) or f.read(1):
+            raise IOError("%s changed its size while it was read" % path)
+
+
+def _per_root(value, n, name):
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != n:
+            raise ValueError("%s: expected %d entries, got %d" % (name, n, len(value)))
+        return list(value)
+    return [value] * n
+
+
+def _parse_wave(pool, device, wave_bytes, paths, lens, ms):
+    """one wave: the files read into the staging buffer, uploaded and parsed -> (the C array of per-file results, the device tensor
+    global token k is written to, {path: exception} of the files that could not be read)"""
+    import torch
+    from . import _capi
+    offs, wbytes = farm_layout(lens)
+    handle, staging, cap = _handle(device, max(wave_bytes, wbytes))
+    buf = memoryview((ctypes.c_char * cap).from_address(staging)).cast("B")
+    t0 = time.perf_counter()
+    nonempty = [(p, o, ln) for p, o, ln in zip(paths, offs, lens) if ln > 0]
+    jobs = [pool.submit(_read_into, p, buf[o:o + ln]) for p, o, ln in nonempty]
+    read_err = {}
+    for (p, _, _), j in zip(nonempty, jobs):
+        try:
+            j.result()
+        except Exception as e:
+            read_err[p] = e
+    ms["read"] += _res._ms(t0)
+    files, ntok = _capi.chain_farm_structure(handle, offs, lens, wbytes)
+    d_out = torch.empty(max(ntok, 1), dtype=torch.float64, device="cuda:%d" % device)     # (between the two steps: the protocol of the header)
+    _capi.chain_farm_parse(handle, d_out.data_ptr(), files, len(paths))
+    st = _capi.chain_farm_stats(handle)
+    ms["upload"] += st["ms_upload"]
+    ms["structure"] += st["ms_structure"]
+    ms["parse"] += st["ms_parse"] + st["ms_patch"]
+    del buf
+    return files, d_out, read_err
+
+
+def _refused(path, f):
+    """the exception of a file the device reader refused: the host reader's, with its row, column and line"""
+    from . import _capi, chain_io
+    chain_io.loadtxt(path)
+    return RuntimeError("mcevidence_amd: the device chain reader refused %s (%s) but the host reader accepts it"
+                        % (path, "ragged lines" if f.status == _capi.FARM_RAGGED else
+                           "a field that is not a number at row %d, column %d" % (f.bad_row, f.bad_col)))
+
+
+def read_files(paths, device=0, wave_bytes=None):
+    """``[chain_io.loadtxt(p) for p in paths]`` parsed on GPU ``device`` in waves of many files (the farm reader alone): one entry per
+    file, the same array bit for bit, or the exception the host reader raises for a file it refuses (a ragged file, a field that is
+    not a number) -- that file only."""
+    import torch
+    from . import _capi, chain_io
+    _capi.require_device()
+    device = int(device)
+    wave_bytes = DEFAULT_WAVE_BYTES if wave_bytes is None else max(TILE, int(wave_bytes) // TILE * TILE)
+    paths = list(paths)
+    lens = [os.stat(p).st_size for p in paths]
+    out = [None] * len(paths)
+    ms = dict(read=0.0, upload=0.0, structure=0.0, parse=0.0)
+    with torch.cuda.device(device), ThreadPoolExecutor(max_workers=MAX_READERS) as pool:
+        for wave in farm_waves([farm_layout([n])[1] for n in lens], wave_bytes):
+            files, d_out, read_err = _parse_wave(pool, device, wave_bytes, [paths[i] for i in wave], [lens[i] for i in wave], ms)
+            host = d_out.cpu().numpy()
+            for k, i in enumerate(wave):
+                f = files[k]
+                try:
+                    if paths[i] in read_err:
+                        raise read_err[paths[i]]
+                    if f.status != _capi.FARM_OK:
+                        raise _refused(paths[i], f)
+                    a = host[int(f.tok_base):int(f.tok_base) + int(f.nrows * f.ncols)].reshape(int(f.nrows), int(f.ncols)).copy()
+                    out[i] = chain_io._shape_like_numpy(a, 2)
+                except Exception as e:
+                    out[i] = e
+    return out
+
+
+class _Root(object):
+    __slots__ = ("index", "files", "lens", "size", "ndim", "pvol", "burn", "thin", "parts", "ncols", "nrows", "nparam", "nd", "rc", "keep", "problem", "scal")
+
+
+def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
+                             idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
+                             require_resident=False, wave_bytes=None, split=False):
+    """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
+    of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
+    per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
+    ``info["route"]`` = ``"farm"``, ``"resident"`` or ``"host"``).
+
+    Roots are packed into waves whose padded text fits ``wave_bytes`` (all files of a root in one wave; a larger root takes the
+    per-root resident route).  A root the farm does not cover -- ``split``, a decline of ``resident.plan`` or one found on the device
+    -- goes to ``evidence_from_files`` after the farm's work; ``require_resident=True`` makes a decline ``ValueError(reason)``.
+    Under an initialised process group the whole call goes to ``evidence_many`` over ``MCEvidence`` objects.  A failing root raises
+    what the host route raises for it (the first in input order), or sits in its slot with ``return_exceptions=True``; it never
+    changes another root's result.  Without a GPU: ``RuntimeError``."""
+    from . import _capi
+    _capi.require_device()
+    roots = list(roots)
+    n = len(roots)
+    ndims = _per_root(ndim, n, "ndim")
+    pvols = _per_root(priorvolume, n, "priorvolume")
+    burns = _per_root(burnlen, n, "burnlen")
+    thins = _per_root(thinlen, n, "thinlen")
+    common = dict(kmax=kmax, idchain=idchain, idpattern=idpattern, iw=iw, ilike=ilike, itheta=itheta)
+    if _res._distributed():
+        from .evidence import MCEvidence, evidence_many
+        extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], **extra) for i, r in enumerate(roots)]
+        return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
+    import torch
+    from .evidence import HipBackend
+    backend = backend or HipBackend()
+    device = int(device)
+    wave_bytes = DEFAULT_WAVE_BYTES if wave_bytes is None else max(TILE, int(wave_bytes) // TILE * TILE)
+    kmax_eff = max(2, int(kmax))
+    results = [None] * n
+    fallback = {}                                  # index -> reason (None: not examined by the farm)
+    ms = dict(read=0.0, upload=0.0, structure=0.0, parse=0.0, prep=0.0, feed=0.0)
+    counts = dict(roots=n, farm=0, waves=0, files=0, fallback=0)
+
+    def fail(i, exc):
+        results[i] = exc
+
+    # ---- planning: pure, per root ----------------------------------------------------------------------------------------------------
+    todo = []
+    for i, root in enumerate(roots):
+        reason = _res.RESIDENT if _res._is_file_root(root) else _res.REASONS["not_files"]
+        if reason == _res.RESIDENT and split:
+            reason = "split: the random split is drawn per root on the host"
+        if reason == _res.RESIDENT:
+            reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i])
+        if reason != _res.RESIDENT:
+            fallback[i] = reason
+            continue
+        try:
+            r = _Root()
+            r.index, r.files = i, _res._resolve_files(root, idchain, idpattern)
+            r.lens = [os.stat(p).st_size for p in r.files]
+            r.size = farm_layout(r.lens)[1]
+            r.ndim, r.pvol, r.burn, r.thin, r.rc, r.keep, r.problem, r.scal = ndims[i], pvols[i], burns[i], thins[i], None, None, None, None
+            todo.append(r)
+        except Exception as e:                     # (no files, an unreadable path: what the host route raises too)
+            fail(i, e)
+    cov = "single" if covtype is None else covtype
+
+    with torch.cuda.device(device), ThreadPoolExecutor(max_workers=MAX_READERS) as pool:
+        dev = "cuda:%d" % device
+        stream = torch.cuda.current_stream(device)
+        for wave in farm_waves([r.size for r in todo], wave_bytes):
+            wroots = [todo[k] for k in wave]
+            if len(wroots) == 1 and wroots[0].size > wave_bytes:
+                fallback[wroots[0].index] = None   # larger than a wave: the per-root resident route
+                continue
+            counts["waves"] += 1
+            paths = [p for r in wroots for p in r.files]
+            lens = [x for r in wroots for x in r.lens]
+            files, d_out, read_err = _parse_wave(pool, device, wave_bytes, paths, lens, ms)
+            counts["files"] += len(paths)
+
+            # ---- per root: its files' verdicts, burn-in, the decline cases known now -------------------------------------------------
+            t0 = time.perf_counter()
+            plain, at = [], 0
+            for r in wroots:
+                ff = [files[at + k] for k in range(len(r.files))]
+                fp = r.files
+                at += len(fp)
+                try:
+                    for path, f in zip(fp, ff):
+                        if path in read_err:
+                            raise read_err[path]
+                        if f.status != _capi.FARM_OK:
+                            raise _refused(path, f)      # (the host reader's ValueError with the row, column and line of the first bad field)
+                    shapes = [(int(f.nrows), int(f.ncols) if f.nrows else 1) for f in ff]       # (np.loadtxt: an empty file is (0, 1))
+                    reason = _res.plan(thinlen=r.thin, ncols=[c for _, c in shapes])
+                    if reason != _res.RESIDENT:
+                        fallback[r.index] = reason
+                        continue
+                    r.ncols = shapes[0][1]
+                    if r.ncols <= max(iw, ilike, itheta) or min(iw, ilike, itheta) < 0:
+                        raise ValueError("columns iw=%d ilike=%d itheta=%d of a chain with %d" % (iw, ilike, itheta, r.ncols))
+                    r.nparam = r.ncols - itheta
+                    nd = r.nparam if r.ndim is None else int(r.ndim)
+                    if nd < 1:
+                        raise ValueError("ndim must be >= 1 (got %r)" % (r.ndim,))
+                    if nd > r.nparam:
+                        logger.warning("ndim=%s exceeds the %s parameter columns of the chain; using all of them" % (r.ndim, r.nparam))
+                        nd = r.nparam
+                    r.nd = nd
+                    if r.thin not in (0, 1):
+                        # integer or bin thinning: the per-root calls, on views of the wave's buffer
+                        tensors = [d_out[int(f.tok_base):int(f.tok_base) + nr * nc].view(nr, nc) if nr else torch.empty((0, 1), dtype=torch.float64, device=dev)
+                                   for f, (nr, nc) in zip(ff, shapes)]
+                        r.rc = _res.ResidentChains(tensors, r.burn, r.thin, iw, ilike, itheta, device)
+                        r.nrows = r.rc.nrows
+                    else:
+                        r.parts = []
+                        for f, (nr, nc) in zip(ff, shapes):
+                            start = 0
+                            if r.burn > 0:                     # (chains.MCSamples.removeBurn; csrc/chain_prep.hpp: burn_start)
+                                start = min(nr, int(nr * r.burn) if r.burn < 1 else int(r.burn))
+                            r.parts.append((d_out.data_ptr() + (int(f.tok_base) + start * nc) * 8 if nr - start > 0 else 0, nr - start))
+                        r.nrows = sum(m for _, m in r.parts)
+                    reason = _res.plan(covtype=cov, ndim=nd, nparam=r.nparam, nrows=r.nrows)
+                    if reason != _res.RESIDENT:
+                        fallback[r.index] = reason
+                        r.rc = None
+                        continue
+                    plain.append(r)
+                except _res.ResidentDecline as d:
+                    fallback[r.index] = d.reason
+                except Exception as e:
+                    fail(r.index, e)
+
+            # ---- preparation: one set of launches for the unthinned roots, the per-root calls for the thinned ones ---------------
+            ready = []
+            seg = [r for r in plain if r.rc is None]
+            if seg:
+                nrows = sum(r.nrows for r in seg)
+                parts = [p for r in seg for p in r.parts]
+                params = torch.empty(sum(r.nrows * r.nparam for r in seg), dtype=torch.float64, device=dev)
+                w = torch.empty(nrows, dtype=torch.float64, device=dev)
+                like = torch.empty(nrows, dtype=torch.float64, device=dev)
+                fs = torch.empty(nrows, dtype=torch.float64, device=dev)
+                wsb = _capi.chain_farm_prep_workspace_bytes(len(seg), len(parts), nrows)
+                ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+                scal = _capi.chain_farm_prep_dev([len(r.parts) for r in seg], [r.ncols for r in seg], parts, iw, ilike, itheta, pos_lnp,
+                                                 params.data_ptr(), w.data_ptr(), like.data_ptr(), fs.data_ptr(), ws.data_ptr(), wsb, stream.cuda_stream)
+                row0 = par0 = 0
+                for k, r in enumerate(seg):
+                    r.scal = tuple(scal[k])
+                    r.keep = (params, w, fs)
+                    r.problem = (params.data_ptr() + par0 * 8, r.nrows, r.nparam, 0, 0, 0, r.nd, 0 if cov == "all" else 1, kmax_eff,
+                                 w.data_ptr() + row0 * 8, fs.data_ptr() + row0 * 8)
+                    row0 += r.nrows
+                    par0 += r.nrows * r.nparam
+            for r in plain:
+                try:
+                    if r.rc is not None:
+                        s1 = r.rc._gather(None, want=("params", "w", "like"))
+                        n1 = int(s1["w"].shape[0])
+                        fs1 = torch.empty(n1, dtype=torch.float64, device=dev)
+                        wsb = _capi.chain_reduce_workspace_bytes(n1)
+                        ws1 = r.rc._ws(wsb)
+                        r.scal = _capi.chain_reduce_dev(s1["like"].data_ptr(), s1["w"].data_ptr(), n1, pos_lnp, fs1.data_ptr(), ws1.data_ptr(), wsb,
+                                                        stream.cuda_stream)
+                        r.keep = (s1, fs1)
+                        r.problem = (s1["params"].data_ptr(), n1, r.nparam, 0, 0, 0, r.nd, 0 if cov == "all" else 1, kmax_eff, s1["w"].data_ptr(),
+                                     fs1.data_ptr())
+                    logLmax, SumW, nan_like, bad_w = r.scal
+                    if bad_w:
+                        raise ValueError("weight contains NaN or infinity")
+                    if nan_like or math.isinf(logLmax):
+                        raise ValueError("fs contains NaN or +infinity")
+                    ready.append(r)
+                except Exception as e:
+                    fail(r.index, e)
+            stream.synchronize()
+            ms["prep"] += _res._ms(t0)
+
+            # ---- feed: every root of the wave in one library call -----------------------------------------------------------------
+            t0 = time.perf_counter()
+            if ready:
+                with backend._scoped():
+                    got = _capi.evidence_feed_batch_dev([r.problem for r in ready], device=device, return_exceptions=True)
+                    for r, g in zip(ready, got):
+                        if isinstance(g, Exception):
+                            # (the library words only the first failure of a batch: this problem alone, for its own message)
+                            try:
+                                p = r.problem
+                                _capi.evidence_feed_part_dev(p[0], p[1], p[2], 0, 0, 0, p[6], p[7], p[8], p[9], p[10], 0, 1, device=device, want_checksum=False)
+                                fail(r.index, g)
+                            except Exception as e:
+                                fail(r.index, e)
+                            continue
+                        dotp, jac, _ = g
+                        logLmax, SumW = r.scal[0], r.scal[1]
+                        n1 = r.problem[1]
+                        mle = np.zeros(kmax_eff)
+                        try:
+                            for k in range(1, kmax_eff):        # (evidence.MCEvidence._feed_finish; reference :1120-1131)
+                                mle[k] = math.log(SumW * (dotp[k] / (n1 * k + 1.0)) * jac) + logLmax - math.log(r.pvol)
+                        except Exception as e:
+                            fail(r.index, e)
+                            continue
+                        out = mle[1:]
+                        counts["farm"] += 1
+                        results[r.index] = out if not info else (out, {"NparamsMC": r.nparam, "Nsamples_read": n1, "Nparams_read": r.nparam,
+                                                                        "NparamsCosmo": r.nd, "Nsamples": str(n1), "route": FARM})
+            ms["feed"] += _res._ms(t0)
+            for r in wroots:
+                r.rc = r.keep = r.parts = None
+            del d_out
+
+    # ---- the roots the farm does not cover, after its work ----------------------------------------------------------------------------
+    for i in sorted(fallback):
+        counts["fallback"] += 1
+        try:
+            kw = dict(common, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], pos_lnp=pos_lnp, split=split, info=True, verbose=0)
+            if covtype != "all":
+                kw["covtype"] = covtype
+            if backend is not None:
+                kw["backend"] = backend
+            mle, inf = _res.evidence_from_files(roots[i], require_resident=require_resident, **kw)
+            results[i] = (mle, inf) if info else mle
+        except Exception as e:
+            fail(i, e)
+    LAST_STATS.clear()
+    LAST_STATS.update(ms=ms, counts=counts)
+    if not return_exceptions:
+        for x in results:
+            if isinstance(x, Exception):
+                raise x
+    return results

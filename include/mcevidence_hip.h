@@ -199,6 +199,28 @@ size_t mce_feed_problem_size(void);   /* sizeof(mce_feed_problem) as built: lets
  * included) as in the host-pointer call. */
 int mce_evidence_feed_batch_dev_f64(mce_feed_problem *problems, int64_t nprob, int32_t device);
 
+/* Convergence batches (reference MCEvidence.py:1034-1131 with nbatch / brange: ln E from the FIRST S_b rows of the chain, for B
+ * sizes) in one call, from one upload.  prefix[nprefix] (host array, non-decreasing, kmax + 1 <= prefix[b] <= n1) holds the sizes;
+ * logl[n1] the log-likelihoods themselves, not yet shifted.  Entry b equals mce_evidence_feed_f64 on S1[:prefix[b]], S2,
+ * w[:prefix[b]] and fs = logl[:p] - max(logl[:p]) -- except that with cov_mode 0 the eigen-system and the Jacobian are those of ALL
+ * n1 (+ n2) rows and the same for every b, as in the reference (:1034-1037, :1057).  Cross evidence searches all of S2 for every
+ * batch (:1075): one search serves them all.  cov_mode 1 with S2 -> MCE_ERR_INVALID (see mce_evidence_feed_f64).
+ *   Outputs (host): dotp[nprefix * kmax], loglmax[b] = max(logl[:prefix[b]]) (NaN once a NaN lies below prefix[b], as np.amax),
+ *       jacobian[nprefix].  A non-positive eigenvalue of any prefix -> MCE_ERR_INVALID, the prefix named in the message.
+ *   mce_options.verify applies to each distinct search; mce_last_verify_rows() then counts the rows of all of them.
+ * The host waits twice whatever nprefix is (for the covariances -- the eigen-solves are the host's -- and at the end). */
+#define MCE_MAX_PREFIX 256
+int mce_evidence_feed_prefix_f64(const double *S1, int64_t n1, int64_t ld1, const double *S2, int64_t n2, int64_t ld2,
+                                 int32_t d, int32_t cov_mode, int32_t kmax, const double *w, const double *logl,
+                                 const int64_t *prefix, int32_t nprefix, double *dotp, double *loglmax, double *jacobian,
+                                 int32_t device);
+/* ... with S1 / S2 / w / logl as device pointers on `device`, produced on a stream the caller has synchronised (as for
+ * mce_evidence_feed_part_dev_f64; the inputs are copied, not modified).  prefix and the outputs stay host-side. */
+int mce_evidence_feed_prefix_dev_f64(const double *dS1, int64_t n1, int64_t ld1, const double *dS2, int64_t n2, int64_t ld2,
+                                     int32_t d, int32_t cov_mode, int32_t kmax, const double *d_w, const double *d_logl,
+                                     const int64_t *prefix, int32_t nprefix, double *dotp, double *loglmax, double *jacobian,
+                                     int32_t device);
+
 /* ---- device-pointer entry points (resident data, caller's stream) ------ */
 
 size_t mce_knn_workspace_bytes(int64_t nq, int64_t nr, int32_t d, int32_t K);

@@ -127,6 +127,10 @@ class FeedProblem(ctypes.Structure):
 SIGNATURES["mce_evidence_feed_batch_f64"] = (_c.c_int, [_c.POINTER(FeedProblem), _c.c_int64, _P, _c.c_int32])
 SIGNATURES["mce_feed_problem_size"] = (_c.c_size_t, [])
 SIGNATURES["mce_evidence_feed_batch_dev_f64"] = (_c.c_int, [_c.POINTER(FeedProblem), _c.c_int64, _c.c_int32])
+MCE_MAX_PREFIX = 256
+_PREFIX_ARGS = [_P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _P, _c.c_int32, _P, _P, _P, _c.c_int32]
+SIGNATURES["mce_evidence_feed_prefix_f64"] = (_c.c_int, _PREFIX_ARGS)
+SIGNATURES["mce_evidence_feed_prefix_dev_f64"] = (_c.c_int, _PREFIX_ARGS)
 
 
 class FarmFile(ctypes.Structure):
@@ -682,6 +686,54 @@ def evidence_feed_whiten(S1, d, kmax, w, fs, d_X_out, d_w_out, d_fs_out, device=
                                            d_X_out, d_w_out, d_fs_out, ctypes.byref(jac), ev.ctypes.data,
                                            ctypes.byref(csum) if want_checksum else None, int(device)))
     return float(jac.value), ev, (int(csum.value) if want_checksum else None)
+
+
+def _prefix_arg(prefix):
+    prefix = np.ascontiguousarray(prefix, dtype=np.int64)
+    if prefix.ndim != 1:
+        raise ValueError("prefix must be a 1-D sequence of row counts")
+    return prefix
+
+
+def evidence_feed_prefix(S1, S2, d, cov_mode, kmax, w, logl, prefix, device=0):
+    """Convergence batches in ONE library call (``mce_evidence_feed_prefix_f64``): entry b is ``evidence_feed`` on the first
+    ``prefix[b]`` rows of S1 with ``fs = logl[:p] - max(logl[:p])`` -- with ``cov_mode`` 0 whitened by the eigen-system of ALL rows.
+    ``logl``: the log-likelihoods, not shifted (a NaN makes every prefix that holds it NaN, like ``np.amax``).
+    Returns (dotp[B, kmax], loglmax[B], jacobian[B])."""
+    lib = load()
+    S1 = _rows_f64(S1, "samples", d, check=False)
+    S2 = None if S2 is None else _rows_f64(S2, "samples2", d, check=False)
+    w = _f64(w, "weight")
+    logl = np.ascontiguousarray(logl, dtype=np.float64)
+    if w.shape != (S1.shape[0],) or logl.shape != w.shape:
+        raise ValueError("weight and logl must have one entry per s1 row")
+    prefix = _prefix_arg(prefix)
+    B = len(prefix)
+    out = np.zeros((max(B, 1), max(int(kmax), 0)))
+    lmax = np.zeros(max(B, 1))
+    jac = np.zeros(max(B, 1))
+    check(lib.mce_evidence_feed_prefix_f64(S1.ctypes.data, S1.shape[0], S1.strides[0] // 8,
+                                           S2.ctypes.data if S2 is not None else None, 0 if S2 is None else S2.shape[0],
+                                           0 if S2 is None else S2.strides[0] // 8, int(d), int(cov_mode), int(kmax),
+                                           w.ctypes.data, logl.ctypes.data, prefix.ctypes.data if B else None, B,
+                                           out.ctypes.data, lmax.ctypes.data, jac.ctypes.data, int(device)))
+    return out[:B], lmax[:B], jac[:B]
+
+
+def evidence_feed_prefix_dev(dS1, n1, ld1, dS2, n2, ld2, d, cov_mode, kmax, d_w, d_logl, prefix, device=0):
+    """``evidence_feed_prefix`` with the inputs on the device already (``mce_evidence_feed_prefix_dev_f64``): device ADDRESSES on
+    ``device`` (rows ``ld`` doubles apart; ``dS2`` = 0 for auto evidence), produced on a stream the caller has synchronised.
+    ``prefix`` and the returns stay host-side."""
+    lib = load()
+    prefix = _prefix_arg(prefix)
+    B = len(prefix)
+    out = np.zeros((max(B, 1), max(int(kmax), 0)))
+    lmax = np.zeros(max(B, 1))
+    jac = np.zeros(max(B, 1))
+    check(lib.mce_evidence_feed_prefix_dev_f64(dS1 or None, int(n1), int(ld1), dS2 or None, int(n2) if dS2 else 0, int(ld2) if dS2 else 0, int(d),
+                                               int(cov_mode), int(kmax), d_w or None, d_logl or None, prefix.ctypes.data if B else None, B,
+                                               out.ctypes.data, lmax.ctypes.data, jac.ctypes.data, int(device)))
+    return out[:B], lmax[:B], jac[:B]
 
 
 def _devices_arg(devices):

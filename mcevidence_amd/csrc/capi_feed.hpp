@@ -309,26 +309,55 @@ int feed_stage_a(FeedJob& j, hipStream_t st)
     return MCE_OK;
 }
 
+// one eigen-system of the feed (stage B): cov[d*d] (row-major, as the covariance kernels left it) -> evec[d*d], the whitening
+// scales 1 / sqrt(lambda) and the eigenvalues (descending).  A covariance that is not finite or not positive definite fails.
+int feed_eig_system(const double* h_cov, int d, double* evec, double* scale, std::vector<double>& lam)
+{
+    std::vector<double> cov(h_cov, h_cov + (size_t)d * d), V;
+    jacobi_eig(cov, d, lam, V);
+    for (int i = 0; i < d; ++i) {
+        if (lam[i] != lam[i] || std::isinf(lam[i])) return fail(MCE_ERR_INVALID, "samples contain NaN or infinity (non-finite covariance)");
+        if (!(lam[i] > 0.0)) return fail(MCE_ERR_INVALID, "math domain error: covariance eigenvalue %d is %g (use fewer parameters, ndim)", i, lam[i]);
+    }
+    std::copy(V.begin(), V.end(), evec);
+    for (int i = 0; i < d; ++i) scale[i] = 1.0 / std::sqrt(lam[i]);
+    return MCE_OK;
+}
+
+// J = sqrt(det cov) from the eigenvalues
+double feed_jacobian(const std::vector<double>& lam)
+{
+    double logdet = 0.0;
+    for (double x : lam) logdet += std::log(x);
+    return std::exp(0.5 * logdet);
+}
+
 int feed_stage_b(FeedJob& j)
 {
     const int d = j.d();
     const int nsys = j.two_systems() ? 2 : 1;
     for (int sidx = 0; sidx < nsys; ++sidx) {
-        std::vector<double> cov(j.h_cov(sidx), j.h_cov(sidx) + (size_t)d * d), lam, V;
-        jacobi_eig(cov, d, lam, V);
-        for (int i = 0; i < d; ++i) {
-            if (lam[i] != lam[i] || std::isinf(lam[i])) return fail(MCE_ERR_INVALID, "samples contain NaN or infinity (non-finite covariance)");
-            if (!(lam[i] > 0.0)) return fail(MCE_ERR_INVALID, "math domain error: covariance eigenvalue %d is %g (use fewer parameters, ndim)", i, lam[i]);
-        }
-        std::copy(V.begin(), V.end(), j.h_evec(sidx));
-        for (int i = 0; i < d; ++i) j.h_scale(sidx)[i] = 1.0 / std::sqrt(lam[i]);
+        std::vector<double> lam;
+        const int rc = feed_eig_system(j.h_cov(sidx), d, j.h_evec(sidx), j.h_scale(sidx), lam);
+        if (rc != MCE_OK) return rc;
         if (sidx == 0) {
-            double logdet = 0.0;
-            for (int i = 0; i < d; ++i) logdet += std::log(lam[i]);
-            j.jac = std::exp(0.5 * logdet);
+            j.jac = feed_jacobian(lam);
             j.lam = lam;
         }
     }
+    return MCE_OK;
+}
+
+// out[r] = (S[r] . evec) * scale for the n rows of S (out may be S); evec / scale on the device already; enqueue only
+int launch_whiten(const double* S, int64_t n, int d, const double* d_evec, const double* d_scale, double* out, hipStream_t st)
+{
+    if (d > 63)
+        hipLaunchKernelGGL(mce::whiten_wide_kernel, dim3((unsigned)((n + mce::kWhitenRows - 1) / mce::kWhitenRows)), dim3(mce::kWhitenRows),
+                           mce::whiten_wide_lds_bytes(d), st, S, n, d, d_evec, d_scale, out);
+    else
+        hipLaunchKernelGGL(mce::whiten_kernel, dim3((unsigned)((n + mce::kWhitenRows - 1) / mce::kWhitenRows)), dim3(mce::kWhitenRows),
+                           mce::whiten_lds_bytes(d), st, S, n, d, d_evec, d_scale, out);
+    MCE_HIP(hipGetLastError());
     return MCE_OK;
 }
 
@@ -337,31 +366,29 @@ int feed_whiten(FeedJob& j, int sidx, double* rows, int64_t n, hipStream_t st)
     const int d = j.d();
     MCE_HIP(hipMemcpyAsync(j.d_evec(), j.h_evec(sidx), (size_t)d * d * sizeof(double), hipMemcpyHostToDevice, st));
     MCE_HIP(hipMemcpyAsync(j.d_scale(), j.h_scale(sidx), (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
-    if (d > 63)
-        hipLaunchKernelGGL(mce::whiten_wide_kernel, dim3((unsigned)((n + mce::kWhitenRows - 1) / mce::kWhitenRows)), dim3(mce::kWhitenRows),
-                           mce::whiten_wide_lds_bytes(d), st, rows, n, d, j.d_evec(), j.d_scale(), rows);
-    else
-        hipLaunchKernelGGL(mce::whiten_kernel, dim3((unsigned)((n + mce::kWhitenRows - 1) / mce::kWhitenRows)), dim3(mce::kWhitenRows),
-                           mce::whiten_lds_bytes(d), st, rows, n, d, j.d_evec(), j.d_scale(), rows);
-    MCE_HIP(hipGetLastError());
+    return launch_whiten(rows, n, d, j.d_evec(), j.d_scale(), rows, st);
+}
+
+// the whitening kernels stage more LDS than the default limit: raise it once per device
+int whiten_attr_once()
+{
+    static std::atomic<bool> attr_set[kMaxDevices];
+    int dev = 0;
+    MCE_HIP(hipGetDevice(&dev));
+    if (dev < kMaxDevices && !attr_set[dev].load()) {
+        MCE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mce::whiten_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mce::whiten_lds_bytes(63)));
+        MCE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mce::whiten_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)mce::whiten_wide_lds_bytes(kFeedMaxDim)));
+        attr_set[dev].store(true);
+    }
     return MCE_OK;
 }
 
 int feed_stage_c(FeedJob& j, hipStream_t st)
 {
     const mce_feed_problem& q = *j.q;
-    {
-        static std::atomic<bool> attr_set[kMaxDevices];
-        int dev = 0;
-        MCE_HIP(hipGetDevice(&dev));
-        if (dev < kMaxDevices && !attr_set[dev].load()) {
-            MCE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mce::whiten_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mce::whiten_lds_bytes(63)));
-            MCE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mce::whiten_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)mce::whiten_wide_lds_bytes(kFeedMaxDim)));
-            attr_set[dev].store(true);
-        }
-    }
-    int rc;
+    int rc = whiten_attr_once();
+    if (rc != MCE_OK) return rc;
     if (j.two_systems()) {
         rc = feed_whiten(j, 0, j.dS1(), q.n1, st);
         if (rc != MCE_OK) return rc;

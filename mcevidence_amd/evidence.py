@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import logging
 import math
+import os
 import statistics
 from collections import namedtuple
 
@@ -40,8 +41,11 @@ class HipBackend(object):
 
     name = "hip"
 
-    def __init__(self, devices=None, verify=True, recheck_rows=None):
+    def __init__(self, devices=None, verify=True, recheck_rows=None, batch_feed=None):
         self.devices = devices
+        # convergence batches (brange / nbatch) in ONE library call (mce_evidence_feed_prefix_f64) instead of one host round
+        # trip per batch.  None: MCE_BATCH_FEED=1 in the environment turns it on; the default is off (docs/design/batch_feed.md)
+        self.batch_feed = (os.environ.get("MCE_BATCH_FEED") == "1") if batch_feed is None else bool(batch_feed)
         self.verify = verify        # multi-rank runs: compare a fingerprint of the inputs across the ranks on every call
         # run-time certificate of the search (mce_options.verify): after every single-process search this many query rows,
         # spread over the set, are re-checked by an exact fp64 scan of all reference rows that shares nothing with the
@@ -119,6 +123,17 @@ class HipBackend(object):
         with self._scoped():
             dotp, jac, _ = _capi.evidence_feed(S1, S2, ndim, cov_mode, kmax, weight, fs)
         return dotp, jac
+
+    def evidence_feed_prefix(self, S1, S2, ndim, cov_mode, kmax, weight, logL, sizes):
+        """the batches of a convergence run -- the first ``sizes[b]`` rows of S1, for every b -- in one library call from one upload.
+        Returns (dotp[B, kmax], logLmax[B], J[B]), or None when this route does not apply: switched off, a multi-process or
+        multi-device run, more than 127 parameters."""
+        from . import parallel
+        if not self.batch_feed or ndim > 127 or parallel.is_distributed() or self.devices not in (None, [0], (0,)):
+            return None
+        from . import _capi
+        with self._scoped():
+            return _capi.evidence_feed_prefix(S1, S2, ndim, cov_mode, kmax, weight, logL, sizes)
 
     def evidence_feed_batch(self, problems):
         """many problems (tuples with evidence_feed's arguments) in one library call; under torchrun
@@ -366,6 +381,31 @@ class MCEvidence(object):
             return None
         return self._feed_finish(ctx, got[0], got[1], logPriorVolume)
 
+    def _batch_route_applies(self, verbose, rand, covtype):
+        """convergence batches through ``backend.evidence_feed_prefix``: the first S_b rows in chain order, eigen-systems the
+        library's (split + 'single' keeps np.linalg.eig, as in ``_feed_route_applies``), every size searchable; anything else
+        takes the host loop, which raises what it always raised"""
+        if self.brange is None or rand or verbose > 1 or covtype not in ("all", "single") or (self.split and covtype == "single"):
+            return False
+        if not hasattr(self.backend, "evidence_feed_prefix"):
+            return False
+        n1 = self.gd.get_shape(name="s1")[0]
+        return all(self.kmax + 1 <= int(ns[0]) <= n1 for ns in self.nchain)
+
+    def _evidence_batch_feed(self, covtype, pos_lnp, logPriorVolume):
+        """evidence() of a batched object with the device work of ALL batches in one library call; the same quantities as the
+        host loop (reference :1034-1131); returns MLE[nbatch, kmax] or None if the backend declines."""
+        s1, lnp, weight = self.gd.arrays("s1")
+        s2 = self.gd.arrays("s2")[0] if self.split else None
+        logL = np.asarray(-lnp if pos_lnp else lnp, dtype=np.float64)
+        sizes = [int(ns[0]) for ns in self.nchain]
+        got = self.backend.evidence_feed_prefix(s1, s2, self.ndim, 0 if covtype == "all" else 1, self.kmax,
+                                                np.asarray(weight, dtype=np.float64), logL, sizes)
+        if got is None:
+            return None
+        dotp, logLmax, jac = got
+        return np.stack([self._feed_finish((S, logLmax[b]), dotp[b], jac[b], logPriorVolume) for b, S in enumerate(sizes)])
+
     def _report(self, MLE, verbose, info):
         if verbose > 0:
             for k in range(1, self.kmax):
@@ -393,6 +433,12 @@ class MCEvidence(object):
             out = self._evidence_device_feeders(covtype, pos_lnp, logPriorVolume)
             if out is not None:
                 return self._report(out[1:], verbose, info)
+
+        # ---- batch-feed route: the convergence batches (brange / nbatch) in one library call (opt-in: HipBackend(batch_feed=True)) ----
+        if self._batch_route_applies(verbose, rand, covtype):
+            out = self._evidence_batch_feed(covtype, pos_lnp, logPriorVolume)
+            if out is not None:
+                return self._report(out[:, 1:], verbose, info)
 
         if covtype == "all":
             covstat = self.get_covariance()

@@ -90,6 +90,12 @@ def _shape_like_numpy(out, ndmin):
     return out
 
 
+def refused(path, why, ndmin=2):
+    """for a file the device reader refused: the host reader's own ValueError (row, column, line), else a RuntimeError that says so"""
+    loadtxt(path, ndmin)
+    return RuntimeError("mcevidence_amd: the device chain reader refused %s (%s) but the host reader accepts it" % (path, why))
+
+
 def loadtxt_device(path, ndmin=2, device=0, return_stats=False):
     """``loadtxt(path, ndmin)`` computed on GPU ``device``: same array, bit for bit.  Always the device -- ``RuntimeError`` without
     one, never a quiet host read.  A ragged line or a field that is not a number raises what ``loadtxt`` raises for the file,
@@ -106,8 +112,7 @@ def loadtxt_device(path, ndmin=2, device=0, return_stats=False):
             try:
                 out, stats = _capi.chain_dev_parse(view.ctypes.data if view is not None else None, size, device)
             except ValueError as dev_err:
-                loadtxt(path, ndmin)            # raises ValueError with the row, column and line of the first bad field
-                raise RuntimeError("mcevidence_amd: the device chain reader refused %s (%s) but the host reader accepts it" % (path, dev_err))
+                raise refused(path, dev_err, ndmin)
             finally:
                 del view
         finally:

@@ -16,22 +16,12 @@
 
 namespace {
 
-struct FarmDev {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct FarmDev : ReaderDev {
     int64_t capacity = 0, tile_cap = 0;
-    unsigned char* text = nullptr;
     char* staging = nullptr;                      // pinned, `capacity` bytes
-    unsigned char *tile_kind = nullptr, *tile_in = nullptr;
-    unsigned *tile_ntok = nullptr, *tile_nterm = nullptr;
-    unsigned long long *tok_base = nullptr, *term_base = nullptr;
-    int64_t *tok_off = nullptr, *tok_line = nullptr;
-    size_t tok_cap = 0;
-    mce::ChainPatch* list = nullptr;
+    mce::ChainPatch* list = nullptr;          // the undecided tokens of a wave and their fixes
     double* fix = nullptr;
-    size_t list_cap = 0;
-    uint64_t* pow5 = nullptr;
-    mce::ChainTotals* tot = nullptr;
+    size_t tok_cap = 0, list_cap = 0;
     // per file: offsets | lengths | first tiles (file_cap + 1 each), first tokens (file_cap + 1), verdicts (file_cap)
     int64_t* d_ftab = nullptr;
     int64_t* d_ftok0 = nullptr;
@@ -46,18 +36,16 @@ struct FarmDev {
     int64_t allocs = 0, allocs_wave = 0, grows = 0, waves = 0, files_total = 0, patched = 0;
     double ms_upload = 0.0, ms_structure = 0.0, ms_parse = 0.0, ms_patch = 0.0;
 
-    ~FarmDev()
+    ~FarmDev()          // (what the wave adds; ~ReaderDev frees the rest and the stream)
     {
         int cur = 0;
         (void)hipGetDevice(&cur);
         if (cur != device) (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : {(void*)text, (void*)tile_kind, (void*)tile_in, (void*)tile_ntok, (void*)tile_nterm, (void*)tok_base, (void*)term_base, (void*)tok_off,
-                        (void*)tok_line, (void*)list, (void*)fix, (void*)pow5, (void*)tot, (void*)d_ftab, (void*)d_ftok0, (void*)d_files})
+        for (void* p : {(void*)list, (void*)fix, (void*)d_ftab, (void*)d_ftok0, (void*)d_files})
             if (p) (void)hipFree(p);
         if (staging) (void)hipHostFree(staging);
         if (h_small) (void)hipHostFree(h_small);
-        if (stream) (void)hipStreamDestroy(stream);
         if (cur != device) (void)hipSetDevice(cur);
     }
 };
@@ -94,27 +82,21 @@ int farm_reserve_files(FarmDev& c, size_t nfiles)
     return MCE_OK;
 }
 
-int farm_reserve_tokens(FarmDev& c, size_t ntok)
+// two arrays of one capacity, grown together to n + 25 % + 1024 elements when n do not fit
+template <class A, class B>
+int farm_reserve(FarmDev& c, size_t n, size_t& cap, A*& a, const char* what_a, B*& b, const char* what_b)
 {
-    if (ntok <= c.tok_cap && c.tok_off) return MCE_OK;
-    const size_t cap = ntok + ntok / 4 + 1024;
+    if (n <= cap && a) return MCE_OK;
+    const size_t grown = n + n / 4 + 1024;
     int rc;
-    if ((rc = farm_alloc(c, c.tok_off, cap, "the token offsets")) != MCE_OK) return rc;
-    if ((rc = farm_alloc(c, c.tok_line, cap, "the token lines")) != MCE_OK) return rc;
-    c.tok_cap = cap;
+    if ((rc = farm_alloc(c, a, grown, what_a)) != MCE_OK) return rc;
+    if ((rc = farm_alloc(c, b, grown, what_b)) != MCE_OK) return rc;
+    cap = grown;
     return MCE_OK;
 }
 
-int farm_reserve_list(FarmDev& c, size_t n)
-{
-    if (n <= c.list_cap && c.list) return MCE_OK;
-    const size_t cap = n + n / 4 + 1024;
-    int rc;
-    if ((rc = farm_alloc(c, c.list, cap, "the list of undecided tokens")) != MCE_OK) return rc;
-    if ((rc = farm_alloc(c, c.fix, cap, "the patched values")) != MCE_OK) return rc;
-    c.list_cap = cap;
-    return MCE_OK;
-}
+int farm_reserve_tokens(FarmDev& c, size_t ntok) { return farm_reserve(c, ntok, c.tok_cap, c.tok_off, "the token offsets", c.tok_line, "the token lines"); }
+int farm_reserve_list(FarmDev& c, size_t n) { return farm_reserve(c, n, c.list_cap, c.list, "the list of undecided tokens", c.fix, "the patched values"); }
 
 int farm_create(FarmDev& c)
 {
@@ -208,13 +190,7 @@ int mce_chain_farm_structure(void* handle, const int64_t* file_off, const int64_
     MCE_HIP(hipMemcpyAsync(c.d_ftab, h_tab, 3 * F * sizeof(int64_t), hipMemcpyHostToDevice, c.stream));
     MCE_HIP(hipMemsetAsync(c.tot, 0, sizeof(ChainTotals), c.stream));
     hipLaunchKernelGGL(farm_pad_kernel, dim3(chain_grid(nfiles, 1)), dim3(kChainThreads), 0, c.stream, c.text, c.d_ftab, c.d_ftab + F, (int64_t)nfiles, wave_bytes);
-    const unsigned grid = chain_grid(c.ntiles, 1);
-    hipLaunchKernelGGL(chain_tile_kernel<0>, dim3(grid), dim3(kChainThreads), 0, c.stream, c.text, c.ntiles, c.tile_kind, c.tile_in, c.tile_ntok, c.tile_nterm,
-                       c.tok_base, c.term_base, (int64_t*)nullptr, (int64_t*)nullptr);
-    hipLaunchKernelGGL(chain_scan_state_kernel, dim3(1), dim3(kChainScanThreads), 0, c.stream, c.tile_kind, c.ntiles, c.tile_in);
-    hipLaunchKernelGGL(chain_tile_kernel<1>, dim3(grid), dim3(kChainThreads), 0, c.stream, c.text, c.ntiles, c.tile_kind, c.tile_in, c.tile_ntok, c.tile_nterm,
-                       c.tok_base, c.term_base, (int64_t*)nullptr, (int64_t*)nullptr);
-    hipLaunchKernelGGL(chain_scan_count_kernel, dim3(1), dim3(kChainScanThreads), 0, c.stream, c.tile_ntok, c.tile_nterm, c.ntiles, c.tok_base, c.term_base, c.tot);
+    reader_count_passes(c, c.ntiles);
     MCE_HIP(hipGetLastError());
     ChainTotals* h_tot = reinterpret_cast<ChainTotals*>(c.h_small + 3 * F * sizeof(int64_t));
     mce_farm::FileVerdict* h_files = reinterpret_cast<mce_farm::FileVerdict*>(h_tot + 1);
@@ -225,9 +201,7 @@ int mce_chain_farm_structure(void* handle, const int64_t* file_off, const int64_
     const int64_t ntok = (int64_t)h_tot->ntok;
     if (ntok < 0 || ntok > wave_bytes) return fail(MCE_ERR_HIP, "chain farm: %lld tokens in %lld bytes", (long long)ntok, (long long)wave_bytes);
     if ((rc = farm_reserve_tokens(c, (size_t)ntok)) != MCE_OK) return rc;
-    if (ntok > 0)
-        hipLaunchKernelGGL(chain_tile_kernel<2>, dim3(grid), dim3(kChainThreads), 0, c.stream, c.text, c.ntiles, c.tile_kind, c.tile_in, c.tile_ntok, c.tile_nterm,
-                           c.tok_base, c.term_base, c.tok_off, c.tok_line);
+    if (ntok > 0) reader_token_pass(c, c.ntiles);
     hipLaunchKernelGGL(farm_files_kernel, dim3(chain_grid(nfiles + 1, kChainThreads)), dim3(kChainThreads), 0, c.stream, c.tok_line, c.d_ftab + 2 * F, (int64_t)nfiles,
                        c.tok_base, c.ntiles, c.tot, c.d_files, c.d_ftok0);
     if (ntok > 0)
@@ -275,39 +249,24 @@ int mce_chain_farm_parse(void* handle, double* d_out, mce_farm_file* files, int3
     if (rc != MCE_OK) return rc;
     const auto t_p = std::chrono::steady_clock::now();
     int64_t nlist = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        MCE_HIP(hipMemsetAsync(&c.tot->nlist, 0, sizeof(unsigned long long), c.stream));
-        hipLaunchKernelGGL(chain_parse_kernel, dim3(chain_grid(c.ntok, kChainThreads)), dim3(kChainThreads), 0, c.stream, reinterpret_cast<const char*>(c.text),
-                           c.wave_bytes, c.tok_off, c.ntok, c.pow5, d_out, c.list, (int64_t)c.list_cap, c.tot);
-        MCE_HIP(hipGetLastError());
-        ChainTotals* h_tot = reinterpret_cast<ChainTotals*>(c.h_small);
-        MCE_HIP(hipMemcpyAsync(h_tot, c.tot, sizeof(ChainTotals), hipMemcpyDeviceToHost, c.stream));
-        MCE_HIP(hipStreamSynchronize(c.stream));
-        nlist = (int64_t)h_tot->nlist;
-        if (nlist <= (int64_t)c.list_cap) break;
-        if (pass == 1) return fail(MCE_ERR_HIP, "chain farm: the list of undecided tokens changed between two passes (%lld > %zu)", (long long)nlist, c.list_cap);
-        if ((rc = farm_reserve_list(c, (size_t)nlist)) != MCE_OK) return rc;          // (a wave of nan columns or 25-digit fields: grown once)
+    ChainTotals* h_tot = reinterpret_cast<ChainTotals*>(c.h_small);
+    if ((rc = reader_parse(c, "chain farm", c.wave_bytes, c.ntok, d_out, c.list, (int64_t)c.list_cap, false, h_tot, &nlist)) != MCE_OK) return rc;
+    if (nlist > (int64_t)c.list_cap) {          // (a wave of nan columns or 25-digit fields: grown once)
+        if ((rc = farm_reserve_list(c, (size_t)nlist)) != MCE_OK) return rc;
+        if ((rc = reader_parse(c, "chain farm", c.wave_bytes, c.ntok, d_out, c.list, (int64_t)c.list_cap, true, h_tot, &nlist)) != MCE_OK) return rc;
     }
     c.ms_parse = ms_since(t_p);
     if (nlist == 0) return MCE_OK;
     const auto t_d = std::chrono::steady_clock::now();
-    std::vector<ChainPatch> patch((size_t)nlist);
-    MCE_HIP(hipMemcpyAsync(patch.data(), c.list, (size_t)nlist * sizeof(ChainPatch), hipMemcpyDeviceToHost, c.stream));
-    MCE_HIP(hipStreamSynchronize(c.stream));
+    std::vector<ChainPatch> patch;          // strtod on the staging bytes (a token holds no pad byte, so these are the file's own)
+    std::vector<double> fixed;
+    std::vector<size_t> failed;
+    if ((rc = reader_host_fixes(c, "chain farm", c.list, nlist, c.ntok, c.wave_bytes, c.staging, patch, fixed, failed)) != MCE_OK) return rc;
     std::vector<int64_t> tok0((size_t)nfiles), bad_tok((size_t)nfiles, -1);
     for (int32_t f = 0; f < nfiles; ++f) tok0[(size_t)f] = c.verdicts[(size_t)f].tok0;
-    std::vector<double> fixed((size_t)nlist);
-    for (size_t i = 0; i < patch.size(); ++i) {
-        const ChainPatch& p = patch[i];
-        if (p.token < 0 || p.token >= c.ntok || p.offset < 0 || p.length < 0 || p.offset + p.length > c.wave_bytes)
-            return fail(MCE_ERR_HIP, "chain farm: a listed token lies outside the text (token %lld, offset %lld, length %lld)", (long long)p.token,
-                        (long long)p.offset, (long long)p.length);
-        // strtod on the staging bytes (a token holds no pad byte, so these are the file's own)
-        if (!mce_parse::parse_slow(c.staging + p.offset, c.staging + p.offset + p.length, &fixed[i])) {
-            fixed[i] = std::nan("");
-            const int64_t f = mce_farm::file_of_token(tok0.data(), nfiles, p.token);
-            if (bad_tok[(size_t)f] < 0 || p.token < bad_tok[(size_t)f]) bad_tok[(size_t)f] = p.token;
-        }
+    for (size_t i : failed) {
+        const int64_t token = patch[i].token, f = mce_farm::file_of_token(tok0.data(), nfiles, token);
+        if (bad_tok[(size_t)f] < 0 || token < bad_tok[(size_t)f]) bad_tok[(size_t)f] = token;
     }
     for (int32_t f = 0; f < nfiles; ++f) {
         if (bad_tok[(size_t)f] < 0 || files[f].status != MCE_FARM_OK || files[f].ncols < 1) continue;
@@ -316,10 +275,7 @@ int mce_chain_farm_parse(void* handle, double* d_out, mce_farm_file* files, int3
         files[f].bad_row = in / files[f].ncols;
         files[f].bad_col = in % files[f].ncols + 1;
     }
-    MCE_HIP(hipMemcpyAsync(c.fix, fixed.data(), (size_t)nlist * sizeof(double), hipMemcpyHostToDevice, c.stream));
-    hipLaunchKernelGGL(prep_patch_kernel, dim3(chain_grid(nlist, kPrepThreads)), dim3(kPrepThreads), 0, c.stream, c.list, c.fix, nlist, c.ntok, d_out);
-    MCE_HIP(hipGetLastError());
-    MCE_HIP(hipStreamSynchronize(c.stream));
+    if ((rc = reader_patch(c, c.list, c.fix, fixed, c.ntok, d_out)) != MCE_OK) return rc;
     c.patched = nlist;
     c.ms_patch = ms_since(t_d);
     return MCE_OK;
@@ -395,9 +351,8 @@ int mce_chain_farm_prep_dev(const int32_t* root_nparts, const int64_t* root_ncol
             return fail(MCE_ERR_INVALID, "chain farm prep: columns iw=%d ilike=%d itheta=%d of a root with %lld", iw, ilike, itheta, (long long)nc);
         int64_t n = 0;
         for (int32_t k = 0; k < root_nparts[r]; ++k, ++p) {
-            if (parts[p].nrows < 0 || parts[p].nrows > ((int64_t)1 << 40) || (parts[p].nrows > 0 && !parts[p].rows))
-                return fail(MCE_ERR_INVALID, "chain farm prep: part %lld has %lld rows at a %s pointer", (long long)p, (long long)parts[p].nrows,
-                            parts[p].rows ? "valid" : "null");
+            const int rc = prep_check_part("chain farm prep", (long long)p, parts[p]);
+            if (rc != MCE_OK) return rc;
             part_first[p] = n;
             part_rows[p] = parts[p].nrows;
             part_ptr[p] = (int64_t)reinterpret_cast<intptr_t>(parts[p].rows);

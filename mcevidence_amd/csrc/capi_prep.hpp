@@ -38,6 +38,15 @@ PrepLayout prep_layout(int64_t n, int32_t nparts)
     return L;
 }
 
+// one entry of a part table (`who`: the caller's prefix): rows at a null pointer, negative rows, rows beyond 2^40
+int prep_check_part(const char* who, long long p, const mce_chain_part& part)
+{
+    if (part.nrows < 0 || (part.nrows > 0 && !part.rows))
+        return fail(MCE_ERR_INVALID, "%s: part %lld has %lld rows at a %s pointer", who, p, (long long)part.nrows, part.rows ? "valid" : "null");
+    if (part.nrows > (int64_t)1 << 40) return fail(MCE_ERR_INVALID, "%s: part %lld has %lld rows", who, p, (long long)part.nrows);
+    return MCE_OK;
+}
+
 // the table of non-empty parts and the total row count
 int prep_parts(const mce_chain_part* parts, int32_t nparts, int64_t ncols, std::vector<mce::PrepPart>& table, int64_t& n)
 {
@@ -46,9 +55,8 @@ int prep_parts(const mce_chain_part* parts, int32_t nparts, int64_t ncols, std::
     n = 0;
     table.clear();
     for (int32_t p = 0; p < nparts; ++p) {
-        if (parts[p].nrows < 0 || (parts[p].nrows > 0 && !parts[p].rows))
-            return fail(MCE_ERR_INVALID, "chain prep: part %d has %lld rows at a %s pointer", p, (long long)parts[p].nrows, parts[p].rows ? "valid" : "null");
-        if (parts[p].nrows > (int64_t)1 << 40) return fail(MCE_ERR_INVALID, "chain prep: part %d has %lld rows", p, (long long)parts[p].nrows);
+        const int rc = prep_check_part("chain prep", p, parts[p]);
+        if (rc != MCE_OK) return rc;
         if (parts[p].nrows > 0) table.push_back(mce::PrepPart{parts[p].rows, n, parts[p].nrows});
         n += parts[p].nrows;
     }
@@ -60,11 +68,6 @@ int prep_need_device()
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(MCE_ERR_NO_DEVICE, "no HIP device visible");
     return MCE_OK;
-}
-
-unsigned prep_grid(int64_t items, int64_t per_block)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)kAssumedCUs * 16));
 }
 
 template <class T> T* prep_at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }

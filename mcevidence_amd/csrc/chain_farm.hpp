@@ -8,9 +8,11 @@
 //                     a file and the comment-state scan needs no notion of files.
 //   * lookups         file_of_tile / file_of_token: the last f with base[f] <= x (binary search; base has a sentinel entry, so an
 //                     empty file -- base[f] == base[f + 1] -- is never the answer).
+//   * byte classes    mce::chain_byte_class: what ends a line, separates fields, starts a comment (chain_kernels.hpp, the driver below).
 //   * verdict         per file, inside its token range [t0, t1): ncols = tokens on the line of the first token; row r of the file
-//                     is ragged if its ncols tokens do not share one line or the token before it lies on the same line
-//                     (chain_kernels.hpp: chain_ncols_kernel / chain_rows_kernel); ntok % ncols != 0 is ragged too.
+//                     is ragged if its ncols tokens do not share one line or the token before it lies on the same line;
+//                     ntok % ncols != 0 is ragged too.  THE one statement of the rule: farm_files_kernel / farm_rows_kernel apply it
+//                     per file of a wave, chain_ncols_kernel / chain_rows_kernel (the single-file reader) with t0 = 0.
 //   * row table       a root is a list of parts (its files after burn-in); roots are numbered consecutively in one global row
 //                     numbering: locate_row maps a global row to (root, part, local row).
 // farm_structure is the serial driver: the same functions over a whole wave on one CPU thread.
@@ -30,6 +32,19 @@
 #endif
 
 #include <vector>
+
+namespace mce {
+
+enum : int { kByteOther = 0, kByteSpace = 1, kByteTerm = 2, kByteHash = 3 };
+
+MCE_HD inline __attribute__((always_inline)) int chain_byte_class(unsigned c)
+{
+    if (c == '\n' || c == '\r') return kByteTerm;
+    if (c == ' ' || c == '\t' || c == '\v' || c == '\f') return kByteSpace;
+    return c == '#' ? kByteHash : kByteOther;
+}
+
+}  // namespace mce
 
 namespace mce_farm {
 
@@ -126,30 +141,24 @@ MCE_HD inline RowPlace locate_row(const int64_t* row0, int64_t nroots, const int
 }
 
 // ---- serial driver -------------------------------------------------------------------------------------------------------------
-inline int byte_class(unsigned char c)      // chain_kernels.hpp: chain_byte_class
-{
-    if (c == '\n' || c == '\r') return 2;
-    if (c == ' ' || c == '\t' || c == '\v' || c == '\f') return 1;
-    return c == '#' ? 3 : 0;
-}
-
 // `text`: the wave as the device sees it (pads filled).  One serial scan gives the tokens' offsets and lines (the definition of
 // chain_kernels.hpp: a token starts outside a comment at a byte that is neither space, line end nor '#' and follows a space, a line end
 // or the start of the text); the per-file verdicts and the token -> file map come from the functions above.
 inline void farm_structure(const unsigned char* text, int64_t wave_bytes, const int64_t* file_off, int64_t nfiles, std::vector<FileVerdict>* verdicts,
                            std::vector<int64_t>* tok_off, std::vector<int64_t>* tok_file)
 {
+    using namespace mce;
     std::vector<int64_t> tok_line, tile_tok((size_t)(wave_bytes / kTileBytes) + 1, 0);
     tok_off->clear();
     bool in_comment = false;
-    int prev = 2;
+    int prev = kByteTerm;
     int64_t line = 0;
     for (int64_t i = 0; i < wave_bytes; ++i) {
         if (i % kTileBytes == 0) tile_tok[(size_t)(i / kTileBytes)] = (int64_t)tok_off->size();
-        const int c = byte_class(text[i]);
-        if (c == 2) { in_comment = false; ++line; }
-        else if (c == 3) in_comment = true;
-        else if (c == 0 && !in_comment && (prev == 1 || prev == 2)) { tok_off->push_back(i); tok_line.push_back(line); }
+        const int c = chain_byte_class(text[i]);
+        if (c == kByteTerm) { in_comment = false; ++line; }
+        else if (c == kByteHash) in_comment = true;
+        else if (c == kByteOther && !in_comment && (prev == kByteSpace || prev == kByteTerm)) { tok_off->push_back(i); tok_line.push_back(line); }
         prev = c;
     }
     tile_tok[(size_t)(wave_bytes / kTileBytes)] = (int64_t)tok_off->size();

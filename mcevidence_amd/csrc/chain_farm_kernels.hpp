@@ -6,10 +6,11 @@
 //   farm_rows_kernel       one lane per token; the lane of a row's first token applies the ragged rule inside its file
 // and the preparation of the roots of a wave that are not thinned (a root: a list of parts, chain_farm.hpp's row table):
 //   farm_gather_kernel     one lane per (row, column) of every root: the packed parameter rows, w and the likelihood column
-//   farm_like_tile_kernel  prep_like_tile_kernel per 512-row tile IN THE ROOT'S OWN ROW NUMBERING (a tile never spans two roots)
-//   farm_like_final_kernel prep_like_final_kernel, one block per root
+//   farm_like_tile_kernel  prep_like_tile per 512-row tile IN THE ROOT'S OWN ROW NUMBERING (a tile never spans two roots)
+//   farm_like_final_kernel prep_like_final, one block per root
 //   farm_fs_kernel         fs = logL - max(logL) of the row's root
-// The reductions repeat the order of chain_prep_kernels.hpp exactly, so a root's bits depend on its own rows only.
+// The reductions ARE those of chain_prep_kernels.hpp (prep_like_tile, prep_like_final, prep_logl, called with the root as the
+// segment), so a root's bits depend on its own rows only and equal what mce_chain_reduce_dev gives the root alone.
 // No floating-point atomics, plain C++ stores, 64-bit indices; a row the table cannot place writes NaN and reads nothing.
 #pragma once
 
@@ -109,38 +110,11 @@ __global__ __launch_bounds__(kPrepThreads) void farm_like_tile_kernel(FarmTables
                                                                      double* __restrict__ tile_max, double* __restrict__ tile_sumw,
                                                                      long long* __restrict__ tile_bad)
 {
-    __shared__ double s_max[kPrepThreads], s_sum[kPrepThreads];
-    __shared__ long long s_bad[kPrepThreads];
-    const int tid = threadIdx.x;
+    __shared__ PrepLikeShared s;
     const int64_t ntiles = t.tile0[t.nroots];
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t root = mce_farm::last_at_or_below(t.tile0, t.nroots, tile);
-        const int64_t n = t.row0[root + 1] - t.row0[root], base = t.row0[root], local_tile = tile - t.tile0[root];
-        double mx = -INFINITY, sum = 0.0;
-        long long bad = 0;
-#pragma unroll
-        for (int k = 0; k < kPrepRowsPerThread; ++k) {
-            const int64_t i = local_tile * kPrepTile + (int64_t)tid * kPrepRowsPerThread + k;
-            if (i < n) {
-                const double l = pos_lnp ? like[base + i] : -like[base + i], v = w[base + i];
-                if (l != l) bad += 1;
-                else mx = l > mx ? l : mx;
-                if (!(v - v == 0.0)) bad += (1ll << 32);
-                sum += v;
-            }
-        }
-        s_max[tid] = mx; s_sum[tid] = sum; s_bad[tid] = bad;
-        __syncthreads();
-        for (int off = kPrepThreads / 2; off > 0; off >>= 1) {
-            if (tid < off) {
-                s_max[tid] = s_max[tid + off] > s_max[tid] ? s_max[tid + off] : s_max[tid];
-                s_sum[tid] += s_sum[tid + off];
-                s_bad[tid] += s_bad[tid + off];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) { tile_max[tile] = s_max[0]; tile_sumw[tile] = s_sum[0]; tile_bad[tile] = s_bad[0]; }
-        __syncthreads();
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {          // (the same trips for every thread of the block: the barriers inside)
+        const int64_t root = mce_farm::last_at_or_below(t.tile0, t.nroots, tile), base = t.row0[root];
+        prep_like_tile(s, like + base, w + base, t.row0[root + 1] - base, tile - t.tile0[root], pos_lnp, tile_max + tile, tile_sumw + tile, tile_bad + tile);
     }
 }
 
@@ -148,35 +122,11 @@ __global__ __launch_bounds__(kPrepThreads) void farm_like_tile_kernel(FarmTables
 __global__ __launch_bounds__(kPrepThreads) void farm_like_final_kernel(FarmTables t, const double* __restrict__ tile_max, const double* __restrict__ tile_sumw,
                                                                       const long long* __restrict__ tile_bad, double* __restrict__ out)
 {
-    __shared__ double s_max[kPrepThreads], s_sum[kPrepThreads];
-    __shared__ long long s_bad[kPrepThreads];
-    const int tid = threadIdx.x;
+    __shared__ PrepLikeShared s;
     for (int64_t root = blockIdx.x; root < t.nroots; root += gridDim.x) {
-        const int64_t b = t.tile0[root], nt = t.tile0[root + 1] - b;
-        double mx = -INFINITY, sum = 0.0;
-        long long bad = 0;
-        for (int64_t k = tid; k < nt; k += kPrepThreads) {
-            mx = tile_max[b + k] > mx ? tile_max[b + k] : mx;
-            sum += tile_sumw[b + k];
-            bad += tile_bad[b + k];
-        }
-        s_max[tid] = mx; s_sum[tid] = sum; s_bad[tid] = bad;
-        __syncthreads();
-        for (int off = kPrepThreads / 2; off > 0; off >>= 1) {
-            if (tid < off) {
-                s_max[tid] = s_max[tid + off] > s_max[tid] ? s_max[tid + off] : s_max[tid];
-                s_sum[tid] += s_sum[tid + off];
-                s_bad[tid] += s_bad[tid + off];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            out[4 * root + 0] = s_max[0];
-            out[4 * root + 1] = s_sum[0];
-            out[4 * root + 2] = (double)(s_bad[0] & 0xFFFFFFFFll);
-            out[4 * root + 3] = (double)(s_bad[0] >> 32);
-        }
-        __syncthreads();
+        const int64_t b = t.tile0[root];
+        prep_like_final(s, tile_max + b, tile_sumw + b, tile_bad + b, t.tile0[root + 1] - b, out + 4 * root);
+        __syncthreads();          // (s is free for the next root)
     }
 }
 
@@ -184,10 +134,8 @@ __global__ __launch_bounds__(kPrepThreads) void farm_fs_kernel(FarmTables t, con
                                                               double* __restrict__ fs)
 {
     const int64_t n = t.row0[t.nroots];
-    for (int64_t g = (int64_t)blockIdx.x * kPrepThreads + threadIdx.x; g < n; g += (int64_t)gridDim.x * kPrepThreads) {
-        const int64_t root = mce_farm::last_at_or_below(t.row0, t.nroots, g);
-        fs[g] = (pos_lnp ? like[g] : -like[g]) - red[4 * root];
-    }
+    for (int64_t g = (int64_t)blockIdx.x * kPrepThreads + threadIdx.x; g < n; g += (int64_t)gridDim.x * kPrepThreads)
+        fs[g] = prep_logl(like[g], pos_lnp) - red[4 * mce_farm::last_at_or_below(t.row0, t.nroots, g)];
 }
 
 }  // namespace mce

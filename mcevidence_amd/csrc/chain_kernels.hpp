@@ -11,7 +11,8 @@
 //   3. chain_tile_kernel<1>   per tile: token starts and line ends in it (two 32-bit counts).
 //   4. chain_scan_count_kernel   exclusive 64-bit sums of the counts, and the totals.
 //   5. chain_tile_kernel<2>   writes for token k its byte offset and its line number (line ends before it).
-//   6. chain_ncols_kernel, chain_rows_kernel   columns = tokens on the first token's line; every group of ncols consecutive tokens
+//   6. chain_ncols_kernel, chain_rows_kernel   the per-file verdict of chain_farm.hpp (file_counts, row_ragged) for the one file that
+//                             starts at token 0: columns = tokens on the first token's line; every group of ncols consecutive tokens
 //                             lies on ONE line and the next group on ANOTHER -- exactly "every line holds 0 or ncols tokens", and
 //                             then token k is row k / ncols, column k % ncols.
 //   7. chain_parse_kernel     one lane per token (neighbouring lanes read neighbouring bytes): chain_parse.hpp's exact paths;
@@ -24,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "chain_farm.hpp"
 #include "chain_parse.hpp"
 
 namespace mce {
@@ -44,14 +46,7 @@ struct ChainPatch {
     int64_t token, offset, length;
 };
 
-enum : int { kByteOther = 0, kByteSpace = 1, kByteTerm = 2, kByteHash = 3 };
-
-__device__ __forceinline__ int chain_byte_class(unsigned c)
-{
-    if (c == '\n' || c == '\r') return kByteTerm;
-    if (c == ' ' || c == '\t' || c == '\v' || c == '\f') return kByteSpace;
-    return c == '#' ? kByteHash : kByteOther;
-}
+// (the byte classes and chain_byte_class are chain_farm.hpp's, which the host check compiles too)
 
 // comment-state elements: 0 identity, 1 "ends outside a comment" (a line end came last), 2 "ends inside" ('#' came last);
 // a then b = b unless b is the identity
@@ -210,34 +205,24 @@ __global__ __launch_bounds__(kChainScanThreads) void chain_scan_count_kernel(con
     }
 }
 
-// columns of the first data line: tokens whose line is the first token's (tok_line is non-decreasing)
+// the verdict of the one file that is the whole text: mce_farm::file_counts over all tokens ...
 __global__ void chain_ncols_kernel(const int64_t* __restrict__ tok_line, ChainTotals* __restrict__ tot)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const int64_t n = (int64_t)tot->ntok;
-    int64_t lo = 0, hi = n;                     // first index whose line exceeds tok_line[0]
-    if (n > 0) {
-        const int64_t first = tok_line[0];
-        while (lo < hi) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (tok_line[mid] > first) hi = mid;
-            else lo = mid + 1;
-        }
-    }
-    tot->ncols = (unsigned long long)lo;
-    tot->ragged = (n > 0 && n % lo != 0) ? 1ull : 0ull;
+    mce_farm::FileVerdict v;
+    mce_farm::file_counts(tok_line, 0, (int64_t)tot->ntok, &v);
+    tot->ncols = (unsigned long long)v.ncols;
+    tot->ragged = (unsigned long long)v.ragged;
 }
 
-// one thread per group of ncols tokens
+// ... and mce_farm::row_ragged, one thread per group of ncols tokens
 __global__ __launch_bounds__(kChainThreads) void chain_rows_kernel(const int64_t* __restrict__ tok_line, ChainTotals* __restrict__ tot)
 {
     const int64_t ncols = (int64_t)tot->ncols, ntok = (int64_t)tot->ntok;
     if (ncols < 1) return;
     const int64_t nrows = ntok / ncols;
-    for (int64_t r = (int64_t)blockIdx.x * kChainThreads + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * kChainThreads) {
-        const int64_t k = r * ncols, line = tok_line[k];
-        if (tok_line[k + ncols - 1] != line || (k > 0 && tok_line[k - 1] == line)) tot->ragged = 1ull;
-    }
+    for (int64_t r = (int64_t)blockIdx.x * kChainThreads + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * kChainThreads)
+        if (mce_farm::row_ragged(tok_line, 0, ncols, r)) tot->ragged = 1ull;
 }
 
 __global__ __launch_bounds__(kChainThreads) void chain_parse_kernel(const char* __restrict__ text, int64_t nbytes, const int64_t* __restrict__ tok_off, int64_t ntok,

@@ -16,7 +16,8 @@
 //               prep_search_kernel    integer rule, factor < max: one binary search in c per output row
 //   gather      prep_gather_kernel    one lane per (output row, column): source row src[rows[r]], 8-byte loads that neighbouring
 //                                     lanes make contiguous (a row of 23 or 29 doubles is 16-byte aligned only every other row)
-//   reduce      prep_like_tile_kernel, prep_like_final_kernel, prep_fs_kernel   max(logL), SumW, fs = logL - max
+//   reduce      prep_like_tile_kernel, prep_like_final_kernel, prep_fs_kernel   max(logL), SumW, fs = logL - max: callers of prep_like_tile /
+//               prep_like_final / prep_logl, which reduce one SEGMENT of rows; the farm's per-root kernels (chain_farm_kernels.hpp) call them too
 // Every sum is formed in an order that depends on the sizes only (serial per thread, then a shared-memory tree), never with
 // floating-point atomics, so two runs give the same bits.  All indices are 64-bit; plain C++ stores only.
 #pragma once
@@ -305,74 +306,92 @@ __global__ __launch_bounds__(kPrepThreads) void prep_gather_kernel(const PrepPar
     }
 }
 
-// logL = pos_lnp ? like : -like.  Per tile: max(logL) (NaN-free tiles only: NaNs are counted), sum of w, counts of NaN logL and of
-// weights that are not finite.
-__global__ __launch_bounds__(kPrepThreads) void prep_like_tile_kernel(const double* __restrict__ like, const double* __restrict__ w, int64_t n, int64_t ntiles,
-                                                                      int pos_lnp, double* __restrict__ tile_max, double* __restrict__ tile_sumw,
-                                                                      long long* __restrict__ tile_bad)
+// ---- the like / fs reduction of one SEGMENT of rows: the whole chain here, one root of a wave in chain_farm_kernels.hpp -------------
+// The order of every sum is fixed by the segment's own size: serial over a thread's 2 rows, a tree over the block from off = 128
+// down, and in the final pass strided by 256 over the segment's tiles and the same tree again.
+struct PrepLikeShared {
+    double mx[kPrepThreads], sum[kPrepThreads];
+    long long bad[kPrepThreads];          // NaN likelihoods in the low 32 bits, weights that are not finite above them
+};
+
+__device__ __forceinline__ double prep_logl(double like, int pos_lnp) { return pos_lnp ? like : -like; }
+
+// max, sum and packed bad count over the block's threads -> s.mx[0], s.sum[0], s.bad[0]; every thread of the block calls it
+__device__ __forceinline__ void prep_like_tree(PrepLikeShared& s, int tid, double mx, double sum, long long bad)
 {
-    __shared__ double s_max[kPrepThreads], s_sum[kPrepThreads];
-    __shared__ long long s_bad[kPrepThreads];
-    const int tid = threadIdx.x;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        double mx = -INFINITY, sum = 0.0;
-        long long bad = 0;
-#pragma unroll
-        for (int k = 0; k < kPrepRowsPerThread; ++k) {
-            const int64_t i = tile * kPrepTile + (int64_t)tid * kPrepRowsPerThread + k;
-            if (i < n) {
-                const double l = pos_lnp ? like[i] : -like[i], v = w[i];
-                if (l != l) bad += 1;
-                else mx = l > mx ? l : mx;
-                if (!(v - v == 0.0)) bad += (1ll << 32);
-                sum += v;
-            }
+    s.mx[tid] = mx; s.sum[tid] = sum; s.bad[tid] = bad;
+    __syncthreads();
+    for (int off = kPrepThreads / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            s.mx[tid] = s.mx[tid + off] > s.mx[tid] ? s.mx[tid + off] : s.mx[tid];
+            s.sum[tid] += s.sum[tid + off];
+            s.bad[tid] += s.bad[tid + off];
         }
-        s_max[tid] = mx; s_sum[tid] = sum; s_bad[tid] = bad;
-        __syncthreads();
-        for (int off = kPrepThreads / 2; off > 0; off >>= 1) {
-            if (tid < off) {
-                s_max[tid] = s_max[tid + off] > s_max[tid] ? s_max[tid + off] : s_max[tid];
-                s_sum[tid] += s_sum[tid + off];
-                s_bad[tid] += s_bad[tid + off];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) { tile_max[tile] = s_max[0]; tile_sumw[tile] = s_sum[0]; tile_bad[tile] = s_bad[0]; }
         __syncthreads();
     }
 }
 
-// out[0] = max(logL), out[1] = SumW, out[2] = NaN likelihoods, out[3] = weights that are not finite; one block
-__global__ __launch_bounds__(kPrepThreads) void prep_like_final_kernel(const double* __restrict__ tile_max, const double* __restrict__ tile_sumw,
-                                                                       const long long* __restrict__ tile_bad, int64_t nt, double* __restrict__ out)
+// Tile `tile` of a segment of n rows (like, w: its first row): max(logL) (NaNs are counted, not compared), sum of w, counts of NaN logL
+// and of weights that are not finite -> *t_max, *t_sum, *t_bad.  Every thread of the block; the closing barrier frees s for the next tile.
+__device__ __forceinline__ void prep_like_tile(PrepLikeShared& s, const double* __restrict__ like, const double* __restrict__ w, int64_t n, int64_t tile,
+                                               int pos_lnp, double* __restrict__ t_max, double* __restrict__ t_sum, long long* __restrict__ t_bad)
 {
-    __shared__ double s_max[kPrepThreads], s_sum[kPrepThreads];
-    __shared__ long long s_bad[kPrepThreads];
+    const int tid = threadIdx.x;
+    double mx = -INFINITY, sum = 0.0;
+    long long bad = 0;
+#pragma unroll
+    for (int k = 0; k < kPrepRowsPerThread; ++k) {
+        const int64_t i = tile * kPrepTile + (int64_t)tid * kPrepRowsPerThread + k;
+        if (i < n) {
+            const double l = prep_logl(like[i], pos_lnp), v = w[i];
+            if (l != l) bad += 1;
+            else mx = l > mx ? l : mx;
+            if (!(v - v == 0.0)) bad += (1ll << 32);
+            sum += v;
+        }
+    }
+    prep_like_tree(s, tid, mx, sum, bad);
+    if (tid == 0) { *t_max = s.mx[0]; *t_sum = s.sum[0]; *t_bad = s.bad[0]; }
+    __syncthreads();
+}
+
+// The nt tiles of a segment (t_*: its first) -> out[0] = max(logL), out[1] = SumW, out[2] = NaN likelihoods, out[3] = weights that are
+// not finite.  Every thread of ONE block; a caller with a next segment puts a barrier before it.
+__device__ __forceinline__ void prep_like_final(PrepLikeShared& s, const double* __restrict__ t_max, const double* __restrict__ t_sum,
+                                                const long long* __restrict__ t_bad, int64_t nt, double* __restrict__ out)
+{
     const int tid = threadIdx.x;
     double mx = -INFINITY, sum = 0.0;
     long long bad = 0;
     for (int64_t t = tid; t < nt; t += kPrepThreads) {
-        mx = tile_max[t] > mx ? tile_max[t] : mx;
-        sum += tile_sumw[t];
-        bad += tile_bad[t];
+        mx = t_max[t] > mx ? t_max[t] : mx;
+        sum += t_sum[t];
+        bad += t_bad[t];
     }
-    s_max[tid] = mx; s_sum[tid] = sum; s_bad[tid] = bad;
-    __syncthreads();
-    for (int off = kPrepThreads / 2; off > 0; off >>= 1) {
-        if (tid < off) {
-            s_max[tid] = s_max[tid + off] > s_max[tid] ? s_max[tid + off] : s_max[tid];
-            s_sum[tid] += s_sum[tid + off];
-            s_bad[tid] += s_bad[tid + off];
-        }
-        __syncthreads();
-    }
+    prep_like_tree(s, tid, mx, sum, bad);
     if (tid == 0) {
-        out[0] = s_max[0];
-        out[1] = s_sum[0];
-        out[2] = (double)(s_bad[0] & 0xFFFFFFFFll);
-        out[3] = (double)(s_bad[0] >> 32);
+        out[0] = s.mx[0];
+        out[1] = s.sum[0];
+        out[2] = (double)(s.bad[0] & 0xFFFFFFFFll);
+        out[3] = (double)(s.bad[0] >> 32);
     }
+}
+
+__global__ __launch_bounds__(kPrepThreads) void prep_like_tile_kernel(const double* __restrict__ like, const double* __restrict__ w, int64_t n, int64_t ntiles,
+                                                                      int pos_lnp, double* __restrict__ tile_max, double* __restrict__ tile_sumw,
+                                                                      long long* __restrict__ tile_bad)
+{
+    __shared__ PrepLikeShared s;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x)          // (the same trips for every thread of the block: the barriers inside)
+        prep_like_tile(s, like, w, n, tile, pos_lnp, tile_max + tile, tile_sumw + tile, tile_bad + tile);
+}
+
+// one block
+__global__ __launch_bounds__(kPrepThreads) void prep_like_final_kernel(const double* __restrict__ tile_max, const double* __restrict__ tile_sumw,
+                                                                       const long long* __restrict__ tile_bad, int64_t nt, double* __restrict__ out)
+{
+    __shared__ PrepLikeShared s;
+    prep_like_final(s, tile_max, tile_sumw, tile_bad, nt, out);
 }
 
 __global__ __launch_bounds__(kPrepThreads) void prep_fs_kernel(const double* __restrict__ like, int64_t n, int pos_lnp, const double* __restrict__ red,
@@ -380,7 +399,7 @@ __global__ __launch_bounds__(kPrepThreads) void prep_fs_kernel(const double* __r
 {
     const double mx = red[0];
     for (int64_t i = (int64_t)blockIdx.x * kPrepThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kPrepThreads)
-        fs[i] = (pos_lnp ? like[i] : -like[i]) - mx;
+        fs[i] = prep_logl(like[i], pos_lnp) - mx;
 }
 
 // the reader's host patches, written into a device array: vals[list[i].token] = patch[i]

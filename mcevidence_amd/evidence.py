@@ -28,6 +28,7 @@ from collections import namedtuple
 import numpy as np
 
 from .chains import MCSamples, rank0_draw
+from .resident import mle_from_sums
 
 FORMAT = "%(levelname)s:%(filename)s.%(funcName)s():%(lineno)-8s %(message)s"
 logger = logging.getLogger("mcevidence_amd")
@@ -355,14 +356,7 @@ class MCEvidence(object):
     def _feed_finish(self, ctx, dotp, Jacobian, logPriorVolume):
         """ln E_k from the reduced sums (reference :1120-1131); returns MLE[kmax]."""
         S, logLmax = ctx
-        kmax = self.kmax
-        k0 = 0 if self.split else 1
-        SumW = np.sum(self.gd.data["s1"].adjusted_weights)
-        mle = np.zeros(kmax)
-        for k in range(k0, kmax):
-            k_nn = k if k0 == 1 else k + 1
-            mle[k] = math.log(SumW * (dotp[k] / (S * k_nn + 1.0)) * Jacobian) + logLmax - logPriorVolume
-        return mle
+        return mle_from_sums(dotp, Jacobian, np.sum(self.gd.data["s1"].adjusted_weights), logLmax, S, self.kmax, logPriorVolume, self.split)
 
     def _feed_route_applies(self, verbose, covtype):
         # cross evidence with covtype 'single' whitens s1 and s2 with DIFFERENT eigen-systems, so the

@@ -155,12 +155,10 @@ def _parse_wave(pool, device, wave_bytes, paths, lens, ms):
 
 
 def _refused(path, f):
-    """the exception of a file the device reader refused: the host reader's, with its row, column and line"""
+    """the exception of a file the device reader refused (``chain_io.refused``)"""
     from . import _capi, chain_io
-    chain_io.loadtxt(path)
-    return RuntimeError("mcevidence_amd: the device chain reader refused %s (%s) but the host reader accepts it"
-                        % (path, "ragged lines" if f.status == _capi.FARM_RAGGED else
-                           "a field that is not a number at row %d, column %d" % (f.bad_row, f.bad_col)))
+    return chain_io.refused(path, "ragged lines" if f.status == _capi.FARM_RAGGED else
+                           "a field that is not a number at row %d, column %d" % (f.bad_row, f.bad_col))
 
 
 def read_files(paths, device=0, wave_bytes=None):
@@ -295,16 +293,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                         fallback[r.index] = reason
                         continue
                     r.ncols = shapes[0][1]
-                    if r.ncols <= max(iw, ilike, itheta) or min(iw, ilike, itheta) < 0:
-                        raise ValueError("columns iw=%d ilike=%d itheta=%d of a chain with %d" % (iw, ilike, itheta, r.ncols))
+                    _res.check_columns(iw, ilike, itheta, r.ncols)
                     r.nparam = r.ncols - itheta
-                    nd = r.nparam if r.ndim is None else int(r.ndim)
-                    if nd < 1:
-                        raise ValueError("ndim must be >= 1 (got %r)" % (r.ndim,))
-                    if nd > r.nparam:
-                        logger.warning("ndim=%s exceeds the %s parameter columns of the chain; using all of them" % (r.ndim, r.nparam))
-                        nd = r.nparam
-                    r.nd = nd
+                    r.nd = nd = _res.effective_ndim(r.ndim, r.nparam)
                     if r.thin not in (0, 1):
                         # integer or bin thinning: the per-root calls, on views of the wave's buffer
                         tensors = [d_out[int(f.tok_base):int(f.tok_base) + nr * nc].view(nr, nc) if nr else torch.empty((0, 1), dtype=torch.float64, device=dev)
@@ -314,9 +305,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                     else:
                         r.parts = []
                         for f, (nr, nc) in zip(ff, shapes):
-                            start = 0
-                            if r.burn > 0:                     # (chains.MCSamples.removeBurn; csrc/chain_prep.hpp: burn_start)
-                                start = min(nr, int(nr * r.burn) if r.burn < 1 else int(r.burn))
+                            start = _res.burn_start(nr, r.burn)
                             r.parts.append((d_out.data_ptr() + (int(f.tok_base) + start * nc) * 8 if nr - start > 0 else 0, nr - start))
                         r.nrows = sum(m for _, m in r.parts)
                     reason = _res.plan(covtype=cov, ndim=nd, nparam=r.nparam, nrows=r.nrows)
@@ -357,19 +346,11 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                     if r.rc is not None:
                         s1 = r.rc._gather(None, want=("params", "w", "like"))
                         n1 = int(s1["w"].shape[0])
-                        fs1 = torch.empty(n1, dtype=torch.float64, device=dev)
-                        wsb = _capi.chain_reduce_workspace_bytes(n1)
-                        ws1 = r.rc._ws(wsb)
-                        r.scal = _capi.chain_reduce_dev(s1["like"].data_ptr(), s1["w"].data_ptr(), n1, pos_lnp, fs1.data_ptr(), ws1.data_ptr(), wsb,
-                                                        stream.cuda_stream)
+                        fs1, r.scal = r.rc._reduce(s1, pos_lnp)
                         r.keep = (s1, fs1)
                         r.problem = (s1["params"].data_ptr(), n1, r.nparam, 0, 0, 0, r.nd, 0 if cov == "all" else 1, kmax_eff, s1["w"].data_ptr(),
                                      fs1.data_ptr())
-                    logLmax, SumW, nan_like, bad_w = r.scal
-                    if bad_w:
-                        raise ValueError("weight contains NaN or infinity")
-                    if nan_like or math.isinf(logLmax):
-                        raise ValueError("fs contains NaN or +infinity")
+                    _res.check_reduced(*r.scal)
                     ready.append(r)
                 except Exception as e:
                     fail(r.index, e)
@@ -392,19 +373,14 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                                 fail(r.index, e)
                             continue
                         dotp, jac, _ = g
-                        logLmax, SumW = r.scal[0], r.scal[1]
                         n1 = r.problem[1]
-                        mle = np.zeros(kmax_eff)
                         try:
-                            for k in range(1, kmax_eff):        # (evidence.MCEvidence._feed_finish; reference :1120-1131)
-                                mle[k] = math.log(SumW * (dotp[k] / (n1 * k + 1.0)) * jac) + logLmax - math.log(r.pvol)
+                            out = _res.mle_from_sums(dotp, jac, r.scal[1], r.scal[0], n1, kmax_eff, math.log(r.pvol), False)[1:]
                         except Exception as e:
                             fail(r.index, e)
                             continue
-                        out = mle[1:]
                         counts["farm"] += 1
-                        results[r.index] = out if not info else (out, {"NparamsMC": r.nparam, "Nsamples_read": n1, "Nparams_read": r.nparam,
-                                                                        "NparamsCosmo": r.nd, "Nsamples": str(n1), "route": FARM})
+                        results[r.index] = out if not info else (out, _res.route_info(FARM, r.nparam, r.nd, n1, [n1]))
             ms["feed"] += _res._ms(t0)
             for r in wroots:
                 r.rc = r.keep = r.parts = None

@@ -130,6 +130,52 @@ def _ms(t0):
     return (time.perf_counter() - t0) * 1e3
 
 
+# ---- the host rules every route shares (this module, farm.py, evidence.py) -------------------------------------------------------
+def burn_start(n, burnlen):
+    """the first row kept of a chain of ``n`` rows (chains.MCSamples.removeBurn; csrc/chain_prep.hpp: burn_start)"""
+    return min(n, int(n * burnlen) if burnlen < 1 else int(burnlen)) if burnlen > 0 else 0
+
+
+def check_columns(iw, ilike, itheta, ncols):
+    if ncols <= max(iw, ilike, itheta) or min(iw, ilike, itheta) < 0:
+        raise ValueError("columns iw=%d ilike=%d itheta=%d of a chain with %d" % (iw, ilike, itheta, ncols))
+
+
+def effective_ndim(ndim, nparam):
+    """the parameter columns the search takes"""
+    nd = nparam if ndim is None else int(ndim)
+    if nd < 1:
+        raise ValueError("ndim must be >= 1 (got %r)" % (ndim,))
+    if nd > nparam:
+        logger.warning("ndim=%s exceeds the %s parameter columns of the chain; using all of them" % (ndim, nparam))
+        nd = nparam
+    return nd
+
+
+def check_reduced(logLmax, SumW, nan_like, bad_w):
+    """what the host route raises for these reduce scalars (``mce_chain_reduce_dev`` / ``_farm_prep_dev``)"""
+    if bad_w:
+        raise ValueError("weight contains NaN or infinity")
+    if nan_like or math.isinf(logLmax):
+        raise ValueError("fs contains NaN or +infinity")
+
+
+def mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, log_prior_volume, cross):
+    """ln E_k from the reduced sums (reference :1120-1131): MLE[kmax]; entry 0 stays 0 without ``cross``"""
+    k0 = 0 if cross else 1
+    mle = np.zeros(kmax)
+    for k in range(k0, kmax):
+        k_nn = k if k0 == 1 else k + 1
+        mle[k] = math.log(SumW * (dotp[k] / (n1 * k_nn + 1.0)) * jac) + logLmax - log_prior_volume
+    return mle
+
+
+def route_info(route, nparam, nd, nread, nsample):
+    """the info dict of ``MCEvidence.evidence(info=True)`` for a route that kept the chain on the device"""
+    return {"NparamsMC": nparam, "Nsamples_read": nread, "Nparams_read": nparam, "NparamsCosmo": nd,
+            "Nsamples": ", ".join(str(x) for x in nsample), "route": route}
+
+
 class ResidentChains(object):
     """One or more chains on GPU ``device``, burned, concatenated and thinned there.
 
@@ -151,16 +197,14 @@ class ResidentChains(object):
         if reason != RESIDENT:
             raise ResidentDecline(reason)
         self.ncols = int(tensors[0].shape[1])
-        if self.ncols <= max(self.iw, self.ilike, self.itheta) or min(self.iw, self.ilike, self.itheta) < 0:
-            raise ValueError("columns iw=%d ilike=%d itheta=%d of a chain with %d" % (self.iw, self.ilike, self.itheta, self.ncols))
+        check_columns(self.iw, self.ilike, self.itheta, self.ncols)
         self.nparam = self.ncols - self.itheta
         self._tensors = list(tensors)                     # (owners of the memory the parts point into)
         self._parts = []
         for t in self._tensors:
             n = int(t.shape[0])
-            start = 0
-            if burnlen > 0:                               # (chains.MCSamples.removeBurn; csrc/chain_prep.hpp: burn_start)
-                start = min(n, int(n * burnlen) if burnlen < 1 else int(burnlen))
+            start = burn_start(n, burnlen)
+            if burnlen > 0:
                 logger.info("Removing %s lines as burn in" % start)
             self._parts.append((t.data_ptr() + start * self.ncols * 8, n - start))
         self.nburned = sum(n for _, n in self._parts)
@@ -222,8 +266,7 @@ class ResidentChains(object):
                                 if handle is not None:
                                     _capi.chain_dev_close(handle)
                         except ValueError as dev_err:
-                            chain_io.loadtxt(path)          # raises ValueError with the row, column and line of the first bad field
-                            raise RuntimeError("mcevidence_amd: the device chain reader refused %s (%s) but the host reader accepts it" % (path, dev_err))
+                            raise chain_io.refused(path, dev_err)
                         finally:
                             del view
                     finally:
@@ -301,6 +344,15 @@ class ResidentChains(object):
                                ws.data_ptr(), wsb, self._stream())
         return out
 
+    def _reduce(self, s1, pos_lnp):
+        """(fs, (max(logL), SumW, NaN likelihoods, weights that are not finite)) of the gathered ``s1``; the stream is synchronised"""
+        from . import _capi
+        n1 = int(s1["w"].shape[0])
+        fs = self._torch.empty(n1, dtype=self._torch.float64, device="cuda:%d" % self.device)
+        wsb = _capi.chain_reduce_workspace_bytes(n1)
+        ws = self._ws(wsb)
+        return fs, _capi.chain_reduce_dev(s1["like"].data_ptr(), s1["w"].data_ptr(), n1, pos_lnp, fs.data_ptr(), ws.data_ptr(), wsb, self._stream())
+
     def to_host(self):
         """the array ``MCSamples(...).samples`` holds: the burned, concatenated, thinned rows, all columns"""
         with self._torch.cuda.device(self.device):
@@ -327,12 +379,7 @@ class ResidentChains(object):
         from .evidence import HipBackend
         backend = backend or HipBackend()
         kmax = max(2, int(kmax))
-        nd = self.nparam if ndim is None else int(ndim)
-        if nd < 1:
-            raise ValueError("ndim must be >= 1 (got %r)" % (ndim,))
-        if nd > self.nparam:
-            logger.warning("ndim=%s exceeds the %s parameter columns of the chain; using all of them" % (ndim, self.nparam))
-            nd = self.nparam
+        nd = effective_ndim(ndim, self.nparam)
         cross = bool(split) or split_rows is not None
         reason = plan(covtype=covtype, split=cross, ndim=nd, nparam=self.nparam, distributed=_distributed(), nrows=self.nrows)
         if reason != RESIDENT:
@@ -358,35 +405,19 @@ class ResidentChains(object):
             if n1 < 2 or (cross and n2 < 1):
                 raise ValueError("invalid sizes n1=%d n2=%d" % (n1, n2))
             t0 = time.perf_counter()
-            fs = torch.empty(n1, dtype=torch.float64, device="cuda:%d" % self.device)
-            wsb = _capi.chain_reduce_workspace_bytes(n1)
-            ws = self._ws(wsb)
-            logLmax, SumW, nan_like, bad_w = _capi.chain_reduce_dev(s1["like"].data_ptr(), s1["w"].data_ptr(), n1, pos_lnp, fs.data_ptr(),
-                                                                    ws.data_ptr(), wsb, self._stream())
+            fs, (logLmax, SumW, nan_like, bad_w) = self._reduce(s1, pos_lnp)
             ms["reduce"] = _ms(t0)
-            if bad_w:
-                raise ValueError("weight contains NaN or infinity")
-            if nan_like or math.isinf(logLmax):
-                raise ValueError("fs contains NaN or +infinity")
+            check_reduced(logLmax, SumW, nan_like, bad_w)
             t0 = time.perf_counter()
             with backend._scoped():
                 dotp, jac, _, _ = _capi.evidence_feed_part_dev(s1["params"].data_ptr(), n1, self.nparam, s2["params"].data_ptr() if cross else 0, n2,
                                                                self.nparam, nd, 0 if covtype == "all" else 1, kmax, s1["w"].data_ptr(), fs.data_ptr(),
                                                                0, 1, device=self.device, want_checksum=False)
             ms["feed"] = _ms(t0)
-        # ln E_k from the reduced sums (evidence.MCEvidence._feed_finish; reference :1120-1131)
-        logPriorVolume = math.log(priorvolume)
-        k0 = 0 if cross else 1
-        mle = np.zeros(kmax)
-        for k in range(k0, kmax):
-            k_nn = k if k0 == 1 else k + 1
-            mle[k] = math.log(SumW * (dotp[k] / (n1 * k_nn + 1.0)) * jac) + logLmax - logPriorVolume
-        out = mle[1:]
+        out = mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, math.log(priorvolume), cross)[1:]
         if not info:
             return out
-        nsample = [n1, n2] if cross else [n1]
-        return out, {"NparamsMC": self.nparam, "Nsamples_read": self.nrows if split_rows is not None else n1, "Nparams_read": self.nparam, "NparamsCosmo": nd,
-                     "Nsamples": ", ".join(str(x) for x in nsample), "route": RESIDENT}
+        return out, route_info(RESIDENT, self.nparam, nd, self.nrows if split_rows is not None else n1, [n1, n2] if cross else [n1])
 
 
 _EVIDENCE_KEYS = ("rand", "info", "profile", "pvolume", "pos_lnp", "nproc", "prewhiten")

@@ -4,6 +4,9 @@
 //                                           the wave is laid out with next_offset, gaps filled with the pad byte, garbage ('7') never
 //                                           left in a gap; <out>: per record {int64 wave_bytes, int64 off[nfiles], per file {int64 nrows,
 //                                           ncols, ragged, tok0, ntok}, int64 ntok, int64 tok_file[ntok], int64 tok_off_in_file[ntok]}
+//   chain_farm_check alone <in> <out>       <in>: as for structure; <out>: per record and file {int64 nrows, ncols, ragged, ntok} inside the
+//                                           wave, then the same four for the file as a wave of its own (nfiles = 1, its tokens from
+//                                           t0 = 0: the calls the single-file reader's kernels make)
 //   chain_farm_check rows <in> <out>        <in>: records {int64 nroots, int64 nparts[nroots], int64 part_rows[sum nparts]};
 //                                           <out>: per record {int64 nrows, then per global row {int64 root, part, local}}
 // Prints "ok records=<count>" last.  Built with -fsanitize=undefined,address.
@@ -32,7 +35,8 @@ int main(int argc, char** argv)
     FILE* out = fopen(argv[3], "wb");
     if (!in || !out) return 2;
     int64_t count = 0;
-    if (!strcmp(argv[1], "structure")) {
+    const bool alone = !strcmp(argv[1], "alone");
+    if (alone || !strcmp(argv[1], "structure")) {
         int64_t nfiles;
         while (get(in, &nfiles)) {
             if (nfiles < 1 || nfiles > (1 << 20)) return 3;
@@ -52,6 +56,21 @@ int main(int argc, char** argv)
             std::vector<mce_farm::FileVerdict> v;
             std::vector<int64_t> tok_off, tok_file;
             mce_farm::farm_structure(text.data(), wave, off.data(), nfiles, &v, &tok_off, &tok_file);
+            if (alone) {
+                for (int64_t f = 0; f < nfiles; ++f) {
+                    const int64_t zero = 0, w1 = mce_farm::next_offset(0, len[(size_t)f]);
+                    std::vector<unsigned char> one((size_t)w1, (unsigned char)mce_farm::kPadByte);
+                    memcpy(one.data(), text.data() + off[(size_t)f], (size_t)len[(size_t)f]);
+                    std::vector<mce_farm::FileVerdict> v1;
+                    mce_farm::farm_structure(one.data(), w1, &zero, 1, &v1, &tok_off, &tok_file);
+                    if (v1[0].tok0 != 0) return 6;
+                    const int64_t rec[8] = {v[(size_t)f].nrows, v[(size_t)f].ncols, v[(size_t)f].ragged, v[(size_t)f].ntok,
+                                            v1[0].nrows, v1[0].ncols, v1[0].ragged, v1[0].ntok};
+                    put(out, rec, 8);
+                }
+                ++count;
+                continue;
+            }
             put(out, &wave);
             put(out, off.data(), (size_t)nfiles);
             for (int64_t f = 0; f < nfiles; ++f) {

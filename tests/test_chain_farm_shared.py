@@ -109,6 +109,26 @@ def test_serial_driver_on_the_adversarial_files(checker, tmp_path):
     assert np.array_equal(fwd[:, :3], rev[:, :3]) and np.array_equal(fwd[:, 4], rev[:, 4])
 
 
+def test_a_file_alone_gets_the_verdict_it_gets_inside_a_wave(checker, tmp_path):
+    """every adversarial file: file_counts + row_ragged at nfiles = 1, t0 = 0 (what the single-file reader's chain_ncols_kernel and
+    chain_rows_kernel call) give the rows, columns, ragged flag and token count the same functions give it inside a wave"""
+    named = boundary_files(big_rows=400) + [("ragged", RAGGED), ("ragged_multiple", RAGGED_MULTIPLE), ("junk", JUNK)]
+    files = [b for _, b in named]
+    waves = [files, files[::-1]]
+    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(fin, "wb") as f:
+        for w in waves:
+            f.write(struct.pack("<q", len(w)))
+            f.write(np.array([len(b) for b in w], dtype="<i8").tobytes())
+            f.write(b"".join(w))
+    out = subprocess.run([checker, "alone", str(fin), str(fout)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok records=%d" % len(waves)), out.stdout[-2000:] + out.stderr[-2000:]
+    got = np.fromfile(fout, dtype="<i8").reshape(len(waves), len(files), 2, 4)
+    assert np.array_equal(got[:, :, 0], got[:, :, 1]), [n for (n, _), g in zip(named, got[0]) if not np.array_equal(g[0], g[1])]
+    assert np.array_equal(got[0], got[1][::-1])
+    assert got[0, :, 0, 2].any() and not got[0, :, 0, 2].all() and (got[0, :, 0, 3] == 0).any()      # ragged, whole and empty files all occur
+
+
 def test_serial_driver_on_random_layouts(checker, tmp_path):
     """200 layouts of 1-9 files, lengths 0-3 tiles +- 1 byte, text drawn from the reader's alphabet"""
     rng = np.random.default_rng(2024)

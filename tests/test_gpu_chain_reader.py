@@ -83,6 +83,29 @@ def test_layout_variants_match_host_reader_and_numpy(tmp_path):
         assert chain_io.loadtxt_device(p, ndmin=1).shape == (0,)
 
 
+def test_more_undecided_tokens_than_the_first_list(tmp_path):
+    """one column of 5 000 'nan': every token is left to the host, more than the 4 096 entries of the single-file reader's first
+    list (its second pass, with a list of the counted size) and more than the list of a farm handle made for this file alone (the
+    list grown once).  The host copy, the device copy and the farm all give the host reader's array"""
+    from mcevidence_amd import _capi, farm, resident
+    p = write(tmp_path, "nan.txt", "nan\n" * 5000)
+    want = chain_io.loadtxt(p)
+    assert want.shape == (5000, 1) and np.isnan(want).all()
+    text = np.fromfile(p, dtype=np.uint8)
+    got, stats = _capi.chain_dev_parse(text.ctypes.data, text.size)
+    assert stats["tokens"] == stats["patched"] == 5000 and same(got, want)
+    rc = resident.ResidentChains.from_files([p], iw=0, ilike=0, itheta=0)
+    assert rc.stats["files"][0]["patched"] == 5000 and same(rc.to_host(), want)
+    farm.release_handles()          # a fresh handle of 64 KiB: room for 11 264 tokens, but its list starts at 1 344 entries
+    try:
+        one, = farm.read_files([p], wave_bytes=65536)
+        st = farm.handle_stats()
+        assert st["capacity"] == 65536 and st["patched"] == 5000 and st["grows"] == 2 and st["allocs_wave"] == 2, st     # the list and the fixes, once
+        assert not isinstance(one, Exception) and same(one, want)
+    finally:
+        farm.release_handles()
+
+
 def big_file(tmp_path, fmt, rows, cols=29, seed=7):
     rng = np.random.default_rng(seed)
     a = rng.standard_normal((rows, cols)) * np.asarray([1e-3, 1.0, 70.0, 100.0])[rng.integers(0, 4, (rows, cols))]

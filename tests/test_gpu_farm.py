@@ -138,10 +138,21 @@ PREP_ROOTS = [       # (columns, rows per file, burn-in, rows left)
 ]
 
 
+def per_root_reference(rc, ncols):
+    """what the per-root calls (gather, mce_chain_reduce_dev) prepare for the resident chain ``rc``"""
+    import torch
+    n = rc.nrows
+    s1 = rc._gather(None, want=("params", "w", "like"))
+    fs = torch.empty(n, dtype=torch.float64, device="cuda:0")
+    wsb = _capi.chain_reduce_workspace_bytes(n)
+    ws = rc._ws(wsb)
+    scal = _capi.chain_reduce_dev(s1["like"].data_ptr(), s1["w"].data_ptr(), n, False, fs.data_ptr(), ws.data_ptr(), wsb, rc._stream())
+    return dict(rc=rc, ncols=ncols, n=n, params=s1["params"].cpu().numpy(), w=s1["w"].cpu().numpy(), fs=fs.cpu().numpy(), scal=scal)
+
+
 @pytest.fixture(scope="module")
 def prep_reference(tmp_path_factory):
     """per root: the resident chain and what ResidentChains prepares for it (parameters, weights, fs, max(logL), SumW), once"""
-    import torch
     td = str(tmp_path_factory.mktemp("prep"))
     rng = np.random.default_rng(5)
     ref = []
@@ -151,12 +162,7 @@ def prep_reference(tmp_path_factory):
         write_cosmomc_chains(root, chs, None, fmt="%.17g")
         rc = pkg.ResidentChains.from_files(root, burnlen=burn)
         assert rc.nrows == left
-        s1 = rc._gather(None, want=("params", "w", "like"))
-        fs = torch.empty(left, dtype=torch.float64, device="cuda:0")
-        wsb = _capi.chain_reduce_workspace_bytes(left)
-        ws = rc._ws(wsb)
-        scal = _capi.chain_reduce_dev(s1["like"].data_ptr(), s1["w"].data_ptr(), left, False, fs.data_ptr(), ws.data_ptr(), wsb, rc._stream())
-        ref.append(dict(rc=rc, ncols=ncols, n=left, params=s1["params"].cpu().numpy(), w=s1["w"].cpu().numpy(), fs=fs.cpu().numpy(), scal=scal))
+        ref.append(per_root_reference(rc, ncols))
     return ref
 
 
@@ -191,6 +197,30 @@ def test_segmented_preparation_equals_the_per_root_calls_bitwise(prep_reference,
         r, g = prep_reference[i], got[i]
         assert same(g["params"], r["params"]) and same(g["w"], r["w"]) and same(g["fs"], r["fs"]), i
         assert same(np.array(g["scal"][:2]), np.array(r["scal"][:2])) and g["scal"][2:] == (0.0, 0.0) and tuple(r["scal"][2:]) == (0, 0), i
+
+
+def test_segmented_preparation_counts_bad_rows_per_root_bitwise():
+    """three roots of 511 / 513 / 1 025 rows after a burn-in of 100 (a partial tile, a tile and a row, two tiles and a row), uploaded
+    as arrays so that no reader is involved: a NaN likelihood in the last row of the second, an infinite weight in row 512 of the
+    third.  Per root max(logL), SumW, both bad counts, fs, weights and parameters are bitwise what mce_chain_reduce_dev gives the
+    root alone, and the clean root is bitwise what it is in a wave of its own"""
+    rng = np.random.default_rng(11)
+    burn, ncols = 100, 6
+    chs = [np.column_stack([1.0 + rng.poisson(3.0, n), 50.0 + rng.random(n) * 20.0, rng.standard_normal((n, ncols - 2))]) for n in (611, 613, 1125)]
+    chs[1][-1, 1] = np.nan
+    chs[2][burn + 512, 0] = np.inf
+    ref = [per_root_reference(pkg.ResidentChains.from_arrays([a], burnlen=burn), ncols) for a in chs]
+    assert [r["n"] for r in ref] == [511, 513, 1025]
+    assert np.isnan(ref[1]["fs"][-1]) and np.isinf(ref[2]["w"][512])          # the planted rows are where the text says
+    got = farm_prep(ref, [0, 1, 2])
+    for i, bad in enumerate([(0, 0), (1, 0), (0, 1)]):
+        r, g = ref[i], got[i]
+        assert same(g["params"], r["params"]) and same(g["w"], r["w"]) and same(g["fs"], r["fs"]), i
+        assert same(np.array(g["scal"][:2]), np.array(r["scal"][:2])), i
+        assert g["scal"][2:] == bad and tuple(r["scal"][2:]) == bad, (i, g["scal"], r["scal"])
+    alone = farm_prep(ref, [0])[0]
+    assert all(same(alone[k], got[0][k]) for k in ("params", "w", "fs")) and same(np.array(alone["scal"]), np.array(got[0]["scal"]))
+    assert np.isinf(got[2]["scal"][1]) and np.isfinite(got[1]["scal"][0])     # SumW with the infinite weight; the max skips the NaN
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. host route and pins

@@ -258,6 +258,7 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
         // kRefineMargin more entries than asked for, so the final K are chosen on exact distances among K + 2 candidates
         // (a wrong row would need three rows within the keys' rounding of each other at the K-th place).
         p.ksel = std::min<int>(K + kRefineMargin, MCE_MAX_K);
+        p.pl_nr = nr;             // (the merge's exact second look walks all reference rows)
         ki = 0;
         while (ki < mce::kNumKcap - 1 && mce::kKcapList[ki] < p.ksel) ++ki;
         p.KCAP = mce::kKcapList[ki];

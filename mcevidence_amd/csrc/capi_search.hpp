@@ -661,7 +661,8 @@ int launch_merge(const Plan& p, bool write_dist, bool fuse, const double* dX, co
 #define MCE_MERGE(W, F, R)                                                                                          \
     hipLaunchKernelGGL((mce::merge_lists_kernel<W, F, R>), dim3(blocks), dim3(mce::kRedThreads), 0, st, pd, pi, p.L,  \
                        p.KCAP, nq, p.nq_pad, dX, dY, (int)d, K, (refine && p.ksel > K) ? p.ksel : K, self_mode, self_offset, d_dist, d_idx, K, k0, kmax, \
-                       d_w, d_fs, lnc, partial, qperm, p.part, p.nparts, qpb, border, nunits, col0, col1)
+                       d_w, d_fs, lnc, partial, qperm, p.part, p.nparts, qpb, border, nunits, col0, col1, p.pl_nr, \
+                       refine ? reinterpret_cast<const double*>(ws + p.off_center) : nullptr)
     if (write_dist && !fuse) { if (refine) MCE_MERGE(true, false, true); else MCE_MERGE(true, false, false); }
     else if (write_dist && fuse) { if (refine) MCE_MERGE(true, true, true); else MCE_MERGE(true, true, false); }
     else { if (refine) MCE_MERGE(false, true, true); else MCE_MERGE(false, true, false); }

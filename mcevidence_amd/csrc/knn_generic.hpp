@@ -90,7 +90,9 @@ __global__ __launch_bounds__(kGenThreads) void knn_generic_kernel(
 }
 
 // lists [1][K][nq_pad] (already sorted, exact keys) -> dist[nq,K] (+ idx); SELF_INCLUDE moves the
-// query's own row to column 0 with distance exactly 0.
+// query's own row to column 0 with distance exactly 0 -- whether or not the sweep kept it: the sweep keeps the EARLIER row
+// on ties, so K or more exact duplicates with lower row numbers push the own row out of the list.  It is a reference row by
+// contract (as in merge_lists_kernel, reduce_kernels.hpp); the list's last entry then makes room for it.
 __global__ __launch_bounds__(256) void generic_finalize_kernel(const double* __restrict__ part_d, const int* __restrict__ part_i,
                                                               int64_t nq, int64_t nq_pad, int K, int self_mode, int64_t self_offset,
                                                               double* __restrict__ dist, int64_t* __restrict__ idx)
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(256) void generic_finalize_kernel(const double* __r
         for (int k = 0; k < K; ++k)
             if (part_i[(int64_t)k * nq_pad + q] == selfj) { pself = k; break; }
     int o = 0;
-    if (pself >= 0) {
+    if (selfj >= 0) {
         dist[q * (int64_t)K] = 0.0;
         if (idx) idx[q * (int64_t)K] = selfj;
         o = 1;

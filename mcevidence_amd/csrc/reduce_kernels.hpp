@@ -53,7 +53,8 @@ __device__ __forceinline__ double block_sum(double v, double* red)
 // the original rows and are re-sorted -- so reported distances equal an exact search's
 // (duplicates give exactly 0, like the reference's KD-tree path) and only the choice
 // between candidates that tie to the last bits could differ -- which is why Kc = K + 2 candidates are selected and refined and
-// the K nearest BY EXACT DISTANCE reported (round 6: the rows then equal an exact search's too).  (REFINE=false when the lists
+// the K nearest BY EXACT DISTANCE reported (round 6: the rows then equal an exact search's too); a row whose last selected key
+// does not prove those K complete is searched again with direct differences (the exact second look below).  (REFINE=false when the lists
 // already hold exact distances: the fp16-filter path.)  Optionally feeds the evidence
 // reduction directly.
 //   part_d/part_i : [L][KCAP][nq_pad]
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(kRedThreads) void merge_lists_kernel(
     double* __restrict__ dist, int64_t* __restrict__ idx, int ld_out,
     int k0, int kmax, const double* __restrict__ w, const double* __restrict__ fs, double lnc,
     double* __restrict__ partial, const int* __restrict__ qperm, int part, int nparts, int qpb, const int* __restrict__ border, int nqblk,
-    int64_t col0, int64_t col1)
+    int64_t col0, int64_t col1, int64_t nr, const double* __restrict__ center)
 {
     __shared__ double red[kRedThreads / 64];
     // nparts > 1: this launch covers the query blocks part, part + nparts, ... (qpb list columns each) of a
@@ -131,6 +132,8 @@ __global__ __launch_bounds__(kRedThreads) void merge_lists_kernel(
         // does not depend on how many lists the plan happened to use
         if (selfj >= 0) { sel_d[0] = -1.0; sel_i[0] = selfj; nsel = 1; }     // (-1: sentinel, sorts first, reported as 0)
         // (REFINE: Kc >= K candidates are selected on the keys and refined; the K nearest by EXACT distance are reported)
+        double tkey = INF;         // REFINE: the key of the last entry selected -- no row left out has a smaller one
+        bool full = false;         // (all Kc places were filled: rows were left out)
         for (int k = nsel; k < (REFINE ? Kc : K); ++k) {
             double bv = INF;
             int bi = 0x7fffffff, bl = -1;
@@ -148,6 +151,8 @@ __global__ __launch_bounds__(kRedThreads) void merge_lists_kernel(
             head[bl]++;
             sel_d[nsel] = bv;
             sel_i[nsel++] = bi;
+            tkey = bv;
+            full = (nsel == Kc);
         }
         // ---- refine: exact direct-difference distances of the selected pairs ----
         // (REFINE=false: the lists already hold exact distances -- fp16-filter path)
@@ -170,6 +175,42 @@ __global__ __launch_bounds__(kRedThreads) void merge_lists_kernel(
             }
             sel_d[p] = dv;
             sel_i[p] = iv;
+        }
+        // ---- exact second look: are the K reported provably the K nearest? ----
+        // A row j left out has key_j >= tkey, and |key_j - d_j^2| <= c(D) u (|a| + |b_j|)^2 (a, b_j: the rows about the centre;
+        // c(D) = 2 D + 4, u = 2^-53: the arithmetic of the sweeps, derived in tests/helpers.py above cert_bound).  If j were no
+        // farther than the K-th reported, d_j <= dK, then |b_j| <= |a| + dK and key_j <= dK^2 + E with E = c(D) u (2 |a| + dK)^2.
+        // So tkey > dK^2 + E proves every row left out strictly farther than the K-th.  Where that fails (neighbours closer in
+        // d^2 than the keys' error: clusters far from the centre, exact ties) the thread finds its K nearest by direct differences
+        // over all nr rows -- the same fma chain as the refine above, ascending, ties by row.  Needs a margin (Kc > K: with
+        // Kc == K the last key IS the K-th distance's and the test never holds; K = 32 keeps the selection on keys).
+        if (REFINE && full && Kc > K && nr > (int64_t)nsel) {
+            double a2 = 0.0;
+            for (int i = 0; i < D; ++i) { const double t = x[i] - center[i]; a2 = fma(t, t, a2); }
+            const double dK2 = fmax(sel_d[K - 1], 0.0);
+            const double rr = 2.0 * sqrt(a2) + sqrt(dK2);
+            const double E = (2.0 * (double)D + 4.0) * 0x1p-53 * rr * rr * (1.0 + 0x1p-20);
+            if (!(tkey > dK2 + E)) {
+                const int64_t skip = (self_mode == 1) ? (int64_t)selfj : (self_mode == 2 ? self_offset + qo : (int64_t)-1);
+                int n = (selfj >= 0) ? 1 : 0;                  // (the own row stays first: sel_d[0] = -1, sel_i[0] = selfj)
+                for (int64_t j = 0; j < nr; ++j) {
+                    if (j == skip) continue;
+                    const double* y = Y + j * D;
+                    double s2 = 0.0;
+                    for (int i = 0; i < D; ++i) { const double t = x[i] - y[i]; s2 = fma(t, t, s2); }
+                    if (n == K && !(s2 < sel_d[K - 1])) continue;          // (rows ascend: an equal distance sorts after)
+                    int p = n < K ? n : K - 1;
+                    while (p > 0 && sel_d[p - 1] > s2) {
+                        sel_d[p] = sel_d[p - 1];
+                        sel_i[p] = sel_i[p - 1];
+                        --p;
+                    }
+                    sel_d[p] = s2;
+                    sel_i[p] = (int)j;
+                    if (n < K) ++n;
+                }
+                nsel = n;
+            }
         }
         for (int k = 0; k < K; ++k) {
             const double d2 = (k < nsel) ? fmax(sel_d[k], 0.0) : INF;

@@ -18,7 +18,7 @@
 #include <omp.h>
 #endif
 
-#define KMAX_ORACLE 64
+#define KMAX_ORACLE 128
 
 /* self_mode: 0 plain; 1 plain (Y==X, self included as sklearn does);
  *            2 skip reference row (self_offset + q). */

@@ -292,6 +292,19 @@ ADVERSARIAL_EXTRA = {
     # already tight passes the gate on its error terms alone -- and the order is the distances', not the row numbers'
     "jittered_lattice": lambda r, n, d: r.integers(-3, 4, size=(n, d)) + 1e-4 * r.standard_normal((n, d)),
 }
+
+
+def offset_clusters(S):
+    """Three clusters S apart in column 0, each 1e-3 wide (tests/test_gpu_adversarial_f64.py): the input on which the fp64
+    sweeps' refine margin matters.  The GEMM-form keys carry an absolute error that grows with S^2 while the neighbour
+    spacings stay those of the 1e-3 clouds, so with S chosen just below the point where a row becomes key-ambiguous
+    (offset_scale) many rows have one or two outsiders within the keys' error of the K-th neighbour, none has m + 1, and
+    every row must come out exactly right."""
+    return lambda r, n, d: r.integers(0, 3, (n, 1)) * S + 1e-3 * r.standard_normal((n, d))
+
+
+#: the separations offset_clusters is tried at, largest first (offset_scale)
+OFFSET_SCALES = (100, 30, 10, 3, 1)
 #: kinds that need at least two columns
 ADVERSARIAL_MIN2 = ("anisotropic", "subnormal_fp16_coords", "constant_column")
 
@@ -371,13 +384,111 @@ def needs_two_columns(kind):
 # may order the pair differently, and the row is judged by C1 - C3 only.  Exact ties (gap == 0) are not ambiguous: both
 # sides break them by row number.  At most AMBIGUOUS_CAP of the rows of a case may be ambiguous, which is checked on the
 # oracle's output before the result under test is looked at.
+#
+# The fp64 sweeps (knn_mfma.hpp, knn_long.hpp) SELECT on GEMM-form keys and keep K + m entries (m = min(K + 2, 32) - K: the
+# plan's kRefineMargin, 1 at K = 31, 0 at K = 32); the merge then reports the K nearest of them by exact direct differences.
+# With `margin=m` the certificate judges that contract.
+#
+# E = key_bound: |key - d^2| <= E[q] = c(D) u (|a| + max_j |b_j|)^2, u = 2^-53, a = x - c and b = y - c the rows about the
+# centre c the library subtracts (any c: d^2 = |a - b|^2 exactly), c(D) = 2 D + 4.  Derivation, from the kernels' arithmetic:
+#   * centred coordinates: fl(x_i - c_i) = a_i (1 + e), |e| <= u, one rounding each (knn_mfma.hpp, long_pack_queries_kernel,
+#     pack_refs_kernel); the factor -2 of the packed references is exact.  A product of two of them is off by 2 u |a_i b_i|, a
+#     square by 2 u a_i^2.
+#   * the two norms: one fma chain over the D squares (pack_refs_kernel, long_query_norms_kernel; knn_mfma.hpp adds four
+#     chains of <= D/4 + 1 terms with two more additions: fewer roundings): at most D u |.|^2, with the squares' own error
+#     (D + 2) u |a|^2 and (D + 2) u |b|^2.
+#   * the MFMA chain of 4 KS terms seeded with |a|^2 adds the D products -2 a_i b_i and 1 * |b|^2; its padding terms are
+#     0 * 0 and add exactly.  Each of the D + 1 non-zero terms enters the accumulator through one fused multiply-add: one
+#     rounding of the partial sum, D + 1 in all.  Every partial sum is bounded by the sum of the terms' magnitudes,
+#     |a|^2 + 2 sum |a_i b_i| + |b|^2 <= (|a| + |b|)^2 (Cauchy-Schwarz), so the chain adds at most (D + 1) u (|a| + |b|)^2
+#     whatever the order of the terms -- the blocks of knn_long.hpp and the k-steps of knn_mfma.hpp alike.
+#   * together: (D + 2) u (|a|^2 + |b|^2) + 4 u |a||b| + (D + 1) u (|a| + |b|)^2 <= (2 D + 3) u (|a| + |b|)^2, since
+#     4 <= 2 (D + 2).  The terms of second order in u are below D^2 u times that; c(D) = 2 D + 4 covers them (and the
+#     distance of NumPy's column mean from the library's, which moves |a| and |b| by parts in 1e12) for D <= 1024 with a
+#     factor of (2 D + 3)^-1 >= 4.8e-4 to spare.  max_j runs over all references: no per-row sharpening is used.
+#   Rows with identical coordinates get identical keys (an MFMA output element depends on its A row, B column and C-in only),
+#   and equal keys are ordered by row, as the oracle orders equal distances.
+# A row is KEY-AMBIGUOUS when a correct selection on keys within E of the truth may lose one of the true K.  A true
+# neighbour i at position s of the oracle's order is lost only if K + m rows precede it in (key, row) order; the s rows
+# before it in truth may, and otherwise only rows o with d_o^2 <= d_i^2 + 2 E whose coordinates differ from i's
+# (key_o <= key_i needs d_o^2 - E <= d_i^2 + E).  So with the references collapsed to distinct points p_0, p_1, ... in
+# the oracle's order, mult_j copies each, cum_j = mult_0 + ... + mult_j: the row is key-ambiguous iff for some j with
+# cum_(j-1) < K:  min(cum_j, K) - 1 + sum of mult_j' over j' > j with d_j'^2 <= d_j^2 + 2 E  >=  K + m.  Without duplicate
+# rows that is od[:, K + m]^2 - od[:, K - 1]^2 <= 2 E (both evaluated with the oracle's own 4B around them).
+#   C3w            dist[q, k]^2 <= od[q, k]^2 (1 + 4B) + 2 E[q] for every k: what the K exact-nearest of the K + m key-nearest
+#                  (the set S) satisfy.  Proof: take the true k + 1 nearest.  If one of them, t, is not in S, every member of S
+#                  has key <= key_t, so d^2 <= d_t^2 + 2 E <= od_k^2 + 2 E for all K + m >= k + 1 of them; otherwise the k + 1
+#                  are in S themselves.  Either way S holds k + 1 rows within od_k^2 + 2 E, and the (k + 1)-th smallest exact
+#                  distance in S is no larger.  (The fp64 rounding of the refined and of the oracle's distance is the 4B; its
+#                  product with 2 E is a part in 1e13 of E's spare.)
+# With `margin`: rows neither oracle- nor key-ambiguous get C1 - C4, key-ambiguous rows C1, C2 and C3w, and in a strict case
+# at most AMBIGUOUS_CAP of the rows may be ambiguous of either kind.  `weak=True` judges every row by C1, C2 and C3w, without
+# a cap; WEAK lists the (kind, self class) pairs that need it, decided on the CPU alone
+# (tests/test_oracle_certificate.py::test_weak_table_is_minimal_and_complete).
 # --------------------------------------------------------------------------------------------------------------------
 SELF_NONE, SELF_INCLUDE, SELF_EXCLUDE = 0, 1, 2
 AMBIGUOUS_CAP = 1e-5
+#: (kind, self class) judged weakly on the GEMM-form families; self classes: "one" (one buffer: exclude, include, none, shard),
+#: "asq", "asr", "cross"
+WEAK = frozenset({("tight_clusters", "one"), ("lattice_ties", "one")})
 
 
 def cert_bound(D):
     return (0.5 * D + 2.0) * 2.0 ** -53
+
+
+def key_bound_c(D):
+    """c(D) of key_bound (derivation above)"""
+    return 2.0 * D + 4.0
+
+
+def key_bound(X, Y):
+    """E[q]: absolute bound on |key - true d^2| of the fp64 sweeps' GEMM-form keys over every pair of query q (above)"""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    c = Y.mean(axis=0)
+    na = np.sqrt(((X - c) ** 2).sum(axis=1))
+    nb = np.sqrt(((Y - c) ** 2).sum(axis=1).max())
+    return key_bound_c(X.shape[1]) * 2.0 ** -53 * (na + nb) ** 2
+
+
+def refine_margin(K):
+    """entries the fp64 sweeps keep beyond K (capi_plan.hpp: min(K + kRefineMargin, MCE_MAX_K) - K)"""
+    return min(K + 2, 32) - K
+
+
+def _key_ambiguous(X, Y, K, m, self_mode, self_offset, od, E):
+    """mask of key-ambiguous rows (above); od: the oracle's K + m + 1 distances (fewer where the set ends)"""
+    nq, D = X.shape
+    B4 = 4.0 * cert_bound(D)
+    if self_mode == SELF_INCLUDE and K == 1:
+        return np.zeros(nq, dtype=bool)                        # (the own row alone: nothing is selected)
+    Yu, inv, counts = np.unique(Y, axis=0, return_inverse=True, return_counts=True)
+    inv = np.asarray(inv).reshape(-1)
+    if len(Yu) == len(Y):                                     # no duplicate rows: positions are points
+        if od.shape[1] <= K + m:
+            return np.zeros(nq, dtype=bool)                    # (fewer than K + m + 1 usable rows: every one is selected)
+        return od[:, K + m] ** 2 * (1.0 - B4) <= od[:, K - 1] ** 2 * (1.0 + B4) + 2.0 * E
+    # distinct points in the oracle's order; the own row (excluded, or reported apart) is no copy of its point
+    P = min(K + m + 2, len(Yu))
+    pd, pi = orc.knn_brute(X, np.ascontiguousarray(Yu), P, self_mode=0)
+    mult = counts[pi].astype(np.int64)
+    Kn = K
+    if self_mode != SELF_NONE:
+        mult -= pi == inv[self_offset + np.arange(nq)][:, None]
+        if self_mode == SELF_INCLUDE:
+            Kn = K - 1                                         # (the others: K - 1 of the K + m - 1 selected)
+    if Kn < 1:
+        return np.zeros(nq, dtype=bool)
+    p2 = pd * pd
+    cum = np.cumsum(mult, axis=1)
+    amb = np.zeros(nq, dtype=bool)
+    for j in range(P):
+        before = cum[:, j] - mult[:, j]
+        band = (p2[:, j + 1:] * (1.0 - B4) <= (p2[:, j] * (1.0 + B4) + 2.0 * E)[:, None])
+        ahead = np.minimum(cum[:, j], Kn) - 1 + (mult[:, j + 1:] * band).sum(axis=1)
+        amb |= (before < Kn) & (mult[:, j] > 0) & (ahead >= Kn + m)
+    return amb
 
 
 class CertificateError(AssertionError):
@@ -388,21 +499,25 @@ class CertificateError(AssertionError):
         self.report = report
 
 
-def oracle_lists(X, Y, K, self_mode, self_offset=0):
+def oracle_lists(X, Y, K, self_mode, self_offset=0, margin=None, weak=False):
     """The oracle's side of the certificate: (od, oi, ambiguous) -- its K + 1 nearest (fewer where the reference set
     ends), in the order the library documents for ``self_mode``, and the mask of ambiguous rows.  Raises when more than
-    AMBIGUOUS_CAP of the rows are ambiguous: such a case cannot judge anybody."""
+    AMBIGUOUS_CAP of the rows are ambiguous: such a case cannot judge anybody.
+    ``margin=m`` (the fp64 sweeps: lists of K + m chosen on GEMM-form keys): K + m + 1 nearest, and the result is
+    (od, oi, ambiguous, key_ambiguous, E) with E = key_bound(X, Y); the cap then counts rows ambiguous of either kind,
+    unless ``weak`` (every row judged by C1, C2 and C3w: no cap)."""
+    more = 1 if margin is None else margin + 1
     X = np.ascontiguousarray(X, dtype=np.float64)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     nq, D = X.shape
     nr = Y.shape[0]
     if self_mode == SELF_NONE:
-        od, oi = orc.knn_brute(X, Y, min(K + 1, nr), self_mode=0)
+        od, oi = orc.knn_brute(X, Y, min(K + more, nr), self_mode=0)
     elif self_mode == SELF_EXCLUDE:
-        od, oi = orc.knn_brute(X, Y, min(K + 1, nr - 1), self_mode=2, self_offset=self_offset)
+        od, oi = orc.knn_brute(X, Y, min(K + more, nr - 1), self_mode=2, self_offset=self_offset)
     elif self_mode == SELF_INCLUDE:           # the own row first, at distance 0, whatever duplicates it has; then the others
         own = self_offset + np.arange(nq, dtype=np.int64)
-        kk = min(K, nr - 1)
+        kk = min(K + more - 1, nr - 1)
         if kk > 0:
             od, oi = orc.knn_brute(X, Y, kk, self_mode=2, self_offset=self_offset)
         else:
@@ -413,13 +528,21 @@ def oracle_lists(X, Y, K, self_mode, self_offset=0):
         raise ValueError("self_mode %r" % (self_mode,))
     if od.shape[1] < K:
         raise ValueError("K = %d exceeds the usable reference rows" % K)
-    gap = np.diff(od, axis=1)
-    ambiguous = np.any((gap > 0) & (gap <= 4.0 * cert_bound(D) * od[:, 1:]), axis=1)
-    namb = int(ambiguous.sum())
-    if namb > AMBIGUOUS_CAP * nq:
+    gap = np.diff(od[:, :K + 1], axis=1)
+    ambiguous = np.any((gap > 0) & (gap <= 4.0 * cert_bound(D) * od[:, 1:K + 1]), axis=1)
+    if margin is None:
+        either = ambiguous
+    else:
+        E = key_bound(X, Y)
+        key_ambiguous = _key_ambiguous(X, Y, K, margin, self_mode, self_offset, od, E)
+        either = ambiguous | key_ambiguous
+    namb = int(either.sum())
+    if namb > AMBIGUOUS_CAP * nq and not (weak and margin is not None):
         raise ValueError("%d of %d rows are ambiguous on the oracle alone (cap %g of the rows): first rows %s -- change the seed "
-                         "or the input" % (namb, nq, AMBIGUOUS_CAP, np.flatnonzero(ambiguous)[:5].tolist()))
-    return od, oi, ambiguous
+                         "or the input" % (namb, nq, AMBIGUOUS_CAP, np.flatnonzero(either)[:5].tolist()))
+    if margin is None:
+        return od, oi, ambiguous
+    return od, oi, ambiguous, key_ambiguous, E
 
 
 _LONGDOUBLE_OK = np.finfo(np.longdouble).eps < 2.0 ** -52
@@ -455,19 +578,27 @@ def _dist_within_bound(X, Y, idx, dist, B):
     return ok, zero
 
 
-def knn_certificate(X, Y, K, dist, idx, self_mode, self_offset=0, kernel=None, oracle=None, max_report=8):
+def knn_certificate(X, Y, K, dist, idx, self_mode, self_offset=0, kernel=None, oracle=None, max_report=8, margin=None, weak=False):
     """Certify a finished K-nearest search ``(dist, idx)`` of the queries X in the references Y, EVERY row (C1 - C4 above).
     Returns the report (dict: rows, K, B, ambiguous, ambiguous_rows, failures = []) or raises CertificateError whose message
     names the first failing rows, the check each failed and ``kernel`` (the caller's ``last_kernel()``); its ``report``
     lists every failure as (row, column, check, detail).  ``oracle``: a precomputed ``oracle_lists(...)`` of the same
-    arguments (several searches of one input)."""
+    arguments (several searches of one input).
+    ``margin=m``: the search selected K + m on GEMM-form keys and refined (the fp64 sweeps): key-ambiguous rows are judged by
+    C1, C2 and C3w, and with ``weak`` every row is; the report also carries key_ambiguous and key_ambiguous_rows."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     nq, D = X.shape
     nr = Y.shape[0]
     B = cert_bound(D)
     # the reference first, and alone: how many rows it cannot judge
-    od, oi, ambiguous = oracle if oracle is not None else oracle_lists(X, Y, K, self_mode, self_offset)
+    if margin is None:
+        assert not weak, "weak judges the margin contract: give margin"
+        od, oi, ambiguous = oracle if oracle is not None else oracle_lists(X, Y, K, self_mode, self_offset)
+        key_amb, E = np.zeros(nq, dtype=bool), None
+    else:
+        od, oi, ambiguous, key_amb, E = oracle if oracle is not None else oracle_lists(X, Y, K, self_mode, self_offset, margin=margin, weak=weak)
+    relaxed = np.ones(nq, dtype=bool) if weak else key_amb      # rows judged by C1, C2 and C3w
     assert od.shape[0] == nq and od.shape[1] >= K
     dist = np.asarray(dist)
     idx = np.asarray(idx)
@@ -512,15 +643,21 @@ def knn_certificate(X, Y, K, dist, idx, self_mode, self_offset=0, kernel=None, o
     note(tie, "C2 tie not by ascending row", lambda q, k: "rows %d, %d at %r" % (idx[q, k - 1], idx[q, k], dist[q, k]))
     # ---- C3
     odk = od[:, :K]
-    note(~(np.abs(np.where(finite, dist, np.inf) - odk) <= 2.0 * B * odk), "C3 not the K nearest",
+    note(~(np.abs(np.where(finite, dist, np.inf) - odk) <= 2.0 * B * odk) & ~relaxed[:, None], "C3 not the K nearest",
          lambda q, k: "dist=%r oracle=%r (row %d, oracle row %d)" % (dist[q, k], od[q, k], idx[q, k], oi[q, k]))
+    if margin is not None:
+        # ---- C3w
+        note(~(np.where(finite, dist, np.inf) ** 2 <= odk * odk * (1.0 + 4.0 * B) + 2.0 * E[:, None]) & relaxed[:, None],
+             "C3w beyond the K nearest by more than the keys' error",
+             lambda q, k: "dist^2=%r oracle^2=%r 2E=%r (row %d, oracle row %d)" % (dist[q, k] ** 2, od[q, k] ** 2, 2.0 * E[q], idx[q, k], oi[q, k]))
     # ---- C4
-    note((idx != oi[:, :K]) & ~ambiguous[:, None], "C4 rows differ from the oracle's",
+    note((idx != oi[:, :K]) & ~ambiguous[:, None] & ~relaxed[:, None], "C4 rows differ from the oracle's",
          lambda q, k: "row %d, oracle row %d at %r / %r" % (idx[q, k], oi[q, k], dist[q, k], od[q, k]))
 
     failures = sorted((q, k, c, t) for (q, c), (k, t) in fails.items())
     report = dict(rows=nq, K=K, B=B, ambiguous=int(ambiguous.sum()), ambiguous_rows=np.flatnonzero(ambiguous), failures=failures,
-                  failed_rows=sorted({f[0] for f in failures}), kernel=kernel)
+                  failed_rows=sorted({f[0] for f in failures}), kernel=kernel, key_ambiguous=int(key_amb.sum()),
+                  key_ambiguous_rows=np.flatnonzero(key_amb), weak=weak)
     if failures:
         lines = ["row %d column %d: %s (%s)" % f for f in failures[:max_report]]
         raise CertificateError("kNN certificate failed on %d of %d rows (nq=%d nr=%d d=%d K=%d self_mode=%d self_offset=%d, "

@@ -141,8 +141,9 @@ def case_id(c):
 CASES = expand()
 
 
-def inputs(c):
-    """(X, Y, self_mode, self_offset) of a case; X is Y (the same array) for one buffer"""
+def inputs(c, KINDS=KINDS, CROSS=CROSS):
+    """(X, Y, self_mode, self_offset) of a case; X is Y (the same array) for one buffer.  KINDS, CROSS: the generator tables
+    (tests/test_gpu_adversarial_f64.py brings one more kind)"""
     rng = np.random.default_rng(zlib.crc32(("%(kind)s-%(d)d-%(n)d-%(self)s" % c).encode()))
     n, nq, d, kind = c["n"], c["nq"], c["d"], c["kind"]
     if c["self"] in ("asq", "asr", "cross"):

@@ -208,7 +208,8 @@ int mce_evidence_feed_batch_dev_f64(mce_feed_problem *problems, int64_t nprob, i
  *   Outputs (host): dotp[nprefix * kmax], loglmax[b] = max(logl[:prefix[b]]) (NaN once a NaN lies below prefix[b], as np.amax),
  *       jacobian[nprefix].  A non-positive eigenvalue of any prefix -> MCE_ERR_INVALID, the prefix named in the message.
  *   mce_options.verify applies to each distinct search; mce_last_verify_rows() then counts the rows of all of them.
- * The host waits twice whatever nprefix is (for the covariances -- the eigen-solves are the host's -- and at the end). */
+ * The host waits twice whatever nprefix is (for the covariances -- the eigen-solves are the host's -- and at the end); once with
+ * mce_options.eig_mode = MCE_EIG_DEVICE (all the systems solved in one launch behind the covariances). */
 #define MCE_MAX_PREFIX 256
 int mce_evidence_feed_prefix_f64(const double *S1, int64_t n1, int64_t ld1, const double *S2, int64_t n2, int64_t ld2,
                                  int32_t d, int32_t cov_mode, int32_t kmax, const double *w, const double *logl,
@@ -330,8 +331,17 @@ typedef struct mce_options {
                               on, one call in eight of the smaller ones (there the check is launch overhead, not rows: 0.16 of
                               0.68 ms at 7 k x 6) -- and one on the fp64 kernels is not; MCE_VERIFY=n in the environment: n rows
                               on EVERY call; MCE_VERIFY=0: off.  ~1 ms at 1 M x 27 with the distances it needs written out */
-    int32_t reserved[2];   /* 0 */
+    int32_t eig_mode;      /* evidence feed (mce_evidence_feed_f64, _batch[_dev], _part[_dev], _whiten[_dev], _prefix[_dev]): who solves the
+                              covariance eigen-system.  0 (what every caller built before this field sends: it was reserved[0]): the
+                              process default -- MCE_FEED_EIG=host|hip in the environment, read once; host when unset.  1: the host
+                              (one core, between two waits).  2: the device (mce_eig_sym_batch_dev_f64 on the call's stream; the
+                              call waits once, a batch once per wave).  The two agree within C eps cond(Cn) per eigenvalue, not bit
+                              for bit (docs/design/device_eig.md) */
+    int32_t reserved[1];   /* 0 */
 } mce_options;
+#define MCE_EIG_DEFAULT 0
+#define MCE_EIG_HOST 1
+#define MCE_EIG_DEVICE 2
 int mce_options_push(const mce_options* opt);
 int mce_options_pop(void);
 int mce_knn_f64_opt(const double* X, int64_t nq, const double* Y, int64_t nr, int32_t d, int32_t K, int32_t self_mode,
@@ -343,6 +353,24 @@ int mce_knn_dotp_f64_dev_opt(const double* dX, int64_t nq, const double* dY, int
                              int64_t self_offset, const double* d_w, const double* d_fs, double* d_dotp, double* d_dist_out,
                              void* ws, size_t ws_bytes, void* stream, const mce_options* opt);
 size_t mce_knn_workspace_bytes_opt(int64_t nq, int64_t nr, int32_t d, int32_t K, const mce_options* opt);
+
+/* Batched symmetric eigen-solver (the feed's, d <= 127): `nsys` row-major symmetric d x d matrices cov[nsys][d*d] -> evec[nsys][d*d]
+ * (eigenvectors in the COLUMNS, each one's first largest-magnitude component positive), scale[nsys][d] = 1 / sqrt(lam),
+ * lam[nsys][d] (descending, ties in the order of a stable sort) and status[nsys][MCE_EIG_STATUS_INTS] = {code, index, sweeps,
+ * rotations}: code 0 ok; 1 the matrix holds a NaN or an infinity (no sweep runs); 2 eigenvalue `index` is not > 0.  A system whose
+ * code is not 0 fails alone and still gets finite evec (the identity) and scale (1).
+ *   _dev: device pointers, one workgroup per system (parallel Jacobi in a round-robin tournament order, the whole matrix in LDS),
+ *         enqueued on `stream`, never synchronises.  A system's bits depend on its own matrix alone.
+ *   host pointers: `mode` MCE_EIG_HOST runs the feed's host solver (cyclic Jacobi; sweeps and rotations are reported as 0),
+ *         MCE_EIG_DEVICE uploads, runs the kernel on `device` and copies back.
+ * mce_last_eig_stats: out[4] = for the calling thread's last evidence-feed call, systems solved on the device, systems solved on the
+ * host, the largest number of sweeps and the rotations in all (device solves only). */
+#define MCE_EIG_STATUS_INTS 4
+int mce_eig_sym_batch_dev_f64(const double* d_cov, int32_t d, int64_t nsys, double* d_evec, double* d_scale, double* d_lam, int32_t* d_status,
+                              void* stream);
+int mce_eig_sym_batch_f64(const double* cov, int32_t d, int64_t nsys, int32_t mode, double* evec, double* scale, double* lam, int32_t* status,
+                          int32_t device);
+int mce_last_eig_stats(double* out, int32_t n);
 
 /* Run-time certificate of a finished search (reference: the result of `nbrs.kneighbors(samples)`, MCEvidence.py:1104, whose
  * exactness everything downstream rests on).  For `nsample` query rows spread evenly over the set (the pattern shifted by

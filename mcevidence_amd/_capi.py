@@ -111,6 +111,9 @@ SIGNATURES = {
     "mce_dotp_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int32]),
     "mce_knn_f64_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "mce_dotp_f64_dev": (_c.c_int, [_P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _P, _P, _c.c_size_t, _P]),
+    "mce_eig_sym_batch_dev_f64": (_c.c_int, [_P, _c.c_int32, _c.c_int64, _P, _P, _P, _P, _P]),
+    "mce_eig_sym_batch_f64": (_c.c_int, [_P, _c.c_int32, _c.c_int64, _c.c_int32, _P, _P, _P, _P, _c.c_int32]),
+    "mce_last_eig_stats": (_c.c_int, [_c.c_void_p, _c.c_int32]),
     "mce_knn_dotp_f64_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
 }
 
@@ -256,12 +259,18 @@ def last_kernel_ms():
 class Options(_c.Structure):
     """``mce_options``: the search / prune / symmetric modes of ONE call (-1: the process default); ``verify`` > 0:
     re-check that many query rows after the search by an exact fp64 scan of all reference rows (RuntimeError if one
-    disagrees; host-pointer entry points)."""
+    disagrees; host-pointer entry points); ``eig_mode``: who solves the evidence feed's eigen-systems -- ``EIG_DEFAULT`` (0:
+    the process default, ``MCE_FEED_EIG=host|hip``), ``EIG_HOST`` or ``EIG_DEVICE``."""
     _fields_ = [("size", _c.c_int32), ("search_mode", _c.c_int32), ("prune_mode", _c.c_int32), ("sym_mode", _c.c_int32),
-                ("same_set", _c.c_int32), ("verify", _c.c_int32), ("reserved", _c.c_int32 * 2)]
+                ("same_set", _c.c_int32), ("verify", _c.c_int32), ("eig_mode", _c.c_int32), ("reserved", _c.c_int32 * 1)]
 
-    def __init__(self, search_mode=-1, prune_mode=-1, sym_mode=-1, same_set=-1, verify=-1):
-        super().__init__(_c.sizeof(Options), int(search_mode), int(prune_mode), int(sym_mode), int(same_set), int(verify))
+    def __init__(self, search_mode=-1, prune_mode=-1, sym_mode=-1, same_set=-1, verify=-1, eig_mode=0):
+        super().__init__(_c.sizeof(Options), int(search_mode), int(prune_mode), int(sym_mode), int(same_set), int(verify), int(eig_mode))
+
+
+EIG_DEFAULT, EIG_HOST, EIG_DEVICE = 0, 1, 2
+EIG_STATUS_INTS = 4          # status of one solve: code (0 ok, 1 not finite, 2 an eigenvalue not > 0), its index, sweeps, rotations
+EIG_MAX_DIM = 127
 
 
 class options(object):
@@ -285,6 +294,38 @@ def last_search_stats():
     out = (_c.c_double * 4)()
     check(load().mce_last_search_stats(_c.cast(out, _c.c_void_p), 4))
     return dict(flops_main=out[0], flops_all=out[1], search_ms=out[2], kernel_ms=out[3])
+
+
+def eig_sym_batch(cov, mode=EIG_DEVICE, device=0):
+    """Both eigen-solvers of the evidence feed through one door (``mce_eig_sym_batch_f64``): ``cov`` [nsys, d, d] (or one [d, d])
+    symmetric matrices; ``mode`` ``EIG_HOST`` (cyclic Jacobi on one core) or ``EIG_DEVICE`` (one workgroup per system).  Returns
+    (evec [nsys, d, d], eigenvectors in the columns; scale [nsys, d] = 1 / sqrt(lam); lam [nsys, d], descending; status [nsys, 4] =
+    code, index, sweeps, rotations).  A system with a non-zero code fails alone: identity, unit scales."""
+    cov = np.ascontiguousarray(cov, dtype=np.float64)
+    if cov.ndim == 2:
+        cov = cov[None]
+    if cov.ndim != 3 or cov.shape[1] != cov.shape[2] or cov.shape[0] < 1 or cov.shape[1] < 1:
+        raise ValueError("cov must be [nsys, d, d]")
+    nsys, d = cov.shape[0], cov.shape[1]
+    evec = np.zeros((nsys, d, d))
+    scale = np.zeros((nsys, d))
+    lam = np.zeros((nsys, d))
+    status = np.zeros((nsys, EIG_STATUS_INTS), dtype=np.int32)
+    check(load().mce_eig_sym_batch_f64(cov.ctypes.data, d, nsys, int(mode), evec.ctypes.data, scale.ctypes.data, lam.ctypes.data, status.ctypes.data,
+                                       int(device)))
+    return evec, scale, lam, status
+
+
+def eig_sym_batch_dev(d_cov, d, nsys, d_evec, d_scale, d_lam, d_status, stream=0):
+    """``mce_eig_sym_batch_dev_f64``: device ADDRESSES, enqueue only."""
+    check(load().mce_eig_sym_batch_dev_f64(d_cov, int(d), int(nsys), d_evec, d_scale, d_lam, d_status, stream or None))
+
+
+def last_eig_stats():
+    """dict(device, host, max_sweeps, rotations): what the calling thread's last evidence-feed call solved where (mce_last_eig_stats)"""
+    out = (_c.c_double * 4)()
+    check(load().mce_last_eig_stats(_c.cast(out, _c.c_void_p), 4))
+    return dict(device=int(out[0]), host=int(out[1]), max_sweeps=int(out[2]), rotations=int(out[3]))
 
 
 def check(rc):

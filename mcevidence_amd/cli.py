@@ -43,7 +43,17 @@ def build_parser(prog=None):
     p.add_argument("--farm", action="store_true",
                    help="root_name is a text file with one chain root per line ('#' starts a comment): all roots in batched GPU passes "
                         "(mcevidence_amd.farm); a root the farm does not cover takes the per-root route")
+    p.add_argument("--device-eig", dest="device_eig", action="store_true",
+                   help="solve the covariance eigen-systems of the device feeders on the GPU (HipBackend(device_eig=True)) instead of on the host")
     return p
+
+
+def _backend_kw(args):
+    """the backend the flags ask for; nothing when they ask for none (the default backend, as ever)"""
+    if not args.device_eig:
+        return {}
+    from .evidence import HipBackend
+    return {"backend": HipBackend(device_eig=True)}
 
 
 def farm_main(args):
@@ -62,7 +72,7 @@ def farm_main(args):
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
     outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
-                                    idchain=args.idchain, split=args.cross)
+                                    idchain=args.idchain, split=args.cross, **_backend_kw(args))
     for r, mle in zip(roots, outs):
         print()
         print("Using file: ", r)
@@ -92,13 +102,13 @@ def main(argv=None):
     if args.resident:
         from .resident import evidence_from_files
         out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
-                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen)
+                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, **_backend_kw(args))
         print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
         print("")
         return out
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
-                     thinlen=args.thinlen)
+                     thinlen=args.thinlen, **_backend_kw(args))
     out = mce.evidence()
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
     print("")

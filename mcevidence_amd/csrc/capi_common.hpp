@@ -68,6 +68,8 @@ std::atomic<int> g_prune_mode{0};
 //   MCE_FEED_WAVE_BYTES=n        batched feed: bytes of host data per upload wave (tests: force several waves)
 //   MCE_FEED_UPLOAD=async        batched feed: uploads on the job's stream (read once)
 //   MCE_VERIFY=n                 rows of the default run-time certificate (256; 0 = off; read once)
+//   MCE_FEED_EIG=host|hip        evidence feed: the eigen-solver where a call's mce_options.eig_mode is 0 (host; read once) -- NOT
+//                                result-neutral: the two solvers agree within the bounds of docs/design/device_eig.md, not bit for bit
 // ---------------------------------------------------------------------------------------------------------------------
 struct Tuning {
     bool sym_kernel_f16 = false, tail_split = true, prune_prof = false, wide = true;
@@ -120,6 +122,7 @@ const char* env_prune_times() { return getenv("MCE_PRUNE_TIMES"); }
 // read once per process
 bool env_long_on() { static const bool v = [] { const char* e = getenv("MCE_LONG"); return !(e && e[0] == '0'); }(); return v; }
 bool env_deep_on() { static const bool v = [] { const char* e = getenv("MCE_DEEP"); return !(e && e[0] == '0'); }(); return v; }
+int env_feed_eig() { static const int v = [] { const char* e = getenv("MCE_FEED_EIG"); return e && !strcmp(e, "hip") ? 2 : 1; }(); return v; }
 bool env_feed_upload_async() { static const bool v = [] { const char* e = getenv("MCE_FEED_UPLOAD"); return e && !strcmp(e, "async"); }(); return v; }
 // (the all-pairs-once partition's workspace layout depends on these two: an environment that changed between the calls on one
 //  workspace would misplace the list sets -- ADVICE round 5)
@@ -128,7 +131,7 @@ int env_pairs_once_panel() { static const int v = [] { const char* e = getenv("M
 // Per-call options (mce_options, include/mcevidence_hip.h): the *_opt entry points and mce_options_push / _pop set them for
 // the calls the CURRENT THREAD makes; -1 = the process-wide default of the setters above.  Threads the library starts
 // itself (one per device) inherit the caller's.  The planner reads the modes through these three functions only.
-struct CallOptions { int search = -1, prune = -1, sym = -1, same_set = -1, verify = -1; };
+struct CallOptions { int search = -1, prune = -1, sym = -1, same_set = -1, verify = -1, eig = 0; };      // (eig: 0 = the process default)
 thread_local CallOptions t_opt;
 thread_local std::vector<CallOptions> t_opt_stack;
 int eff_search_mode() { return t_opt.search >= 0 ? t_opt.search : g_mode.load(); }

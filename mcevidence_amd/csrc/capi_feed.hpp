@@ -3,65 +3,7 @@
 #pragma once
 namespace {
 
-// cyclic Jacobi eigen-solver for a symmetric d x d matrix (row-major A, destroyed); eigenvalues in
-// lam[d], eigenvectors in the COLUMNS of V (row-major [d][d]).  d <= 1024.  Per-element stopping rule
-// (Demmel & Veselic 1992): a rotation is skipped when |a_pq| <= 1e-16 sqrt(a_pp a_qq), and the solver stops
-// after a sweep without one.  Every eigenvalue then carries a RELATIVE error of about eps * cond(Cn), Cn the
-// correlation matrix diag(A)^-1/2 A diag(A)^-1/2 -- the accuracy A's own rounding allows -- however graded A is.
-// (A rule relative to the whole diagonal, off(A) <= 1e-32 |diag A|^2, stops while the smallest eigenvalues of a
-// graded covariance are still wrong by 2e-9 relative, and by up to 9e-4 on few rows: tests/test_gpu_feeders.py.)
-void jacobi_eig(std::vector<double>& A, int d, std::vector<double>& lam, std::vector<double>& V)
-{
-    V.assign((size_t)d * d, 0.0);
-    for (int i = 0; i < d; ++i) V[(size_t)i * d + i] = 1.0;
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        bool rotated = false;
-        for (int p = 0; p < d - 1; ++p)
-            for (int q = p + 1; q < d; ++q) {
-                const double apq = A[(size_t)p * d + q];
-                if (std::fabs(apq) <= 1e-16 * std::sqrt(std::fabs(A[(size_t)p * d + p] * A[(size_t)q * d + q]))) continue;
-                rotated = true;
-                const double app = A[(size_t)p * d + p], aqq = A[(size_t)q * d + q];
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < d; ++k) {          // A <- A J   (columns p, q)
-                    const double akp = A[(size_t)k * d + p], akq = A[(size_t)k * d + q];
-                    A[(size_t)k * d + p] = c * akp - s * akq;
-                    A[(size_t)k * d + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < d; ++k) {          // A <- J^T A (rows p, q)
-                    const double apk = A[(size_t)p * d + k], aqk = A[(size_t)q * d + k];
-                    A[(size_t)p * d + k] = c * apk - s * aqk;
-                    A[(size_t)q * d + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < d; ++k) {          // V <- V J
-                    const double vkp = V[(size_t)k * d + p], vkq = V[(size_t)k * d + q];
-                    V[(size_t)k * d + p] = c * vkp - s * vkq;
-                    V[(size_t)k * d + q] = s * vkp + c * vkq;
-                }
-            }
-        if (!rotated) break;
-    }
-    // canonical form: eigenvalues descending, each eigenvector's largest component positive.  Two
-    // sets whitened with their OWN systems (covtype 'single' cross evidence) are then rotated
-    // consistently whenever their covariances are close, whatever the sweep order did.
-    std::vector<int> order(d);
-    for (int i = 0; i < d; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return A[(size_t)a * d + a] > A[(size_t)b * d + b]; });
-    lam.resize(d);
-    std::vector<double> Vs((size_t)d * d);
-    for (int c = 0; c < d; ++c) {
-        const int src = order[c];
-        lam[c] = A[(size_t)src * d + src];
-        int big = 0;
-        for (int k = 1; k < d; ++k)
-            if (std::fabs(V[(size_t)k * d + src]) > std::fabs(V[(size_t)big * d + src])) big = k;
-        const double sgn = V[(size_t)big * d + src] < 0.0 ? -1.0 : 1.0;
-        for (int k = 0; k < d; ++k) Vs[(size_t)k * d + c] = sgn * V[(size_t)k * d + src];
-    }
-    V.swap(Vs);
-}
+// (the host eigen-solver, jacobi_eig, lives in eig_jacobi.hpp with the rules it shares with the device solver)
 
 // covariance (two-pass, unweighted, n-1) of the device matrix S[n, d] -> device cov[d*d]; enqueue only
 int launch_covariance(const double* dS, int64_t n, int d, double* scratch_partial, double* d_mean3, double* d_cov, hipStream_t st)
@@ -135,6 +77,9 @@ static_assert(kFeedMaxDim <= mce::kWideMaxDim && mce::whiten_wide_lds_bytes(kFee
 //   B  d x d Jacobi eigen-solve, whitening scales, Jacobian
 //   C  upload eVec/scale, whiten in place, fused search + reduction, copy dotp back (async, pinned)
 //   D  hand the results to the caller
+// With the device eigen-solver (mce_options.eig_mode 2, capi_eig.hpp) A ends with the solver's launch on the job's stream, B is
+// skipped, C whitens from the solver's device-side output and copies the eigenvalues and the solve's status back behind the
+// sums, and D reads the status first: a problem waits once, a batch once per wave (docs/design/device_eig.md).
 // A batch is pipelined two deep in groups of kFeedGroup problems: while the device runs stage C of
 // group g, the host performs the (blocking, pageable) uploads of group g+1 and that group's
 // covariance kernels run beside the searches on a second stream set.  The searches themselves fill
@@ -168,6 +113,9 @@ struct FeedJob {
     unsigned long long checksum = 0;
     int64_t q_lo = 0, q_hi = 0;       // cross evidence of a part: its rows of s1
     std::vector<double> lam;  // eigenvalues of the system that defines J (s1's in 'single' mode)
+    bool dev_eig = false;     // the eigen-systems on the device (mce_options.eig_mode 2): stage B is skipped
+    size_t o_eig = 0;         // its block: cov[nsys] | evec[nsys] | scale[nsys] | lam[nsys] | status[nsys] (nsys slots: both systems in one launch)
+    EigStats eig;             // what this job solved where
     std::string err;
     hipEvent_t upload_ev = nullptr;   // orders the job's stream behind its blocking uploads
     ~FeedJob() { if (upload_ev) (void)hipEventDestroy(upload_ev); }
@@ -197,6 +145,15 @@ struct FeedJob {
     double* d_vdist() const { return reinterpret_cast<double*>(dbase + o_vd); }
     int32_t* d_vres() const { return reinterpret_cast<int32_t*>(dbase + o_vr); }
     bool two_systems() const { return q->cov_mode == 1 && q->S2 != nullptr; }
+    int nsys() const { return two_systems() ? 2 : 1; }
+    double* e_cov(int i) const { return reinterpret_cast<double*>(dbase + o_eig) + (size_t)i * q->d * q->d; }
+    double* e_evec(int i) const { return e_cov(nsys()) + (size_t)i * q->d * q->d; }
+    double* e_scale(int i) const { return e_evec(nsys()) + (size_t)i * q->d; }
+    double* e_lam(int i) const { return e_scale(nsys()) + (size_t)i * q->d; }
+    int32_t* e_status(int i) const { return reinterpret_cast<int32_t*>(e_lam(nsys())) + i * mce_eig::kStatInts; }
+    size_t e_back_bytes() const { return (size_t)nsys() * (q->d * sizeof(double) + mce_eig::kStatInts * sizeof(int32_t)); }      // lam | status: one copy
+    double* h_lam(int i) const { return reinterpret_cast<double*>(h_verify() + 2) + (size_t)i * q->d; }
+    int32_t* h_status(int i) const { return reinterpret_cast<int32_t*>(h_lam(nsys())) + i * mce_eig::kStatInts; }
     void set_error(int code) { rc = code; err = g_err; }
 };
 
@@ -246,8 +203,13 @@ int feed_plan(FeedJob& j)
         j.o_vw = off; off = align_up(off + mce_verify_workspace_bytes(j.nverify, j.K), 256);
         j.o_vr = off; off = align_up(off + 2 * sizeof(int), 256);
     }
+    j.dev_eig = eff_eig_mode() == 2;
+    if (j.dev_eig) {
+        j.o_eig = off;
+        off = align_up(off + (size_t)j.nsys() * (2 * d * d + 2 * d) * sizeof(double) + (size_t)j.nsys() * mce_eig::kStatInts * sizeof(int32_t), 256);
+    }
     j.dev_bytes = off;
-    j.host_bytes = align_up((size_t)(4 * d * d + 2 * d + q.kmax + 2) * sizeof(double), 64);
+    j.host_bytes = align_up((size_t)(4 * d * d + 2 * d + q.kmax + 2) * sizeof(double) + (j.dev_eig ? j.e_back_bytes() : 0), 64);
     return MCE_OK;
 }
 
@@ -297,6 +259,13 @@ int feed_stage_a(FeedJob& j, hipStream_t st)
         }
         MCE_HIP(hipMemcpyAsync(j.h_sum(), j.d_sum(), sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     }
+    if (j.dev_eig) {
+        // the covariances into the solver's slots, both systems of a 'single' cross evidence in ONE launch; nothing comes down
+        int rc = launch_covariance(j.dS1(), q.cov_mode == 0 ? j.ntot : q.n1, d, j.d_part(), j.d_mean3(), j.e_cov(0), st);
+        if (rc == MCE_OK && j.two_systems()) rc = launch_covariance(j.dS2(), q.n2, d, j.d_part(), j.d_mean3(), j.e_cov(1), st);
+        if (rc != MCE_OK) return rc;
+        return launch_eig(j.e_cov(0), d, j.nsys(), j.e_evec(0), j.e_scale(0), j.e_lam(0), j.e_status(0), st);
+    }
     // "all": one eigen-system from s1 U s2; "single": s1's own, and s2's own for s2 (J stays s1's)
     int rc = launch_covariance(j.dS1(), q.cov_mode == 0 ? j.ntot : q.n1, d, j.d_part(), j.d_mean3(), j.d_cov(), st);
     if (rc != MCE_OK) return rc;
@@ -340,6 +309,7 @@ int feed_stage_b(FeedJob& j)
         std::vector<double> lam;
         const int rc = feed_eig_system(j.h_cov(sidx), d, j.h_evec(sidx), j.h_scale(sidx), lam);
         if (rc != MCE_OK) return rc;
+        j.eig.host += 1;
         if (sidx == 0) {
             j.jac = feed_jacobian(lam);
             j.lam = lam;
@@ -349,14 +319,15 @@ int feed_stage_b(FeedJob& j)
 }
 
 // out[r] = (S[r] . evec) * scale for the n rows of S (out may be S); evec / scale on the device already; enqueue only
-int launch_whiten(const double* S, int64_t n, int d, const double* d_evec, const double* d_scale, double* out, hipStream_t st)
+// d_status (may be null): the device eigen-solve's status word; not 0 -> placeholder rows (feeders.hpp)
+int launch_whiten(const double* S, int64_t n, int d, const double* d_evec, const double* d_scale, double* out, hipStream_t st, const int32_t* d_status = nullptr)
 {
     if (d > 63)
         hipLaunchKernelGGL(mce::whiten_wide_kernel, dim3((unsigned)((n + mce::kWhitenRows - 1) / mce::kWhitenRows)), dim3(mce::kWhitenRows),
-                           mce::whiten_wide_lds_bytes(d), st, S, n, d, d_evec, d_scale, out);
+                           mce::whiten_wide_lds_bytes(d), st, S, n, d, d_evec, d_scale, out, d_status);
     else
         hipLaunchKernelGGL(mce::whiten_kernel, dim3((unsigned)((n + mce::kWhitenRows - 1) / mce::kWhitenRows)), dim3(mce::kWhitenRows),
-                           mce::whiten_lds_bytes(d), st, S, n, d, d_evec, d_scale, out);
+                           mce::whiten_lds_bytes(d), st, S, n, d, d_evec, d_scale, out, d_status);
     MCE_HIP(hipGetLastError());
     return MCE_OK;
 }
@@ -364,6 +335,7 @@ int launch_whiten(const double* S, int64_t n, int d, const double* d_evec, const
 int feed_whiten(FeedJob& j, int sidx, double* rows, int64_t n, hipStream_t st)
 {
     const int d = j.d();
+    if (j.dev_eig) return launch_whiten(rows, n, d, j.e_evec(sidx), j.e_scale(sidx), rows, st, j.e_status(sidx));
     MCE_HIP(hipMemcpyAsync(j.d_evec(), j.h_evec(sidx), (size_t)d * d * sizeof(double), hipMemcpyHostToDevice, st));
     MCE_HIP(hipMemcpyAsync(j.d_scale(), j.h_scale(sidx), (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
     return launch_whiten(rows, n, d, j.d_evec(), j.d_scale(), rows, st);
@@ -415,6 +387,7 @@ int feed_stage_c(FeedJob& j, hipStream_t st)
                                   j.nverify > 0 ? j.d_vdist() : nullptr, j.ws(), j.wsb, st);
     if (rc != MCE_OK) return rc;
     MCE_HIP(hipMemcpyAsync(j.h_dotp(), j.dO(), (size_t)q.kmax * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (j.dev_eig) MCE_HIP(hipMemcpyAsync(j.h_lam(0), j.e_lam(0), j.e_back_bytes(), hipMemcpyDeviceToHost, st));
     if (j.nverify > 0) {
         // mce_options.verify: the whitened rows the search ran on are still here; re-check a sample of them (stream-ordered)
         rc = mce_verify_knn_f64_dev(j.dS1(), q.n1, q.S2 ? j.dS2() : j.dS1(), j.nr, q.d, j.K, j.k0 == 1 ? MCE_SELF_EXCLUDE : MCE_SELF_NONE, 0, j.d_vdist(),
@@ -429,6 +402,18 @@ int feed_stage_c(FeedJob& j, hipStream_t st)
 void feed_stage_d(FeedJob& j)
 {
     mce_feed_problem& q = *j.q;
+    if (j.dev_eig) {
+        // the solve's status first: the search of a failed system ran on placeholder rows, whatever its certificate says
+        for (int i = 0; i < j.nsys(); ++i) eig_stats_add(j.eig, j.h_status(i));
+        for (int i = 0; i < j.nsys(); ++i)
+            if (j.h_status(i)[mce_eig::kStatCode] != mce_eig::kStatusOk) {
+                j.set_error(eig_status_fail(j.h_status(i), j.h_lam(i)));
+                g_last_verify_rows.store(0);
+                return;
+            }
+        j.lam.assign(j.h_lam(0), j.h_lam(0) + q.d);
+        j.jac = feed_jacobian(j.lam);
+    }
     std::copy(j.h_dotp(), j.h_dotp() + q.kmax, q.dotp);
     q.jacobian = j.jac;
     if (q.eigenvalues) std::copy(j.lam.begin(), j.lam.end(), q.eigenvalues);
@@ -506,7 +491,7 @@ int feed_run_on_device(int device, std::vector<FeedJob*>& jobs)
             FeedJob& j = *jobs[lo];
             if (j.rc == MCE_OK) {
                 int r = feed_stage_a(j, nullptr);
-                if (r == MCE_OK) { MCE_HIP(hipStreamSynchronize(nullptr)); r = feed_stage_b(j); }
+                if (r == MCE_OK && !j.dev_eig) { MCE_HIP(hipStreamSynchronize(nullptr)); r = feed_stage_b(j); }
                 if (r == MCE_OK) r = feed_stage_c(j, nullptr);
                 if (r == MCE_OK) { MCE_HIP(hipStreamSynchronize(nullptr)); feed_stage_d(j); }
                 else { j.set_error(r); (void)hipStreamSynchronize(nullptr); }
@@ -535,8 +520,9 @@ int feed_run_on_device(int device, std::vector<FeedJob*>& jobs)
             for (size_t i = g0; i < g1; ++i) {
                 FeedJob& j = *jobs[i];
                 if (j.rc != MCE_OK) continue;
-                MCE_HIP(hipEventSynchronize(events[i - g0]));
-                int r = feed_stage_b(j);
+                int r = MCE_OK;
+                if (j.dev_eig) MCE_HIP(hipStreamWaitEvent(sc[i % sc.size()], events[i - g0], 0));      // the device waits for stage A, the host does not
+                else { MCE_HIP(hipEventSynchronize(events[i - g0])); r = feed_stage_b(j); }
                 if (r == MCE_OK) r = feed_stage_c(j, sc[i % sc.size()]);
                 if (r != MCE_OK) j.set_error(r);
             }
@@ -564,6 +550,7 @@ size_t mce_feed_problem_size(void) { return sizeof(mce_feed_problem); }
 static int feed_batch_impl(bool src_device, mce_feed_problem* problems, int64_t nprob, const int32_t* devices, int32_t ndev)
 {
     if (nprob < 0 || (nprob > 0 && !problems)) return fail(MCE_ERR_INVALID, "invalid problem list");
+    g_eig_stats = EigStats();
     if (nprob == 0) return MCE_OK;
     std::vector<FeedJob> jobs((size_t)nprob);
     for (int64_t i = 0; i < nprob; ++i) {
@@ -612,6 +599,7 @@ static int feed_batch_impl(bool src_device, mce_feed_problem* problems, int64_t 
         for (int i = 0; i < n; ++i) th.emplace_back([&, i]() { t_opt = inherited; work(i); });
         for (auto& t : th) t.join();
     }
+    for (const FeedJob& j : jobs) eig_stats_merge(g_eig_stats, j.eig);
     for (int i = 0; i < n; ++i)
         if (rcs[i] != MCE_OK) return fail(rcs[i], "device %d: %s", devs[i], errs[i].c_str());
     int first = MCE_OK;
@@ -673,10 +661,12 @@ static int feed_part_impl(bool src_device, const double* S1, int64_t n1, int64_t
     job.nparts = nparts;
     job.src_device = src_device;
     job.want_sum = checksum != nullptr;
+    g_eig_stats = EigStats();
     int rc = feed_plan(job);
     if (rc != MCE_OK) return rc;
     std::vector<FeedJob*> jobs{&job};
     rc = feed_run_on_device(device, jobs);
+    g_eig_stats = job.eig;
     if (rc != MCE_OK) return rc;
     if (job.rc != MCE_OK) return fail(job.rc, "%s", job.err.c_str());
     *jacobian = q.jacobian;
@@ -717,10 +707,12 @@ static int feed_whiten_impl(bool src_device, const double* S1, int64_t n1, int64
     job.out_X = d_X_out; job.out_w = d_w_out; job.out_f = d_fs_out;
     job.src_device = src_device;
     job.want_sum = checksum != nullptr;
+    g_eig_stats = EigStats();
     int rc = feed_plan(job);
     if (rc != MCE_OK) return rc;
     std::vector<FeedJob*> jobs{&job};
     rc = feed_run_on_device(device, jobs);
+    g_eig_stats = job.eig;
     if (rc != MCE_OK) return rc;
     if (job.rc != MCE_OK) return fail(job.rc, "%s", job.err.c_str());
     *jacobian = q.jacobian;

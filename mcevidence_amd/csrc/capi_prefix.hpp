@@ -8,6 +8,8 @@
 //   cov_mode 0, cross   one whitening of s1 U s2, ONE search of S1[:p_max] against all of S2 that leaves its distances, and the
 //                       B reductions from them (every batch searches all of s2: reference :1075)
 // on one stream.  The host waits twice whatever B is: for the covariances (the eigen-solves are the host's), and at the end.
+// With the device eigen-solver (mce_options.eig_mode 2, capi_eig.hpp) all the systems are solved in ONE launch behind the
+// covariances, every whitening reads its own slot of the solver's output, and the host waits once, at the end.
 #pragma once
 namespace {
 
@@ -27,7 +29,14 @@ struct PrefixJob {
            o_vr = 0, o_dp = 0;
     char* dbase = nullptr;
     char* hbase = nullptr;
+    bool dev_eig = false;               // the eigen-systems on the device: stage B is skipped
+    size_t o_eig = 0;                   // its output, nsys slots each: evec | scale | lam | status
 
+    double* e_evec(int i) const { return reinterpret_cast<double*>(dbase + o_eig) + (size_t)i * d * d; }
+    double* e_scale(int i) const { return e_evec(nsys) + (size_t)i * d; }
+    double* e_lam(int i) const { return e_scale(nsys) + (size_t)i * d; }
+    int32_t* e_status(int i) const { return reinterpret_cast<int32_t*>(e_lam(nsys)) + i * mce_eig::kStatInts; }
+    size_t e_back_bytes() const { return (size_t)nsys * (d * sizeof(double) + mce_eig::kStatInts * sizeof(int32_t)); }          // lam | status: one copy
     bool cross() const { return S2 != nullptr; }
     int64_t size_of(int i) const { return prefix[first[i]]; }
     double* dS1() const { return reinterpret_cast<double*>(dbase + o_S); }
@@ -56,6 +65,8 @@ struct PrefixJob {
     double* h_dotp() const { return h_scale(nsys); }
     double* h_lmax() const { return h_dotp() + (size_t)B * kmax; }
     int* h_verify(int i) const { return reinterpret_cast<int*>(h_lmax() + B) + 2 * i; }
+    double* h_elam(int i) const { return h_lmax() + B + nsearch + 1 + (size_t)i * d; }          // device eigen-solver: lam [nsys][d] | status [nsys]
+    int32_t* h_estatus(int i) const { return reinterpret_cast<int32_t*>(h_elam(nsys)) + i * mce_eig::kStatInts; }
 };
 
 // argument checks + sizes; no device work
@@ -126,8 +137,13 @@ int prefix_plan(PrefixJob& j, const double* dotp, const double* loglmax, const d
     j.o_vw = off;    off = align_up(off + j.vws, 256);
     j.o_vr = off;    off = align_up(off + (size_t)j.nsearch * 2 * sizeof(int), 256);
     j.o_dp = off;    off = align_up(off + (j.cross() ? (size_t)j.B * j.nblk_dotp * j.kmax * sizeof(double) : 0), 256);
+    j.dev_eig = eff_eig_mode() == 2;
+    if (j.dev_eig) {
+        j.o_eig = off;
+        off = align_up(off + (size_t)j.nsys * (d * d + 2 * d) * sizeof(double) + (size_t)j.nsys * mce_eig::kStatInts * sizeof(int32_t), 256);
+    }
     j.dev_bytes = off;
-    j.host_bytes = align_up(((size_t)j.nsys * (d * d + d) + (size_t)j.B * j.kmax + j.B + j.nsearch + 1) * sizeof(double), 64);
+    j.host_bytes = align_up(((size_t)j.nsys * (d * d + d) + (size_t)j.B * j.kmax + j.B + j.nsearch + 1) * sizeof(double) + (j.dev_eig ? j.e_back_bytes() : 0), 64);
     return MCE_OK;
 }
 
@@ -152,6 +168,7 @@ int prefix_stage_a(PrefixJob& j, hipStream_t st)
         const int rc = launch_covariance(j.dS1(), j.cov_mode == 0 ? j.ntot : j.size_of(i), d, j.d_part(), j.d_mean3(), j.d_cov(i), st);
         if (rc != MCE_OK) return rc;
     }
+    if (j.dev_eig) return launch_eig(j.d_cov(0), d, j.nsys, j.e_evec(0), j.e_scale(0), j.e_lam(0), j.e_status(0), st);      // all systems, one launch
     MCE_HIP(hipMemcpyAsync(j.h_sys(0), j.d_cov(0), (size_t)j.nsys * d * d * sizeof(double), hipMemcpyDeviceToHost, st));
     return MCE_OK;
 }
@@ -168,9 +185,37 @@ int prefix_stage_b(PrefixJob& j, std::vector<double>& jac)
             const std::string msg = g_err;
             return fail(rc, "prefix %d (%lld rows): %s", j.first[i], (long long)j.size_of(i), msg.c_str());
         }
+        g_eig_stats.host += 1;
         jac[i] = feed_jacobian(lam);
     }
     return MCE_OK;
+}
+
+int prefix_upload_system(PrefixJob& j, int i, hipStream_t st);
+
+// the same from the device solver's results, once the call has finished: the first system that failed names the error
+int prefix_eig_results(PrefixJob& j, std::vector<double>& jac)
+{
+    jac.assign(j.nsys, 0.0);
+    for (int i = 0; i < j.nsys; ++i) eig_stats_add(g_eig_stats, j.h_estatus(i));
+    for (int i = 0; i < j.nsys; ++i) {
+        if (j.h_estatus(i)[mce_eig::kStatCode] != mce_eig::kStatusOk) {
+            const int rc = eig_status_fail(j.h_estatus(i), j.h_elam(i));
+            if (j.cov_mode == 0) return rc;
+            const std::string msg = g_err;
+            return fail(rc, "prefix %d (%lld rows): %s", j.first[i], (long long)j.size_of(i), msg.c_str());
+        }
+        jac[i] = feed_jacobian(std::vector<double>(j.h_elam(i), j.h_elam(i) + j.d));
+    }
+    return MCE_OK;
+}
+
+// the whitening of system i's rows: from the host's solve (uploaded here) or from the device solver's slot, with its status
+int prefix_whiten(PrefixJob& j, int i, int64_t n, double* out, hipStream_t st)
+{
+    if (j.dev_eig) return launch_whiten(j.dS1(), n, j.d, j.e_evec(i), j.e_scale(i), out, st, j.e_status(i));
+    const int rc = prefix_upload_system(j, i, st);
+    return rc == MCE_OK ? launch_whiten(j.dS1(), n, j.d, j.d_evec(), j.d_scale(), out, st) : rc;
 }
 
 int prefix_upload_system(PrefixJob& j, int i, hipStream_t st)
@@ -207,8 +252,7 @@ int prefix_stage_c(PrefixJob& j, hipStream_t st)
     if (rc != MCE_OK) return rc;
     const int d = j.d;
     if (j.cov_mode == 0) {
-        rc = prefix_upload_system(j, 0, st);
-        if (rc == MCE_OK) rc = launch_whiten(j.dS1(), j.ntot, d, j.d_evec(), j.d_scale(), j.dS1(), st);
+        rc = prefix_whiten(j, 0, j.ntot, j.dS1(), st);
         if (rc != MCE_OK) return rc;
     }
     SameSetHint hint(!j.cross());          // as in prefix_plan: the workspace was sized with it
@@ -232,8 +276,7 @@ int prefix_stage_c(PrefixJob& j, hipStream_t st)
             const int64_t p = j.size_of(i);
             const double* X = j.dS1();
             if (j.cov_mode == 1) {          // the prefix's own system: out of place, the raw rows serve the next prefix
-                rc = prefix_upload_system(j, i, st);
-                if (rc == MCE_OK) rc = launch_whiten(j.dS1(), p, d, j.d_evec(), j.d_scale(), j.dX(), st);
+                rc = prefix_whiten(j, i, p, j.dX(), st);
                 if (rc != MCE_OK) return rc;
                 X = j.dX();
             }
@@ -249,6 +292,7 @@ int prefix_stage_c(PrefixJob& j, hipStream_t st)
         }
     }
     MCE_HIP(hipMemcpyAsync(j.h_dotp(), j.dO(), (size_t)j.B * j.kmax * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (j.dev_eig) MCE_HIP(hipMemcpyAsync(j.h_elam(0), j.e_lam(0), j.e_back_bytes(), hipMemcpyDeviceToHost, st));
     return MCE_OK;
 }
 
@@ -281,6 +325,7 @@ int feed_prefix_impl(bool src_device, const double* S1, int64_t n1, int64_t ld1,
                      int32_t kmax, const double* w, const double* logl, const int64_t* prefix, int32_t nprefix, double* dotp, double* loglmax,
                      double* jacobian, int32_t device)
 {
+    g_eig_stats = EigStats();
     PrefixJob j;
     j.S1 = S1; j.n1 = n1; j.ld1 = ld1;
     j.S2 = S2; j.n2 = S2 ? n2 : 0; j.ld2 = S2 ? ld2 : 0;
@@ -305,13 +350,19 @@ int feed_prefix_impl(bool src_device, const double* S1, int64_t n1, int64_t ld1,
     std::vector<double> jac;
     rc = prefix_stage_a(j, st);
     if (rc != MCE_OK) return rc;
-    MCE_HIP(hipStreamSynchronize(st));
-    rc = prefix_stage_b(j, jac);
-    if (rc != MCE_OK) return rc;
+    if (!j.dev_eig) {
+        MCE_HIP(hipStreamSynchronize(st));
+        rc = prefix_stage_b(j, jac);
+        if (rc != MCE_OK) return rc;
+    }
     rc = prefix_stage_c(j, st);
     if (rc != MCE_OK) return rc;
     MCE_HIP(hipStreamSynchronize(st));
     quiesce.armed = false;
+    if (j.dev_eig) {          // the solves' status first: a failed system's searches ran on placeholder rows
+        rc = prefix_eig_results(j, jac);
+        if (rc != MCE_OK) return rc;
+    }
     return prefix_stage_d(j, jac, dotp, loglmax, jacobian);
 }
 

@@ -80,14 +80,34 @@ __global__ __launch_bounds__(kCovThreads) void cov_final_kernel(const double* __
 
 // out[r][c] = (sum_k S[r][k] * evec[k][c]) * scale[c],  scale = 1/sqrt(eval).  64 rows per workgroup,
 // staged through LDS both ways so global reads and writes are contiguous runs.  `out` may alias `S`.
+// `status` (may be null: none): the status word of the device eigen-solve that produced evec / scale (eig_kernels.hpp).  When it is
+// not 0 the solve failed and the host will refuse the problem once it reads the status at the end of the call; until then the
+// search behind this kernel must not see rows that a bad covariance made non-finite, so the input is ignored and finite, pairwise
+// distinct placeholder rows are written: the row index in base 16, a digit per coordinate (the last of min(d, 16) coordinates takes
+// what is left; zeros beyond) -- values of the size whitened rows have, so that the search sees nothing unusual.
 constexpr int kWhitenRows = 64;
+__device__ __forceinline__ bool whiten_placeholder(const int32_t* status, int64_t n, int d, double* out)
+{
+    if (!status || *status == 0) return false;          // (uniform over the workgroup)
+    const int64_t row0 = (int64_t)blockIdx.x * kWhitenRows;
+    const int64_t e0 = row0 * d, e1 = ((row0 + kWhitenRows < n) ? row0 + kWhitenRows : n) * (int64_t)d;
+    const int nd = d < 16 ? d : 16;
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += kWhitenRows) {
+        const int64_t r = e / d;
+        const int c = (int)(e - r * d);
+        out[e] = c < nd - 1 ? (double)((r >> (4 * c)) & 15) : c == nd - 1 ? (double)(r >> (4 * c)) : 0.0;
+    }
+    return true;
+}
 __host__ __device__ constexpr size_t whiten_lds_bytes(int d) { return ((size_t)d * d + (size_t)2 * kWhitenRows * (d | 1)) * sizeof(double); }
 
 __global__ __launch_bounds__(kWhitenRows) void whiten_kernel(const double* S, int64_t n, int d,
                                                              const double* __restrict__ evec /*[d][d] row-major*/,
-                                                             const double* __restrict__ scale /*[d]*/, double* out)
+                                                             const double* __restrict__ scale /*[d]*/, double* out,
+                                                             const int32_t* __restrict__ status)
 {
     extern __shared__ double sh[];                   // evec d*d | rows in 64*(d|1) | rows out 64*(d|1)
+    if (whiten_placeholder(status, n, d, out)) return;
     const int ld = d | 1;
     double* U = sh;
     double* rin = sh + d * d;
@@ -122,9 +142,11 @@ __global__ __launch_bounds__(kWhitenRows) void whiten_kernel(const double* S, in
 // their terms in the same order: the results are what the narrow kernel's would be.
 __host__ __device__ constexpr size_t whiten_wide_lds_bytes(int d) { return ((size_t)2 * kWhitenRows * (d | 1)) * sizeof(double); }
 __global__ __launch_bounds__(kWhitenRows) void whiten_wide_kernel(const double* S, int64_t n, int d, const double* __restrict__ evec,
-                                                                  const double* __restrict__ scale, double* out)
+                                                                  const double* __restrict__ scale, double* out,
+                                                                  const int32_t* __restrict__ status)
 {
     extern __shared__ double sh[];                   // rows in 64*(d|1) | rows out 64*(d|1)
+    if (whiten_placeholder(status, n, d, out)) return;
     const int ld = d | 1;
     double* rin = sh;
     double* rout = rin + kWhitenRows * ld;

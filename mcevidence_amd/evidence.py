@@ -42,8 +42,12 @@ class HipBackend(object):
 
     name = "hip"
 
-    def __init__(self, devices=None, verify=True, recheck_rows=None, batch_feed=None):
+    def __init__(self, devices=None, verify=True, recheck_rows=None, batch_feed=None, device_eig=None):
         self.devices = devices
+        # the covariance eigen-systems of the feed routes on the device (mce_options.eig_mode; docs/design/device_eig.md) instead
+        # of on one host core between two waits.  None: the library's default -- MCE_FEED_EIG=hip in the environment turns it on;
+        # True / False: this backend's calls say so themselves, whatever the environment holds
+        self.device_eig = None if device_eig is None else bool(device_eig)
         # convergence batches (brange / nbatch) in ONE library call (mce_evidence_feed_prefix_f64) instead of one host round
         # trip per batch.  None: MCE_BATCH_FEED=1 in the environment turns it on; the default is off (docs/design/batch_feed.md)
         self.batch_feed = (os.environ.get("MCE_BATCH_FEED") == "1") if batch_feed is None else bool(batch_feed)
@@ -59,7 +63,16 @@ class HipBackend(object):
         """the per-call options of this backend's library calls (thread-scoped: mce_options_push / _pop)"""
         import contextlib
         from . import _capi
-        return _capi.options(verify=self.recheck_rows) if self.recheck_rows is not None else contextlib.nullcontext()
+        modes = {}
+        if self.recheck_rows is not None:
+            modes["verify"] = self.recheck_rows
+        if self.device_eig is not None:
+            modes["eig_mode"] = _capi.EIG_DEVICE if self.device_eig else _capi.EIG_HOST
+        return _capi.options(**modes) if modes else contextlib.nullcontext()
+
+    def uses_device_eig(self):
+        """whether this backend's feed calls solve their eigen-systems on the device (its own setting, else MCE_FEED_EIG)"""
+        return (os.environ.get("MCE_FEED_EIG") == "hip") if self.device_eig is None else self.device_eig
 
     def evidence_feed(self, S1, S2, ndim, cov_mode, kmax, weight, fs):
         """feeders on the device too (get_covariance + diagonalise_chain + the hot path, one upload);
@@ -105,17 +118,18 @@ class HipBackend(object):
                 hostsum = parallel._HostFingerprint(S1, S2, ndim, weight, fs) if (self.verify and want_node) else None
                 gathered = parallel.gather_chain_on_device(S1, S2, ndim, weight, fs, group, local_ok=want_node)      # (collective whatever this rank wants)
             try:
-                if gathered is not None:
-                    Sg, wg, fg = gathered
-                    n1 = int(np.asarray(S1).shape[0])
-                    n2 = 0 if S2 is None else int(np.asarray(S2).shape[0])
-                    part, jac, _, _ = _capi.evidence_feed_part_dev(Sg.data_ptr(), n1, ndim, Sg[n1:].data_ptr() if n2 else 0, n2, ndim, ndim, cov_mode, kmax,
-                                                                   wg.data_ptr(), fg.data_ptr(), dist.get_rank(group), dist.get_world_size(group),
-                                                                   device=dev, want_checksum=False)
-                    csum = hostsum.value() if hostsum is not None else None
-                else:
-                    part, jac, _, csum = _capi.evidence_feed_part(S1, S2, ndim, cov_mode, kmax, weight, fs, dist.get_rank(group),
-                                                                  dist.get_world_size(group), device=dev, want_checksum=self.verify)
+                with self._scoped():
+                    if gathered is not None:
+                        Sg, wg, fg = gathered
+                        n1 = int(np.asarray(S1).shape[0])
+                        n2 = 0 if S2 is None else int(np.asarray(S2).shape[0])
+                        part, jac, _, _ = _capi.evidence_feed_part_dev(Sg.data_ptr(), n1, ndim, Sg[n1:].data_ptr() if n2 else 0, n2, ndim, ndim, cov_mode, kmax,
+                                                                       wg.data_ptr(), fg.data_ptr(), dist.get_rank(group), dist.get_world_size(group),
+                                                                       device=dev, want_checksum=False)
+                        csum = hostsum.value() if hostsum is not None else None
+                    else:
+                        part, jac, _, csum = _capi.evidence_feed_part(S1, S2, ndim, cov_mode, kmax, weight, fs, dist.get_rank(group),
+                                                                      dist.get_world_size(group), device=dev, want_checksum=self.verify)
             except Exception as exc:        # still join the collective (with a failure flag): the other ranks must not hang in it
                 failed = exc
             return parallel.feed_part_reduce(part, csum, group, failed=failed), jac

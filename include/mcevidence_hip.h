@@ -448,6 +448,29 @@ int mce_chain_gather_dev(const mce_chain_part* parts, int32_t nparts, int64_t nc
 int mce_chain_reduce_dev(const double* d_like, const double* d_w, int64_t n, int32_t pos_lnp, double* d_fs, double* out, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* The autocorrelation length of burned chains that are on the device, and with it the thinning factor of thin_corr (the reference's
+ * command line promises "thinlen < 0: the autocorrelation length of the chain" and raises; here the length is measured under its own
+ * keyword).  The rule is stated in csrc/chain_corr.hpp and docs/design/chain_corr.md: the series of a part is its rows repeated
+ * trunc(w) times (integer weights: *rule = 1, weight units) or the rows themselves (*rule = 2, row units), the rule being
+ * mce_chain_weights_dev's verdict for thinlen = 2; *rule < 0 is that call's decline and nothing else is set.  The first `ndim`
+ * columns from `itheta` are measured (1 <= ndim <= 127): per column the pooled lagged sums S_j(t) over the parts -- a pair never
+ * spans two parts --, rho_j(t), cut[j] = the first t in 1 .. cap with rho_j(t) <= min_corr (0 <= min_corr < 1) and
+ * length[j] = 1 + 2 sum_{t < cut[j]} rho_j(t); *cap = min(max_lag, largest part's units / 4), max_lag in 1 .. 65536; *units = the
+ * units of all parts.  status[0]: 0 ok, 1 some column has no cut within the cap, 2 a column with S_j(0) not > 0 (constant), 3 a value
+ * that is not finite in a measured column; status[1] = that column.  length / cut of a column without a cut: the sum so far and 0.
+ * rho (host, may be NULL): rho[t * ndim + j] for t < *rho_rows, the lags that were summed (the windows stop after the one in which the
+ * last column found its cut); later rows of the table are left untouched.  fp64, sums in a fixed order: two runs give the same bits.
+ * Parts, workspace and stream are the caller's (mce_chain_corr_workspace_bytes(rows of all parts, nparts, ndim, max_lag)); the stream
+ * is synchronised on return.  mce_chain_corr_f64 takes HOST parts, uploads them to `device` and calls the device form.
+ * Argument errors: MCE_ERR_INVALID (no device needed); no visible device: MCE_ERR_NO_DEVICE. */
+size_t mce_chain_corr_workspace_bytes(int64_t n, int32_t nparts, int32_t ndim, int64_t max_lag);
+int mce_chain_corr_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncols, int32_t iw, int32_t itheta, int32_t ndim, double min_corr,
+                       int64_t max_lag, int32_t* rule, int32_t* status, int64_t* units, int64_t* cap, double* length, int64_t* cut,
+                       double* rho, int64_t* rho_rows, void* ws, size_t ws_bytes, void* stream);
+int mce_chain_corr_f64(const mce_chain_part* parts, int32_t nparts, int64_t ncols, int32_t iw, int32_t itheta, int32_t ndim, double min_corr,
+                       int64_t max_lag, int32_t* rule, int32_t* status, int64_t* units, int64_t* cap, double* length, int64_t* cut,
+                       double* rho, int64_t* rho_rows, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

@@ -107,6 +107,11 @@ SIGNATURES = {
     "mce_chain_gather_dev": (_c.c_int, [_P, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P,
                                         _P, _c.c_size_t, _P]),
     "mce_chain_reduce_dev": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P, _P, _P, _c.c_size_t, _P]),
+    "mce_chain_corr_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int64]),
+    "mce_chain_corr_dev": (_c.c_int, [_P, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_double, _c.c_int64, _c.POINTER(_c.c_int32), _P,
+                                      _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _P, _P, _P, _c.POINTER(_c.c_int64), _P, _c.c_size_t, _P]),
+    "mce_chain_corr_f64": (_c.c_int, [_P, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_double, _c.c_int64, _c.POINTER(_c.c_int32), _P,
+                                      _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _P, _P, _P, _c.POINTER(_c.c_int64), _c.c_int32]),
     "mce_knn_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32]),
     "mce_dotp_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int32]),
     "mce_knn_f64_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
@@ -519,6 +524,39 @@ def chain_reduce_dev(d_like, d_w, n, pos_lnp, d_fs, ws, ws_bytes, stream=0):
     check(load().mce_chain_reduce_dev(d_like or None, d_w or None, int(n), 1 if pos_lnp else 0, d_fs or None, _c.cast(out, _P), ws or None, int(ws_bytes),
                                       stream or None))
     return float(out[0]), float(out[1]), int(out[2]), int(out[3])
+
+
+def chain_corr_workspace_bytes(n, nparts, ndim, max_lag):
+    return int(load().mce_chain_corr_workspace_bytes(int(n), int(nparts), int(ndim), int(max_lag)))
+
+
+def _chain_corr(call, parts, ncols, iw, itheta, ndim, min_corr, max_lag, want_rho, tail):
+    rule, units, cap, rows = _c.c_int32(0), _c.c_int64(0), _c.c_int64(0), _c.c_int64(0)
+    status = (_c.c_int32 * 2)()
+    nd = max(int(ndim), 1)
+    length = np.zeros(nd)
+    cut = np.zeros(nd, dtype=np.int64)
+    rho = np.full((max(int(max_lag), 0) + 1, nd), np.nan) if want_rho else None
+    arr = chain_parts(parts)
+    check(call(_c.cast(arr, _P), len(parts), int(ncols), int(iw), int(itheta), int(ndim), float(min_corr), int(max_lag), _c.byref(rule), _c.cast(status, _P),
+               _c.byref(units), _c.byref(cap), length.ctypes.data, cut.ctypes.data, rho.ctypes.data if want_rho else None, _c.byref(rows), *tail))
+    return dict(rule=int(rule.value), status=int(status[0]), column=int(status[1]), units=int(units.value), cap=int(cap.value), per_param=length, cut=cut,
+                rho=rho[:int(rows.value)] if want_rho else None, rho_rows=int(rows.value))
+
+
+def chain_corr_dev(parts, ncols, iw, itheta, ndim, min_corr, max_lag, ws, ws_bytes, stream=0, want_rho=False):
+    """mce_chain_corr_dev -> dict(rule, status, column, units, cap, per_param [ndim], cut [ndim], rho [lags summed, ndim] or None, rho_rows);
+    ``parts``: [(device address, rows)]"""
+    return _chain_corr(load().mce_chain_corr_dev, parts, ncols, iw, itheta, ndim, min_corr, max_lag, want_rho, (ws or None, int(ws_bytes), stream or None))
+
+
+def chain_corr(arrays, iw, itheta, ndim, min_corr=0.05, max_lag=1024, device=0, want_rho=True):
+    """mce_chain_corr_f64: the same from HOST arrays (one 2-D fp64 array per burned chain), uploaded by the library"""
+    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+    if not arrays or any(a.ndim != 2 or a.shape[1] != arrays[0].shape[1] for a in arrays):
+        raise ValueError("chains must be 2-D arrays of one column count")
+    parts = [(a.ctypes.data if a.shape[0] else 0, a.shape[0]) for a in arrays]
+    return _chain_corr(load().mce_chain_corr_f64, parts, arrays[0].shape[1], iw, itheta, ndim, min_corr, max_lag, want_rho, (int(device),))
 
 
 # ---------------------------------------------------------------------------

@@ -174,13 +174,138 @@ def thin_rows(weights, nthin):
 
 
 # ---------------------------------------------------------------------------
+# thin_corr: thinning by the measured autocorrelation length (docs/design/chain_corr.md; csrc/chain_corr.hpp has the same rule)
+# ---------------------------------------------------------------------------
+CORR_MIN = 0.05
+CORR_MAX_LAG = 1024
+CORR_UNITS = {1: "weight", 2: "rows"}           # by rule: integer weights -> weight units, otherwise row units
+CORR_OK, CORR_NO_CUT, CORR_CONSTANT, CORR_NOT_FINITE = 0, 1, 2, 3
+CORR_BAD_WEIGHTS = "a weight is negative, not finite or beyond 2^53"
+
+
+def thin_corr_scale(thin_corr, thinlen=0):
+    """The scale ``thin_corr`` asks for -- None / False: off (returns None), True: 1.0, a number > 0: itself.  Together with a
+    ``thinlen`` other than 0 it is a ValueError: the two say how to thin in different ways."""
+    if thin_corr is None or thin_corr is False:
+        return None
+    scale = 1.0 if thin_corr is True else float(thin_corr)
+    if not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError("thin_corr must be True or a number > 0 (got %r)" % (thin_corr,))
+    if thinlen:
+        raise ValueError("thin_corr=%r and thinlen=%r are both set: thin by the measured length (thin_corr) or by a given one (thinlen)"
+                         % (thin_corr, thinlen))
+    return scale
+
+
+def corr_factor(scale, length):
+    """the thinning factor: max(1, ceil(scale * L))"""
+    return max(1, int(np.ceil(scale * length)))
+
+
+def corr_status_error(status, column, cap, min_corr):
+    """the ValueError of a measurement that did not end well, in the words every route uses"""
+    if status == CORR_NO_CUT:
+        return ValueError("thin_corr: the autocorrelation of parameter column %d stays above corr_min=%g up to cap=%d lags; raise corr_max_lag "
+                          "or burn more" % (column, min_corr, cap))
+    if status == CORR_CONSTANT:
+        return ValueError("thin_corr: parameter column %d is constant (its S(0) is not > 0); leave it out with ndim" % column)
+    return ValueError("thin_corr: a value that is not finite in parameter column %d" % column)
+
+
+def corr_info(res, scale):
+    """``info["thin_corr"]`` from a measurement (``correlation_length`` / ``_capi.chain_corr_dev``); raises for a non-zero status"""
+    if res["status"] != CORR_OK:
+        raise corr_status_error(res["status"], res["column"], res["cap"], res.get("min_corr", CORR_MIN))
+    length = float(np.max(res["per_param"]))
+    return {"length": length, "per_param": [float(x) for x in res["per_param"]], "cut": [int(x) for x in res["cut"]],
+            "factor": corr_factor(scale, length), "units": CORR_UNITS[res["rule"]], "cap": int(res["cap"])}
+
+
+def correlation_length(parts, iw=0, itheta=2, ndim=None, min_corr=CORR_MIN, max_lag=CORR_MAX_LAG):
+    """The pooled, per-parameter integrated autocorrelation length of burned chains ``parts`` (2-D arrays, not concatenated), in NumPy.
+
+    The series of a part is each row repeated ``trunc(w)`` times (integer weights, as ``integer_weight_thin`` decides: weight units;
+    rows of weight 0 vanish) or the rows themselves (row units).  Columns ``itheta .. itheta + ndim`` are measured (``ndim=None``: all):
+    ``S_j(t)`` sums the products of the centred series ``t`` apart over every part (a pair never spans two parts), ``n(t)`` counts them,
+    ``rho_j(t) = (S_j(t) / n(t)) / (S_j(0) / n(0))``; ``cut_j`` is the first ``t`` in ``1 .. cap = min(max_lag, longest series // 4)`` with
+    ``rho_j(t) <= min_corr`` and ``L_j = 1 + 2 sum(rho_j(1 .. cut_j - 1))``.  Lags are summed up to the last cut and no further.
+    Returns dict(rule 1 | 2, status, column, units, cap, per_param, cut, rho [lags summed, ndim], rho_rows, min_corr); status 0 ok,
+    1 a column without a cut, 2 a constant column, 3 a value that is not finite (``corr_status_error`` words them)."""
+    if not (0.0 <= min_corr < 1.0) or not (1 <= int(max_lag) <= 65536):          # (the bounds mce_chain_corr_dev sets)
+        raise ValueError("thin_corr: corr_min=%r (0 <= corr_min < 1 expected), corr_max_lag=%r (1 .. 65536 expected)" % (min_corr, max_lag))
+    parts = [np.asarray(p, dtype=np.float64) for p in parts]
+    parts = [p for p in parts if p.shape[0] > 0]
+    if not parts:
+        raise ValueError("the chains array is empty")
+    nparam = parts[0].shape[1] - itheta
+    nd = nparam if ndim is None else min(int(ndim), nparam)
+    if nd < 1:
+        raise ValueError("ndim must be >= 1 (got %r)" % (ndim,))
+    w = np.concatenate([p[:, iw] for p in parts])
+    if not np.all((w >= 0) & (w <= 2.0 ** 53)):
+        raise ValueError("thin_corr: " + CORR_BAD_WEIGHTS)
+    wi = w.astype(np.int64)
+    rule = 1 if abs(float(np.sum(wi)) - float(np.sum(w))) <= 1e-4 else 2          # (integer_weight_thin's own test)
+    series = []
+    for p in parts:
+        y = p[:, itheta:itheta + nd]
+        if rule == 1:
+            y = np.repeat(y, p[:, iw].astype(np.int64), axis=0)
+        if y.shape[0]:
+            lo, hi = y.min(axis=0), y.max(axis=0)
+            with np.errstate(invalid="ignore"):
+                m = np.where(lo == hi, lo, y.sum(axis=0) / y.shape[0])             # (a column constant over the part centres to exact zeros)
+                y = y - m
+        series.append(y)
+    units = [y.shape[0] for y in series]
+    cap = min(int(max_lag), max(units) // 4)
+    out = dict(rule=rule, status=CORR_OK, column=-1, units=int(sum(units)), cap=cap, per_param=np.zeros(nd), cut=np.zeros(nd, dtype=np.int64),
+               rho=np.ones((1, nd)), rho_rows=1, min_corr=float(min_corr))
+
+    def lagged(t):
+        s = np.zeros(nd)
+        for y in series:
+            if y.shape[0] > t:
+                with np.errstate(invalid="ignore", over="ignore"):
+                    s += np.einsum("ij,ij->j", y[:y.shape[0] - t], y[t:])
+        return s, float(sum(max(u - t, 0) for u in units))
+
+    s0, n0 = lagged(0)
+    bad = np.nonzero(~np.isfinite(s0))[0]
+    if len(bad):
+        out.update(status=CORR_NOT_FINITE, column=int(bad[0]))
+        return out
+    flat = np.nonzero(~(s0 > 0))[0]
+    if len(flat):
+        out.update(status=CORR_CONSTANT, column=int(flat[0]))
+        return out
+    cut, acc, rows = out["cut"], np.zeros(nd), [np.ones(nd)]
+    for t in range(1, cap + 1):
+        s, nt = lagged(t)
+        rho = (s / nt) / (s0 / n0)
+        rows.append(rho)
+        found = (cut == 0) & (rho <= min_corr)
+        acc += np.where((cut == 0) & ~found, rho, 0.0)
+        cut[found] = t
+        if np.all(cut > 0):
+            break
+    out.update(per_param=1.0 + 2.0 * acc, rho=np.asarray(rows), rho_rows=len(rows))
+    missing = np.nonzero(cut == 0)[0]
+    if len(missing):
+        out.update(status=CORR_NO_CUT, column=int(missing[0]))
+    return out
+
+
+# ---------------------------------------------------------------------------
 class MCSamples(object):
     """Container for one or more MCMC chains.
 
     str_or_dict : chain file root / file name / wildcard (str), or list/tuple/dict of
                   2-D arrays (one per chain).
     csplit      : object with .split/.frac/.shuffle, or None (no split).
-    kwargs      : iw, ilike, itheta, log_level, burnlen, thinlen, idchain, idpattern.
+    kwargs      : iw, ilike, itheta, log_level, burnlen, thinlen, idchain, idpattern; thin_corr (None / False: off, True: scale 1,
+                  a number > 0: the scale), corr_min, corr_max_lag, ndim: files are thinned by ``ceil(scale * L)``, L their measured
+                  autocorrelation length over the first ``ndim`` parameters (``correlation_length``); the result is ``thin_corr_info``.
     """
 
     def __init__(self, str_or_dict, trueval=None, debug=False, csplit=None, names=None, labels=None,
@@ -199,6 +324,7 @@ class MCSamples(object):
         kwargs.pop("log_level", None)
         self.logger = logger
         self.chains = None
+        self.thin_corr_info = None
 
         if isinstance(str_or_dict, str):
             self.logger.info("Loading chain from " + str_or_dict)
@@ -250,9 +376,12 @@ class MCSamples(object):
             raise ValueError("the chains array is empty")
         burnlen = kwargs.pop("burnlen", 0)
         thinlen = kwargs.pop("thinlen", 0)
+        scale = thin_corr_scale(kwargs.pop("thin_corr", None), thinlen)
         self.nchains = len(self.chains)
         if burnlen > 0:
             self.chains = [self.removeBurn(burnlen, chain=c) for c in self.chains]
+        if scale is not None:
+            thinlen = self.measure_thin(scale, kwargs.pop("ndim", None), kwargs.pop("corr_min", CORR_MIN), kwargs.pop("corr_max_lag", CORR_MAX_LAG))
         self.chain_offsets = np.cumsum([0] + [c.shape[0] for c in self.chains])
         self.ichain = np.concatenate([(i + 1) * np.ones(len(c)) for i, c in enumerate(self.chains)])
         self.samples = np.concatenate(self.chains)
@@ -266,6 +395,14 @@ class MCSamples(object):
         start = int(chain.shape[0] * remove) if remove < 1 else int(remove)
         self.logger.info("Removing %s lines as burn in" % start)
         return chain[start:, :]
+
+    def measure_thin(self, scale, ndim, corr_min, corr_max_lag):
+        """thin_corr: the thinning factor from the burned chains' autocorrelation length, as a thinlen"""
+        res = correlation_length(self.chains, self.iw, self.itheta, ndim, corr_min, corr_max_lag)
+        self.thin_corr_info = corr_info(res, scale)
+        self.logger.info("thin_corr: autocorrelation length %.3f %s units (cap %d) -> thinning factor %d"
+                         % (self.thin_corr_info["length"], self.thin_corr_info["units"], res["cap"], self.thin_corr_info["factor"]))
+        return float(self.thin_corr_info["factor"])
 
     def thin(self, nthin=1, chain=None):
         if nthin == 1:

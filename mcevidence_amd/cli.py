@@ -32,6 +32,9 @@ def build_parser(prog=None):
                    help="Burn-in length or fraction; burnlen<1 is a fraction, e.g. 0.3 = 30%%")
     p.add_argument("--thin", "--thinlen", dest="thinlen", default=0, type=float,
                    help="Thinning: 0<thinlen<1 Poisson-resampled weights; thinlen>1 weighted thinning")
+    p.add_argument("--thin-corr", dest="thin_corr", nargs="?", const=True, default=None, type=float, metavar="SCALE",
+                   help="thin by SCALE (default 1) times the measured autocorrelation length of the chains instead of a given --thin; "
+                        "write it after root_name, or as --thin-corr=SCALE: directly in front of root_name it would take the root for SCALE")
     p.add_argument("-vb", "--verbose", dest="verbose", default=1, type=int, help="0: WARNINGS, 1: INFO, 2: DEBUG")
     p.add_argument("-pv", "--pvolume", dest="priorvolume", default=None, type=float,
                    help="prior volume to use; if *.ranges exists the volume estimated from it is used")
@@ -56,6 +59,11 @@ def _backend_kw(args):
     return {"backend": HipBackend(device_eig=True)}
 
 
+def _thin_kw(args):
+    """--thin-corr, where it was given"""
+    return {} if args.thin_corr is None else {"thin_corr": args.thin_corr}
+
+
 def farm_main(args):
     """``--farm``: every root of the list file, each with the ndim and the prior volume a single run would compute for it"""
     import copy
@@ -72,7 +80,7 @@ def farm_main(args):
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
     outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
-                                    idchain=args.idchain, split=args.cross, **_backend_kw(args))
+                                    idchain=args.idchain, split=args.cross, **_thin_kw(args), **_backend_kw(args))
     for r, mle in zip(roots, outs):
         print()
         print("Using file: ", r)
@@ -102,13 +110,13 @@ def main(argv=None):
     if args.resident:
         from .resident import evidence_from_files
         out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
-                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, **_backend_kw(args))
+                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, **_thin_kw(args), **_backend_kw(args))
         print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
         print("")
         return out
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
-                     thinlen=args.thinlen, **_backend_kw(args))
+                     thinlen=args.thinlen, **_thin_kw(args), **_backend_kw(args))
     out = mce.evidence()
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
     print("")

@@ -197,6 +197,8 @@ class MCEvidence(object):
         ndim        number of leading parameter columns to use (default all)
         split       cross-evidence: neighbours of s1 points are searched in s2
         priorvolume prior volume; burnlen/thinlen as in the reference (files only)
+        thin_corr   (with corr_min, corr_max_lag; files only) thin by the chains' measured autocorrelation length times this
+                    scale (True: 1) instead of a given thinlen: chains.correlation_length; reported in info["thin_corr"]
         nbatch, brange, bscale   batched runs; only bscale='logpower' is supported
         """
         self.backend = gdkwargs.pop("backend", None) or HipBackend()
@@ -229,6 +231,8 @@ class MCEvidence(object):
 
         gdkwargs.setdefault("thinlen", thinlen)
         gdkwargs.setdefault("burnlen", burnlen)
+        if gdkwargs.get("thin_corr") not in (None, False):
+            gdkwargs.setdefault("ndim", ndim)              # thin_corr measures the columns the estimator uses
         csplit = namedtuple("split_var", "split frac shuffle")(split=split, frac=s1frac, shuffle=shuffle)
         self.gd = MCSamples(method, csplit=csplit, debug=self.debug, **gdkwargs)
 
@@ -237,6 +241,8 @@ class MCEvidence(object):
             if self.split:
                 self.gd.importance_sample(isfunc, name="s2")
 
+        if self.gd.thin_corr_info is not None:
+            self.info["thin_corr"] = self.gd.thin_corr_info
         self.info["NparamsMC"] = self.gd.nparamMC
         self.info["Nsamples_read"] = self.gd.get_shape()[0]
         self.info["Nparams_read"] = self.gd.get_shape()[1]

@@ -198,7 +198,7 @@ class _Root(object):
 
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
-                             require_resident=False, wave_bytes=None, split=False):
+                             require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -209,7 +209,8 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     -- goes to ``evidence_from_files`` after the farm's work; ``require_resident=True`` makes a decline ``ValueError(reason)``.
     Under an initialised process group the whole call goes to ``evidence_many`` over ``MCEvidence`` objects.  A failing root raises
     what the host route raises for it (the first in input order), or sits in its slot with ``return_exceptions=True``; it never
-    changes another root's result.  Without a GPU: ``RuntimeError``."""
+    changes another root's result.  ``thin_corr`` (one value or one per root; with ``corr_min``, ``corr_max_lag``): such a root is thinned
+    by its measured autocorrelation length on the per-root resident route.  Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
     roots = list(roots)
@@ -218,11 +219,14 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     pvols = _per_root(priorvolume, n, "priorvolume")
     burns = _per_root(burnlen, n, "burnlen")
     thins = _per_root(thinlen, n, "thinlen")
+    tcorr = _per_root(thin_corr, n, "thin_corr")
+    corr_kw = {k: v for k, v in (("corr_min", corr_min), ("corr_max_lag", corr_max_lag)) if v is not None}
     common = dict(kmax=kmax, idchain=idchain, idpattern=idpattern, iw=iw, ilike=ilike, itheta=itheta)
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], **extra) for i, r in enumerate(roots)]
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **extra)
+                for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
     from .evidence import HipBackend
@@ -245,7 +249,13 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
         if reason == _res.RESIDENT and split:
             reason = "split: the random split is drawn per root on the host"
         if reason == _res.RESIDENT:
-            reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i])
+            try:
+                reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i])
+            except ValueError as e:                # (thin_corr together with thinlen)
+                fail(i, e)
+                continue
+        if reason == _res.RESIDENT and _res._chains.thin_corr_scale(tcorr[i]) is not None:
+            reason = _res.REASONS["thin_corr"]
         if reason != _res.RESIDENT:
             fallback[i] = reason
             continue
@@ -391,6 +401,8 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
         counts["fallback"] += 1
         try:
             kw = dict(common, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], pos_lnp=pos_lnp, split=split, info=True, verbose=0)
+            if tcorr[i] not in (None, False):
+                kw.update(corr_kw, thin_corr=tcorr[i])
             if covtype != "all":
                 kw["covtype"] = covtype
             if backend is not None:

@@ -47,6 +47,7 @@ REASONS = {
     "ischain": "ischain=False: the host route raises",
     "ambiguous_weights": "the weights' fractional parts sum to within 1e-6 of the integer-weight threshold 1e-4",
     "bad_weights": "a weight is negative, not finite or beyond 2^53",
+    "thin_corr": "thin_corr: the autocorrelation length is measured root by root (the per-root resident route)",
 }
 
 
@@ -64,12 +65,14 @@ class ResidentDecline(Exception):
 
 
 def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all", split=False, ndim=None, nparam=None,
-         distributed=False, ncols=None, nrows=None, ischain=True):
+         distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None):
     """``"resident"`` or the reason why the route declines.  A pure function of the call's keywords and of what is known
     about the data at the time (``ncols``: the files' column counts, ``nrows``: rows left after burn-in / thinning,
-    ``nparam``: parameter columns; None: not known yet)."""
+    ``nparam``: parameter columns; None: not known yet).  ``thin_corr`` (thinning by the measured autocorrelation length) is resident
+    work and declines nothing; together with a ``thinlen`` other than 0 it is the ValueError every route raises."""
     if not ischain:
         return REASONS["ischain"]
+    _chains.thin_corr_scale(thin_corr, thinlen)
     if thinlen < 0:
         return REASONS["negative_thinlen"]
     if 0 < thinlen < 1:
@@ -182,9 +185,12 @@ class ResidentChains(object):
     ``nrows`` / ``nparam``: the shape ``MCSamples(...).samples[:, itheta:]`` has; ``rule``: ``"none" | "integer" | "bin"``
     (the thinning rule taken); ``keep()``: the kept rows in the burned, concatenated numbering (the host's ``keep``);
     ``to_host()``: the array ``MCSamples(...).samples`` holds; ``stats``: reader statistics per file and milliseconds per
-    stage.  Raises ``ResidentDecline`` where the route does not apply, ``RuntimeError`` without a GPU."""
+    stage.  ``thin_corr`` (None / False, True or a scale > 0; with ``corr_min``, ``corr_max_lag`` and the estimator's ``ndim``) thins by
+    the autocorrelation length measured on the device (``mce_chain_corr_dev``) instead of a given ``thinlen``; ``thin_corr`` holds what
+    was found.  Raises ``ResidentDecline`` where the route does not apply, ``RuntimeError`` without a GPU."""
 
-    def __init__(self, tensors, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, device=0, reader_stats=None):
+    def __init__(self, tensors, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, device=0, reader_stats=None, thin_corr=None,
+                 corr_min=_chains.CORR_MIN, corr_max_lag=_chains.CORR_MAX_LAG, ndim=None):
         import torch
         self._torch = torch
         self.device = int(device)
@@ -193,6 +199,8 @@ class ResidentChains(object):
         self.nchains = len(tensors)
         if not tensors:
             raise ValueError("the chains array is empty")
+        scale = _chains.thin_corr_scale(thin_corr, thinlen)
+        self.thin_corr = None
         reason = plan(thinlen=thinlen, ncols=[t.shape[1] for t in tensors], distributed=_distributed())
         if reason != RESIDENT:
             raise ResidentDecline(reason)
@@ -214,6 +222,10 @@ class ResidentChains(object):
         if self.nburned < 1:                              # (nothing to select from; fewer than 2 rows decline in evidence())
             raise ResidentDecline(REASONS["rows"])
         t0 = time.perf_counter()
+        if scale is not None:
+            thinlen = self._measure(scale, ndim, corr_min, corr_max_lag)
+            self.stats["ms"]["corr"] = _ms(t0)
+            t0 = time.perf_counter()                      # ("select" keeps its meaning: the thinning alone)
         if thinlen not in (0, 1):
             self._select(float(thinlen))
         self.stats["ms"]["select"] = _ms(t0)
@@ -221,7 +233,7 @@ class ResidentChains(object):
 
     # -- construction ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_arrays(cls, arrays, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, device=0):
+    def from_arrays(cls, arrays, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, device=0, **corr):
         """Host arrays (one per chain) uploaded as they are.  Unlike ``MCSamples``, which ignores ``burnlen`` / ``thinlen``
         for chains passed in memory (and keeps doing so), this entry HONOURS them, with the rules files get: it exists so
         that the device preparation can be used and tested apart from the reader."""
@@ -236,11 +248,13 @@ class ResidentChains(object):
                 if a.ndim != 2:
                     raise ValueError("a chain must be a 2-D array, got shape %r" % (a.shape,))
                 tensors.append(torch.from_numpy(a).to("cuda:%d" % int(device)))
-            return cls(tensors, burnlen, thinlen, iw, ilike, itheta, device)
+            return cls(tensors, burnlen, thinlen, iw, ilike, itheta, device, **corr)
 
     @classmethod
-    def from_files(cls, root_or_paths, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, idchain=0, idpattern="_?.txt", device=0):
-        """Chain text files parsed on the device and left there; the files are those ``MCSamples.load_from_file`` reads."""
+    def from_files(cls, root_or_paths, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, idchain=0, idpattern="_?.txt", device=0,
+                   **corr):
+        """Chain text files parsed on the device and left there; the files are those ``MCSamples.load_from_file`` reads.  ``corr``:
+        thin_corr, corr_min, corr_max_lag, ndim."""
         import mmap
         from . import _capi, chain_io
         _capi.require_device()
@@ -275,8 +289,8 @@ class ResidentChains(object):
                 if nrows == 0:                               # (np.loadtxt: an empty file is an array of shape (0, 1))
                     out = torch.empty((0, 1), dtype=torch.float64, device="cuda:%d" % int(device))
                 tensors.append(out)
-            self = cls(tensors, burnlen, thinlen, iw, ilike, itheta, device, reader_stats=stats)
-        self.stats["ms"]["read"] = _ms(t0) - self.stats["ms"]["select"]
+            self = cls(tensors, burnlen, thinlen, iw, ilike, itheta, device, reader_stats=stats, **corr)
+        self.stats["ms"]["read"] = _ms(t0) - self.stats["ms"]["select"] - self.stats["ms"].get("corr", 0.0)
         return self
 
     def _stream(self):
@@ -284,6 +298,26 @@ class ResidentChains(object):
 
     def _ws(self, nbytes):
         return self._torch.empty(max(int(nbytes), 1), dtype=self._torch.uint8, device="cuda:%d" % self.device)
+
+    def _measure(self, scale, ndim, corr_min, corr_max_lag):
+        """thin_corr: the thinning factor from the autocorrelation length of the burned parts, measured on the device"""
+        from . import _capi
+        nd = effective_ndim(ndim, self.nparam)
+        if nd > 127:
+            raise ResidentDecline(REASONS["ndim"])
+        nparts = len(self._parts)
+        wsb = _capi.chain_corr_workspace_bytes(self.nburned, nparts, nd, corr_max_lag)
+        if wsb == 0:
+            raise ValueError("thin_corr: corr_max_lag=%r" % (corr_max_lag,))
+        ws = self._ws(wsb)
+        res = _capi.chain_corr_dev(self._parts, self.ncols, self.iw, self.itheta, nd, corr_min, corr_max_lag, ws.data_ptr(), wsb, self._stream())
+        if res["rule"] < 0:
+            raise ResidentDecline(REASONS[DECLINE_REASON[res["rule"]]])
+        res["min_corr"] = corr_min
+        self.thin_corr = _chains.corr_info(res, scale)
+        logger.info("thin_corr: autocorrelation length %.3f %s units (cap %d) -> thinning factor %d"
+                    % (self.thin_corr["length"], self.thin_corr["units"], res["cap"], self.thin_corr["factor"]))
+        return float(self.thin_corr["factor"])
 
     def _select(self, thinlen):
         from . import _capi
@@ -417,7 +451,10 @@ class ResidentChains(object):
         out = mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, math.log(priorvolume), cross)[1:]
         if not info:
             return out
-        return out, route_info(RESIDENT, self.nparam, nd, self.nrows if split_rows is not None else n1, [n1, n2] if cross else [n1])
+        inf = route_info(RESIDENT, self.nparam, nd, self.nrows if split_rows is not None else n1, [n1, n2] if cross else [n1])
+        if self.thin_corr is not None:
+            inf["thin_corr"] = self.thin_corr
+        return out, inf
 
 
 _EVIDENCE_KEYS = ("rand", "info", "profile", "pvolume", "pos_lnp", "nproc", "prewhiten")
@@ -441,7 +478,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     if reason == RESIDENT:
         reason = plan(thinlen=ctor.get("thinlen", 0.0), isfunc=ctor.get("isfunc"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1),
                       verbose=max(ctor.get("verbose", 1), 2 if ctor.get("debug") else 0), covtype=covtype, split=split, ndim=None,
-                      distributed=_distributed(), ischain=ctor.get("ischain", True))
+                      distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"))
     if reason == RESIDENT:
         level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
         if not logging.getLogger().handlers:
@@ -451,7 +488,9 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
         try:
             rc = ResidentChains.from_files(root, burnlen=ctor.get("burnlen", 0.0), thinlen=ctor.get("thinlen", 0.0), iw=ctor.get("iw", 0),
                                            ilike=ctor.get("ilike", 1), itheta=ctor.get("itheta", 2), idchain=ctor.get("idchain", 0),
-                                           idpattern=ctor.get("idpattern", "_?.txt"))
+                                           idpattern=ctor.get("idpattern", "_?.txt"), thin_corr=ctor.get("thin_corr"),
+                                           corr_min=ctor.get("corr_min", _chains.CORR_MIN), corr_max_lag=ctor.get("corr_max_lag", _chains.CORR_MAX_LAG),
+                                           ndim=ctor.get("ndim"))
             pv = call.get("pvolume")
             got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,

@@ -471,6 +471,29 @@ int mce_chain_corr_f64(const mce_chain_part* parts, int32_t nparts, int64_t ncol
                        int64_t max_lag, int32_t* rule, int32_t* status, int64_t* units, int64_t* cap, double* length, int64_t* cut,
                        double* rho, int64_t* rho_rows, int32_t device);
 
+/* Delete-a-group jackknife of the evidence reduction from ONE neighbour search (docs/design/jackknife.md; rule: csrc/jack.hpp).
+ * Every query row q has an ascending list of L entries, d_dist / d_idx [nq][L] (what mce_knn_f64_dev leaves; a row below 0 ends the
+ * list), a weight, a term fs and a group d_gq[q] in [0, G); every reference row has a group d_gr[nr].  With K = kmax - k0:
+ *   d_dotp_groups[b * kmax + k] = the sum mce_dotp_f64_dev forms for column k, over the rows with d_gq != b, each taken at the
+ *                                 (k - k0 + 1)-th entry of its list once entries whose reference row is in group b are skipped;
+ *   d_dotp_full[k]              = the same with no group deleted (with no short row: mce_dotp_f64_dev's sum, bit for bit).
+ * k0 = 1 (auto evidence): the entry whose reference row is the query's own -- d_qid[q], or q where d_qid is NULL -- is skipped too.
+ * A row is SHORT when skipping some group other than its own (or none) leaves fewer than K entries: it enters no sum; its row
+ * number (d_qid[q] or q) is appended to d_short_rows [nq], ascending, and *d_nshort (device) counts them.  d_gq, d_w, d_fs are
+ * indexed by q, not by d_qid.  2 <= G <= MCE_JACK_MAX_GROUPS, K <= L <= MCE_GENERIC_MAX_K + 1, K <= MCE_MAX_K.  Lists of up to 32
+ * entries are processed from registers, longer ones from memory.  fp64, plain stores, sums in an order the sizes fix: two runs give
+ * the same bits.  The stream is synchronised on return.  mce_jack_dotp_f64 takes HOST pointers (nshort too), uploads to `device`
+ * and calls the device form.  Argument errors -- G out of range, a group id out of range, L < K -- : MCE_ERR_INVALID. */
+#define MCE_JACK_MAX_GROUPS 64
+size_t mce_jack_workspace_bytes(int64_t nq, int32_t G, int32_t kmax);
+int mce_jack_dotp_dev(const double* d_dist, const int64_t* d_idx, int64_t nq, int32_t L, const int64_t* d_qid, const int32_t* d_gq,
+                      const int32_t* d_gr, int64_t nr, int32_t G, int32_t k0, int32_t kmax, int32_t d, const double* d_w, const double* d_fs,
+                      double* d_dotp_groups, double* d_dotp_full, int64_t* d_short_rows, int64_t* d_nshort, void* ws, size_t ws_bytes,
+                      void* stream);
+int mce_jack_dotp_f64(const double* dist, const int64_t* idx, int64_t nq, int32_t L, const int64_t* qid, const int32_t* gq, const int32_t* gr,
+                      int64_t nr, int32_t G, int32_t k0, int32_t kmax, int32_t d, const double* w, const double* fs, double* dotp_groups,
+                      double* dotp_full, int64_t* short_rows, int64_t* nshort, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

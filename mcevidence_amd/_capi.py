@@ -158,6 +158,13 @@ SIGNATURES["mce_chain_farm_prep_workspace_bytes"] = (_c.c_size_t, [_c.c_int32, _
 SIGNATURES["mce_chain_farm_prep_dev"] = (_c.c_int, [_P, _P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _P, _P, _P,
                                                      _P, _c.c_size_t, _P])
 
+MCE_JACK_MAX_GROUPS = 64
+SIGNATURES["mce_jack_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_jack_dotp_dev"] = (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P, _P, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P,
+                                              _P, _P, _P, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_jack_dotp_f64"] = (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P, _P, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P,
+                                              _P, _P, _P, _P, _c.c_int32])
+
 _lib = None
 
 
@@ -938,6 +945,50 @@ def knn_dev(dX, nq, dY, nr, d, K, self_mode, self_offset, d_dist, d_idx, ws, ws_
 
 def dotp_dev(d_dist, nq, ld, k0, kmax, d, d_w, d_fs, d_dotp, ws, ws_bytes, stream=0):
     check(load().mce_dotp_f64_dev(d_dist, nq, ld, k0, kmax, d, d_w, d_fs, d_dotp, ws, ws_bytes, stream or None))
+
+
+def jack_workspace_bytes(nq, G, kmax):
+    """scratch bytes of ``jack_dotp_dev``"""
+    n = int(load().mce_jack_workspace_bytes(int(nq), int(G), int(kmax)))
+    if n == 0:
+        raise ValueError("jackknife: invalid sizes nq=%d G=%d kmax=%d" % (nq, G, kmax))
+    return n
+
+
+def jack_dotp_dev(d_dist, d_idx, nq, L, d_qid, d_gq, d_gr, nr, G, k0, kmax, d, d_w, d_fs, d_dotp_groups, d_dotp_full, d_short_rows, d_nshort,
+                  ws, ws_bytes, stream=0):
+    """the leave-one-group-out sums of lists that are on the device (``mce_jack_dotp_dev``); device POINTERS, the stream is
+    synchronised on return"""
+    check(load().mce_jack_dotp_dev(d_dist, d_idx, int(nq), int(L), d_qid or None, d_gq, d_gr, int(nr), int(G), int(k0), int(kmax), int(d), d_w, d_fs,
+                                   d_dotp_groups, d_dotp_full, d_short_rows, d_nshort, ws, ws_bytes, stream or None))
+
+
+def jack_dotp(dist, idx, gq, gr, G, k0, kmax, d, w, fs, qid=None, device=0):
+    """``mce_jack_dotp_f64``: the leave-one-group-out sums from neighbour lists ``dist`` / ``idx`` [nq, L] on the host.
+    Returns (dotp_groups[G, kmax], dotp_full[kmax], short_rows int64, ascending)."""
+    lib = load()
+    dist = _f64_allow_inf(dist)
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    gq = np.ascontiguousarray(gq, dtype=np.int32)
+    gr = np.ascontiguousarray(gr, dtype=np.int32)
+    w = _f64(w, "weight")
+    fs = _f64_fs(fs)
+    if dist.ndim != 2 or idx.shape != dist.shape or w.shape != (dist.shape[0],) or fs.shape != w.shape or gq.shape != w.shape or gr.ndim != 1:
+        raise ValueError("shape mismatch: dist %r, idx %r, w %r, fs %r, gq %r, gr %r" % (dist.shape, idx.shape, w.shape, fs.shape, gq.shape, gr.shape))
+    nq, L = dist.shape
+    if qid is not None:
+        qid = np.ascontiguousarray(qid, dtype=np.int64)
+        if qid.shape != (nq,):
+            raise ValueError("qid must have one entry per query row")
+    G, kmax = int(G), int(kmax)
+    groups = np.zeros((max(G, 1), max(kmax, 1)), dtype=np.float64)
+    full = np.zeros(max(kmax, 1), dtype=np.float64)
+    short = np.zeros(max(nq, 1), dtype=np.int64)
+    nshort = _c.c_int64(0)
+    check(lib.mce_jack_dotp_f64(dist.ctypes.data, idx.ctypes.data, nq, L, qid.ctypes.data if qid is not None else None, gq.ctypes.data, gr.ctypes.data,
+                                gr.shape[0], G, int(k0), kmax, int(d), w.ctypes.data, fs.ctypes.data, groups.ctypes.data, full.ctypes.data,
+                                short.ctypes.data, _c.addressof(nshort), int(device)))
+    return groups, full, short[:int(nshort.value)].copy()
 
 
 def prune_part_applies(nr, d, kmax, nparts):

@@ -385,6 +385,7 @@ class MCSamples(object):
         self.chain_offsets = np.cumsum([0] + [c.shape[0] for c in self.chains])
         self.ichain = np.concatenate([(i + 1) * np.ones(len(c)) for i, c in enumerate(self.chains)])
         self.samples = np.concatenate(self.chains)
+        self.row_chain = self.ichain.astype(np.int64) - 1          # the chain (0-based) of every surviving row: thin() keeps it in step
         if abs(thinlen) > 0:
             self.samples = self.thin(nthin=thinlen, chain=self.samples)
         self.chains = None
@@ -413,6 +414,8 @@ class MCSamples(object):
         keep, neww = thin_rows(w, nthin)
         out = chain[keep, :]
         out[:, self.iw] = neww
+        if getattr(self, "row_chain", None) is not None and len(self.row_chain) == len(w):
+            self.row_chain = self.row_chain[keep]
         self.logger.info("Thinning with thin length=%s: #old_chain=%s, #new_chain=%s" % (nthin, len(w), len(neww)))
         return out
 

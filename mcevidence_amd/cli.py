@@ -48,6 +48,11 @@ def build_parser(prog=None):
                         "(mcevidence_amd.farm); a root the farm does not cover takes the per-root route")
     p.add_argument("--device-eig", dest="device_eig", action="store_true",
                    help="solve the covariance eigen-systems of the device feeders on the GPU (HipBackend(device_eig=True)) instead of on the host")
+    p.add_argument("--jackknife", dest="jackknife", nargs="?", const=16, default=None, type=int, metavar="G",
+                   help="delete-a-group jackknife error bars on ln(B) from one neighbour search, G groups (default 16); prints ln(B)[k] = x +- sigma "
+                        "(conservative, not a calibrated 1 sigma); write it after root_name, or as --jackknife=G")
+    p.add_argument("--jackknife-by", dest="jackknife_by", choices=("blocks", "chains"), default="blocks",
+                   help="the groups: contiguous blocks of the burned / thinned chain, or one group per chain file")
     return p
 
 
@@ -117,7 +122,17 @@ def main(argv=None):
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
                      thinlen=args.thinlen, **_thin_kw(args), **_backend_kw(args))
-    out = mce.evidence()
+    if args.jackknife is not None:
+        if args.resident or args.farm:
+            raise ValueError("--jackknife with --resident / --farm is not supported")
+        mce.jackknife = {"groups": args.jackknife, "by": args.jackknife_by}
+        out = mce.evidence()
+        jk = mce.info["jackknife"]
+        for k in range(1, len(jk["lnE"]) + 1):
+            print("   ln(B)[k={}] = {} \u00b1 {}".format(k, jk["lnE"][k - 1], jk["sigma"][k - 1]))
+        print("* \u00b1: delete-a-group jackknife over {} {} (conservative, not a calibrated 1 sigma).".format(jk["groups"], jk["by"]))
+    else:
+        out = mce.evidence()
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
     print("")
     return out

@@ -163,6 +163,16 @@ class HipBackend(object):
         with self._scoped():
             return [(dotp, jac) for dotp, jac, _ in _capi.evidence_feed_batch(problems, devices=self.devices)]
 
+    def jackknife_lists(self, S1, S2, ndim, kmax, weight, fs, gq, gr, G, whitened=False):
+        """The device side of ``evidence_jackknife`` (jackknife.HipSession): rows, weights, terms and groups on the device, one
+        search and one ``mce_jack_dotp_dev`` per rung of the ladder.  ``whitened=False``: S1 are raw rows, whitened on the device
+        (auto evidence); ``whitened=True``: S1 / S2 are whitened already.  One process, one device."""
+        from .jackknife import HipSession
+        if self.devices not in (None, [0], (0,)) and len(self.devices) != 1:
+            raise ValueError("jackknife runs on one device (devices=%r)" % (self.devices,))
+        with self._scoped():
+            return HipSession(S1, S2, ndim, kmax, weight, fs, gq, gr, G, device=self.devices[0] if self.devices else 0, whitened=whitened)
+
     def knn_dotp(self, X, Y, weight, fs, kmax, k0, want_dist=False):
         from . import parallel
         if parallel.is_distributed():
@@ -187,9 +197,11 @@ class MCEvidence(object):
                  **gdkwargs):
         """Evidence estimation from MCMC chains (Heavens et al. 2017, arXiv:1704.03472).
 
-        Parameters have the reference's meaning.  One keyword is added and consumed here
-        (it is not forwarded to the chain reader): ``backend`` -- an object with a
-        ``knn_dotp`` method; default ``HipBackend()``.
+        Parameters have the reference's meaning.  Two keywords are added and consumed here
+        (they are not forwarded to the chain reader): ``backend`` -- an object with a
+        ``knn_dotp`` method; default ``HipBackend()`` -- and ``jackknife`` -- None, True, a number of
+        groups or a dict of ``evidence_jackknife``'s keywords: ``evidence()`` then also stores the jackknife
+        error bars in ``info["jackknife"]``.
 
         method      chain root name / file name(s), or list/tuple/dict of chain arrays
                     (columns: weight, -lnL, parameters...)
@@ -202,6 +214,9 @@ class MCEvidence(object):
         nbatch, brange, bscale   batched runs; only bscale='logpower' is supported
         """
         self.backend = gdkwargs.pop("backend", None) or HipBackend()
+        # jackknife error bars with every evidence() call (docs/design/jackknife.md): None (off), True (16 blocks), a number of blocks,
+        # or a dict of evidence_jackknife's keywords; evidence() keeps the reference's signature, so the switch lives here
+        self.jackknife = gdkwargs.pop("jackknife", None)
         self.logger = logger
         self.verbose = verbose
         self.debug = bool(debug or verbose > 1)
@@ -433,7 +448,16 @@ class MCEvidence(object):
         """ln-evidence for k = 1..kmax-1 nearest neighbours (auto), or k = 2..kmax (cross,
         ``split=True``).  Returns the array ``MLE[1:]`` like the reference (and the info
         dict if ``info=True``).  ``nproc``/``profile``/``prewhiten`` are accepted for
-        signature compatibility (the reference ignores the last two as well)."""
+        signature compatibility (the reference ignores the last two as well).
+        With ``self.jackknife`` set (the constructor's ``jackknife`` keyword; None: nothing changes) the result of
+        ``evidence_jackknife`` is stored in ``info["jackknife"]``; what is returned is what is always returned."""
+        jackknife = self.jackknife
+        if jackknife is not None and jackknife is not False:
+            kw = dict(jackknife) if isinstance(jackknife, dict) else ({} if jackknife is True else {"groups": int(jackknife)})
+            kw.setdefault("covtype", covtype)
+            kw.setdefault("pvolume", pvolume)
+            kw.setdefault("pos_lnp", pos_lnp)
+            self.info["jackknife"] = self.evidence_jackknife(**kw)
         if verbose is None:
             verbose = self.verbose
         logPriorVolume = math.log(self.priorvolume if pvolume is None else pvolume)
@@ -504,6 +528,19 @@ class MCEvidence(object):
 
         MLE = MLE[0, 1:] if self.brange is None else MLE[:, 1:]
         return self._report(MLE, verbose, info)
+
+
+def _evidence_jackknife(self, groups=16, by="blocks", covtype="all", pvolume=None, pos_lnp=False):
+    """ln E with a delete-a-group jackknife error bar from ONE neighbour search (jackknife.py; docs/design/jackknife.md).
+    ``by="blocks"``: ``groups`` contiguous stretches of the burned / thinned chain; ``by="chains"``: one group per chain file or input
+    array.  Returns dict(lnE, sigma, lnE_groups, lnE_bias_corrected, groups, by, rows_per_level), the columns of ``evidence()``.
+    sigma is conservative, not a calibrated 1 sigma.  ValueError with brange / nbatch > 1, with split and covtype='single', and
+    under an initialised process group."""
+    from .jackknife import evidence_jackknife
+    return evidence_jackknife(self, groups=groups, by=by, covtype=covtype, pvolume=pvolume, pos_lnp=pos_lnp)
+
+
+MCEvidence.evidence_jackknife = _evidence_jackknife
 
 
 def evidence_many(mces, verbose=None, info=False, covtype="all", pvolume=None, pos_lnp=False, **kwargs):

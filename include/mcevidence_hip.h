@@ -494,6 +494,30 @@ int mce_jack_dotp_f64(const double* dist, const int64_t* idx, int64_t nq, int32_
                       int64_t nr, int32_t G, int32_t k0, int32_t kmax, int32_t d, const double* w, const double* fs, double* dotp_groups,
                       double* dotp_full, int64_t* short_rows, int64_t* nshort, int32_t device);
 
+/* The Gelman-Rubin statistic "R-1" of burned chains that are on the device, for MANY systems (the roots of a farm wave) in one call:
+ * the variance of the chain means over the mean of the chain variances, in the worst direction of parameter space.  The rule is stated
+ * in csrc/chain_conv.hpp and docs/design/chain_conv.md.  `segs` are runs of rows of `ncols` doubles (a whole chain, or a half of one: a
+ * segment whose pointer is offset -- halves are the caller's business); seg_sys[s] in 0 .. nsys - 1, non-decreasing, names the system
+ * of segment s; a system has at most MCE_CONV_MAX_SEGMENTS segments.  The RAW weights of column `iw` weigh the first `ndim` columns
+ * from `itheta` (1 <= ndim <= 127); one call takes one (ncols, ndim).  A segment without rows or of total weight 0 is skipped;
+ * nseg_used[y] counts the others.  Outputs are HOST arrays: r_minus_1[nsys], per_param[nsys * ndim] (B_jj / W_jj), status[2 * y] =
+ * 0 ok, 2 a column whose within-chain variance is not > 0 (constant), 3 a value that is not finite in a measured column or a weight
+ * that is negative or not finite, 4 the within-chain correlation matrix is not positive definite (per_param is still set, r_minus_1
+ * is NaN), 5 fewer than two segments with weight; status[2 * y + 1] = the offending column (-1: a weight, or none).  Where the status is
+ * 2, 3 or 5, r_minus_1 and per_param are NaN.  A system's bits depend on its own rows alone, not on its neighbours, its position or
+ * the call; fp64, sums in a fixed order: two runs give the same bits.  Segments, workspace and stream are the caller's
+ * (mce_chain_conv_workspace_bytes(rows of all segments, nseg, nsys, ndim)); everything is enqueued on the stream, which is
+ * synchronised once, on return.  mce_chain_conv_f64 takes HOST segments, uploads them to `device` and calls the device form.
+ * Argument errors: MCE_ERR_INVALID (no device needed) -- ndim outside 1 .. 127, more than MCE_CONV_MAX_SEGMENTS segments in a system,
+ * a system with fewer than 2 segments with rows, seg_sys out of order; no visible device: MCE_ERR_NO_DEVICE. */
+#define MCE_CONV_MAX_SEGMENTS 128
+size_t mce_chain_conv_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t nsys, int32_t ndim);
+int mce_chain_conv_dev(const mce_chain_part* segs, const int32_t* seg_sys, int32_t nseg, int32_t nsys, int64_t ncols, int32_t iw, int32_t itheta,
+                       int32_t ndim, double* r_minus_1, double* per_param, int32_t* status, int32_t* nseg_used, void* ws, size_t ws_bytes,
+                       void* stream);
+int mce_chain_conv_f64(const mce_chain_part* segs, const int32_t* seg_sys, int32_t nseg, int32_t nsys, int64_t ncols, int32_t iw, int32_t itheta,
+                       int32_t ndim, double* r_minus_1, double* per_param, int32_t* status, int32_t* nseg_used, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

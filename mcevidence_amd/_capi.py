@@ -112,6 +112,9 @@ SIGNATURES = {
                                       _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _P, _P, _P, _c.POINTER(_c.c_int64), _P, _c.c_size_t, _P]),
     "mce_chain_corr_f64": (_c.c_int, [_P, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_double, _c.c_int64, _c.POINTER(_c.c_int32), _P,
                                       _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _P, _P, _P, _c.POINTER(_c.c_int64), _c.c_int32]),
+    "mce_chain_conv_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32]),
+    "mce_chain_conv_dev": (_c.c_int, [_P, _P, _c.c_int32, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
+    "mce_chain_conv_f64": (_c.c_int, [_P, _P, _c.c_int32, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _P, _P, _c.c_int32]),
     "mce_knn_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32]),
     "mce_dotp_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int32]),
     "mce_knn_f64_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
@@ -564,6 +567,43 @@ def chain_corr(arrays, iw, itheta, ndim, min_corr=0.05, max_lag=1024, device=0, 
         raise ValueError("chains must be 2-D arrays of one column count")
     parts = [(a.ctypes.data if a.shape[0] else 0, a.shape[0]) for a in arrays]
     return _chain_corr(load().mce_chain_corr_f64, parts, arrays[0].shape[1], iw, itheta, ndim, min_corr, max_lag, want_rho, (int(device),))
+
+
+CONV_MAX_SEGMENTS = 128
+
+
+def chain_conv_workspace_bytes(nrows_total, nseg, nsys, ndim):
+    return int(load().mce_chain_conv_workspace_bytes(int(nrows_total), int(nseg), int(nsys), int(ndim)))
+
+
+def _chain_conv(call, segs, seg_sys, nsys, ncols, iw, itheta, ndim, tail):
+    nsys, nd = int(nsys), max(int(ndim), 1)
+    r = np.full(max(nsys, 1), np.nan)
+    per = np.full((max(nsys, 1), nd), np.nan)
+    status = np.zeros((max(nsys, 1), 2), dtype=np.int32)
+    used = np.zeros(max(nsys, 1), dtype=np.int32)
+    sys_ = np.ascontiguousarray(seg_sys, dtype=np.int32)
+    if sys_.shape != (len(segs),):
+        raise ValueError("chain conv: one system number per segment expected")
+    arr = chain_parts(segs)
+    check(call(_c.cast(arr, _P), sys_.ctypes.data, len(segs), nsys, int(ncols), int(iw), int(itheta), int(ndim), r.ctypes.data, per.ctypes.data,
+               status.ctypes.data, used.ctypes.data, *tail))
+    return dict(r_minus_1=r, per_param=per, status=status[:, 0].copy(), column=status[:, 1].copy(), used=used)
+
+
+def chain_conv_dev(segs, seg_sys, nsys, ncols, iw, itheta, ndim, ws, ws_bytes, stream=0):
+    """mce_chain_conv_dev: the Gelman-Rubin R-1 of ``nsys`` systems of segments that are on the device -> dict(r_minus_1 [nsys],
+    per_param [nsys, ndim], status [nsys], column [nsys], used [nsys]); ``segs``: [(device address, rows)], ``seg_sys``: the system of each"""
+    return _chain_conv(load().mce_chain_conv_dev, segs, seg_sys, nsys, ncols, iw, itheta, ndim, (ws or None, int(ws_bytes), stream or None))
+
+
+def chain_conv(arrays, seg_sys, nsys, iw, itheta, ndim, device=0):
+    """mce_chain_conv_f64: the same from HOST arrays (one 2-D fp64 array per segment), uploaded by the library"""
+    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+    if not arrays or any(a.ndim != 2 or a.shape[1] != arrays[0].shape[1] for a in arrays):
+        raise ValueError("segments must be 2-D arrays of one column count")
+    segs = [(a.ctypes.data if a.shape[0] else 0, a.shape[0]) for a in arrays]
+    return _chain_conv(load().mce_chain_conv_f64, segs, seg_sys, nsys, arrays[0].shape[1], iw, itheta, ndim, (int(device),))
 
 
 # ---------------------------------------------------------------------------

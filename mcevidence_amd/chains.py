@@ -297,6 +297,163 @@ def correlation_length(parts, iw=0, itheta=2, ndim=None, min_corr=CORR_MIN, max_
 
 
 # ---------------------------------------------------------------------------
+# converge: the Gelman-Rubin R-1 of the chains (docs/design/chain_conv.md; csrc/chain_conv.hpp has the same rule)
+# ---------------------------------------------------------------------------
+CONV_OK, CONV_CONSTANT, CONV_NOT_FINITE, CONV_NOT_POSITIVE, CONV_FEW_SEGMENTS = 0, 2, 3, 4, 5
+CONV_MAX_SEGMENTS = 128
+CONV_MAX_DIM = 127
+CONV_BY = ("auto", "chains", "halves")
+CONV_PD_TOL = 64.0 * 2.0 ** -52                 # Wn is positive definite when its smallest eigenvalue is > CONV_PD_TOL * ndim
+
+
+def converge_spec(converge, converge_by="auto"):
+    """What ``converge`` / ``converge_by`` ask for -- None / False: off (returns None); True: measure only, ``(None, by)``; a number
+    > 0: the threshold, ``(threshold, by)``."""
+    if converge is None or converge is False:
+        return None
+    if converge_by not in CONV_BY:
+        raise ValueError("converge_by must be one of %s (got %r)" % (", ".join(repr(b) for b in CONV_BY), converge_by))
+    if converge is True:
+        return None, converge_by
+    threshold = float(converge)
+    if not (threshold > 0.0 and np.isfinite(threshold)):
+        raise ValueError("converge must be True or a threshold > 0 (got %r)" % (converge,))
+    return threshold, converge_by
+
+
+def conv_segments(nrows, by="auto"):
+    """The segments of parts of ``nrows`` rows each -> (the ``by`` taken, [(part, first row, rows)]): ``"chains"`` one per part,
+    ``"halves"`` rows ``[0, n // 2)`` and ``[n // 2, n)`` of every part, ``"auto"`` chains when at least two parts have rows, otherwise
+    halves.  More than CONV_MAX_SEGMENTS segments, or fewer than two with rows, is a ValueError."""
+    nrows = [int(n) for n in nrows]
+    if by not in CONV_BY:
+        raise ValueError("converge_by must be one of %s (got %r)" % (", ".join(repr(b) for b in CONV_BY), by))
+    if by == "auto":
+        by = "chains" if sum(1 for n in nrows if n > 0) >= 2 else "halves"
+    if by == "chains":
+        segs = [(p, 0, n) for p, n in enumerate(nrows)]
+    else:
+        segs = [(p, f, m) for p, n in enumerate(nrows) for f, m in ((0, n // 2), (n // 2, n - n // 2))]
+    if len(segs) > CONV_MAX_SEGMENTS:
+        raise ValueError("converge: %d segments (at most %d: %d chains by halves)" % (len(segs), CONV_MAX_SEGMENTS, CONV_MAX_SEGMENTS // 2))
+    if sum(1 for _, _, m in segs if m > 0) < 2:
+        raise conv_status_error(CONV_FEW_SEGMENTS, -1)
+    return by, segs
+
+
+def conv_status_error(status, column):
+    """the ValueError of a measurement that did not end well, in the words every route uses"""
+    if status == CONV_FEW_SEGMENTS:
+        return ValueError("converge: fewer than 2 segments with rows and weight; use converge_by=\"halves\", or give more rows")
+    if status == CONV_CONSTANT:
+        return ValueError("converge: parameter column %d is constant within the chains (its variance is not > 0); leave it out with ndim" % column)
+    if status == CONV_NOT_FINITE and column < 0:
+        return ValueError("converge: a weight is negative or not finite")
+    return ValueError("converge: a value that is not finite in parameter column %d" % column)
+
+
+def conv_info(res, by, segments, rows, threshold=None, log=None):
+    """``info["converge"]`` from one system's measurement (``r_minus_1``, ``per_param``, ``status``, ``column``, ``used``); raises for
+    the statuses 2, 3 and 5; status 4 (the within-chain correlation matrix is not positive definite) and a threshold exceeded are
+    logged as WARNINGs."""
+    log = log or logger
+    status = int(res["status"])
+    if status not in (CONV_OK, CONV_NOT_POSITIVE):
+        raise conv_status_error(status, int(res["column"]))
+    per = [float(x) for x in res["per_param"]]
+    r = float(res["r_minus_1"]) if status == CONV_OK else float("nan")
+    worst = int(np.argmax(per))
+    out = {"r_minus_1": r, "per_param": per, "worst_param": worst, "by": by, "segments": int(res["used"]),
+           "segments_skipped": int(segments) - int(res["used"]), "rows": int(rows), "threshold": threshold, "converged": None, "status": status}
+    if status == CONV_NOT_POSITIVE:
+        log.warning("converge: the within-chain correlation matrix is not positive definite (fewer independent rows than parameters, or "
+                    "linearly dependent columns): R-1 is not defined; the largest per-parameter value is %.4g (parameter %d)" % (per[worst], worst))
+    if threshold is not None:
+        out["converged"] = bool(r <= threshold)          # (NaN: False)
+        if not out["converged"]:
+            log.warning("converge: R-1 = %.4g exceeds the threshold %g (worst parameter %d: %.4g); the chains have not converged and ln E "
+                        "is not to be trusted" % (r, threshold, worst, per[worst]))
+    return out
+
+
+def conv_line(c):
+    """``info["converge"]`` in one line, as the command line prints it before the ln(B) lines"""
+    j = c["worst_param"]
+    tail = "" if c["converged"] is None else "; threshold %g: %s" % (c["threshold"], "converged" if c["converged"] else "NOT converged")
+    return "R-1 = %.6g (worst parameter %d: %.6g) by %s over %d segments%s" % (c["r_minus_1"], j, c["per_param"][j], c["by"], c["segments"], tail)
+
+
+def _conv_measure(segs, iw, itheta, nd):
+    """the rule on one system's segments (2-D arrays) -> dict(r_minus_1, per_param, status, column, used)"""
+    out = dict(r_minus_1=float("nan"), per_param=np.full(nd, np.nan), status=CONV_OK, column=-1, used=0)
+    w = [s[:, iw] for s in segs]
+    x = [s[:, itheta:itheta + nd] for s in segs]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        W = np.array([float(np.sum(v)) for v in w])
+        use = [k for k in range(len(segs)) if len(w[k]) > 0 and W[k] > 0.0]
+        out["used"] = M = len(use)
+        if any(not np.all((v >= 0) & np.isfinite(v)) for v in w):
+            out.update(status=CONV_NOT_FINITE, column=-1)
+            return out
+        bad = np.nonzero(np.any([~np.all(np.isfinite(v), axis=0) for v in x if len(v)], axis=0))[0]
+        if len(bad):
+            out.update(status=CONV_NOT_FINITE, column=int(bad[0]))
+            return out
+        if M < 2:
+            out.update(status=CONV_FEW_SEGMENTS)
+            return out
+        c = np.sum([w[k] @ x[k] for k in range(len(segs))], axis=0) / np.sum(W)                    # step 1
+        a = np.array([(w[k] @ (x[k] - c)) / W[k] for k in use])                                   # step 2
+        Wu = W[use]
+        o = (Wu @ a) / np.sum(Wu)                                                                 # step 3
+        delta = a - o
+        Wc = np.zeros((nd, nd))
+        for m, k in enumerate(use):                                                               # steps 4, 5
+            y = (x[k] - c) - a[m]
+            Wc += ((y * w[k][:, None]).T @ y) / W[k]
+        Wc /= M
+        diag = np.diag(Wc).copy()
+        flat = np.nonzero(~(diag > 0))[0]
+        if len(flat):
+            out.update(status=CONV_CONSTANT, column=int(flat[0]))
+            return out
+        sigma = np.sqrt(diag)                                                                     # step 6
+        out["per_param"] = np.sum(delta * delta, axis=0) / (M - 1) / diag
+        Wn = Wc / np.outer(sigma, sigma)                                                          # step 7
+        Wn = 0.5 * (Wn + Wn.T)
+        np.fill_diagonal(Wn, 1.0)
+        lam, U = np.linalg.eigh(Wn)
+        if not (np.all(np.isfinite(lam)) and lam[0] > CONV_PD_TOL * nd):
+            out.update(status=CONV_NOT_POSITIVE, column=0)
+            return out
+        v = ((delta / sigma) @ U) / np.sqrt(lam)                                                  # step 8
+        T = (v.T @ v) / (M - 1)
+        out["r_minus_1"] = float(np.linalg.eigvalsh(T + np.eye(nd))[-1] - 1.0)
+    return out
+
+
+def gelman_rubin(parts, iw=0, itheta=2, ndim=None, by="auto", threshold=None):
+    """The Gelman-Rubin statistic "R-1" of burned chains ``parts`` (2-D arrays, one per chain, not concatenated), in NumPy: the
+    variance of the segment means over the mean of the segment variances in the worst direction of parameter space, segments counting
+    equally (GetDist's ``getGelmanRubin``).  The RAW weights of column ``iw`` weigh the columns ``itheta .. itheta + ndim`` (``ndim=None``:
+    all; at most 127).  ``by``: ``conv_segments``.  A segment without rows or of total weight 0 is skipped.  Returns what
+    ``info["converge"]`` holds: dict(r_minus_1, per_param, worst_param, by, segments, segments_skipped, rows, threshold, converged,
+    status).  A constant column, a value that is not finite, a bad weight or fewer than two segments is a ValueError
+    (``conv_status_error``); a within-chain correlation matrix that is not positive definite gives ``r_minus_1 = nan``, status 4 and
+    a warning."""
+    parts = [np.asarray(p, dtype=np.float64) for p in parts]
+    if not parts or any(p.ndim != 2 or p.shape[1] != parts[0].shape[1] for p in parts):
+        raise ValueError("chains must be 2-D arrays of one column count")
+    nparam = parts[0].shape[1] - itheta
+    nd = nparam if ndim is None else min(int(ndim), nparam)
+    if nd < 1 or nd > CONV_MAX_DIM:
+        raise ValueError("converge: ndim=%r (1 .. %d expected)" % (nd, CONV_MAX_DIM))
+    by, table = conv_segments([p.shape[0] for p in parts], by)
+    res = _conv_measure([parts[p][f:f + m] for p, f, m in table], iw, itheta, nd)
+    return conv_info(res, by, len(table), sum(p.shape[0] for p in parts), threshold)
+
+
+# ---------------------------------------------------------------------------
 class MCSamples(object):
     """Container for one or more MCMC chains.
 
@@ -306,6 +463,9 @@ class MCSamples(object):
     kwargs      : iw, ilike, itheta, log_level, burnlen, thinlen, idchain, idpattern; thin_corr (None / False: off, True: scale 1,
                   a number > 0: the scale), corr_min, corr_max_lag, ndim: files are thinned by ``ceil(scale * L)``, L their measured
                   autocorrelation length over the first ``ndim`` parameters (``correlation_length``); the result is ``thin_corr_info``.
+                  converge (None / False: off, True: measure, a number > 0: a threshold), converge_by ("auto", "chains", "halves"):
+                  the Gelman-Rubin R-1 of the burned, unthinned chains over the first ``ndim`` parameters (``gelman_rubin``) -- files
+                  and arrays alike, a single array by halves; the result is ``converge_info``.
     """
 
     def __init__(self, str_or_dict, trueval=None, debug=False, csplit=None, names=None, labels=None,
@@ -325,6 +485,9 @@ class MCSamples(object):
         self.logger = logger
         self.chains = None
         self.thin_corr_info = None
+        self.converge_info = None
+        self._converge = converge_spec(kwargs.pop("converge", None), kwargs.pop("converge_by", "auto"))
+        self._converge_ndim = kwargs.get("ndim")
 
         if isinstance(str_or_dict, str):
             self.logger.info("Loading chain from " + str_or_dict)
@@ -380,6 +543,9 @@ class MCSamples(object):
         self.nchains = len(self.chains)
         if burnlen > 0:
             self.chains = [self.removeBurn(burnlen, chain=c) for c in self.chains]
+        if self._converge is not None:                      # the burned, unthinned chains, whatever the thinning
+            self.converge_info = gelman_rubin(self.chains, self.iw, self.itheta, self._converge_ndim, self._converge[1], self._converge[0])
+            self.logger.debug(conv_line(self.converge_info))
         if scale is not None:
             thinlen = self.measure_thin(scale, kwargs.pop("ndim", None), kwargs.pop("corr_min", CORR_MIN), kwargs.pop("corr_max_lag", CORR_MAX_LAG))
         self.chain_offsets = np.cumsum([0] + [c.shape[0] for c in self.chains])

@@ -35,6 +35,11 @@ def build_parser(prog=None):
     p.add_argument("--thin-corr", dest="thin_corr", nargs="?", const=True, default=None, type=float, metavar="SCALE",
                    help="thin by SCALE (default 1) times the measured autocorrelation length of the chains instead of a given --thin; "
                         "write it after root_name, or as --thin-corr=SCALE: directly in front of root_name it would take the root for SCALE")
+    p.add_argument("--converge", dest="converge", nargs="?", const=True, default=None, type=float, metavar="THRESHOLD",
+                   help="measure the Gelman-Rubin R-1 of the burned chains and print it before the ln(B) lines; with THRESHOLD, warn when R-1 "
+                        "exceeds it.  Write it after root_name, or as --converge=THRESHOLD")
+    p.add_argument("--converge-by", dest="converge_by", default="auto", choices=("auto", "chains", "halves"),
+                   help="the segments R-1 compares: whole chains, halves of every chain, or (auto) chains when there are at least two")
     p.add_argument("-vb", "--verbose", dest="verbose", default=1, type=int, help="0: WARNINGS, 1: INFO, 2: DEBUG")
     p.add_argument("-pv", "--pvolume", dest="priorvolume", default=None, type=float,
                    help="prior volume to use; if *.ranges exists the volume estimated from it is used")
@@ -69,6 +74,18 @@ def _thin_kw(args):
     return {} if args.thin_corr is None else {"thin_corr": args.thin_corr}
 
 
+def _converge_kw(args):
+    """--converge / --converge-by, where the first was given"""
+    return {} if args.converge is None else {"converge": args.converge, "converge_by": args.converge_by}
+
+
+def _print_converge(info):
+    """the R-1 line, before the ln(B) lines"""
+    from .chains import conv_line
+    if (info or {}).get("converge"):
+        print(conv_line(info["converge"]))
+
+
 def farm_main(args):
     """``--farm``: every root of the list file, each with the ndim and the prior volume a single run would compute for it"""
     import copy
@@ -85,10 +102,14 @@ def farm_main(args):
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
     outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
-                                    idchain=args.idchain, split=args.cross, **_thin_kw(args), **_backend_kw(args))
-    for r, mle in zip(roots, outs):
+                                    idchain=args.idchain, split=args.cross, info=args.converge is not None, **_thin_kw(args), **_converge_kw(args),
+                                    **_backend_kw(args))
+    infos = [o[1] for o in outs] if args.converge is not None else [None] * len(outs)
+    outs = [o[0] for o in outs] if args.converge is not None else outs
+    for r, mle, inf in zip(roots, outs, infos):
         print()
         print("Using file: ", r)
+        _print_converge(inf)
         for k in range(1, len(mle) + 1):
             print("   ln(B)[k={}] = {}".format(k, mle[k - 1]))
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
@@ -115,13 +136,14 @@ def main(argv=None):
     if args.resident:
         from .resident import evidence_from_files
         out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
-                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, **_thin_kw(args), **_backend_kw(args))
+                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_backend_kw(args))
         print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
         print("")
         return out
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
-                     thinlen=args.thinlen, **_thin_kw(args), **_backend_kw(args))
+                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_backend_kw(args))
+    _print_converge(getattr(mce, "info", None))
     if args.jackknife is not None:
         if args.resident or args.farm:
             raise ValueError("--jackknife with --resident / --farm is not supported")

@@ -211,6 +211,9 @@ class MCEvidence(object):
         priorvolume prior volume; burnlen/thinlen as in the reference (files only)
         thin_corr   (with corr_min, corr_max_lag; files only) thin by the chains' measured autocorrelation length times this
                     scale (True: 1) instead of a given thinlen: chains.correlation_length; reported in info["thin_corr"]
+        converge    (with converge_by) None / False: off; True: measure the Gelman-Rubin R-1 of the burned, unthinned chains over
+                    the first ndim parameters (chains.gelman_rubin); a number > 0: also compare it with this threshold and log a
+                    WARNING when it is exceeded (nothing is raised); reported in info["converge"]
         nbatch, brange, bscale   batched runs; only bscale='logpower' is supported
         """
         self.backend = gdkwargs.pop("backend", None) or HipBackend()
@@ -248,6 +251,8 @@ class MCEvidence(object):
         gdkwargs.setdefault("burnlen", burnlen)
         if gdkwargs.get("thin_corr") not in (None, False):
             gdkwargs.setdefault("ndim", ndim)              # thin_corr measures the columns the estimator uses
+        if gdkwargs.get("converge") not in (None, False):
+            gdkwargs.setdefault("ndim", ndim)              # and so does converge
         csplit = namedtuple("split_var", "split frac shuffle")(split=split, frac=s1frac, shuffle=shuffle)
         self.gd = MCSamples(method, csplit=csplit, debug=self.debug, **gdkwargs)
 
@@ -258,6 +263,8 @@ class MCEvidence(object):
 
         if self.gd.thin_corr_info is not None:
             self.info["thin_corr"] = self.gd.thin_corr_info
+        if self.gd.converge_info is not None:
+            self.info["converge"] = self.gd.converge_info
         self.info["NparamsMC"] = self.gd.nparamMC
         self.info["Nsamples_read"] = self.gd.get_shape()[0]
         self.info["Nparams_read"] = self.gd.get_shape()[1]

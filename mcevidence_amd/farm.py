@@ -193,12 +193,12 @@ def read_files(paths, device=0, wave_bytes=None):
 
 
 class _Root(object):
-    __slots__ = ("index", "files", "lens", "size", "ndim", "pvol", "burn", "thin", "parts", "ncols", "nrows", "nparam", "nd", "rc", "keep", "problem", "scal")
+    __slots__ = ("index", "files", "lens", "size", "ndim", "pvol", "burn", "thin", "parts", "ncols", "nrows", "nparam", "nd", "rc", "keep", "problem", "scal", "conv")
 
 
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
-                             require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None):
+                             require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto"):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -210,7 +210,10 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     Under an initialised process group the whole call goes to ``evidence_many`` over ``MCEvidence`` objects.  A failing root raises
     what the host route raises for it (the first in input order), or sits in its slot with ``return_exceptions=True``; it never
     changes another root's result.  ``thin_corr`` (one value or one per root; with ``corr_min``, ``corr_max_lag``): such a root is thinned
-    by its measured autocorrelation length on the per-root resident route.  Without a GPU: ``RuntimeError``."""
+    by its measured autocorrelation length on the per-root resident route.  ``converge`` (one value or one per root; with
+    ``converge_by``): the Gelman-Rubin R-1 of every such root's burned, unthinned chains, in ``info["converge"]`` -- ONE
+    ``mce_chain_conv_dev`` call per wave and per (columns, ndim) group covers the unthinned roots of the wave; a thinned or a
+    ``thin_corr`` root is measured on its per-root route.  Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
     roots = list(roots)
@@ -221,11 +224,13 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     thins = _per_root(thinlen, n, "thinlen")
     tcorr = _per_root(thin_corr, n, "thin_corr")
     corr_kw = {k: v for k, v in (("corr_min", corr_min), ("corr_max_lag", corr_max_lag)) if v is not None}
+    convs = _per_root(converge, n, "converge")
+    conv_kw = [{} if c in (None, False) else {"converge": c, "converge_by": converge_by} for c in convs]
     common = dict(kmax=kmax, idchain=idchain, idpattern=idpattern, iw=iw, ilike=ilike, itheta=itheta)
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **extra)
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **extra)
                 for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
@@ -250,8 +255,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             reason = "split: the random split is drawn per root on the host"
         if reason == _res.RESIDENT:
             try:
-                reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i])
-            except ValueError as e:                # (thin_corr together with thinlen)
+                reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i],
+                                   converge=convs[i], converge_by=converge_by)
+            except ValueError as e:                # (thin_corr together with thinlen; a converge value no route takes)
                 fail(i, e)
                 continue
         if reason == _res.RESIDENT and _res._chains.thin_corr_scale(tcorr[i]) is not None:
@@ -265,6 +271,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             r.lens = [os.stat(p).st_size for p in r.files]
             r.size = farm_layout(r.lens)[1]
             r.ndim, r.pvol, r.burn, r.thin, r.rc, r.keep, r.problem, r.scal = ndims[i], pvols[i], burns[i], thins[i], None, None, None, None
+            r.conv = _res._chains.converge_spec(convs[i], converge_by)          # None, or (threshold, by); afterwards: info["converge"]
             todo.append(r)
         except Exception as e:                     # (no files, an unreadable path: what the host route raises too)
             fail(i, e)
@@ -310,8 +317,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                         # integer or bin thinning: the per-root calls, on views of the wave's buffer
                         tensors = [d_out[int(f.tok_base):int(f.tok_base) + nr * nc].view(nr, nc) if nr else torch.empty((0, 1), dtype=torch.float64, device=dev)
                                    for f, (nr, nc) in zip(ff, shapes)]
-                        r.rc = _res.ResidentChains(tensors, r.burn, r.thin, iw, ilike, itheta, device)
+                        r.rc = _res.ResidentChains(tensors, r.burn, r.thin, iw, ilike, itheta, device, ndim=r.ndim, **conv_kw[r.index])
                         r.nrows = r.rc.nrows
+                        r.conv = r.rc.converge
                     else:
                         r.parts = []
                         for f, (nr, nc) in zip(ff, shapes):
@@ -328,6 +336,32 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                     fallback[r.index] = d.reason
                 except Exception as e:
                     fail(r.index, e)
+
+            # ---- converge: the unthinned roots of the wave, one call per (columns, ndim) group -----------------------------------------
+            groups = {}
+            for r in plain:
+                if r.rc is None and r.conv is not None:
+                    groups.setdefault((r.ncols, r.nd), []).append(r)
+            for (nc, nd), members in sorted(groups.items()):
+                systems, took = [], []
+                for r in members:
+                    try:
+                        if nd > _res._chains.CONV_MAX_DIM:
+                            raise ValueError("converge: ndim=%r (1 .. %d expected)" % (nd, _res._chains.CONV_MAX_DIM))
+                        by, segs = _res.conv_device_segments(r.parts, nc, r.conv[1])
+                        systems.append(segs)
+                        took.append((r, by))
+                    except Exception as e:
+                        fail(r.index, e)
+                        plain.remove(r)
+                if not took:
+                    continue
+                for (r, by), res, segs in zip(took, _res.conv_measure_dev(systems, nc, iw, itheta, nd, device, stream.cuda_stream), systems):
+                    try:
+                        r.conv = _res._chains.conv_info(res, by, len(segs), r.nrows, r.conv[0])
+                    except Exception as e:
+                        fail(r.index, e)
+                        plain.remove(r)
 
             # ---- preparation: one set of launches for the unthinned roots, the per-root calls for the thinned ones ---------------
             ready = []
@@ -390,7 +424,10 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                             fail(r.index, e)
                             continue
                         counts["farm"] += 1
-                        results[r.index] = out if not info else (out, _res.route_info(FARM, r.nparam, r.nd, n1, [n1]))
+                        inf = _res.route_info(FARM, r.nparam, r.nd, n1, [n1])
+                        if r.conv is not None:
+                            inf["converge"] = r.conv
+                        results[r.index] = out if not info else (out, inf)
             ms["feed"] += _res._ms(t0)
             for r in wroots:
                 r.rc = r.keep = r.parts = None
@@ -403,6 +440,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             kw = dict(common, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], pos_lnp=pos_lnp, split=split, info=True, verbose=0)
             if tcorr[i] not in (None, False):
                 kw.update(corr_kw, thin_corr=tcorr[i])
+            kw.update(conv_kw[i])
             if covtype != "all":
                 kw["covtype"] = covtype
             if backend is not None:

@@ -65,14 +65,17 @@ class ResidentDecline(Exception):
 
 
 def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all", split=False, ndim=None, nparam=None,
-         distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None):
+         distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None, converge=None, converge_by="auto"):
     """``"resident"`` or the reason why the route declines.  A pure function of the call's keywords and of what is known
     about the data at the time (``ncols``: the files' column counts, ``nrows``: rows left after burn-in / thinning,
     ``nparam``: parameter columns; None: not known yet).  ``thin_corr`` (thinning by the measured autocorrelation length) is resident
-    work and declines nothing; together with a ``thinlen`` other than 0 it is the ValueError every route raises."""
+    work and declines nothing; together with a ``thinlen`` other than 0 it is the ValueError every route raises.  ``converge`` /
+    ``converge_by`` (the Gelman-Rubin R-1 of the burned chains) are resident work too and decline nothing; a value they cannot take
+    is the ValueError every route raises."""
     if not ischain:
         return REASONS["ischain"]
     _chains.thin_corr_scale(thin_corr, thinlen)
+    _chains.converge_spec(converge, converge_by)
     if thinlen < 0:
         return REASONS["negative_thinlen"]
     if 0 < thinlen < 1:
@@ -173,6 +176,29 @@ def mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, log_prior_volume, cross):
     return mle
 
 
+def conv_device_segments(parts, ncols, by):
+    """the segments of burned parts ``[(device address, rows)]`` -> (the ``by`` taken, [(device address, rows)]): a half is a segment
+    whose address is offset (chains.conv_segments)"""
+    by, table = _chains.conv_segments([n for _, n in parts], by)
+    return by, [((parts[p][0] + f * int(ncols) * 8) if m > 0 else 0, m) for p, f, m in table]
+
+
+def conv_measure_dev(systems, ncols, iw, itheta, nd, device, stream):
+    """ONE ``mce_chain_conv_dev`` call for ``systems`` (a list of segment lists ``[(device address, rows)]`` of one ``ncols`` and
+    ``nd``) -> one result dict per system (``chains.conv_info`` takes it)"""
+    import torch
+    from . import _capi
+    segs = [sg for sy in systems for sg in sy]
+    seg_sys = [y for y, sy in enumerate(systems) for _ in sy]
+    wsb = _capi.chain_conv_workspace_bytes(sum(n for _, n in segs), len(segs), len(systems), nd)
+    if wsb == 0:
+        raise ValueError("converge: ndim=%r (1 .. %d expected)" % (nd, _chains.CONV_MAX_DIM))
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda:%d" % int(device))
+    res = _capi.chain_conv_dev(segs, seg_sys, len(systems), ncols, iw, itheta, nd, ws.data_ptr(), wsb, stream)
+    return [dict(r_minus_1=res["r_minus_1"][y], per_param=res["per_param"][y], status=res["status"][y], column=res["column"][y], used=res["used"][y])
+            for y in range(len(systems))]
+
+
 def route_info(route, nparam, nd, nread, nsample):
     """the info dict of ``MCEvidence.evidence(info=True)`` for a route that kept the chain on the device"""
     return {"NparamsMC": nparam, "Nsamples_read": nread, "Nparams_read": nparam, "NparamsCosmo": nd,
@@ -187,10 +213,12 @@ class ResidentChains(object):
     ``to_host()``: the array ``MCSamples(...).samples`` holds; ``stats``: reader statistics per file and milliseconds per
     stage.  ``thin_corr`` (None / False, True or a scale > 0; with ``corr_min``, ``corr_max_lag`` and the estimator's ``ndim``) thins by
     the autocorrelation length measured on the device (``mce_chain_corr_dev``) instead of a given ``thinlen``; ``thin_corr`` holds what
-    was found.  Raises ``ResidentDecline`` where the route does not apply, ``RuntimeError`` without a GPU."""
+    was found.  ``converge`` (None / False, True or a threshold > 0; with ``converge_by`` and ``ndim``) measures the Gelman-Rubin R-1 of
+    the burned, unthinned parts on the device (``mce_chain_conv_dev``); ``converge`` then holds what ``info["converge"]`` reports.
+    Raises ``ResidentDecline`` where the route does not apply, ``RuntimeError`` without a GPU."""
 
     def __init__(self, tensors, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, device=0, reader_stats=None, thin_corr=None,
-                 corr_min=_chains.CORR_MIN, corr_max_lag=_chains.CORR_MAX_LAG, ndim=None):
+                 corr_min=_chains.CORR_MIN, corr_max_lag=_chains.CORR_MAX_LAG, ndim=None, converge=None, converge_by="auto"):
         import torch
         self._torch = torch
         self.device = int(device)
@@ -201,6 +229,8 @@ class ResidentChains(object):
             raise ValueError("the chains array is empty")
         scale = _chains.thin_corr_scale(thin_corr, thinlen)
         self.thin_corr = None
+        spec = _chains.converge_spec(converge, converge_by)
+        self.converge = None
         reason = plan(thinlen=thinlen, ncols=[t.shape[1] for t in tensors], distributed=_distributed())
         if reason != RESIDENT:
             raise ResidentDecline(reason)
@@ -222,6 +252,10 @@ class ResidentChains(object):
         if self.nburned < 1:                              # (nothing to select from; fewer than 2 rows decline in evidence())
             raise ResidentDecline(REASONS["rows"])
         t0 = time.perf_counter()
+        if spec is not None:
+            self._converge(spec, ndim)
+            self.stats["ms"]["converge"] = _ms(t0)
+            t0 = time.perf_counter()
         if scale is not None:
             thinlen = self._measure(scale, ndim, corr_min, corr_max_lag)
             self.stats["ms"]["corr"] = _ms(t0)
@@ -254,7 +288,7 @@ class ResidentChains(object):
     def from_files(cls, root_or_paths, burnlen=0, thinlen=0, iw=0, ilike=1, itheta=2, idchain=0, idpattern="_?.txt", device=0,
                    **corr):
         """Chain text files parsed on the device and left there; the files are those ``MCSamples.load_from_file`` reads.  ``corr``:
-        thin_corr, corr_min, corr_max_lag, ndim."""
+        thin_corr, corr_min, corr_max_lag, ndim, converge, converge_by."""
         import mmap
         from . import _capi, chain_io
         _capi.require_device()
@@ -290,7 +324,7 @@ class ResidentChains(object):
                     out = torch.empty((0, 1), dtype=torch.float64, device="cuda:%d" % int(device))
                 tensors.append(out)
             self = cls(tensors, burnlen, thinlen, iw, ilike, itheta, device, reader_stats=stats, **corr)
-        self.stats["ms"]["read"] = _ms(t0) - self.stats["ms"]["select"] - self.stats["ms"].get("corr", 0.0)
+        self.stats["ms"]["read"] = _ms(t0) - self.stats["ms"]["select"] - self.stats["ms"].get("corr", 0.0) - self.stats["ms"].get("converge", 0.0)
         return self
 
     def _stream(self):
@@ -318,6 +352,16 @@ class ResidentChains(object):
         logger.info("thin_corr: autocorrelation length %.3f %s units (cap %d) -> thinning factor %d"
                     % (self.thin_corr["length"], self.thin_corr["units"], res["cap"], self.thin_corr["factor"]))
         return float(self.thin_corr["factor"])
+
+    def _converge(self, spec, ndim):
+        """converge: the Gelman-Rubin R-1 of the burned, unthinned parts, measured on the device"""
+        nd = effective_ndim(ndim, self.nparam)
+        if nd > _chains.CONV_MAX_DIM:
+            raise ResidentDecline(REASONS["ndim"])
+        by, segs = conv_device_segments(self._parts, self.ncols, spec[1])
+        res, = conv_measure_dev([segs], self.ncols, self.iw, self.itheta, nd, self.device, self._stream())
+        self.converge = _chains.conv_info(res, by, len(segs), self.nburned, spec[0])
+        logger.info(_chains.conv_line(self.converge))
 
     def _select(self, thinlen):
         from . import _capi
@@ -454,6 +498,8 @@ class ResidentChains(object):
         inf = route_info(RESIDENT, self.nparam, nd, self.nrows if split_rows is not None else n1, [n1, n2] if cross else [n1])
         if self.thin_corr is not None:
             inf["thin_corr"] = self.thin_corr
+        if self.converge is not None:
+            inf["converge"] = self.converge
         return out, inf
 
 
@@ -478,7 +524,8 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     if reason == RESIDENT:
         reason = plan(thinlen=ctor.get("thinlen", 0.0), isfunc=ctor.get("isfunc"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1),
                       verbose=max(ctor.get("verbose", 1), 2 if ctor.get("debug") else 0), covtype=covtype, split=split, ndim=None,
-                      distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"))
+                      distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"),
+                      converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"))
     if reason == RESIDENT:
         level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
         if not logging.getLogger().handlers:
@@ -490,7 +537,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
                                            ilike=ctor.get("ilike", 1), itheta=ctor.get("itheta", 2), idchain=ctor.get("idchain", 0),
                                            idpattern=ctor.get("idpattern", "_?.txt"), thin_corr=ctor.get("thin_corr"),
                                            corr_min=ctor.get("corr_min", _chains.CORR_MIN), corr_max_lag=ctor.get("corr_max_lag", _chains.CORR_MAX_LAG),
-                                           ndim=ctor.get("ndim"))
+                                           ndim=ctor.get("ndim"), converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"))
             pv = call.get("pvolume")
             got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,

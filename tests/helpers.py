@@ -664,3 +664,220 @@ def knn_certificate(X, Y, K, dist, idx, self_mode, self_offset=0, kernel=None, o
                                "%d ambiguous rows); kernel: %s\n  %s" % (len(report["failed_rows"]), nq, nq, nr, D, K, self_mode, self_offset,
                                                                      report["ambiguous"], kernel, "\n  ".join(lines)), report)
     return report
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Sum certificate: the evidence sums dotp[k] = sum_q sign(w_q) exp(lnC_D + D ln r_qk - ln |w_q| + fs_q) of the fused and
+# partitioned entry points (mce_knn_dotp_*), judged against np.longdouble on inputs where EVERY row counts.  w and fs are free
+# inputs: equalised_inputs() sets fs_q = -D ln od[q, col] + u_q, u_q in (-1, 0], so that every term of column `col` is of order 1
+# (C_D / w e^u) whatever the data's dynamic range -- one wrong neighbour on one row then moves the sum by a share of 1 / n, not by
+# a share of nothing.  Plain NumPy on the host, nothing shared with the library.
+#
+# T_k = sum_bound(): the tolerance on column k, derived from the kernel's arithmetic (reduce_kernels.hpp), u = 2^-53, not measured:
+#   * the squared distance: the refined (merge_lists_kernel: one fma chain over the D squared differences) or filter-exact d^2 is
+#     within 2B relative, B = (D/2 + 2) u as derived above cert_bound for its square root (without the root's halving and rounding).
+#   * the exponent a = lnC - ln |w| + fs + (D/2) ln d^2 (`base + 0.5 * D * log(d2)`):  ln (d^2 (1 + 2B)) moves by 2B, times D/2: D B.
+#     log |w| is off by L_log u |ln |w||, log d^2 by L_log u |ln d^2| (times D/2; 0.5 * D is exact); `lnc - log|w|` rounds once
+#     (u (|lnC| + |ln |w||)), `+ fs` once (u (|lnC| + |ln |w|| + |fs|)), the product `0.5 D * log d2` once (u (D/2) |ln d^2|), the
+#     last addition once (u |a|).  With amax = max over the rows of |lnC| + |ln |w|| + |fs| + (D/2) |ln d^2| -- the SUM of the
+#     magnitudes, not |a|: the equalised fs cancels against the volume term -- the four roundings stay below 3 u amax and the two
+#     logarithms below L_log u amax:  |delta a| <= D B + (L_log + 3) u amax.
+#     lnC itself comes from the host (capi_search.hpp ln_unit_ball: 0.5 d log(pi) - lgamma(1 + d/2) in double): a product and a
+#     logarithm of 1 ulp, glibc's stated 4 ulp on lgamma, one subtraction -- below 5 u ((D/2) ln pi + |ln Gamma(1 + D/2)|), added to
+#     delta a (the truth takes lnC from exact factorials in np.longdouble).
+#   * the term t = sign(w) exp(a) is therefore within  delta a (1 + delta a) + L_exp u  relative.
+#   * the summation: a fixed tree, in which a term passes through 6 additions of wave_sum and 4 of block_sum in the merge (or
+#     dotp_partial_kernel), at most ceil(blocks / 256) = ceil(n / 65536) additions of the strided pass of dotp_final_kernel and 10
+#     more of its block_sum, then the host's addition of the W parts: every partial sum is bounded by A_k = sum_q |t_qk|, so the
+#     tree adds at most (ceil(n / 65536) + 20 + W) u A_k (n: the query rows of the call; a part's launch covers fewer).
+#   * the unfused dotp_partial_kernel takes D ln r from r = sqrt(d^2): one more rounding of r, times D (`unfused=True`; the d^2
+#     term stays: the distances it is given are an exact search's, within B).
+#   T_k = [delta a (1 + delta a) + L_exp u + (ceil(n / 65536) + 20 + W) u] A_k (1 + 2^-20)
+# L_log, L_exp: the ulp errors of the device's double log and exp.  No document shipped with the ROCm installation states them
+# (searched: share/doc, share/html); SUM_LOG_ULP = SUM_EXP_ULP = 2 is taken, twice the 1 ulp the HIP math reference is believed to
+# state.  The choice is not delicate: the effects to be seen are >= 1e-10 A_k, the bound comes out at 1e-14 ... 1e-12 A_k.
+#
+# A row is BLIND when taking its next neighbour instead (od[q, c] -> od[q, c + 1] at the equalised column c) changes that
+# column's sum by more than 0 and at most 2 T: a result within T of a sum that is wrong by that much passes.  Exact ties
+# (change == 0) are not blind: either row is a valid answer.  Counted on the oracle alone before the library is called; a case with
+# more than AMBIGUOUS_CAP of its rows blind is refused.
+# --------------------------------------------------------------------------------------------------------------------
+SUM_LOG_ULP = 2.0
+SUM_EXP_ULP = 2.0
+_LD = np.longdouble
+_LD_PI = 4 * np.arctan(_LD(1))
+
+
+def ln_unit_ball_ld(D):
+    """ln (pi^(D/2) / Gamma(1 + D/2)) in np.longdouble; Gamma from its recurrence down to Gamma(1) = 1 or Gamma(1/2) = sqrt(pi)"""
+    x, lg = _LD(D) / 2, _LD(0)
+    while x > 0:
+        lg += np.log(x)
+        x -= 1
+    if D % 2:
+        lg += np.log(_LD_PI) / 2
+    return _LD(D) / 2 * np.log(_LD_PI) - lg
+
+
+def exact_distances(X, Y, oi):
+    """np.longdouble distances from X[q] to the rows Y[oi[q, :]] (the oracle's rows; its own fp64 distances are rounded)"""
+    X = np.asarray(X, dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    out = np.empty(oi.shape, dtype=_LD)
+    step = max(1, (1 << 21) // max(1, oi.shape[1] * X.shape[1]))
+    for s in range(0, len(X), step):
+        diff = X[s:s + step, None, :].astype(_LD) - Y[oi[s:s + step]].astype(_LD)
+        out[s:s + step] = np.sqrt((diff * diff).sum(-1))
+    return out
+
+
+def _ln_terms(od, w, fs, D):
+    """(ln |t| [nq, cols] in np.longdouble, -inf where the term is exactly 0; sign(w) [nq, 1])"""
+    od = np.asarray(od, dtype=_LD)
+    w = np.asarray(w, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ln = ln_unit_ball_ld(D) + _LD(D) * np.log(od) - np.log(np.abs(w.astype(_LD)))[:, None] + np.asarray(fs, dtype=_LD)[:, None]
+    ln[(od == 0) | np.isneginf(np.asarray(fs, dtype=np.float64))[:, None]] = -np.inf
+    return ln, np.where(w < 0, _LD(-1), _LD(1))[:, None]
+
+
+def equalised_inputs(od, D, col, rng):
+    """(w, fs) for the oracle's distances od[nq, >= col + 1]: w from the integers 1 .. 5, fs_q = -D ln od[q, col] + u_q with
+    u_q in (-1, 0] (fs_q = u_q where od[q, col] == 0); three rows dealt by rng get fs = -inf, three others a negative weight."""
+    od = np.asarray(od, dtype=_LD)
+    nq = od.shape[0]
+    w = rng.integers(1, 6, nq).astype(np.float64)
+    u = -rng.random(nq)
+    r = od[:, col]
+    with np.errstate(divide="ignore"):
+        fs = np.where(r > 0, -_LD(D) * np.log(np.where(r > 0, r, _LD(1))), _LD(0)) + u
+    fs = np.asarray(fs, dtype=np.float64)
+    special = rng.permutation(nq)[:6]
+    fs[special[:3]] = -np.inf
+    w[special[3:]] *= -1.0
+    return w, fs
+
+
+def sum_truth(od, w, fs, D, k0, kmax):
+    """(S, A): S[k] = sum_q t_qk and A[k] = sum_q |t_qk| for k0 <= k < kmax (0 below k0), t = sign(w) exp(lnC_D + D ln r - ln |w| + fs)
+    in np.longdouble in the log domain; od[:, k - k0] is the distance of reference column k (further columns are ignored)."""
+    ln, sgn = _ln_terms(np.asarray(od)[:, :kmax - k0], w, fs, D)
+    t = np.exp(ln)
+    S, A = np.zeros(kmax, dtype=_LD), np.zeros(kmax, dtype=_LD)
+    S[k0:] = (sgn * t).sum(axis=0)
+    A[k0:] = t.sum(axis=0)
+    return S, A
+
+
+def sum_amax(od, w, fs, D, k0, kmax):
+    """the largest |lnC| + |ln |w|| + |fs| + D |ln r| over the terms that are not exactly 0 (0.0 if there is none)"""
+    od = np.asarray(od, dtype=_LD)[:, :kmax - k0]
+    fs = np.asarray(fs, dtype=np.float64)
+    live = (od > 0) & np.isfinite(fs)[:, None]
+    if not live.any():
+        return 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = (abs(ln_unit_ball_ld(D)) + np.abs(np.log(np.abs(np.asarray(w, dtype=_LD))))[:, None] + np.abs(fs.astype(_LD))[:, None]
+             + _LD(D) * np.abs(np.log(np.where(live, od, _LD(1)))))
+    return float(np.max(np.where(live, m, 0)))
+
+
+def sum_bound(D, n, A, amax, W=1, unfused=False):
+    """T[k]: the tolerance on |S_hat[k] - S[k]| (derivation above); n: query rows, W: parts added on the host"""
+    u = 2.0 ** -53
+    B = cert_bound(D)
+    lnpi_half = 0.5 * D * math.log(math.pi)
+    da = D * B + (SUM_LOG_ULP + 3.0) * u * amax + 5.0 * u * (lnpi_half + abs(math.lgamma(1.0 + 0.5 * D)))
+    if unfused:
+        da += D * u
+    rel = da * (1.0 + da) + SUM_EXP_ULP * u + (math.ceil(n / 65536.0) + 20 + W) * u
+    return np.asarray(A, dtype=_LD) * _LD(rel * (1.0 + 2.0 ** -20))
+
+
+def blind_rows(od, w, fs, D, c, T):
+    """mask of the rows whose next neighbour at list column c (od[q, c] -> od[q, c + 1]) changes the column's sum by more than 0
+    and at most 2 T (T: sum_bound of that column); rows without a next neighbour are not blind"""
+    od = np.asarray(od, dtype=_LD)
+    if od.shape[1] <= c + 1:
+        return np.zeros(od.shape[0], dtype=bool)
+    ln, _ = _ln_terms(od[:, c:c + 2], w, fs, D)
+    t = np.exp(ln)
+    eff = np.abs(t[:, 1] - t[:, 0])
+    return (eff > 0) & (eff <= 2 * _LD(T))
+
+
+def sum_oracle(od, D, k0, kmax, first, rng, n=None, W=1, unfused=False):
+    """The oracle's side of the sum certificate, before the library is called.  od: np.longdouble distances, kmax - k0 + 1 columns
+    (fewer where the set ends).  first: equalise the FIRST list column (a wrong nearest neighbour seen with the power the last
+    column gives a wrong K-th) -- unless a term of another column would then overflow, which falls back to the last.
+    -> dict(w, fs, S, A, T, amax, col (list column equalised), blind (rows), rows); raises ValueError above AMBIGUOUS_CAP."""
+    od = np.asarray(od, dtype=_LD)
+    nq, K = od.shape[0], kmax - k0
+    state = rng.bit_generator.state
+    for c in ((0, K - 1) if first else (K - 1,)):
+        rng.bit_generator.state = state
+        w, fs = equalised_inputs(od, D, c, rng)
+        ln, _ = _ln_terms(od[:, :K], w, fs, D)
+        if c == K - 1 or float(ln.max()) < 700.0:
+            break
+    S, A = sum_truth(od, w, fs, D, k0, kmax)
+    amax = sum_amax(od, w, fs, D, k0, kmax)
+    T = sum_bound(D, nq if n is None else n, A, amax, W=W, unfused=unfused)
+    blind = blind_rows(od, w, fs, D, c, T[k0 + c])
+    if int(blind.sum()) > AMBIGUOUS_CAP * nq:
+        raise ValueError("%d of %d rows are blind to the sum certificate (cap %g of the rows): first rows %s" % (
+            int(blind.sum()), nq, AMBIGUOUS_CAP, np.flatnonzero(blind)[:5].tolist()))
+    return dict(w=w, fs=fs, S=S, A=A, T=T, amax=amax, col=c, blind=int(blind.sum()), blind_rows=np.flatnonzero(blind), rows=nq)
+
+
+def sum_certificate(S_hat, S, A, T, k0, what=""):
+    """|S_hat[k] - S[k]| <= T[k] for k >= k0, S_hat[k] == 0 exactly where A[k] == 0 and for k < k0, every entry finite.
+    Returns the largest |S_hat - S| / T over the columns with T > 0 (0.0 if none)."""
+    S_hat = np.asarray(S_hat)
+    assert S_hat.dtype == np.float64 and S_hat.shape == np.shape(S), (S_hat.dtype, S_hat.shape)
+    assert np.all(np.isfinite(S_hat)), "sum certificate: not finite: %s %s" % (S_hat.tolist(), what)
+    assert np.all(S_hat[:k0] == 0.0), "sum certificate: columns below k0 = %d not 0: %s %s" % (k0, S_hat[:k0].tolist(), what)
+    err = np.abs(S_hat.astype(_LD) - S)
+    worst = 0.0
+    for k in range(k0, len(S_hat)):
+        if A[k] == 0:
+            assert S_hat[k] == 0.0, "sum certificate: column %d must be exactly 0 (every term is), got %r %s" % (k, S_hat[k], what)
+            continue
+        assert err[k] <= T[k], "sum certificate: column %d: |S_hat - S| = %.3g > T = %.3g (%.3g T; S = %.17g, S_hat = %.17g, A = %.6g) %s" % (
+            k, float(err[k]), float(T[k]), float(err[k] / T[k]), float(S[k]), S_hat[k], float(A[k]), what)
+        worst = max(worst, float(err[k] / T[k]))
+    return worst
+
+
+def kd_partition_shares(capi, Yd, n, d, kmax, W, wd, fd, ws, wsb):
+    """The distributed k-d preparation of a pruned auto-evidence search on W ranks, run one after the other on this GPU with the
+    exchange emulated (tests/test_gpu_parity.py::test_distributed_kd_preparation_is_the_single_gpu_order): every rank's
+    mce_prune_part_prepare_dev, the all-reduce(SUM) of the permutation arrays, then per rank its share with the replicated
+    preparation (mce_knn_dotp_part_f64_dev), the summed permutation copied back, and its share on that shared order
+    (mce_knn_dotp_part_prepared_f64_dev).  Yd, wd, fd, ws: torch tensors on the device.
+    -> dict(ranges [(off, cnt, lo, hi)], perms, total, single, replicated [W arrays], prepared [W arrays])"""
+    import torch
+    ranges, perms = [], []
+    for r in range(W):
+        off, cnt, lo, hi = capi.prune_part_prepare_dev(Yd.data_ptr(), n, d, kmax, r, W, ws.data_ptr(), wsb, 0, want_range=True)
+        torch.cuda.synchronize()
+        ranges.append((off, cnt, lo, hi))
+        perms.append(ws[off:off + 4 * cnt].view(torch.int32).clone())
+    total = torch.stack(perms).sum(dim=0)
+    # reference order: the replicated preparation
+    ref = torch.zeros(kmax, dtype=torch.float64, device="cuda")
+    capi.knn_dotp_part_dev(Yd.data_ptr(), n, d, kmax, 0, W, wd.data_ptr(), fd.data_ptr(), ref.data_ptr(), ws.data_ptr(), wsb, 0)
+    torch.cuda.synchronize()
+    single = ws[off:off + 4 * cnt].view(torch.int32).clone()
+    replicated, prepared = [], []
+    for r in range(W):
+        rep = torch.zeros(kmax, dtype=torch.float64, device="cuda")
+        capi.knn_dotp_part_dev(Yd.data_ptr(), n, d, kmax, r, W, wd.data_ptr(), fd.data_ptr(), rep.data_ptr(), ws.data_ptr(), wsb, 0)
+        torch.cuda.synchronize()
+        ws[off:off + 4 * cnt].view(torch.int32).copy_(total)            # what the all-reduce hands every rank
+        got = torch.zeros(kmax, dtype=torch.float64, device="cuda")
+        capi.knn_dotp_part_prepared_dev(Yd.data_ptr(), n, d, kmax, r, W, wd.data_ptr(), fd.data_ptr(), got.data_ptr(), ws.data_ptr(), wsb, 0)
+        torch.cuda.synchronize()
+        replicated.append(rep)
+        prepared.append(got)
+    return dict(ranges=ranges, perms=perms, total=total, single=single, replicated=replicated, prepared=prepared)

@@ -6,7 +6,7 @@ import math
 import numpy as np
 import pytest
 
-from helpers import ADVERSARIAL, DIST_RTOL, LNE_TOL, OracleBackend, build_mce, chain_of, load_golden, orc
+from helpers import ADVERSARIAL, DIST_RTOL, LNE_TOL, OracleBackend, build_mce, chain_of, kd_partition_shares, load_golden, orc
 
 pytestmark = pytest.mark.gpu
 logging.disable(logging.CRITICAL)
@@ -1696,33 +1696,23 @@ def test_distributed_kd_preparation_is_the_single_gpu_order(prune_modes, n, d, k
         for W in (2, 4, 8):
             assert capi.prune_part_applies(n, d, kmax, W)
             # the single-GPU permutation: what the plain call above left in the workspace (same plan, same offset)
-            perms, segs = [], []
+            kd = kd_partition_shares(capi, Yd, n, d, kmax, W, w, fs, ws, wsb)          # (prepare / sum / copy back: tests/helpers.py)
+            perms, segs = kd["perms"], []
             for r in range(W):
-                off, cnt, lo, hi = capi.prune_part_prepare_dev(Yd.data_ptr(), n, d, kmax, r, W, ws.data_ptr(), wsb, 0, want_range=True)
-                torch.cuda.synchronize()
+                off, cnt, lo, hi = kd["ranges"][r]
                 assert cnt > 0 and cnt % 2048 == 0 and lo % 2048 == 0 and 0 <= lo < hi <= cnt
-                pr = ws[off:off + 4 * cnt].view(torch.int32).clone()
+                pr = perms[r]
                 assert int(torch.count_nonzero(pr[:lo])) == 0 and int(torch.count_nonzero(pr[hi:])) == 0        # zeros outside the own range
                 segs.append((lo, hi))
-                perms.append(pr)
-            total = torch.stack(perms).sum(dim=0)
+            total = kd["total"]
             assert segs[0][0] == 0 and segs[-1][1] == cnt and all(a[1] == b[0] for a, b in zip(segs[:-1], segs[1:]))      # rank order, tiling the array
             # reference order: the replicated preparation
-            ref = torch.zeros(kmax, dtype=torch.float64, device="cuda")
-            capi.knn_dotp_part_dev(Yd.data_ptr(), n, d, kmax, 0, W, w.data_ptr(), fs.data_ptr(), ref.data_ptr(), ws.data_ptr(), wsb, 0)
-            torch.cuda.synchronize()
-            single = ws[off:off + 4 * cnt].view(torch.int32).clone()
+            single = kd["single"]
             assert torch.equal(total, single)                        # bit for bit the single-GPU order
             assert int((single >= 0).sum()) == n and set(single[single >= 0].cpu().numpy().tolist()) == set(range(n))
             acc = np.zeros(kmax)
             for r in range(W):
-                rep = torch.zeros(kmax, dtype=torch.float64, device="cuda")
-                capi.knn_dotp_part_dev(Yd.data_ptr(), n, d, kmax, r, W, w.data_ptr(), fs.data_ptr(), rep.data_ptr(), ws.data_ptr(), wsb, 0)
-                torch.cuda.synchronize()
-                ws[off:off + 4 * cnt].view(torch.int32).copy_(total)            # what the all-reduce hands every rank
-                got = torch.zeros(kmax, dtype=torch.float64, device="cuda")
-                capi.knn_dotp_part_prepared_dev(Yd.data_ptr(), n, d, kmax, r, W, w.data_ptr(), fs.data_ptr(), got.data_ptr(), ws.data_ptr(), wsb, 0)
-                torch.cuda.synchronize()
+                rep, got = kd["replicated"][r], kd["prepared"][r]
                 assert torch.equal(got, rep), (W, r)
                 acc += got.cpu().numpy()
             assert np.allclose(acc[1:], one.cpu().numpy()[1:], rtol=1e-12, atol=0), W

@@ -518,6 +518,28 @@ int mce_chain_conv_dev(const mce_chain_part* segs, const int32_t* seg_sys, int32
 int mce_chain_conv_f64(const mce_chain_part* segs, const int32_t* seg_sys, int32_t nseg, int32_t nsys, int64_t ncols, int32_t iw, int32_t itheta,
                        int32_t ndim, double* r_minus_1, double* per_param, int32_t* status, int32_t* nseg_used, int32_t device);
 
+/* The weighted moments of the likelihood column behind information= (<ln L>_P, the Bayesian model dimensionality 2 Var_P(ln L), N_eff),
+ * for MANY systems (the ready roots of a farm wave) in one call.  The rule is stated in csrc/like_moments.hpp and
+ * docs/design/information.md.  A system is one segment: fs[n] = logL - logLmax and w[n], the weights, of the s1 partition the estimator
+ * sums over; a row with w == 0 is skipped and its fs never read into a sum.  out (HOST, MCE_MOMENTS_OUT doubles per system) =
+ * {W = sum w, c = sum w fs / W, v = sum w (fs - c)^2 / W about the computed c, A2 = sum w^2, rows used, status}; status 0 ok, 3 a weight
+ * that is not finite or a used row whose fs is not finite (-inf included), 5 W is not > 0 (a segment without a used row included); where
+ * the status is not 0 the four values are NaN, and that system fails alone.  A system's bits depend on its own rows alone, not on its
+ * neighbours, its position or the call; fp64, sums in a fixed order, no atomics: two runs give the same bits.  Four launches whatever
+ * nseg is, all on the caller's stream, which is synchronised once, on return.  Segments and workspace
+ * (mce_like_moments_workspace_bytes(rows of all segments, nseg)) are the caller's.  mce_like_moments_f64 takes HOST segments, uploads
+ * them to `device` and calls the device form.  Argument errors: MCE_ERR_INVALID (no device needed); no visible device:
+ * MCE_ERR_NO_DEVICE. */
+#define MCE_MOMENTS_OUT 6
+typedef struct mce_moments_seg {
+    const double* fs;
+    const double* w;
+    int64_t n;
+} mce_moments_seg;
+size_t mce_like_moments_workspace_bytes(int64_t nrows_total, int32_t nseg);
+int mce_like_moments_dev(const mce_moments_seg* segs, int32_t nseg, double* out, void* ws, size_t ws_bytes, void* stream);
+int mce_like_moments_f64(const mce_moments_seg* segs, int32_t nseg, double* out, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

@@ -168,6 +168,20 @@ SIGNATURES["mce_jack_dotp_dev"] = (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P
 SIGNATURES["mce_jack_dotp_f64"] = (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P, _P, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P,
                                               _P, _P, _P, _P, _c.c_int32])
 
+
+
+class MomentsSeg(ctypes.Structure):
+    """``mce_moments_seg``: one system of ``mce_like_moments_*`` -- the addresses of its fs and w columns, its rows."""
+    _fields_ = [("fs", _P), ("w", _P), ("n", _c.c_int64)]
+
+
+MCE_MOMENTS_OUT = 6
+MOMENTS_FIELDS = ("W", "c", "v", "A2", "rows", "status")
+MOMENTS_OK, MOMENTS_NOT_FINITE, MOMENTS_NO_WEIGHT = 0, 3, 5
+SIGNATURES["mce_like_moments_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32])
+SIGNATURES["mce_like_moments_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_like_moments_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
+
 _lib = None
 
 
@@ -604,6 +618,33 @@ def chain_conv(arrays, seg_sys, nsys, iw, itheta, ndim, device=0):
         raise ValueError("segments must be 2-D arrays of one column count")
     segs = [(a.ctypes.data if a.shape[0] else 0, a.shape[0]) for a in arrays]
     return _chain_conv(load().mce_chain_conv_f64, segs, seg_sys, nsys, arrays[0].shape[1], iw, itheta, ndim, (int(device),))
+
+
+def like_moments_workspace_bytes(nrows_total, nseg):
+    return int(load().mce_like_moments_workspace_bytes(int(nrows_total), int(nseg)))
+
+
+def _like_moments(call, segs, tail):
+    arr = (MomentsSeg * max(len(segs), 1))()
+    for i, (fs, w, n) in enumerate(segs):
+        arr[i].fs, arr[i].w, arr[i].n = fs or None, w or None, int(n)
+    out = np.full((max(len(segs), 1), MCE_MOMENTS_OUT), np.nan)
+    check(call(_c.cast(arr, _P), len(segs), out.ctypes.data, *tail))
+    return out[:len(segs)]
+
+
+def like_moments_dev(segs, ws, ws_bytes, stream=0):
+    """mce_like_moments_dev: the weighted moments of the likelihood column of ``len(segs)`` systems that are on the device -> float64
+    [nseg, 6]: ``MOMENTS_FIELDS`` per system; ``segs``: [(device address of fs, device address of w, rows)]"""
+    return _like_moments(load().mce_like_moments_dev, segs, (ws or None, int(ws_bytes), stream or None))
+
+
+def like_moments(systems, device=0):
+    """mce_like_moments_f64: the same from HOST arrays, ``systems`` = [(fs, w)], uploaded by the library"""
+    keep = [(np.ascontiguousarray(f, dtype=np.float64).reshape(-1), np.ascontiguousarray(w, dtype=np.float64).reshape(-1)) for f, w in systems]
+    if any(f.shape != w.shape for f, w in keep):
+        raise ValueError("like moments: fs and w of one length expected")
+    return _like_moments(load().mce_like_moments_f64, [(f.ctypes.data if f.size else 0, w.ctypes.data if w.size else 0, f.size) for f, w in keep], (int(device),))
 
 
 # ---------------------------------------------------------------------------

@@ -58,7 +58,23 @@ def build_parser(prog=None):
                         "(conservative, not a calibrated 1 sigma); write it after root_name, or as --jackknife=G")
     p.add_argument("--jackknife-by", dest="jackknife_by", choices=("blocks", "chains"), default="blocks",
                    help="the groups: contiguous blocks of the burned / thinned chain, or one group per chain file")
+    p.add_argument("--information", dest="information", action="store_true",
+                   help="print <ln L>, the Bayesian model dimensionality d, N_eff and D_KL[k] = <ln L> - ln(B)[k] before the ln(B) lines "
+                        "(with --jackknife: each with +- sigma); D_KL is relative to the flat prior over the given volume")
     return p
+
+
+def _information_kw(args):
+    """--information, where it was given"""
+    return {"information": True} if args.information else {}
+
+
+def _print_information(info):
+    """the information lines, before the ln(B) lines"""
+    from .information import lines
+    if (info or {}).get("information"):
+        for line in lines(info["information"]):
+            print(line)
 
 
 def _backend_kw(args):
@@ -101,15 +117,17 @@ def farm_main(args):
         ndims.append(a.ndim)
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
+    want_info = args.converge is not None or args.information
     outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
-                                    idchain=args.idchain, split=args.cross, info=args.converge is not None, **_thin_kw(args), **_converge_kw(args),
-                                    **_backend_kw(args))
-    infos = [o[1] for o in outs] if args.converge is not None else [None] * len(outs)
-    outs = [o[0] for o in outs] if args.converge is not None else outs
+                                    idchain=args.idchain, split=args.cross, info=want_info, **_thin_kw(args), **_converge_kw(args),
+                                    **_information_kw(args), **_backend_kw(args))
+    infos = [o[1] for o in outs] if want_info else [None] * len(outs)
+    outs = [o[0] for o in outs] if want_info else outs
     for r, mle, inf in zip(roots, outs, infos):
         print()
         print("Using file: ", r)
         _print_converge(inf)
+        _print_information(inf)
         for k in range(1, len(mle) + 1):
             print("   ln(B)[k={}] = {}".format(k, mle[k - 1]))
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
@@ -136,13 +154,13 @@ def main(argv=None):
     if args.resident:
         from .resident import evidence_from_files
         out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
-                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_backend_kw(args))
+                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_backend_kw(args))
         print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
         print("")
         return out
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
-                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_backend_kw(args))
+                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_backend_kw(args))
     _print_converge(getattr(mce, "info", None))
     if args.jackknife is not None:
         if args.resident or args.farm:
@@ -150,6 +168,7 @@ def main(argv=None):
         mce.jackknife = {"groups": args.jackknife, "by": args.jackknife_by}
         out = mce.evidence()
         jk = mce.info["jackknife"]
+        _print_information(mce.info)
         for k in range(1, len(jk["lnE"]) + 1):
             print("   ln(B)[k={}] = {} \u00b1 {}".format(k, jk["lnE"][k - 1], jk["sigma"][k - 1]))
         print("* \u00b1: delete-a-group jackknife over {} {} (conservative, not a calibrated 1 sigma).".format(jk["groups"], jk["by"]))

@@ -27,6 +27,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import information as _information
 from .chains import MCSamples, rank0_draw
 from .resident import mle_from_sums
 
@@ -201,7 +202,8 @@ class MCEvidence(object):
         (they are not forwarded to the chain reader): ``backend`` -- an object with a
         ``knn_dotp`` method; default ``HipBackend()`` -- and ``jackknife`` -- None, True, a number of
         groups or a dict of ``evidence_jackknife``'s keywords: ``evidence()`` then also stores the jackknife
-        error bars in ``info["jackknife"]``.
+        error bars in ``info["jackknife"]`` -- and ``information`` -- None or True: ``evidence()`` then also stores <ln L>_P, D_KL and the
+        Bayesian model dimensionality in ``info["information"]`` (information.py; docs/design/information.md).
 
         method      chain root name / file name(s), or list/tuple/dict of chain arrays
                     (columns: weight, -lnL, parameters...)
@@ -220,6 +222,10 @@ class MCEvidence(object):
         # jackknife error bars with every evidence() call (docs/design/jackknife.md): None (off), True (16 blocks), a number of blocks,
         # or a dict of evidence_jackknife's keywords; evidence() keeps the reference's signature, so the switch lives here
         self.jackknife = gdkwargs.pop("jackknife", None)
+        # <ln L>_P, D_KL and the model dimensionality with every evidence() call (docs/design/information.md): None (off: nothing
+        # changes) or True; consumed here for the same reason
+        self.information = gdkwargs.pop("information", None)
+        _information.refuse(self.information, brange=brange, nbatch=nbatch, isfunc=isfunc)
         self.logger = logger
         self.verbose = verbose
         self.debug = bool(debug or verbose > 1)
@@ -442,7 +448,28 @@ class MCEvidence(object):
         dotp, logLmax, jac = got
         return np.stack([self._feed_finish((S, logLmax[b]), dotp[b], jac[b], logPriorVolume) for b, S in enumerate(sizes)])
 
-    def _report(self, MLE, verbose, info):
+    def _fill_information(self, MLE, pos_lnp):
+        """``info["information"]`` of this call (the constructor's ``information`` keyword; unset: nothing happens): the rule of
+        information.py on s1's weights and fs, on the host -- under a process group every rank computes its own, no collective"""
+        if not _information.wanted(self.information):
+            return
+        _information.refuse(self.information, brange=self.brange, nbatch=self.nbatch)
+        _, lnp, _ = self.gd.arrays("s1")
+        logL = np.asarray(-lnp if pos_lnp else lnp, dtype=np.float64)
+        logLmax = np.amax(logL)
+        a, fs = self.gd.data["s1"].adjusted_weights, logL - logLmax
+        inf = _information.build(_information.moments(a, fs), logLmax, MLE)
+        jk = self.info.get("jackknife") if _information.wanted(self.jackknife) else None
+        if jk is not None:
+            from .jackknife import group_ids
+            _information.with_jackknife(inf, a, fs, group_ids(self.gd, "s1", jk["groups"], jk["by"]), logLmax, jk)
+        self.info["information"] = inf
+
+    def _report(self, MLE, verbose, info, pos_lnp=False):
+        self._fill_information(MLE, pos_lnp)
+        if verbose > 0 and "information" in self.info and _information.wanted(self.information):
+            for line in _information.lines(self.info["information"]):
+                self.logger.info(line)
         if verbose > 0:
             for k in range(1, self.kmax):
                 self.logger.info("   ln(B)[k={}] = {}".format(k, MLE[k - 1] if self.brange is None else MLE[:, k - 1]))
@@ -457,7 +484,8 @@ class MCEvidence(object):
         dict if ``info=True``).  ``nproc``/``profile``/``prewhiten`` are accepted for
         signature compatibility (the reference ignores the last two as well).
         With ``self.jackknife`` set (the constructor's ``jackknife`` keyword; None: nothing changes) the result of
-        ``evidence_jackknife`` is stored in ``info["jackknife"]``; what is returned is what is always returned."""
+        ``evidence_jackknife`` is stored in ``info["jackknife"]``; with ``self.information`` set (the ``information`` keyword) <ln L>_P,
+        D_KL and the model dimensionality are stored in ``info["information"]``; what is returned is what is always returned."""
         jackknife = self.jackknife
         if jackknife is not None and jackknife is not False:
             kw = dict(jackknife) if isinstance(jackknife, dict) else ({} if jackknife is True else {"groups": int(jackknife)})
@@ -477,13 +505,13 @@ class MCEvidence(object):
         if self._feed_route_applies(verbose, covtype) and hasattr(self.backend, "evidence_feed"):
             out = self._evidence_device_feeders(covtype, pos_lnp, logPriorVolume)
             if out is not None:
-                return self._report(out[1:], verbose, info)
+                return self._report(out[1:], verbose, info, pos_lnp)
 
         # ---- batch-feed route: the convergence batches (brange / nbatch) in one library call (opt-in: HipBackend(batch_feed=True)) ----
         if self._batch_route_applies(verbose, rand, covtype):
             out = self._evidence_batch_feed(covtype, pos_lnp, logPriorVolume)
             if out is not None:
-                return self._report(out[:, 1:], verbose, info)
+                return self._report(out[:, 1:], verbose, info, pos_lnp)
 
         if covtype == "all":
             covstat = self.get_covariance()
@@ -534,7 +562,7 @@ class MCEvidence(object):
                         k, S, dotp[k], medvol, amax, MLE[ipow, k]))
 
         MLE = MLE[0, 1:] if self.brange is None else MLE[:, 1:]
-        return self._report(MLE, verbose, info)
+        return self._report(MLE, verbose, info, pos_lnp)
 
 
 def _evidence_jackknife(self, groups=16, by="blocks", covtype="all", pvolume=None, pos_lnp=False):
@@ -581,7 +609,7 @@ def evidence_many(mces, verbose=None, info=False, covtype="all", pvolume=None, p
             m = mces[i]
             lpv = math.log(m.priorvolume if pvols[i] is None else pvols[i])
             v = m.verbose if verbose is None else verbose
-            results[i] = m._report(m._feed_finish(ctx, dotp, jac, lpv)[1:], v, info)
+            results[i] = m._report(m._feed_finish(ctx, dotp, jac, lpv)[1:], v, info, pos_lnp)
     for i, m in enumerate(mces):
         if results[i] is None:
             results[i] = m.evidence(verbose=verbose, info=info, covtype=covtype, pvolume=pvols[i], pos_lnp=pos_lnp, **kwargs)

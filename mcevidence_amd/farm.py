@@ -19,6 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from . import information as _information
 from . import resident as _res
 
 logger = logging.getLogger("mcevidence_amd")
@@ -198,7 +199,8 @@ class _Root(object):
 
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
-                             require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto"):
+                             require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto",
+                             information=None):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -213,7 +215,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     by its measured autocorrelation length on the per-root resident route.  ``converge`` (one value or one per root; with
     ``converge_by``): the Gelman-Rubin R-1 of every such root's burned, unthinned chains, in ``info["converge"]`` -- ONE
     ``mce_chain_conv_dev`` call per wave and per (columns, ndim) group covers the unthinned roots of the wave; a thinned or a
-    ``thin_corr`` root is measured on its per-root route.  Without a GPU: ``RuntimeError``."""
+    ``thin_corr`` root is measured on its per-root route.  ``information`` (one value or one per root): <ln L>_P, D_KL and the model
+    dimensionality of every such root in ``info["information"]`` -- ONE ``mce_like_moments_dev`` call per wave over all its ready roots,
+    thinned and unthinned alike.  Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
     roots = list(roots)
@@ -226,11 +230,13 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     corr_kw = {k: v for k, v in (("corr_min", corr_min), ("corr_max_lag", corr_max_lag)) if v is not None}
     convs = _per_root(converge, n, "converge")
     conv_kw = [{} if c in (None, False) else {"converge": c, "converge_by": converge_by} for c in convs]
+    infos = _per_root(information, n, "information")
+    info_kw = [{"information": v} if _information.wanted(v) else {} for v in infos]      # (what a root takes with it to another route)
     common = dict(kmax=kmax, idchain=idchain, idpattern=idpattern, iw=iw, ilike=ilike, itheta=itheta)
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **extra)
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **extra)
                 for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
@@ -404,6 +410,10 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             # ---- feed: every root of the wave in one library call -----------------------------------------------------------------
             t0 = time.perf_counter()
             if ready:
+                # information: the ready roots that ask for it, thinned and unthinned alike, in one call (problem: .., n1 at 1, w at 9, fs at 10)
+                asked = [r for r in ready if _information.wanted(infos[r.index])]
+                moms = dict(zip((r.index for r in asked),
+                                _res.moments_measure_dev([(r.problem[10], r.problem[9], r.problem[1]) for r in asked], device, stream.cuda_stream))) if asked else {}
                 with backend._scoped():
                     got = _capi.evidence_feed_batch_dev([r.problem for r in ready], device=device, return_exceptions=True)
                     for r, g in zip(ready, got):
@@ -427,6 +437,8 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                         inf = _res.route_info(FARM, r.nparam, r.nd, n1, [n1])
                         if r.conv is not None:
                             inf["converge"] = r.conv
+                        if r.index in moms:
+                            inf["information"] = _information.build(moms[r.index], r.scal[0], out)
                         results[r.index] = out if not info else (out, inf)
             ms["feed"] += _res._ms(t0)
             for r in wroots:
@@ -441,6 +453,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             if tcorr[i] not in (None, False):
                 kw.update(corr_kw, thin_corr=tcorr[i])
             kw.update(conv_kw[i])
+            kw.update(info_kw[i])
             if covtype != "all":
                 kw["covtype"] = covtype
             if backend is not None:

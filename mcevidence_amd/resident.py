@@ -23,6 +23,7 @@ import time
 import numpy as np
 
 from . import chains as _chains
+from . import information as _information
 
 logger = logging.getLogger("mcevidence_amd")
 
@@ -199,6 +200,16 @@ def conv_measure_dev(systems, ncols, iw, itheta, nd, device, stream):
             for y in range(len(systems))]
 
 
+def moments_measure_dev(systems, device, stream):
+    """ONE ``mce_like_moments_dev`` call for ``systems`` = [(device address of fs, device address of w, rows)] -> one
+    ``information.moments`` dict per system"""
+    import torch
+    from . import _capi
+    wsb = _capi.like_moments_workspace_bytes(sum(n for _, _, n in systems), len(systems))
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
+    return [_information.from_block(b) for b in _capi.like_moments_dev(systems, ws.data_ptr(), wsb, stream)]
+
+
 def route_info(route, nparam, nd, nread, nsample):
     """the info dict of ``MCEvidence.evidence(info=True)`` for a route that kept the chain on the device"""
     return {"NparamsMC": nparam, "Nsamples_read": nread, "Nparams_read": nparam, "NparamsCosmo": nd,
@@ -231,6 +242,7 @@ class ResidentChains(object):
         self.thin_corr = None
         spec = _chains.converge_spec(converge, converge_by)
         self.converge = None
+        self.information = None                            # (what the last evidence(information=True) found)
         reason = plan(thinlen=thinlen, ncols=[t.shape[1] for t in tensors], distributed=_distributed())
         if reason != RESIDENT:
             raise ResidentDecline(reason)
@@ -448,11 +460,12 @@ class ResidentChains(object):
 
     # -- the estimator ---------------------------------------------------------------------------------------------------
     def evidence(self, kmax=5, ndim=None, priorvolume=1, covtype="all", pos_lnp=False, split=False, s1frac=0.5, split_rows=None,
-                 info=False, backend=None):
+                 info=False, backend=None, information=None):
         """ln E as ``MCEvidence(...).evidence(...)`` returns it (``MLE[1:]``, and the info dict if ``info=True``; it
         carries ``info["route"] = "resident"``).  ``split=True``: the reference's random split, drawn on the host with the
         call ``MCSamples.chain_split`` makes (same RNG consumption); ``split_rows=(s1, s2)``: ``set_split``.
-        ``backend``: a ``HipBackend`` whose ``recheck_rows`` applies to the search."""
+        ``backend``: a ``HipBackend`` whose ``recheck_rows`` applies to the search.  ``information`` (None or True): <ln L>_P, D_KL and
+        the model dimensionality in ``info["information"]``, from one ``mce_like_moments_dev`` call on the gathered weights and fs."""
         from . import _capi
         from .evidence import HipBackend
         backend = backend or HipBackend()
@@ -492,7 +505,13 @@ class ResidentChains(object):
                                                                self.nparam, nd, 0 if covtype == "all" else 1, kmax, s1["w"].data_ptr(), fs.data_ptr(),
                                                                0, 1, device=self.device, want_checksum=False)
             ms["feed"] = _ms(t0)
+            mom = None
+            if _information.wanted(information):
+                t0 = time.perf_counter()
+                mom, = moments_measure_dev([(fs.data_ptr(), s1["w"].data_ptr(), n1)], self.device, self._stream())
+                ms["information"] = _ms(t0)
         out = mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, math.log(priorvolume), cross)[1:]
+        self.information = None if mom is None else _information.build(mom, logLmax, out)
         if not info:
             return out
         inf = route_info(RESIDENT, self.nparam, nd, self.nrows if split_rows is not None else n1, [n1, n2] if cross else [n1])
@@ -500,7 +519,16 @@ class ResidentChains(object):
             inf["thin_corr"] = self.thin_corr
         if self.converge is not None:
             inf["converge"] = self.converge
+        if self.information is not None:
+            inf["information"] = self.information
         return out, inf
+
+
+def log_information(inf):
+    """the information lines, before the ln(B) lines"""
+    if (inf or {}).get("information"):
+        for line in _information.lines(inf["information"]):
+            logger.info(line)
 
 
 _EVIDENCE_KEYS = ("rand", "info", "profile", "pvolume", "pos_lnp", "nproc", "prewhiten")
@@ -520,6 +548,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     covtype = ctor.get("covtype", "all")               # (given: the call's covtype too; not given: evidence()'s default)
     covtype = "single" if covtype is None else covtype
     split = bool(ctor.get("split", False))
+    _information.refuse(ctor.get("information"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     reason = RESIDENT if _is_file_root(root) else REASONS["not_files"]
     if reason == RESIDENT:
         reason = plan(thinlen=ctor.get("thinlen", 0.0), isfunc=ctor.get("isfunc"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1),
@@ -541,9 +570,10 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
             pv = call.get("pvolume")
             got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,
-                              backend=ctor.get("backend"))
+                              backend=ctor.get("backend"), information=ctor.get("information"))
             mle, inf = got
             if ctor.get("verbose", 1) > 0:
+                log_information(inf)
                 for k in range(1, len(mle) + 1):
                     logger.info("   ln(B)[k={}] = {}".format(k, mle[k - 1]))
             return (mle, inf) if want_info else mle

@@ -494,6 +494,52 @@ int mce_jack_dotp_f64(const double* dist, const int64_t* idx, int64_t nq, int32_
                       int64_t nr, int32_t G, int32_t k0, int32_t kmax, int32_t d, const double* w, const double* fs, double* dotp_groups,
                       double* dotp_full, int64_t* short_rows, int64_t* nshort, int32_t device);
 
+/* The bookkeeping of the delete-a-group jackknife for chains that stay on the device (the resident route and the farm;
+ * docs/design/jackknife_resident.md; rule: csrc/jack_groups.hpp), for MANY systems (the asking roots of a farm wave) in one call.
+ *
+ * mce_jack_groups_dev: the group of every row.  Row i of a segment is sample row r = rows[i] (rows NULL: r = i) of a burned,
+ * concatenated, thinned sample of N rows.  by = MCE_JACK_BY_BLOCKS: out[i] = r * G / N in 64-bit integers.  by = MCE_JACK_BY_CHAINS:
+ * s = src[r] (src NULL: s = r) is the row's number in the burned, concatenated numbering and out[i] = the last part p with
+ * part_first[p] <= s; part_first is a HOST array of nparts == G non-decreasing first rows starting at 0 (an empty part shares its first
+ * row with the next one and is never the answer).  rows [n], src [N] and out [n] are DEVICE pointers.  An r outside [0, N) gives -1,
+ * which mce_jack_dotp_dev and mce_jack_leave_out_dev refuse.  One launch whatever nseg is; the stream is synchronised on return.
+ *
+ * mce_jack_leave_out_dev: one block of MCE_JACK_LEAVE_OUT doubles per slot of every system, packed in segment order: system s owns
+ * G_s + 1 consecutive blocks, slot 0 with nothing deleted and slot 1 + b with group b deleted, each taken over the rows with g != b:
+ * {rows (zero-weight rows count), SumW = sum w, and mce_like_moments_dev's block on that set: W, c, v about the slot's own computed c,
+ * A2, rows used, status}.  fs NULL: the six moment values are NaN and the status is -1.  Status 0 / 3 / 5 and NaN as in
+ * mce_like_moments_dev; a slot that fails does so alone.  Every sum is a sum of the set's own terms (additions only, never total -
+ * group), fp64, in an order the system's row count fixes: two runs give the same bits and a system's bits depend on its own rows
+ * alone.  Four launches whatever nseg is, all on the caller's stream, which is synchronised once, on return.  Segments and workspace
+ * (mce_jack_leave_out_workspace_bytes(rows of all segments, nseg, the largest G)) are the caller's.  mce_jack_leave_out_f64 takes HOST
+ * segments, uploads them to `device` and calls the device form.  Argument errors -- G outside 2 .. MCE_JACK_MAX_GROUPS, a group id
+ * outside [0, G) -- : MCE_ERR_INVALID; no visible device: MCE_ERR_NO_DEVICE. */
+#define MCE_JACK_LEAVE_OUT 8
+#define MCE_JACK_BY_BLOCKS 0
+#define MCE_JACK_BY_CHAINS 1
+typedef struct mce_jack_groups_seg {
+    const int64_t* rows;
+    const int64_t* src;
+    const int64_t* part_first;
+    int64_t nparts;
+    int64_t n;
+    int64_t N;
+    int32_t G;
+    int32_t by;
+    int32_t* out;
+} mce_jack_groups_seg;
+typedef struct mce_jack_leave_out_seg {
+    const double* w;
+    const double* fs;
+    const int32_t* g;
+    int64_t n;
+    int32_t G;
+} mce_jack_leave_out_seg;
+int mce_jack_groups_dev(const mce_jack_groups_seg* segs, int32_t nseg, void* stream);
+size_t mce_jack_leave_out_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t Gmax);
+int mce_jack_leave_out_dev(const mce_jack_leave_out_seg* segs, int32_t nseg, double* out, void* ws, size_t ws_bytes, void* stream);
+int mce_jack_leave_out_f64(const mce_jack_leave_out_seg* segs, int32_t nseg, double* out, int32_t device);
+
 /* The Gelman-Rubin statistic "R-1" of burned chains that are on the device, for MANY systems (the roots of a farm wave) in one call:
  * the variance of the chain means over the mean of the chain variances, in the worst direction of parameter space.  The rule is stated
  * in csrc/chain_conv.hpp and docs/design/chain_conv.md.  `segs` are runs of rows of `ncols` doubles (a whole chain, or a half of one: a

@@ -182,6 +182,25 @@ SIGNATURES["mce_like_moments_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c
 SIGNATURES["mce_like_moments_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_size_t, _P])
 SIGNATURES["mce_like_moments_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
 
+class JackGroupsSeg(ctypes.Structure):
+    """``mce_jack_groups_seg``: one system of ``mce_jack_groups_dev`` (rows / src / out: device addresses; part_first: a host array)."""
+    _fields_ = [("rows", _P), ("src", _P), ("part_first", _P), ("nparts", _c.c_int64), ("n", _c.c_int64), ("N", _c.c_int64), ("G", _c.c_int32),
+                ("by", _c.c_int32), ("out", _P)]
+
+
+class JackLeaveOutSeg(ctypes.Structure):
+    """``mce_jack_leave_out_seg``: one system of ``mce_jack_leave_out_*`` -- the addresses of its w, fs (or none) and group columns."""
+    _fields_ = [("w", _P), ("fs", _P), ("g", _P), ("n", _c.c_int64), ("G", _c.c_int32)]
+
+
+MCE_JACK_LEAVE_OUT = 8
+JACK_LEAVE_OUT_FIELDS = ("nrows", "SumW", "W", "c", "v", "A2", "rows", "status")
+JACK_BY = {"blocks": 0, "chains": 1}
+SIGNATURES["mce_jack_groups_dev"] = (_c.c_int, [_P, _c.c_int32, _P])
+SIGNATURES["mce_jack_leave_out_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_jack_leave_out_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_jack_leave_out_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
+
 _lib = None
 
 
@@ -645,6 +664,53 @@ def like_moments(systems, device=0):
     if any(f.shape != w.shape for f, w in keep):
         raise ValueError("like moments: fs and w of one length expected")
     return _like_moments(load().mce_like_moments_f64, [(f.ctypes.data if f.size else 0, w.ctypes.data if w.size else 0, f.size) for f, w in keep], (int(device),))
+
+
+def jack_groups_dev(segs, stream=0):
+    """mce_jack_groups_dev: the jackknife group of every row of ``len(segs)`` systems in one launch.  ``segs``: [(rows, src, part_first,
+    n, N, G, by, out)] with rows / src / out device addresses (rows, src: 0 for none), part_first a sequence of the parts' first rows
+    (``by="chains"``) or None, by "blocks" / "chains"; int32 [n] is written at ``out``"""
+    arr = (JackGroupsSeg * max(len(segs), 1))()
+    keep = []
+    for i, (rows, src, part_first, n, N, G, by, out) in enumerate(segs):
+        pf = np.ascontiguousarray([] if part_first is None else part_first, dtype=np.int64)
+        keep.append(pf)
+        arr[i].rows, arr[i].src, arr[i].part_first = rows or None, src or None, pf.ctypes.data if pf.size else None
+        arr[i].nparts, arr[i].n, arr[i].N, arr[i].G, arr[i].by, arr[i].out = int(pf.size), int(n), int(N), int(G), JACK_BY[by], out or None
+    check(load().mce_jack_groups_dev(_c.cast(arr, _P), len(segs), stream or None))
+
+
+def jack_leave_out_workspace_bytes(nrows_total, nseg, Gmax):
+    return int(load().mce_jack_leave_out_workspace_bytes(int(nrows_total), int(nseg), int(Gmax)))
+
+
+def _jack_leave_out(call, segs, tail):
+    arr = (JackLeaveOutSeg * max(len(segs), 1))()
+    for i, (w, fs, g, n, G) in enumerate(segs):
+        arr[i].w, arr[i].fs, arr[i].g, arr[i].n, arr[i].G = w or None, fs or None, g or None, int(n), int(G)
+    nslots = [int(G) + 1 if 0 <= int(G) <= MCE_JACK_MAX_GROUPS else 1 for _, _, _, _, G in segs]
+    out = np.full((max(sum(nslots), 1), MCE_JACK_LEAVE_OUT), np.nan)
+    check(call(_c.cast(arr, _P), len(segs), out.ctypes.data, *tail))
+    at = np.concatenate([[0], np.cumsum(nslots)]).astype(int)
+    return [out[at[i]:at[i + 1]].copy() for i in range(len(segs))]
+
+
+def jack_leave_out_dev(segs, ws, ws_bytes, stream=0):
+    """mce_jack_leave_out_dev: the leave-one-group-out blocks of ``len(segs)`` systems that are on the device -> one float64
+    [G + 1, 8] per system (``JACK_LEAVE_OUT_FIELDS``; row 0: nothing deleted, row 1 + b: group b deleted); ``segs``: [(device address
+    of w, of fs or 0, of the int32 groups, rows, G)]"""
+    return _jack_leave_out(load().mce_jack_leave_out_dev, segs, (ws or None, int(ws_bytes), stream or None))
+
+
+def jack_leave_out(systems, device=0):
+    """mce_jack_leave_out_f64: the same from HOST arrays, ``systems`` = [(w, fs or None, g, G)], uploaded by the library"""
+    keep = [(np.ascontiguousarray(w, dtype=np.float64).reshape(-1), None if f is None else np.ascontiguousarray(f, dtype=np.float64).reshape(-1),
+             np.ascontiguousarray(g, dtype=np.int32).reshape(-1), int(G)) for w, f, g, G in systems]
+    if any((f is not None and f.shape != w.shape) or g.shape != w.shape for w, f, g, _ in keep):
+        raise ValueError("jackknife leave-out: w, fs and g of one length expected")
+    return _jack_leave_out(load().mce_jack_leave_out_f64,
+                           [(w.ctypes.data if w.size else 0, f.ctypes.data if f is not None and f.size else 0, g.ctypes.data if g.size else 0, w.size, G)
+                            for w, f, g, G in keep], (int(device),))
 
 
 # ---------------------------------------------------------------------------

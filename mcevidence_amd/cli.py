@@ -77,6 +77,27 @@ def _print_information(info):
             print(line)
 
 
+def _jackknife_kw(args):
+    """--jackknife / --jackknife-by, where the first was given (the resident route and the farm take them as a keyword)"""
+    return {} if args.jackknife is None else {"jackknife": {"groups": args.jackknife, "by": args.jackknife_by}}
+
+
+def _print_lnb(mle, info):
+    """the ln(B) lines: with a jackknife, x +- sigma as the host route prints them; returns whether it did"""
+    jk = (info or {}).get("jackknife")
+    if jk is None:
+        for k in range(1, len(mle) + 1):
+            print("   ln(B)[k={}] = {}".format(k, mle[k - 1]))
+        return False
+    for k in range(1, len(jk["lnE"]) + 1):
+        print("   ln(B)[k={}] = {} \u00b1 {}".format(k, jk["lnE"][k - 1], jk["sigma"][k - 1]))
+    return jk
+
+
+def _print_jackknife_note(jk):
+    print("* \u00b1: delete-a-group jackknife over {} {} (conservative, not a calibrated 1 sigma).".format(jk["groups"], jk["by"]))
+
+
 def _backend_kw(args):
     """the backend the flags ask for; nothing when they ask for none (the default backend, as ever)"""
     if not args.device_eig:
@@ -117,19 +138,21 @@ def farm_main(args):
         ndims.append(a.ndim)
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
-    want_info = args.converge is not None or args.information
+    want_info = args.converge is not None or args.information or args.jackknife is not None
     outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
                                     idchain=args.idchain, split=args.cross, info=want_info, **_thin_kw(args), **_converge_kw(args),
-                                    **_information_kw(args), **_backend_kw(args))
+                                    **_information_kw(args), **_jackknife_kw(args), **_backend_kw(args))
     infos = [o[1] for o in outs] if want_info else [None] * len(outs)
     outs = [o[0] for o in outs] if want_info else outs
+    note = None
     for r, mle, inf in zip(roots, outs, infos):
         print()
         print("Using file: ", r)
         _print_converge(inf)
         _print_information(inf)
-        for k in range(1, len(mle) + 1):
-            print("   ln(B)[k={}] = {}".format(k, mle[k - 1]))
+        note = _print_lnb(mle, inf) or note
+    if note:
+        _print_jackknife_note(note)
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
     print("")
     return outs
@@ -154,7 +177,13 @@ def main(argv=None):
     if args.resident:
         from .resident import evidence_from_files
         out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
-                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_backend_kw(args))
+                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, info=args.jackknife is not None,
+                                  **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_jackknife_kw(args), **_backend_kw(args))
+        if args.jackknife is not None:
+            out, inf = out
+            jk = _print_lnb(out, inf)
+            if jk:
+                _print_jackknife_note(jk)
         print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
         print("")
         return out
@@ -163,8 +192,6 @@ def main(argv=None):
                      thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_backend_kw(args))
     _print_converge(getattr(mce, "info", None))
     if args.jackknife is not None:
-        if args.resident or args.farm:
-            raise ValueError("--jackknife with --resident / --farm is not supported")
         mce.jackknife = {"groups": args.jackknife, "by": args.jackknife_by}
         out = mce.evidence()
         jk = mce.info["jackknife"]

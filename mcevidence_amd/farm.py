@@ -194,13 +194,13 @@ def read_files(paths, device=0, wave_bytes=None):
 
 
 class _Root(object):
-    __slots__ = ("index", "files", "lens", "size", "ndim", "pvol", "burn", "thin", "parts", "ncols", "nrows", "nparam", "nd", "rc", "keep", "problem", "scal", "conv")
+    __slots__ = ("index", "files", "lens", "size", "ndim", "pvol", "burn", "thin", "parts", "ncols", "nrows", "nparam", "nd", "rc", "keep", "problem", "scal", "conv", "jack")
 
 
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
                              require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto",
-                             information=None):
+                             information=None, jackknife=None):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -217,7 +217,11 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     ``mce_chain_conv_dev`` call per wave and per (columns, ndim) group covers the unthinned roots of the wave; a thinned or a
     ``thin_corr`` root is measured on its per-root route.  ``information`` (one value or one per root): <ln L>_P, D_KL and the model
     dimensionality of every such root in ``info["information"]`` -- ONE ``mce_like_moments_dev`` call per wave over all its ready roots,
-    thinned and unthinned alike.  Without a GPU: ``RuntimeError``."""
+    thinned and unthinned alike.  ``jackknife`` (one value or one per root: None, True, a number of groups or dict(groups, by)): the
+    delete-a-group error bars of every such root in ``info["jackknife"]``, as ``evidence_from_files(root, jackknife=...)`` returns them --
+    the group ids of all asking roots of a wave come from ONE ``mce_jack_groups_dev`` call and their leave-one-group-out blocks from ONE
+    ``mce_jack_leave_out_dev`` call; the ladders (whitening, searches, ``mce_jack_dotp_dev``) run root by root after the wave's batched
+    feed, and a root whose ladder raises fails alone.  Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
     roots = list(roots)
@@ -232,11 +236,13 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     conv_kw = [{} if c in (None, False) else {"converge": c, "converge_by": converge_by} for c in convs]
     infos = _per_root(information, n, "information")
     info_kw = [{"information": v} if _information.wanted(v) else {} for v in infos]      # (what a root takes with it to another route)
+    jacks = _per_root(jackknife, n, "jackknife")
+    jack_kw = [{} if v is None or v is False else {"jackknife": v} for v in jacks]
     common = dict(kmax=kmax, idchain=idchain, idpattern=idpattern, iw=iw, ilike=ilike, itheta=itheta)
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **extra)
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **extra)
                 for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
@@ -262,8 +268,8 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
         if reason == _res.RESIDENT:
             try:
                 reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i],
-                                   converge=convs[i], converge_by=converge_by)
-            except ValueError as e:                # (thin_corr together with thinlen; a converge value no route takes)
+                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i])
+            except ValueError as e:                # (thin_corr together with thinlen; a converge or jackknife value no route takes)
                 fail(i, e)
                 continue
         if reason == _res.RESIDENT and _res._chains.thin_corr_scale(tcorr[i]) is not None:
@@ -278,8 +284,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             r.size = farm_layout(r.lens)[1]
             r.ndim, r.pvol, r.burn, r.thin, r.rc, r.keep, r.problem, r.scal = ndims[i], pvols[i], burns[i], thins[i], None, None, None, None
             r.conv = _res._chains.converge_spec(convs[i], converge_by)          # None, or (threshold, by); afterwards: info["converge"]
+            r.jack = _res.jack_spec(jacks[i], len(r.files))                     # None, or dict(groups, by, G)
             todo.append(r)
-        except Exception as e:                     # (no files, an unreadable path: what the host route raises too)
+        except Exception as e:                     # (no files, an unreadable path, by="chains" of one file: what the host route raises too)
             fail(i, e)
     cov = "single" if covtype is None else covtype
 
@@ -414,6 +421,17 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                 asked = [r for r in ready if _information.wanted(infos[r.index])]
                 moms = dict(zip((r.index for r in asked),
                                 _res.moments_measure_dev([(r.problem[10], r.problem[9], r.problem[1]) for r in asked], device, stream.cuda_stream))) if asked else {}
+                # jackknife: the group ids of the ready roots that ask for it in one call, their leave-one-group-out blocks in another
+                # (src: the kept rows of a thinned root; fs only where the deleted sets' moments are wanted)
+                jasked = [r for r in ready if r.jack is not None]
+                jgroups, jblocks, pending = {}, {}, []
+                if jasked:
+                    jgroups = dict(zip((r.index for r in jasked),
+                                       _res.jack_groups_dev([(r.rc._src if r.rc is not None else None, r.rc._parts if r.rc is not None else r.parts,
+                                                              r.problem[1], r.jack["G"], r.jack["by"]) for r in jasked], device, stream.cuda_stream)))
+                    jblocks = dict(zip((r.index for r in jasked),
+                                       _res.jack_leave_out_dev([(r.problem[9], r.problem[10] if r.index in moms else 0, jgroups[r.index], r.problem[1], r.jack["G"])
+                                                                for r in jasked], device, stream.cuda_stream)))
                 with backend._scoped():
                     got = _capi.evidence_feed_batch_dev([r.problem for r in ready], device=device, return_exceptions=True)
                     for r, g in zip(ready, got):
@@ -439,7 +457,22 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                             inf["converge"] = r.conv
                         if r.index in moms:
                             inf["information"] = _information.build(moms[r.index], r.scal[0], out)
+                        if r.jack is not None:
+                            pending.append((r, out, inf))
+                            continue
                         results[r.index] = out if not info else (out, inf)
+                # the ladders, root by root (a root whose ladder raises -- rows still short after the last rung -- fails alone)
+                for r, out, inf in pending:
+                    try:
+                        p = r.problem
+                        run = _res.jack_run(p[0], p[1], p[2], p[6], p[8], p[9], p[10], jgroups[r.index], r.jack, device, backend)
+                        inf["jackknife"] = _res.jack_result(run, jblocks[r.index], r.jack, r.scal[1], r.scal[0], p[1], kmax_eff, math.log(r.pvol))
+                        if "information" in inf:
+                            _res.jack_information(inf["information"], jblocks[r.index], r.scal[0], inf["jackknife"])
+                        results[r.index] = out if not info else (out, inf)
+                    except Exception as e:
+                        fail(r.index, e)
+                        counts["farm"] -= 1
             ms["feed"] += _res._ms(t0)
             for r in wroots:
                 r.rc = r.keep = r.parts = None
@@ -454,6 +487,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                 kw.update(corr_kw, thin_corr=tcorr[i])
             kw.update(conv_kw[i])
             kw.update(info_kw[i])
+            kw.update(jack_kw[i])
             if covtype != "all":
                 kw["covtype"] = covtype
             if backend is not None:

@@ -10,7 +10,8 @@ fp64, every sum in an order the sizes alone fix:
 
 status 3: a weight that is not finite, or a used row whose f is not finite (-inf included); 5: W is not > 0.  A status other than 0
 makes every value NaN, logs one WARNING and raises nothing.  ``moments`` is the rule in NumPy, ``from_block`` takes the device's result
-block (``_capi.like_moments_dev``), ``build`` makes ``info["information"]`` from either, ``with_jackknife`` adds the error bars.
+block (``_capi.like_moments_dev``), ``build`` makes ``info["information"]`` from either, ``with_jackknife`` adds the error bars
+(``with_jackknife_moments``: from the deleted sets' moments, where the columns stay on the device).
 
 D_KL is the divergence from the FLAT prior over the given volume when the likelihood column is -ln L over that box; with priors folded
 into the column, or ``ndim`` below the sampled parameters, it carries exactly the caveats ln E carries.
@@ -23,7 +24,7 @@ import numpy as np
 
 logger = logging.getLogger("mcevidence_amd")
 
-__all__ = ["moments", "from_block", "build", "with_jackknife", "leave_one_out", "lines", "wanted", "refuse", "STATUS_WORDS"]
+__all__ = ["moments", "from_block", "from_leave_out", "build", "with_jackknife", "with_jackknife_moments", "leave_one_out", "lines", "wanted", "refuse", "STATUS_WORDS"]
 
 OK, NOT_FINITE, NO_WEIGHT = 0, 3, 5
 STATUS_WORDS = {
@@ -104,14 +105,25 @@ def leave_one_out(a, f, gq, G):
 def with_jackknife(inf, a, f, gq, logLmax, jk):
     """adds sigma {mean_logL, bmd, D_KL}, groups and by to ``inf``: the delete-a-group values against ``jk["lnE_groups"]``, through
     ``jackknife.summarise``'s formula"""
+    return with_jackknife_moments(inf, leave_one_out(a, f, gq, int(jk["groups"])), logLmax, jk)
+
+
+def with_jackknife_moments(inf, moms, logLmax, jk):
+    """``with_jackknife`` from the G deleted sets' ``moments`` dicts themselves (the resident route and the farm: the blocks of
+    ``mce_jack_leave_out_dev``, the columns never on the host)"""
     from .jackknife import summarise
     G = int(jk["groups"])
-    vals = [_values(m, logLmax, jk["lnE_groups"][b]) for b, m in enumerate(leave_one_out(a, f, gq, G))]
+    vals = [_values(m, logLmax, jk["lnE_groups"][b]) for b, m in enumerate(moms)]
     sig = lambda full, col: summarise(np.atleast_1d(full), np.array([np.atleast_1d(v[col]) for v in vals]))[0]      # noqa: E731
     inf["sigma"] = {"mean_logL": float(sig(inf["mean_logL"], 0)[0]), "bmd": float(sig(inf["bmd"], 2)[0]), "D_KL": sig(inf["D_KL"], 4)}
     inf["groups"] = G
     inf["by"] = jk["by"]
     return inf
+
+
+def from_leave_out(block):
+    """one slot of ``mce_jack_leave_out_dev`` ({rows, SumW, W, c, v, A2, rows used, status}) -> what ``moments`` returns"""
+    return from_block(block[2:8])
 
 
 def lines(inf):

@@ -11,6 +11,8 @@ list: the ladder ``LADDER``.
 ``summarise``       sigma and the bias-corrected value from the G leave-one-group-out values
 ``run_ladder``      the ladder over a session (``HipBackend.jackknife_lists`` -> ``HipSession``; ``HostSession`` otherwise)
 ``evidence_jackknife``   what ``MCEvidence.evidence_jackknife`` returns
+``spec`` / ``resolve_groups`` / ``result``   the keyword, the number of groups and the result dict every route shares (the resident route
+                    and the farm, docs/design/jackknife_resident.md, form the group ids and the leave-one-group-out sums on the device)
 
 The rule is also csrc/jack.hpp (shared by the kernels and a serial driver); the kernels are csrc/jack_kernels.hpp.
 """
@@ -22,7 +24,8 @@ import numpy as np
 
 from .resident import mle_from_sums
 
-__all__ = ["group_ids", "jackknife_host", "summarise", "run_ladder", "evidence_jackknife", "ladder", "LADDER", "MAX_GROUPS", "MAX_LIST"]
+__all__ = ["group_ids", "jackknife_host", "summarise", "run_ladder", "evidence_jackknife", "ladder", "LADDER", "MAX_GROUPS", "MAX_LIST", "spec",
+           "resolve_groups", "result"]
 
 LADDER = (16, 32, 128, 1024)
 MAX_GROUPS = 64          # == MCE_JACK_MAX_GROUPS
@@ -38,6 +41,36 @@ def ladder(K, first=None):
     if first not in LADDER or first < K:
         raise ValueError("jackknife: the first rung must be one of %r and at least K=%d (got %r)" % (LADDER, K, first))
     return tuple(L for L in LADDER if L >= first)
+
+
+def spec(jackknife):
+    """the ``jackknife`` keyword of the resident route and the farm -- None / False (off), True (16 blocks), a number of blocks, or a dict
+    with ``groups`` and ``by`` -- as a dict(groups, by), or None"""
+    if jackknife is None or jackknife is False:
+        return None
+    kw = dict(jackknife) if isinstance(jackknife, dict) else ({} if jackknife is True else {"groups": int(jackknife)})
+    unknown = sorted(set(kw) - {"groups", "by"})
+    if unknown:
+        raise ValueError("jackknife: unknown key%s %s ('groups' and 'by' expected)" % ("" if len(unknown) == 1 else "s", ", ".join(map(repr, unknown))))
+    return {"groups": kw.get("groups", 16), "by": kw.get("by", "blocks")}
+
+
+def resolve_groups(groups, by, nchains):
+    """G of a call: ``groups`` under ``by="blocks"``, the number of chains under ``by="chains"`` (``nchains`` None: not known yet, nothing
+    is said about it); the ValueErrors every route raises"""
+    if by == "chains":
+        if nchains is None:
+            return None
+        G = int(nchains)
+        if G < 2:
+            raise ValueError("jackknife by='chains' needs at least 2 chains (got %d)" % G)
+    elif by == "blocks":
+        G = int(groups)
+    else:
+        raise ValueError("jackknife: by=%r ('blocks' or 'chains' expected)" % (by,))
+    if not (2 <= G <= MAX_GROUPS):
+        raise ValueError("jackknife: G=%r groups (2 .. %d expected)" % (G, MAX_GROUPS))
+    return G
 
 
 def group_ids(gd, name, groups, by="blocks"):
@@ -189,6 +222,20 @@ class HostSession(object):
         return group_share(self.lists(L, rows)[1], self.gr)
 
 
+class _DeviceGroups(object):
+    """the group ids of a session built from device tensors, copied to the host only where the capacity error's message wants them"""
+
+    def __init__(self, g):
+        self.g = g
+
+    def __len__(self):
+        return int(self.g.shape[0])
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.g.cpu().numpy()
+        return a if dtype is None else a.astype(dtype)
+
+
 class HipSession(object):
     """Whitened rows, weights, terms and groups on the device; a level is one ``mce_knn_f64_dev`` and one ``mce_jack_dotp_dev``.
     ``whitened=False`` (auto evidence only): S1 are the RAW rows, whitened on the device by ``mce_evidence_feed_whiten_f64``
@@ -227,6 +274,27 @@ class HipSession(object):
         self.gr = self.gq if S2 is None else torch.from_numpy(np.ascontiguousarray(gr, dtype=np.int32)).to(self.dev)
         self.gr_host = np.asarray(gr)
         self.kernel_ms = []
+
+    @classmethod
+    def from_device(cls, X, w, fs, gq, kmax, G, jac=None, device=0):
+        """Auto evidence from DEVICE tensors that are whitened already (what ``mce_evidence_feed_whiten_dev_f64`` leaves): X [n, d], w [n],
+        fs [n] in fp64 and the int32 groups gq [n] (``mce_jack_groups_dev``).  Nothing is copied; the group ids are checked on the
+        device by every ``mce_jack_dotp_dev``."""
+        import torch
+        from . import _capi
+        if not (2 <= int(G) <= MAX_GROUPS):
+            raise ValueError("jackknife: G=%r groups (2 .. %d expected)" % (G, MAX_GROUPS))
+        self = cls.__new__(cls)
+        self.torch, self.capi = torch, _capi
+        self.dev = torch.device("cuda", device)
+        self.kmax, self.G, self.d, self.k0 = int(kmax), int(G), int(X.shape[1]), 1
+        self.n1 = self.nr = int(X.shape[0])
+        self.jac = jac
+        self.X = self.Y = X
+        self.w, self.fs, self.gq, self.gr = w, fs, gq, gq
+        self.gr_host = _DeviceGroups(gq)
+        self.kernel_ms = []
+        return self
 
     def _search(self, Xq, L, self_mode):
         """(dist, idx) [nq, L] on the device"""
@@ -280,6 +348,17 @@ class HipSession(object):
         return group_share(self.lists(L, rows)[1].cpu().numpy(), self.gr_host)
 
 
+def result(dotp_groups, dotp_full, per_level, jac, sumw, n1, sumw_groups, rows_groups, logLmax, kmax, logpv, G, by, cross=False):
+    """the dict every route returns, from the ladder's sums and the leave-one-group-out bookkeeping: ``sumw`` / ``n1`` the full sample's
+    weight sum and rows, ``sumw_groups[b]`` / ``rows_groups[b]`` those of the rows not in group b"""
+    lnE = mle_from_sums(dotp_full, jac, sumw, logLmax, n1, kmax, logpv, cross)[1:]
+    lnE_groups = np.zeros((G, kmax - 1))
+    for b in range(G):
+        lnE_groups[b] = mle_from_sums(dotp_groups[b], jac, sumw_groups[b], logLmax, int(rows_groups[b]), kmax, logpv, cross)[1:]
+    sigma, bc = summarise(lnE, lnE_groups)
+    return {"lnE": lnE, "sigma": sigma, "lnE_groups": lnE_groups, "lnE_bias_corrected": bc, "groups": G, "by": by, "rows_per_level": per_level}
+
+
 def _refuse(mce, covtype):
     from . import parallel
     if mce.brange is not None or mce.nbatch > 1:
@@ -301,16 +380,7 @@ def evidence_jackknife(mce, groups=16, by="blocks", covtype="all", pvolume=None,
         covtype = mce.covtype
     _refuse(mce, covtype)
     gd = mce.gd
-    if by == "chains":
-        G = int(gd.nchains)
-        if G < 2:
-            raise ValueError("jackknife by='chains' needs at least 2 chains (got %d)" % G)
-    elif by == "blocks":
-        G = int(groups)
-    else:
-        raise ValueError("jackknife: by=%r ('blocks' or 'chains' expected)" % (by,))
-    if not (2 <= G <= MAX_GROUPS):
-        raise ValueError("jackknife: G=%r groups (2 .. %d expected)" % (G, MAX_GROUPS))
+    G = resolve_groups(groups, by, gd.nchains)
     kmax, ndim, split = mce.kmax, mce.ndim, bool(mce.split)
     k0 = 0 if split else 1
     s1, lnp, weight = gd.arrays("s1")
@@ -338,13 +408,9 @@ def evidence_jackknife(mce, groups=16, by="blocks", covtype="all", pvolume=None,
 
     logpv = math.log(mce.priorvolume if pvolume is None else pvolume)
     aw = np.asarray(gd.data["s1"].adjusted_weights, dtype=np.float64)
-    lnE = mle_from_sums(dotp_full, jac, np.sum(aw), logLmax, n1, kmax, logpv, split)[1:]
-    lnE_groups = np.zeros((G, kmax - 1))
-    for b in range(G):
-        rest = gq != b
-        lnE_groups[b] = mle_from_sums(dotp_groups[b], jac, np.sum(aw[rest]), logLmax, int(rest.sum()), kmax, logpv, split)[1:]
-    sigma, bc = summarise(lnE, lnE_groups)
-    out = {"lnE": lnE, "sigma": sigma, "lnE_groups": lnE_groups, "lnE_bias_corrected": bc, "groups": G, "by": by, "rows_per_level": per_level}
+    rest = [gq != b for b in range(G)]
+    out = result(dotp_groups, dotp_full, per_level, jac, np.sum(aw), n1, [np.sum(aw[r]) for r in rest], [int(r.sum()) for r in rest], logLmax, kmax, logpv,
+                 G, by, split)
     if getattr(session, "kernel_ms", None):
         out["kernel_ms"] = list(session.kernel_ms)
     return out

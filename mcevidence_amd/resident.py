@@ -49,6 +49,7 @@ REASONS = {
     "ambiguous_weights": "the weights' fractional parts sum to within 1e-6 of the integer-weight threshold 1e-4",
     "bad_weights": "a weight is negative, not finite or beyond 2^53",
     "thin_corr": "thin_corr: the autocorrelation length is measured root by root (the per-root resident route)",
+    "jackknife_cross": "jackknife of a cross evidence whitens on the host",
 }
 
 
@@ -66,17 +67,20 @@ class ResidentDecline(Exception):
 
 
 def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all", split=False, ndim=None, nparam=None,
-         distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None, converge=None, converge_by="auto"):
+         distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None, converge=None, converge_by="auto", jackknife=None, nchains=None):
     """``"resident"`` or the reason why the route declines.  A pure function of the call's keywords and of what is known
     about the data at the time (``ncols``: the files' column counts, ``nrows``: rows left after burn-in / thinning,
     ``nparam``: parameter columns; None: not known yet).  ``thin_corr`` (thinning by the measured autocorrelation length) is resident
     work and declines nothing; together with a ``thinlen`` other than 0 it is the ValueError every route raises.  ``converge`` /
     ``converge_by`` (the Gelman-Rubin R-1 of the burned chains) are resident work too and decline nothing; a value they cannot take
-    is the ValueError every route raises."""
+    is the ValueError every route raises.  ``jackknife`` (the delete-a-group error bars; ``nchains``: the chains, where known) is resident
+    work for an auto evidence; with a split it declines to the host route, which whitens s1 and s2 there; a number of groups or a
+    ``by`` it cannot take is the ValueError every route raises."""
     if not ischain:
         return REASONS["ischain"]
     _chains.thin_corr_scale(thin_corr, thinlen)
     _chains.converge_spec(converge, converge_by)
+    jspec = jack_spec(jackknife, nchains)
     if thinlen < 0:
         return REASONS["negative_thinlen"]
     if 0 < thinlen < 1:
@@ -91,6 +95,8 @@ def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all"
         return REASONS["covtype"]
     if split and covtype == "single":
         return REASONS["split_single"]
+    if jspec is not None and split:
+        return REASONS["jackknife_cross"]
     eff = ndim if nparam is None else (nparam if ndim is None else min(int(ndim), nparam))
     if eff is not None and eff > 127:
         return REASONS["ndim"]
@@ -210,6 +216,77 @@ def moments_measure_dev(systems, device, stream):
     return [_information.from_block(b) for b in _capi.like_moments_dev(systems, ws.data_ptr(), wsb, stream)]
 
 
+# ---- the jackknife of a chain that stays on the device (docs/design/jackknife_resident.md; this module and farm.py) -----------------
+def jack_spec(jackknife, nchains=None):
+    """None, or dict(groups, by, G) of the ``jackknife`` keyword: G is the number of groups (None while ``by="chains"`` does not
+    know the chains yet); raises the ValueErrors the host route raises, with its words"""
+    from . import jackknife as _jk
+    spec = _jk.spec(jackknife)
+    if spec is not None:
+        spec["G"] = _jk.resolve_groups(spec["groups"], spec["by"], nchains)
+    return spec
+
+
+def jack_groups_dev(systems, device, stream):
+    """ONE ``mce_jack_groups_dev`` call for ``systems`` = [(src: the int64 device tensor of the kept rows or None, parts [(address, rows)],
+    n, G, by)] of auto evidences (row i is sample row i, the sample has n rows) -> one int32 device tensor [n] per system"""
+    import torch
+    from . import _capi
+    outs = [torch.empty(max(int(n), 1), dtype=torch.int32, device="cuda:%d" % int(device))[:int(n)] for _, _, n, _, _ in systems]
+    segs = []
+    for (src, parts, n, G, by), out in zip(systems, outs):
+        first = None
+        if by == "chains":
+            first = np.concatenate([[0], np.cumsum([m for _, m in parts])])[:len(parts)]
+        segs.append((0, src.data_ptr() if src is not None else 0, first, n, n, G, by, out.data_ptr()))
+    _capi.jack_groups_dev(segs, stream)
+    return outs
+
+
+def jack_leave_out_dev(systems, device, stream):
+    """ONE ``mce_jack_leave_out_dev`` call for ``systems`` = [(device address of w, of fs or 0: no moments, the int32 group tensor, rows,
+    G)] -> one [G + 1, 8] block per system (``_capi.JACK_LEAVE_OUT_FIELDS``)"""
+    import torch
+    from . import _capi
+    wsb = _capi.jack_leave_out_workspace_bytes(sum(n for _, _, _, n, _ in systems), len(systems), max(G for _, _, _, _, G in systems))
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
+    return _capi.jack_leave_out_dev([(w, fs, g.data_ptr(), n, G) for w, fs, g, n, G in systems], ws.data_ptr(), wsb, stream)
+
+
+def jack_run(params, n1, ld, nd, kmax, w, fs, gq, spec, device, backend):
+    """the ladder of one auto evidence whose rows are on the device: ``mce_evidence_feed_whiten_dev_f64`` on the gathered rows (device
+    addresses ``params`` [n1, ld], ``w``, ``fs``), then ``jackknife.run_ladder`` over a ``HipSession`` of device tensors -> (dotp_groups,
+    dotp_full, rows_per_level, jacobian, kernel_ms)"""
+    import torch
+    from . import _capi
+    from .jackknife import HipSession, run_ladder
+    dev = "cuda:%d" % int(device)
+    X = torch.empty((n1, nd), dtype=torch.float64, device=dev)
+    w2 = torch.empty(n1, dtype=torch.float64, device=dev)
+    fs2 = torch.empty(n1, dtype=torch.float64, device=dev)
+    with backend._scoped():
+        jac, _, _ = _capi.evidence_feed_whiten_dev(params, n1, ld, nd, kmax, w, fs, X.data_ptr(), w2.data_ptr(), fs2.data_ptr(), device=device,
+                                                   want_checksum=False)
+    session = HipSession.from_device(X, w2, fs2, gq, kmax, spec["G"], jac, device)
+    groups, full, per_level = run_ladder(session, n1, spec["G"], 1, kmax)
+    return groups, full, per_level, jac, list(session.kernel_ms)
+
+
+def jack_result(run, block, spec, SumW, logLmax, n1, kmax, log_prior_volume):
+    """``info["jackknife"]`` from the ladder's sums and the leave-out block: S_b and SumW_b are the block's rows and weight sums"""
+    from .jackknife import result
+    groups, full, per_level, jac, kernel_ms = run
+    out = result(groups, full, per_level, jac, SumW, n1, block[1:, 1], block[1:, 0], logLmax, kmax, log_prior_volume, spec["G"], spec["by"])
+    if kernel_ms:
+        out["kernel_ms"] = kernel_ms
+    return out
+
+
+def jack_information(inf, block, logLmax, jk):
+    """sigma, groups and by of ``info["information"]`` from the deleted sets' moments of the leave-out block"""
+    return _information.with_jackknife_moments(inf, [_information.from_leave_out(b) for b in block[1:]], logLmax, jk)
+
+
 def route_info(route, nparam, nd, nread, nsample):
     """the info dict of ``MCEvidence.evidence(info=True)`` for a route that kept the chain on the device"""
     return {"NparamsMC": nparam, "Nsamples_read": nread, "Nparams_read": nparam, "NparamsCosmo": nd,
@@ -243,6 +320,8 @@ class ResidentChains(object):
         spec = _chains.converge_spec(converge, converge_by)
         self.converge = None
         self.information = None                            # (what the last evidence(information=True) found)
+        self.jackknife = None                              # (what the last evidence(jackknife=...) found,
+        self.jackknife_block = None                        #  and its leave-one-group-out block: _capi.JACK_LEAVE_OUT_FIELDS per slot)
         reason = plan(thinlen=thinlen, ncols=[t.shape[1] for t in tensors], distributed=_distributed())
         if reason != RESIDENT:
             raise ResidentDecline(reason)
@@ -460,21 +539,27 @@ class ResidentChains(object):
 
     # -- the estimator ---------------------------------------------------------------------------------------------------
     def evidence(self, kmax=5, ndim=None, priorvolume=1, covtype="all", pos_lnp=False, split=False, s1frac=0.5, split_rows=None,
-                 info=False, backend=None, information=None):
+                 info=False, backend=None, information=None, jackknife=None):
         """ln E as ``MCEvidence(...).evidence(...)`` returns it (``MLE[1:]``, and the info dict if ``info=True``; it
         carries ``info["route"] = "resident"``).  ``split=True``: the reference's random split, drawn on the host with the
         call ``MCSamples.chain_split`` makes (same RNG consumption); ``split_rows=(s1, s2)``: ``set_split``.
         ``backend``: a ``HipBackend`` whose ``recheck_rows`` applies to the search.  ``information`` (None or True): <ln L>_P, D_KL and
-        the model dimensionality in ``info["information"]``, from one ``mce_like_moments_dev`` call on the gathered weights and fs."""
+        the model dimensionality in ``info["information"]``, from one ``mce_like_moments_dev`` call on the gathered weights and fs.
+        ``jackknife`` (None, True, a number of groups or dict(groups, by)): the delete-a-group error bars of the host route's
+        ``evidence_jackknife`` in ``info["jackknife"]`` (and ``self.jackknife``) -- after the usual feed, whose result is returned
+        unchanged, the gathered rows are whitened on the device, ``mce_jack_groups_dev`` forms the group ids, the ladder runs on device
+        tensors and ONE ``mce_jack_leave_out_dev`` call gives S_b, SumW_b and, with ``information``, the deleted sets' moments."""
         from . import _capi
         from .evidence import HipBackend
         backend = backend or HipBackend()
         kmax = max(2, int(kmax))
         nd = effective_ndim(ndim, self.nparam)
         cross = bool(split) or split_rows is not None
-        reason = plan(covtype=covtype, split=cross, ndim=nd, nparam=self.nparam, distributed=_distributed(), nrows=self.nrows)
+        reason = plan(covtype=covtype, split=cross, ndim=nd, nparam=self.nparam, distributed=_distributed(), nrows=self.nrows, jackknife=jackknife,
+                      nchains=self.nchains)
         if reason != RESIDENT:
             raise ResidentDecline(reason)
+        jspec = jack_spec(jackknife, self.nchains)
         torch = self._torch
         ms = self.stats["ms"]
         with torch.cuda.device(self.device):
@@ -510,8 +595,19 @@ class ResidentChains(object):
                 t0 = time.perf_counter()
                 mom, = moments_measure_dev([(fs.data_ptr(), s1["w"].data_ptr(), n1)], self.device, self._stream())
                 ms["information"] = _ms(t0)
+            jrun = jblock = None
+            if jspec is not None:
+                t0 = time.perf_counter()
+                gq, = jack_groups_dev([(self._src, self._parts, n1, jspec["G"], jspec["by"])], self.device, self._stream())
+                jrun = jack_run(s1["params"].data_ptr(), n1, self.nparam, nd, kmax, s1["w"].data_ptr(), fs.data_ptr(), gq, jspec, self.device, backend)
+                jblock, = jack_leave_out_dev([(s1["w"].data_ptr(), fs.data_ptr() if mom is not None else 0, gq, n1, jspec["G"])], self.device, self._stream())
+                ms["jackknife"] = _ms(t0)
         out = mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, math.log(priorvolume), cross)[1:]
         self.information = None if mom is None else _information.build(mom, logLmax, out)
+        self.jackknife_block = jblock
+        self.jackknife = None if jrun is None else jack_result(jrun, jblock, jspec, SumW, logLmax, n1, kmax, math.log(priorvolume))
+        if self.jackknife is not None and self.information is not None:
+            jack_information(self.information, jblock, logLmax, self.jackknife)
         if not info:
             return out
         inf = route_info(RESIDENT, self.nparam, nd, self.nrows if split_rows is not None else n1, [n1, n2] if cross else [n1])
@@ -521,6 +617,8 @@ class ResidentChains(object):
             inf["converge"] = self.converge
         if self.information is not None:
             inf["information"] = self.information
+        if self.jackknife is not None:
+            inf["jackknife"] = self.jackknife
         return out, inf
 
 
@@ -538,7 +636,8 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     """``MCEvidence(root, **ctor).evidence(**call)`` with the keywords of both in ``kwargs``, through the resident route
     where it applies (``plan``) and through that very expression where it does not.  With ``info=True`` the info dict
     says which: ``info["route"]`` is ``"resident"`` or ``"host"``, and ``info["declined"]`` gives the reason.
-    ``require_resident=True`` turns a decline into ``ValueError(reason)``.  Without a GPU: ``RuntimeError``."""
+    ``require_resident=True`` turns a decline into ``ValueError(reason)``.  ``jackknife`` (None, True, a number of groups or dict(groups,
+    by)) puts the delete-a-group error bars in ``info["jackknife"]`` on either route.  Without a GPU: ``RuntimeError``."""
     from . import _capi
     from .evidence import MCEvidence
     _capi.require_device()
@@ -554,7 +653,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
         reason = plan(thinlen=ctor.get("thinlen", 0.0), isfunc=ctor.get("isfunc"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1),
                       verbose=max(ctor.get("verbose", 1), 2 if ctor.get("debug") else 0), covtype=covtype, split=split, ndim=None,
                       distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"),
-                      converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"))
+                      converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"), jackknife=ctor.get("jackknife"))
     if reason == RESIDENT:
         level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
         if not logging.getLogger().handlers:
@@ -570,7 +669,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
             pv = call.get("pvolume")
             got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,
-                              backend=ctor.get("backend"), information=ctor.get("information"))
+                              backend=ctor.get("backend"), information=ctor.get("information"), jackknife=ctor.get("jackknife"))
             mle, inf = got
             if ctor.get("verbose", 1) > 0:
                 log_information(inf)

@@ -586,6 +586,49 @@ size_t mce_like_moments_workspace_bytes(int64_t nrows_total, int32_t nseg);
 int mce_like_moments_dev(const mce_moments_seg* segs, int32_t nseg, double* out, void* ws, size_t ws_bytes, void* stream);
 int mce_like_moments_f64(const mce_moments_seg* segs, int32_t nseg, double* out, int32_t device);
 
+/* The posterior summary behind summary= (weighted mean, variance, extremes, weighted quantiles and the best-fit sample of the first d
+ * parameter columns), for MANY systems (the ready roots of a farm wave) in one call.  The rule is stated in csrc/param_summary.hpp and
+ * docs/design/summary.md.  One system is one segment: x[n][ld] the RAW rows (the first d columns are measured), w[n] the weights and
+ * fs[n] = logL - logLmax of the s1 partition the estimator sums over; segments may differ in d and ld.  A row with w == 0 is skipped
+ * and nothing of it is read into a result.  q[nq]: the targets, each in (0, 1); Q_j(q) is the smallest value of column j among the used
+ * rows whose cumulative weight reaches q W (no interpolation).  out (HOST, packed in segment order, mce_param_summary_out_doubles(d, nq)
+ * doubles per system) = {W, A2 = sum w^2, rows used, status, column, best-fit row, best-fit f, reserved} then mean[d], var[d] (about the
+ * computed mean), min[d], max[d], bestfit[d] and nq rows of quantiles [d].  status 0 ok (column -1); 3 a weight that is negative or not
+ * finite (column -1), else a used row whose f is NaN (column -2), else a used row with a value that is not finite (column: the lowest
+ * such); 5 W is not > 0 (a segment without a used row included).  Where the status is not 0 every value is NaN, the best-fit row -1, and
+ * that system fails alone.  fs == NULL: the best-fit entries are NaN / -1 and nothing else changes.  pass_elems: 0 for
+ * MCE_SUMMARY_PASS_ELEMS, or the largest number of (row, column) elements sorted in one pass; a column longer than that is a pass of
+ * its own.  A system's bits depend on its own rows alone, not on its neighbours, its position, the call or pass_elems; two runs give the
+ * same bits; fp64, sums in a fixed order, no floating-point atomics, plain stores, 64-bit row indices.  The number of launches depends on
+ * the number of passes, not on nseg; everything runs on the caller's stream, which this library synchronises once, on return.  One
+ * caveat: the sort of a pass is rocprim::segmented_radix_sort_pairs, and from its partitioning threshold of runs in a pass on (3 000 in
+ * its default configuration; a farm wave of 24 roots of 27 columns has 648) rocPRIM itself reads two segment counts back and waits
+ * for the stream before it sorts: one more host wait per such pass, inside the call.  Segments and workspace
+ * (mce_param_summary_workspace_bytes(rows of all segments, the longest segment, nseg, the largest d, nq, pass_elems)) are the caller's.
+ * The size holds on the host and for the device it was asked on: it includes rocPRIM's temporary, which is asked of rocPRIM for the
+ * largest pass and the largest number of runs the arguments allow (on the assumption that it does not shrink when either grows) where
+ * a device is visible, and is an estimate where none is -- a size formed without a device is for planning only and must not be
+ * carried to another host.  The device form asks rocPRIM again for every pass and returns MCE_ERR_WORKSPACE, before it sorts, if that
+ * pass needs more than was planned.  mce_param_summary_f64 takes HOST segments, uploads them to `device` and calls the device form.  Argument errors (d outside
+ * 1 .. 127, nq outside 1 .. MCE_SUMMARY_MAX_Q, a q outside (0, 1), ld < d, negative sizes): MCE_ERR_INVALID (no device needed); no visible
+ * device: MCE_ERR_NO_DEVICE. */
+#define MCE_SUMMARY_MAX_Q 16
+#define MCE_SUMMARY_HEAD 8
+#define MCE_SUMMARY_PASS_ELEMS (1 << 25)
+typedef struct mce_summary_seg {
+    const double* x;
+    int64_t ld;
+    int64_t n;
+    int32_t d;
+    const double* w;
+    const double* fs;
+} mce_summary_seg;
+size_t mce_param_summary_out_doubles(int32_t d, int32_t nq);
+size_t mce_param_summary_workspace_bytes(int64_t nrows_total, int64_t nrows_max, int32_t nseg, int32_t dmax, int32_t nq, int64_t pass_elems);
+int mce_param_summary_dev(const mce_summary_seg* segs, int32_t nseg, const double* q, int32_t nq, int64_t pass_elems, double* out, void* ws, size_t ws_bytes,
+                          void* stream);
+int mce_param_summary_f64(const mce_summary_seg* segs, int32_t nseg, const double* q, int32_t nq, int64_t pass_elems, double* out, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

@@ -182,6 +182,21 @@ SIGNATURES["mce_like_moments_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c
 SIGNATURES["mce_like_moments_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_size_t, _P])
 SIGNATURES["mce_like_moments_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
 
+
+class SummarySeg(ctypes.Structure):
+    """``mce_summary_seg``: one system of ``mce_param_summary_*`` -- its raw rows (address, row stride in doubles, rows, measured
+    columns) and the addresses of its w and fs columns"""
+    _fields_ = [("x", _P), ("ld", _c.c_int64), ("n", _c.c_int64), ("d", _c.c_int32), ("w", _P), ("fs", _P)]
+
+
+MCE_SUMMARY_MAX_Q = 16
+MCE_SUMMARY_HEAD = 8
+MCE_SUMMARY_PASS_ELEMS = 1 << 25
+SIGNATURES["mce_param_summary_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_summary_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64])
+SIGNATURES["mce_param_summary_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int64, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_param_summary_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int64, _P, _c.c_int32])
+
 class JackGroupsSeg(ctypes.Structure):
     """``mce_jack_groups_seg``: one system of ``mce_jack_groups_dev`` (rows / src / out: device addresses; part_first: a host array)."""
     _fields_ = [("rows", _P), ("src", _P), ("part_first", _P), ("nparts", _c.c_int64), ("n", _c.c_int64), ("N", _c.c_int64), ("G", _c.c_int32),
@@ -664,6 +679,55 @@ def like_moments(systems, device=0):
     if any(f.shape != w.shape for f, w in keep):
         raise ValueError("like moments: fs and w of one length expected")
     return _like_moments(load().mce_like_moments_f64, [(f.ctypes.data if f.size else 0, w.ctypes.data if w.size else 0, f.size) for f, w in keep], (int(device),))
+
+
+def param_summary_out_doubles(d, nq):
+    return int(load().mce_param_summary_out_doubles(int(d), int(nq)))
+
+
+def param_summary_workspace_bytes(nrows_total, nrows_max, nseg, dmax, nq, pass_elems=0):
+    return int(load().mce_param_summary_workspace_bytes(int(nrows_total), int(nrows_max), int(nseg), int(dmax), int(nq), int(pass_elems)))
+
+
+def _param_summary(call, segs, q, pass_elems, tail):
+    arr = (SummarySeg * max(len(segs), 1))()
+    for i, (x, ld, n, d, w, fs) in enumerate(segs):
+        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, fs or None
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+    nq = q.size
+    sizes = [summary_block_doubles(d, nq) if 1 <= int(d) <= 127 else 0 for _, _, _, d, _, _ in segs]
+    out = np.full(max(sum(sizes), 1), np.nan)
+    check(call(_c.cast(arr, _P), len(segs), q.ctypes.data, nq, int(pass_elems), out.ctypes.data, *tail))
+    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
+    return [out[at[i]:at[i + 1]] for i in range(len(segs))]
+
+
+def summary_block_doubles(d, nq):
+    """doubles of one system's result block: MCE_SUMMARY_HEAD + d * (5 + nq)"""
+    return MCE_SUMMARY_HEAD + int(d) * (5 + int(nq))
+
+
+def param_summary_dev(segs, q, ws, ws_bytes, stream=0, pass_elems=0):
+    """mce_param_summary_dev: the posterior summary of ``len(segs)`` systems that are on the device -> one float64 block per system
+    (``summary.from_block`` reads it); ``segs``: [(device address of the rows, row stride in doubles, rows, measured columns, device
+    address of w, device address of fs or 0)], ``q``: the targets"""
+    return _param_summary(load().mce_param_summary_dev, segs, q, pass_elems, (ws or None, int(ws_bytes), stream or None))
+
+
+def param_summary(systems, q, device=0, pass_elems=0):
+    """mce_param_summary_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w, fs or None)], uploaded by the library"""
+    keep = []
+    for x, d, w, f in systems:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        f = None if f is None else np.ascontiguousarray(f, dtype=np.float64).reshape(-1)
+        if x.shape[0] != w.size or (f is not None and f.size != w.size):
+            raise ValueError("param summary: rows, w and fs of one length expected")
+        keep.append((x, int(d), w, f))
+    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0, f.ctypes.data if f is not None and f.size else 0)
+            for x, d, w, f in keep]
+    return _param_summary(load().mce_param_summary_f64, segs, q, pass_elems, (int(device),))
 
 
 def jack_groups_dev(segs, stream=0):

@@ -61,7 +61,26 @@ def build_parser(prog=None):
     p.add_argument("--information", dest="information", action="store_true",
                    help="print <ln L>, the Bayesian model dimensionality d, N_eff and D_KL[k] = <ln L> - ln(B)[k] before the ln(B) lines "
                         "(with --jackknife: each with +- sigma); D_KL is relative to the flat prior over the given volume")
+    p.add_argument("--summary", dest="summary", nargs="*", default=None, type=float, metavar="P",
+                   help="print the weighted mean, standard deviation, equal-tailed limits (probabilities P ...; default 0.68 0.95) and the "
+                        "best-fit sample of every parameter used, after the information lines and before the ln(B) lines: logged with them "
+                        "at -vb 1, printed where the ln(B) lines are printed (--farm, --jackknife) at -vb 0; write it after root_name")
     return p
+
+
+def _summary_kw(args):
+    """--summary, where it was given: True, or the probabilities"""
+    if args.summary is None:
+        return {}
+    return {"summary": tuple(args.summary) if args.summary else True}
+
+
+def _print_summary(info, logged=False):
+    """the summary lines, after the information lines and before the ln(B) lines; ``logged``: the route has logged them already"""
+    from .summary import lines
+    if (info or {}).get("summary") and not logged:
+        for line in lines(info["summary"]):
+            print(line)
 
 
 def _information_kw(args):
@@ -138,10 +157,10 @@ def farm_main(args):
         ndims.append(a.ndim)
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
-    want_info = args.converge is not None or args.information or args.jackknife is not None
+    want_info = args.converge is not None or args.information or args.jackknife is not None or args.summary is not None
     outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
                                     idchain=args.idchain, split=args.cross, info=want_info, **_thin_kw(args), **_converge_kw(args),
-                                    **_information_kw(args), **_jackknife_kw(args), **_backend_kw(args))
+                                    **_information_kw(args), **_summary_kw(args), **_jackknife_kw(args), **_backend_kw(args))
     infos = [o[1] for o in outs] if want_info else [None] * len(outs)
     outs = [o[0] for o in outs] if want_info else outs
     note = None
@@ -150,6 +169,7 @@ def farm_main(args):
         print("Using file: ", r)
         _print_converge(inf)
         _print_information(inf)
+        _print_summary(inf)
         note = _print_lnb(mle, inf) or note
     if note:
         _print_jackknife_note(note)
@@ -178,9 +198,10 @@ def main(argv=None):
         from .resident import evidence_from_files
         out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
                                   kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, info=args.jackknife is not None,
-                                  **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_jackknife_kw(args), **_backend_kw(args))
+                                  **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_jackknife_kw(args), **_backend_kw(args))
         if args.jackknife is not None:
             out, inf = out
+            _print_summary(inf, logged=args.verbose >= 1)
             jk = _print_lnb(out, inf)
             if jk:
                 _print_jackknife_note(jk)
@@ -189,13 +210,14 @@ def main(argv=None):
         return out
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
-                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_backend_kw(args))
+                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_backend_kw(args))
     _print_converge(getattr(mce, "info", None))
     if args.jackknife is not None:
         mce.jackknife = {"groups": args.jackknife, "by": args.jackknife_by}
         out = mce.evidence()
         jk = mce.info["jackknife"]
         _print_information(mce.info)
+        _print_summary(mce.info, logged=args.verbose >= 1)
         for k in range(1, len(jk["lnE"]) + 1):
             print("   ln(B)[k={}] = {} \u00b1 {}".format(k, jk["lnE"][k - 1], jk["sigma"][k - 1]))
         print("* \u00b1: delete-a-group jackknife over {} {} (conservative, not a calibrated 1 sigma).".format(jk["groups"], jk["by"]))

@@ -28,6 +28,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import information as _information
+from . import summary as _summary
 from .chains import MCSamples, rank0_draw
 from .resident import mle_from_sums
 
@@ -203,7 +204,10 @@ class MCEvidence(object):
         ``knn_dotp`` method; default ``HipBackend()`` -- and ``jackknife`` -- None, True, a number of
         groups or a dict of ``evidence_jackknife``'s keywords: ``evidence()`` then also stores the jackknife
         error bars in ``info["jackknife"]`` -- and ``information`` -- None or True: ``evidence()`` then also stores <ln L>_P, D_KL and the
-        Bayesian model dimensionality in ``info["information"]`` (information.py; docs/design/information.md).
+        Bayesian model dimensionality in ``info["information"]`` (information.py; docs/design/information.md) -- and ``summary`` -- None,
+        True (68 % and 95 %) or up to 7 probabilities: ``evidence()`` then also stores the weighted means, standard deviations,
+        equal-tailed limits and the best-fit sample of the first ``ndim`` parameters in ``info["summary"]`` and in
+        ``self.param_summary`` (summary.py; docs/design/summary.md; ``self.summary()`` stays the reference's printing method).
 
         method      chain root name / file name(s), or list/tuple/dict of chain arrays
                     (columns: weight, -lnL, parameters...)
@@ -226,6 +230,12 @@ class MCEvidence(object):
         # changes) or True; consumed here for the same reason
         self.information = gdkwargs.pop("information", None)
         _information.refuse(self.information, brange=brange, nbatch=nbatch, isfunc=isfunc)
+        # posterior means, credible limits and the best fit with every evidence() call (docs/design/summary.md): None (off: nothing
+        # changes), True or the probabilities of the limits; consumed here for the same reason
+        self.summary_spec = gdkwargs.pop("summary", None)
+        # (what the last evidence() found is kept as ``param_summary``: ``summary`` is the reference's method of this class)
+        self.param_summary = None
+        _summary.refuse(self.summary_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
         self.logger = logger
         self.verbose = verbose
         self.debug = bool(debug or verbose > 1)
@@ -465,10 +475,29 @@ class MCEvidence(object):
             _information.with_jackknife(inf, a, fs, group_ids(self.gd, "s1", jk["groups"], jk["by"]), logLmax, jk)
         self.info["information"] = inf
 
+    def _fill_summary(self, pos_lnp):
+        """``info["summary"]`` of this call (the constructor's ``summary`` keyword; unset: nothing happens): the rule of summary.py on
+        s1's weights, its raw first ``ndim`` columns and fs, on the host -- under a process group every rank computes its own, no
+        collective"""
+        probs = _summary.spec(self.summary_spec)
+        if probs is None:
+            return
+        _summary.refuse(self.summary_spec, brange=self.brange, nbatch=self.nbatch)
+        samples, lnp, _ = self.gd.arrays("s1")
+        logL = np.asarray(-lnp if pos_lnp else lnp, dtype=np.float64)
+        logLmax = np.amax(logL)
+        blk = _summary.measure(self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim], logL - logLmax,
+                               _summary.targets(probs))
+        self.param_summary = self.info["summary"] = _summary.build(blk, probs, logLmax, _summary.param_names(self.fname, self.ndim))
+
     def _report(self, MLE, verbose, info, pos_lnp=False):
         self._fill_information(MLE, pos_lnp)
+        self._fill_summary(pos_lnp)
         if verbose > 0 and "information" in self.info and _information.wanted(self.information):
             for line in _information.lines(self.info["information"]):
+                self.logger.info(line)
+        if verbose > 0 and "summary" in self.info and _summary.wanted(self.summary_spec):
+            for line in _summary.lines(self.info["summary"]):
                 self.logger.info(line)
         if verbose > 0:
             for k in range(1, self.kmax):

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import information as _information
 from . import resident as _res
+from . import summary as _summary
 
 logger = logging.getLogger("mcevidence_amd")
 
@@ -126,6 +127,20 @@ def _per_root(value, n, name):
     return [value] * n
 
 
+def _per_root_summary(value, n):
+    """``summary`` of the farm -> one value per root.  The value itself may be a sequence (of probabilities), so the rule is by the
+    ENTRIES: a list / tuple whose entries are all None, a bool or a sequence is one entry per root and must have ``n`` of them; a
+    sequence of bare numbers is ONE value, the probabilities of every root; a mixture of the two is refused"""
+    if isinstance(value, (list, tuple, np.ndarray)) and len(value) > 0:
+        slot = [v is None or isinstance(v, (bool, np.bool_, list, tuple, np.ndarray)) for v in value]
+        if all(slot):
+            return _per_root(list(value), n, "summary")
+        if any(slot):
+            raise ValueError("summary=%r: either probabilities (one value for every root) or one entry per root (None, True or a sequence of "
+                             "probabilities each), not a mixture" % (value,))
+    return [value] * n
+
+
 def _parse_wave(pool, device, wave_bytes, paths, lens, ms):
     """one wave: the files read into the staging buffer, uploaded and parsed -> (the C array of per-file results, the device tensor
     global token k is written to, {path: exception} of the files that could not be read)"""
@@ -200,7 +215,7 @@ class _Root(object):
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
                              require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto",
-                             information=None, jackknife=None):
+                             information=None, jackknife=None, summary=None):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -221,7 +236,12 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     delete-a-group error bars of every such root in ``info["jackknife"]``, as ``evidence_from_files(root, jackknife=...)`` returns them --
     the group ids of all asking roots of a wave come from ONE ``mce_jack_groups_dev`` call and their leave-one-group-out blocks from ONE
     ``mce_jack_leave_out_dev`` call; the ladders (whitening, searches, ``mce_jack_dotp_dev``) run root by root after the wave's batched
-    feed, and a root whose ladder raises fails alone.  Without a GPU: ``RuntimeError``."""
+    feed, and a root whose ladder raises fails alone.  ``summary`` (None, True or up to 7 probabilities for every root -- a sequence of bare numbers is ONE value; or one entry per
+    root, a list whose entries are each None, True or a sequence of probabilities, so ``[(0.9,), (0.5,)]`` and not ``[0.9, 0.5]`` gives two
+    roots one probability each; a list of such entries of another length, or a mixture, is a ``ValueError`` before any work): the
+    weighted means, standard deviations, equal-tailed limits and the best-fit sample of every such root's first ``ndim`` parameters in
+    ``info["summary"]`` -- ONE ``mce_param_summary_dev`` call per wave (and per set of probabilities) over all its ready roots, thinned
+    and unthinned alike, before the feed.  Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
     roots = list(roots)
@@ -238,11 +258,13 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     info_kw = [{"information": v} if _information.wanted(v) else {} for v in infos]      # (what a root takes with it to another route)
     jacks = _per_root(jackknife, n, "jackknife")
     jack_kw = [{} if v is None or v is False else {"jackknife": v} for v in jacks]
+    sums = _per_root_summary(summary, n)
+    sum_kw = [{"summary": v} if _summary.wanted(v) else {} for v in sums]
     common = dict(kmax=kmax, idchain=idchain, idpattern=idpattern, iw=iw, ilike=ilike, itheta=itheta)
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **extra)
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **sum_kw[i], **extra)
                 for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
@@ -268,7 +290,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
         if reason == _res.RESIDENT:
             try:
                 reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i],
-                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i])
+                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i])
             except ValueError as e:                # (thin_corr together with thinlen; a converge or jackknife value no route takes)
                 fail(i, e)
                 continue
@@ -421,6 +443,14 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                 asked = [r for r in ready if _information.wanted(infos[r.index])]
                 moms = dict(zip((r.index for r in asked),
                                 _res.moments_measure_dev([(r.problem[10], r.problem[9], r.problem[1]) for r in asked], device, stream.cuda_stream))) if asked else {}
+                # summary: the ready roots that ask for it in one call per set of probabilities, while the gathered rows are raw (the
+                # ladders below whiten them) (problem: params at 0, n1 at 1, nparam at 2, nd at 6, w at 9, fs at 10)
+                sblks = {}
+                for probs in sorted(set(_summary.spec(sums[r.index]) for r in ready if _summary.wanted(sums[r.index]))):
+                    sasked = [r for r in ready if _summary.wanted(sums[r.index]) and _summary.spec(sums[r.index]) == probs]
+                    sblks.update(zip((r.index for r in sasked),
+                                     _res.summary_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9], r.problem[10]) for r in sasked],
+                                                              _summary.targets(probs), device, stream.cuda_stream)))
                 # jackknife: the group ids of the ready roots that ask for it in one call, their leave-one-group-out blocks in another
                 # (src: the kept rows of a thinned root; fs only where the deleted sets' moments are wanted)
                 jasked = [r for r in ready if r.jack is not None]
@@ -457,6 +487,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                             inf["converge"] = r.conv
                         if r.index in moms:
                             inf["information"] = _information.build(moms[r.index], r.scal[0], out)
+                        if r.index in sblks:
+                            inf["summary"] = _summary.build(sblks[r.index], _summary.spec(sums[r.index]), r.scal[0],
+                                                            _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
                         if r.jack is not None:
                             pending.append((r, out, inf))
                             continue
@@ -488,6 +521,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             kw.update(conv_kw[i])
             kw.update(info_kw[i])
             kw.update(jack_kw[i])
+            kw.update(sum_kw[i])
             if covtype != "all":
                 kw["covtype"] = covtype
             if backend is not None:

@@ -24,6 +24,7 @@ import numpy as np
 
 from . import chains as _chains
 from . import information as _information
+from . import summary as _summary
 
 logger = logging.getLogger("mcevidence_amd")
 
@@ -67,7 +68,8 @@ class ResidentDecline(Exception):
 
 
 def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all", split=False, ndim=None, nparam=None,
-         distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None, converge=None, converge_by="auto", jackknife=None, nchains=None):
+         distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None, converge=None, converge_by="auto", jackknife=None, nchains=None,
+         summary=None):
     """``"resident"`` or the reason why the route declines.  A pure function of the call's keywords and of what is known
     about the data at the time (``ncols``: the files' column counts, ``nrows``: rows left after burn-in / thinning,
     ``nparam``: parameter columns; None: not known yet).  ``thin_corr`` (thinning by the measured autocorrelation length) is resident
@@ -75,7 +77,9 @@ def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all"
     ``converge_by`` (the Gelman-Rubin R-1 of the burned chains) are resident work too and decline nothing; a value they cannot take
     is the ValueError every route raises.  ``jackknife`` (the delete-a-group error bars; ``nchains``: the chains, where known) is resident
     work for an auto evidence; with a split it declines to the host route, which whitens s1 and s2 there; a number of groups or a
-    ``by`` it cannot take is the ValueError every route raises."""
+    ``by`` it cannot take is the ValueError every route raises.  ``summary`` (the posterior summary of the parameters) is resident work
+    and declines nothing; a value it cannot take is the ValueError every route raises."""
+    _summary.spec(summary)
     if not ischain:
         return REASONS["ischain"]
     _chains.thin_corr_scale(thin_corr, thinlen)
@@ -216,6 +220,18 @@ def moments_measure_dev(systems, device, stream):
     return [_information.from_block(b) for b in _capi.like_moments_dev(systems, ws.data_ptr(), wsb, stream)]
 
 
+def summary_measure_dev(systems, q, device, stream, pass_elems=0):
+    """ONE ``mce_param_summary_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
+    columns, device address of w, device address of fs)] and the targets ``q`` -> one ``summary.measure`` dict per system"""
+    import torch
+    from . import _capi
+    wsb = _capi.param_summary_workspace_bytes(sum(s[2] for s in systems), max(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(q),
+                                              pass_elems)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
+    blocks = _capi.param_summary_dev(systems, q, ws.data_ptr(), wsb, stream, pass_elems)
+    return [_summary.from_block(b, s[3], len(q)) for b, s in zip(blocks, systems)]
+
+
 # ---- the jackknife of a chain that stays on the device (docs/design/jackknife_resident.md; this module and farm.py) -----------------
 def jack_spec(jackknife, nchains=None):
     """None, or dict(groups, by, G) of the ``jackknife`` keyword: G is the number of groups (None while ``by="chains"`` does not
@@ -320,6 +336,8 @@ class ResidentChains(object):
         spec = _chains.converge_spec(converge, converge_by)
         self.converge = None
         self.information = None                            # (what the last evidence(information=True) found)
+        self.summary = None                                # (what the last evidence(summary=..) found)
+        self.names_root = None                             # (the root whose .paramnames file names the parameters, where there is one)
         self.jackknife = None                              # (what the last evidence(jackknife=...) found,
         self.jackknife_block = None                        #  and its leave-one-group-out block: _capi.JACK_LEAVE_OUT_FIELDS per slot)
         reason = plan(thinlen=thinlen, ncols=[t.shape[1] for t in tensors], distributed=_distributed())
@@ -539,7 +557,7 @@ class ResidentChains(object):
 
     # -- the estimator ---------------------------------------------------------------------------------------------------
     def evidence(self, kmax=5, ndim=None, priorvolume=1, covtype="all", pos_lnp=False, split=False, s1frac=0.5, split_rows=None,
-                 info=False, backend=None, information=None, jackknife=None):
+                 info=False, backend=None, information=None, jackknife=None, summary=None):
         """ln E as ``MCEvidence(...).evidence(...)`` returns it (``MLE[1:]``, and the info dict if ``info=True``; it
         carries ``info["route"] = "resident"``).  ``split=True``: the reference's random split, drawn on the host with the
         call ``MCSamples.chain_split`` makes (same RNG consumption); ``split_rows=(s1, s2)``: ``set_split``.
@@ -548,7 +566,10 @@ class ResidentChains(object):
         ``jackknife`` (None, True, a number of groups or dict(groups, by)): the delete-a-group error bars of the host route's
         ``evidence_jackknife`` in ``info["jackknife"]`` (and ``self.jackknife``) -- after the usual feed, whose result is returned
         unchanged, the gathered rows are whitened on the device, ``mce_jack_groups_dev`` forms the group ids, the ladder runs on device
-        tensors and ONE ``mce_jack_leave_out_dev`` call gives S_b, SumW_b and, with ``information``, the deleted sets' moments."""
+        tensors and ONE ``mce_jack_leave_out_dev`` call gives S_b, SumW_b and, with ``information``, the deleted sets' moments.
+        ``summary`` (None, True or up to 7 probabilities): the weighted means, standard deviations, equal-tailed limits and the best-fit
+        sample of the first ``ndim`` parameters in ``info["summary"]``, from one ``mce_param_summary_dev`` call on the gathered rows,
+        weights and fs -- BEFORE the feed and the jackknife ladder, while the rows are certainly raw (the ladder whitens them)."""
         from . import _capi
         from .evidence import HipBackend
         backend = backend or HipBackend()
@@ -560,6 +581,7 @@ class ResidentChains(object):
         if reason != RESIDENT:
             raise ResidentDecline(reason)
         jspec = jack_spec(jackknife, self.nchains)
+        probs = _summary.spec(summary)
         torch = self._torch
         ms = self.stats["ms"]
         with torch.cuda.device(self.device):
@@ -584,6 +606,12 @@ class ResidentChains(object):
             fs, (logLmax, SumW, nan_like, bad_w) = self._reduce(s1, pos_lnp)
             ms["reduce"] = _ms(t0)
             check_reduced(logLmax, SumW, nan_like, bad_w)
+            sblk = None
+            if probs is not None:
+                t0 = time.perf_counter()
+                sblk, = summary_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr(), fs.data_ptr())], _summary.targets(probs),
+                                            self.device, self._stream())
+                ms["summary"] = _ms(t0)
             t0 = time.perf_counter()
             with backend._scoped():
                 dotp, jac, _, _ = _capi.evidence_feed_part_dev(s1["params"].data_ptr(), n1, self.nparam, s2["params"].data_ptr() if cross else 0, n2,
@@ -604,6 +632,7 @@ class ResidentChains(object):
                 ms["jackknife"] = _ms(t0)
         out = mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, math.log(priorvolume), cross)[1:]
         self.information = None if mom is None else _information.build(mom, logLmax, out)
+        self.summary = None if sblk is None else _summary.build(sblk, probs, logLmax, _summary.param_names(self.names_root, nd))
         self.jackknife_block = jblock
         self.jackknife = None if jrun is None else jack_result(jrun, jblock, jspec, SumW, logLmax, n1, kmax, math.log(priorvolume))
         if self.jackknife is not None and self.information is not None:
@@ -619,13 +648,18 @@ class ResidentChains(object):
             inf["information"] = self.information
         if self.jackknife is not None:
             inf["jackknife"] = self.jackknife
+        if self.summary is not None:
+            inf["summary"] = self.summary
         return out, inf
 
 
 def log_information(inf):
-    """the information lines, before the ln(B) lines"""
+    """the information lines, then the summary lines, before the ln(B) lines"""
     if (inf or {}).get("information"):
         for line in _information.lines(inf["information"]):
+            logger.info(line)
+    if (inf or {}).get("summary"):
+        for line in _summary.lines(inf["summary"]):
             logger.info(line)
 
 
@@ -648,12 +682,14 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     covtype = "single" if covtype is None else covtype
     split = bool(ctor.get("split", False))
     _information.refuse(ctor.get("information"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
+    _summary.refuse(ctor.get("summary"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     reason = RESIDENT if _is_file_root(root) else REASONS["not_files"]
     if reason == RESIDENT:
         reason = plan(thinlen=ctor.get("thinlen", 0.0), isfunc=ctor.get("isfunc"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1),
                       verbose=max(ctor.get("verbose", 1), 2 if ctor.get("debug") else 0), covtype=covtype, split=split, ndim=None,
                       distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"),
-                      converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"), jackknife=ctor.get("jackknife"))
+                      converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"), jackknife=ctor.get("jackknife"),
+                      summary=ctor.get("summary"))
     if reason == RESIDENT:
         level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
         if not logging.getLogger().handlers:
@@ -666,10 +702,12 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
                                            idpattern=ctor.get("idpattern", "_?.txt"), thin_corr=ctor.get("thin_corr"),
                                            corr_min=ctor.get("corr_min", _chains.CORR_MIN), corr_max_lag=ctor.get("corr_max_lag", _chains.CORR_MAX_LAG),
                                            ndim=ctor.get("ndim"), converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"))
+            rc.names_root = root if isinstance(root, str) else None
             pv = call.get("pvolume")
             got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,
-                              backend=ctor.get("backend"), information=ctor.get("information"), jackknife=ctor.get("jackknife"))
+                              backend=ctor.get("backend"), information=ctor.get("information"), jackknife=ctor.get("jackknife"),
+                              summary=ctor.get("summary"))
             mle, inf = got
             if ctor.get("verbose", 1) > 0:
                 log_information(inf)

@@ -9,47 +9,45 @@
 
 namespace {
 
-struct ConvLayout {
-    size_t off_segs = 0, off_sys = 0, off_tiles = 0, off_tbad = 0, off_seg1 = 0, off_segbad = 0, off_seg2 = 0, off_centre = 0, off_partial = 0, off_Cs = 0,
-           off_Wn = 0, off_dn = 0, off_v = 0, off_evec = 0, off_scale = 0, off_lam = 0, off_stat1 = 0, off_stat2 = 0, off_T = 0, off_pp = 0, off_status = 0,
-           off_used = 0, off_pd = 0, off_res = 0, total = 0;
-    int64_t max_tiles = 0;
+// the workspace of a call: nrows rows in nseg segments of nsys systems, ndim columns
+struct ConvWs {
+    mce::ConvSeg* segs;
+    mce::ConvSys* sys;
+    double *tiles, *seg1, *seg2, *centre, *partial, *Cs, *Wn, *dn, *v, *evec, *scale, *lam, *T, *pp, *res;
+    int32_t *tbad, *segbad, *stat1, *stat2, *status, *used, *pd;
+    size_t total;
+    ConvWs(int64_t nrows, int32_t nseg, int32_t nsys, int32_t ndim, void* ws = nullptr)
+    {
+        const size_t max_tiles = (size_t)(nrows / mce::kConvTileRows + nseg);
+        const size_t nc = (size_t)ndim + 1, npair = (size_t)mce_conv::conv_npair(ndim), dd = (size_t)ndim * ndim, S = (size_t)nseg, Y = (size_t)nsys;
+        WsPlan P(ws);
+        segs = P.take<mce::ConvSeg>(S);
+        sys = P.take<mce::ConvSys>(Y);
+        tiles = P.take<double>(max_tiles * nc);
+        tbad = P.take<int32_t>(max_tiles * nc);
+        seg1 = P.take<double>(S * nc);
+        segbad = P.take<int32_t>(S * nc);
+        seg2 = P.take<double>(S * nc);
+        centre = P.take<double>(Y * ndim);
+        partial = P.take<double>(max_tiles * npair);
+        Cs = P.take<double>(S * npair);
+        Wn = P.take<double>(Y * dd);
+        dn = P.take<double>(S * ndim);
+        v = P.take<double>(S * ndim);
+        evec = P.take<double>(Y * dd);
+        scale = P.take<double>(Y * ndim);
+        lam = P.take<double>(Y * ndim);
+        stat1 = P.take<int32_t>(Y * mce_eig::kStatInts);
+        stat2 = P.take<int32_t>(Y * mce_eig::kStatInts);
+        T = P.take<double>(Y * dd);
+        pp = P.take<double>(Y * ndim);
+        status = P.take<int32_t>(Y * 2);
+        used = P.take<int32_t>(Y);
+        pd = P.take<int32_t>(Y);
+        res = P.take<double>(Y * ((size_t)ndim + 4));
+        total = P.total;
+    }
 };
-
-ConvLayout conv_layout(int64_t nrows, int32_t nseg, int32_t nsys, int32_t ndim)
-{
-    ConvLayout L;
-    L.max_tiles = nrows / mce::kConvTileRows + nseg;
-    const size_t nc = (size_t)ndim + 1, npair = (size_t)mce_conv::conv_npair(ndim), dd = (size_t)ndim * ndim, S = (size_t)nseg, Y = (size_t)nsys;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += prep_align(bytes); return at; };
-    L.off_segs = take(S * sizeof(mce::ConvSeg));
-    L.off_sys = take(Y * sizeof(mce::ConvSys));
-    L.off_tiles = take((size_t)L.max_tiles * nc * 8);
-    L.off_tbad = take((size_t)L.max_tiles * nc * 4);
-    L.off_seg1 = take(S * nc * 8);
-    L.off_segbad = take(S * nc * 4);
-    L.off_seg2 = take(S * nc * 8);
-    L.off_centre = take(Y * ndim * 8);
-    L.off_partial = take((size_t)L.max_tiles * npair * 8);
-    L.off_Cs = take(S * npair * 8);
-    L.off_Wn = take(Y * dd * 8);
-    L.off_dn = take(S * ndim * 8);
-    L.off_v = take(S * ndim * 8);
-    L.off_evec = take(Y * dd * 8);
-    L.off_scale = take(Y * ndim * 8);
-    L.off_lam = take(Y * ndim * 8);
-    L.off_stat1 = take(Y * mce_eig::kStatInts * 4);
-    L.off_stat2 = take(Y * mce_eig::kStatInts * 4);
-    L.off_T = take(Y * dd * 8);
-    L.off_pp = take(Y * ndim * 8);
-    L.off_status = take(Y * 2 * 4);
-    L.off_used = take(Y * 4);
-    L.off_pd = take(Y * 4);
-    L.off_res = take(Y * ((size_t)ndim + 4) * 8);
-    L.total = off;
-    return L;
-}
 
 // the argument checks of both forms, and the tables: seg_sys non-decreasing in 0 .. nsys - 1, at most MCE_CONV_MAX_SEGMENTS segments
 // and at least two with rows per system
@@ -100,7 +98,7 @@ extern "C" {
 size_t mce_chain_conv_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t nsys, int32_t ndim)
 {
     if (nrows_total < 0 || nseg < 1 || nsys < 1 || nsys > (1 << 20) || nseg > (1 << 24) || ndim < 1 || ndim > mce_conv::kConvMaxDim) return 0;
-    return conv_layout(nrows_total, nseg, nsys, ndim).total;
+    return ConvWs(nrows_total, nseg, nsys, ndim).total;
 }
 
 int mce_chain_conv_dev(const mce_chain_part* segs, const int32_t* seg_sys, int32_t nseg, int32_t nsys, int64_t ncols, int32_t iw, int32_t itheta,
@@ -114,71 +112,46 @@ int mce_chain_conv_dev(const mce_chain_part* segs, const int32_t* seg_sys, int32
     int rc = conv_tables(segs, seg_sys, nseg, nsys, ncols, iw, itheta, ndim, table, systems, nrows, ntiles);
     if (rc != MCE_OK) return rc;
     if (!ws) return fail(MCE_ERR_INVALID, "null pointer argument");
-    const ConvLayout L = conv_layout(nrows, nseg, nsys, ndim);
-    if (ws_bytes < L.total) return fail(MCE_ERR_WORKSPACE, "chain conv: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+    const ConvWs W(nrows, nseg, nsys, ndim, ws);
+    if (ws_bytes < W.total) return fail(MCE_ERR_WORKSPACE, "chain conv: workspace of %zu bytes, %zu needed", ws_bytes, W.total);
     if ((rc = prep_need_device()) != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
 
-    ConvSeg* d_segs = prep_at<ConvSeg>(ws, L.off_segs);
-    ConvSys* d_sys = prep_at<ConvSys>(ws, L.off_sys);
-    double* d_tiles = prep_at<double>(ws, L.off_tiles);
-    int32_t* d_tbad = prep_at<int32_t>(ws, L.off_tbad);
-    double* d_seg1 = prep_at<double>(ws, L.off_seg1);
-    int32_t* d_segbad = prep_at<int32_t>(ws, L.off_segbad);
-    double* d_seg2 = prep_at<double>(ws, L.off_seg2);
-    double* d_centre = prep_at<double>(ws, L.off_centre);
-    double* d_partial = prep_at<double>(ws, L.off_partial);
-    double* d_Cs = prep_at<double>(ws, L.off_Cs);
-    double* d_Wn = prep_at<double>(ws, L.off_Wn);
-    double* d_dn = prep_at<double>(ws, L.off_dn);
-    double* d_v = prep_at<double>(ws, L.off_v);
-    double* d_evec = prep_at<double>(ws, L.off_evec);
-    double* d_scale = prep_at<double>(ws, L.off_scale);
-    double* d_lam = prep_at<double>(ws, L.off_lam);
-    int32_t* d_stat1 = prep_at<int32_t>(ws, L.off_stat1);
-    int32_t* d_stat2 = prep_at<int32_t>(ws, L.off_stat2);
-    double* d_T = prep_at<double>(ws, L.off_T);
-    double* d_pp = prep_at<double>(ws, L.off_pp);
-    int32_t* d_status = prep_at<int32_t>(ws, L.off_status);
-    int32_t* d_used = prep_at<int32_t>(ws, L.off_used);
-    int32_t* d_pd = prep_at<int32_t>(ws, L.off_pd);
-    double* d_res = prep_at<double>(ws, L.off_res);
-
-    MCE_HIP(hipMemcpyAsync(d_segs, table.data(), table.size() * sizeof(ConvSeg), hipMemcpyHostToDevice, st));
-    MCE_HIP(hipMemcpyAsync(d_sys, systems.data(), systems.size() * sizeof(ConvSys), hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemcpyAsync(W.segs, table.data(), table.size() * sizeof(ConvSeg), hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemcpyAsync(W.sys, systems.data(), systems.size() * sizeof(ConvSys), hipMemcpyHostToDevice, st));
     const int nc = ndim + 1, npair = mce_conv::conv_npair(ndim);
     int cl = 1;
     while (cl < nc) cl <<= 1;
     auto grid = [](int64_t work) { return dim3((unsigned)((work + kConvThreads - 1) / kConvThreads)); };
     const dim3 tb(kConvThreads);
     // steps 1, 2: the sums, the centre, the sums about the centre
-    hipLaunchKernelGGL(conv_sum_tile_kernel, dim3((unsigned)ntiles), tb, 0, st, d_segs, (int)nseg, ncols, (int)iw, (int)itheta, (int)ndim, cl,
-                       (const double*)nullptr, d_tiles, d_tbad);
-    hipLaunchKernelGGL(conv_sum_final_kernel, grid((int64_t)nseg * nc), tb, 0, st, d_segs, (int)nseg, (int)ndim, d_tiles, d_tbad, d_seg1, d_segbad);
-    hipLaunchKernelGGL(conv_centre_kernel, grid((int64_t)nsys * ndim), tb, 0, st, d_sys, (int)nsys, (int)ndim, d_seg1, d_centre);
-    hipLaunchKernelGGL(conv_sum_tile_kernel, dim3((unsigned)ntiles), tb, 0, st, d_segs, (int)nseg, ncols, (int)iw, (int)itheta, (int)ndim, cl, d_centre, d_tiles,
+    hipLaunchKernelGGL(conv_sum_tile_kernel, dim3((unsigned)ntiles), tb, 0, st, W.segs, (int)nseg, ncols, (int)iw, (int)itheta, (int)ndim, cl,
+                       (const double*)nullptr, W.tiles, W.tbad);
+    hipLaunchKernelGGL(conv_sum_final_kernel, grid((int64_t)nseg * nc), tb, 0, st, W.segs, (int)nseg, (int)ndim, W.tiles, W.tbad, W.seg1, W.segbad);
+    hipLaunchKernelGGL(conv_centre_kernel, grid((int64_t)nsys * ndim), tb, 0, st, W.sys, (int)nsys, (int)ndim, W.seg1, W.centre);
+    hipLaunchKernelGGL(conv_sum_tile_kernel, dim3((unsigned)ntiles), tb, 0, st, W.segs, (int)nseg, ncols, (int)iw, (int)itheta, (int)ndim, cl, W.centre, W.tiles,
                        (int32_t*)nullptr);
-    hipLaunchKernelGGL(conv_sum_final_kernel, grid((int64_t)nseg * nc), tb, 0, st, d_segs, (int)nseg, (int)ndim, d_tiles, (const int32_t*)nullptr, d_seg2,
+    hipLaunchKernelGGL(conv_sum_final_kernel, grid((int64_t)nseg * nc), tb, 0, st, W.segs, (int)nseg, (int)ndim, W.tiles, (const int32_t*)nullptr, W.seg2,
                        (int32_t*)nullptr);
     // step 4
     const int nbd = (ndim + kConvBlock - 1) / kConvBlock, nblk = nbd * (nbd + 1) / 2;
-    hipLaunchKernelGGL(conv_moment_kernel, dim3((unsigned)ntiles, (unsigned)((nblk + kConvThreads - 1) / kConvThreads)), tb, 0, st, d_segs, (int)nseg, ncols, (int)iw,
-                       (int)itheta, (int)ndim, d_centre, d_seg1, d_seg2, d_partial);
-    hipLaunchKernelGGL(conv_moment_final_kernel, grid((int64_t)nseg * npair), tb, 0, st, d_segs, (int)nseg, (int)ndim, d_seg1, d_partial, d_Cs);
+    hipLaunchKernelGGL(conv_moment_kernel, dim3((unsigned)ntiles, (unsigned)((nblk + kConvThreads - 1) / kConvThreads)), tb, 0, st, W.segs, (int)nseg, ncols, (int)iw,
+                       (int)itheta, (int)ndim, W.centre, W.seg1, W.seg2, W.partial);
+    hipLaunchKernelGGL(conv_moment_final_kernel, grid((int64_t)nseg * npair), tb, 0, st, W.segs, (int)nseg, (int)ndim, W.seg1, W.partial, W.Cs);
     // steps 3, 5, 6, 7
-    hipLaunchKernelGGL(conv_system_kernel, dim3((unsigned)nsys), tb, 0, st, d_segs, d_sys, (int)ndim, d_seg1, d_segbad, d_seg2, d_Cs, d_Wn, d_dn, d_pp, d_status,
-                       d_used);
+    hipLaunchKernelGGL(conv_system_kernel, dim3((unsigned)nsys), tb, 0, st, W.segs, W.sys, (int)ndim, W.seg1, W.segbad, W.seg2, W.Cs, W.Wn, W.dn, W.pp, W.status,
+                       W.used);
     MCE_HIP(hipGetLastError());
-    if ((rc = launch_eig(d_Wn, ndim, nsys, d_evec, d_scale, d_lam, d_stat1, st)) != MCE_OK) return rc;
+    if ((rc = launch_eig(W.Wn, ndim, nsys, W.evec, W.scale, W.lam, W.stat1, st)) != MCE_OK) return rc;
     // step 8
-    hipLaunchKernelGGL(conv_t_kernel, dim3((unsigned)nsys), tb, 0, st, d_sys, (int)ndim, d_dn, d_evec, d_scale, d_lam, d_stat1, d_used, d_v, d_T, d_pd);
+    hipLaunchKernelGGL(conv_t_kernel, dim3((unsigned)nsys), tb, 0, st, W.sys, (int)ndim, W.dn, W.evec, W.scale, W.lam, W.stat1, W.used, W.v, W.T, W.pd);
     MCE_HIP(hipGetLastError());
-    if ((rc = launch_eig(d_T, ndim, nsys, d_evec, d_scale, d_lam, d_stat2, st)) != MCE_OK) return rc;
-    hipLaunchKernelGGL(conv_result_kernel, grid((int64_t)nsys * (ndim + 4)), tb, 0, st, (int)nsys, (int)ndim, d_lam, d_stat1, d_pd, d_stat2, d_status, d_used, d_pp,
-                       d_res);
+    if ((rc = launch_eig(W.T, ndim, nsys, W.evec, W.scale, W.lam, W.stat2, st)) != MCE_OK) return rc;
+    hipLaunchKernelGGL(conv_result_kernel, grid((int64_t)nsys * (ndim + 4)), tb, 0, st, (int)nsys, (int)ndim, W.lam, W.stat1, W.pd, W.stat2, W.status, W.used, W.pp,
+                       W.res);
     MCE_HIP(hipGetLastError());
     std::vector<double> res((size_t)nsys * (ndim + 4));
-    MCE_HIP(hipMemcpyAsync(res.data(), d_res, res.size() * 8, hipMemcpyDeviceToHost, st));
+    MCE_HIP(hipMemcpyAsync(res.data(), W.res, res.size() * 8, hipMemcpyDeviceToHost, st));
     MCE_HIP(hipStreamSynchronize(st));                            // the one wait
     for (int32_t y = 0; y < nsys; ++y) {
         const double* r = res.data() + (size_t)y * (ndim + 4);

@@ -18,32 +18,37 @@ constexpr int64_t kCorrChunkBudget = 4096;
 
 int64_t corr_chunks_per_part(int32_t nparts) { return nparts <= 64 ? kCorrChunksPerPart : std::max<int64_t>(1, kCorrChunkBudget / nparts); }
 
-struct CorrLayout {
-    size_t off_sel = 0, off_parts = 0, off_ends = 0, off_mtiles = 0, off_mean = 0, off_ntau = 0, off_S = 0, off_rho = 0, off_state = 0, off_partial = 0, total = 0;
-    int64_t lag_rows = 0, max_chunks = 0, mean_chunks = 0;
+// the workspace of a chain of n rows in nparts parts, ndim columns, lags up to max_lag: the select workspace of the chain first
+struct CorrWs {
+    char* sel;
+    size_t sel_bytes;
+    mce::CorrPart* parts;
+    long long* ends;
+    double *mtiles, *mean, *ntau, *S, *rho;
+    mce::CorrState* state;
+    double* partial;
+    size_t total;
+    int64_t lag_rows, max_chunks, mean_chunks;
+    CorrWs(int64_t n, int32_t nparts, int32_t ndim, int64_t max_lag, void* ws = nullptr)
+    {
+        lag_rows = max_lag + 1 + kCorrMaxLaunchLags;             // (a window may run past the cap; its lags are summed and not used)
+        max_chunks = (int64_t)nparts * corr_chunks_per_part(nparts);
+        mean_chunks = n / mce::kCorrMeanRows + nparts;
+        sel_bytes = PrepWs(n, nparts).total;
+        WsPlan P(ws);
+        sel = P.take_bytes<char>(sel_bytes);
+        parts = P.take<mce::CorrPart>((size_t)nparts);
+        ends = P.take<long long>((size_t)nparts);
+        mtiles = P.take<double>((size_t)mean_chunks * ndim * 3);
+        mean = P.take<double>((size_t)nparts * ndim);
+        ntau = P.take<double>((size_t)lag_rows);
+        S = P.take<double>((size_t)lag_rows * ndim);
+        rho = P.take<double>((size_t)lag_rows * ndim);
+        state = P.take<mce::CorrState>((size_t)ndim);
+        partial = P.take<double>((size_t)max_chunks * ndim * kCorrMaxLaunchLags);
+        total = P.total;
+    }
 };
-
-CorrLayout corr_layout(int64_t n, int32_t nparts, int32_t ndim, int64_t max_lag)
-{
-    CorrLayout L;
-    L.lag_rows = max_lag + 1 + kCorrMaxLaunchLags;               // (a window may run past the cap; its lags are summed and not used)
-    L.max_chunks = (int64_t)nparts * corr_chunks_per_part(nparts);
-    L.mean_chunks = n / mce::kCorrMeanRows + nparts;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += prep_align(bytes); return at; };
-    L.off_sel = take(prep_layout(n, nparts).total);
-    L.off_parts = take((size_t)nparts * sizeof(mce::CorrPart));
-    L.off_ends = take((size_t)nparts * 8);
-    L.off_mtiles = take((size_t)L.mean_chunks * ndim * 3 * 8);
-    L.off_mean = take((size_t)nparts * ndim * 8);
-    L.off_ntau = take((size_t)L.lag_rows * 8);
-    L.off_S = take((size_t)L.lag_rows * ndim * 8);
-    L.off_rho = take((size_t)L.lag_rows * ndim * 8);
-    L.off_state = take((size_t)ndim * sizeof(mce::CorrState));
-    L.off_partial = take((size_t)L.max_chunks * ndim * kCorrMaxLaunchLags * 8);
-    L.total = off;
-    return L;
-}
 
 int corr_check_scalars(int64_t ncols, int32_t iw, int32_t itheta, int32_t ndim, double min_corr, int64_t max_lag)
 {
@@ -64,7 +69,7 @@ extern "C" {
 size_t mce_chain_corr_workspace_bytes(int64_t n, int32_t nparts, int32_t ndim, int64_t max_lag)
 {
     if (n < 0 || nparts < 1 || nparts > kPrepMaxParts || ndim < 1 || ndim > mce::kCorrMaxDim || max_lag < 1 || max_lag > kCorrMaxLagArg) return 0;
-    return corr_layout(n, nparts, ndim, max_lag).total;
+    return CorrWs(n, nparts, ndim, max_lag).total;
 }
 
 int mce_chain_corr_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncols, int32_t iw, int32_t itheta, int32_t ndim, double min_corr,
@@ -79,7 +84,7 @@ int mce_chain_corr_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncol
     if (rc != MCE_OK) return rc;
     if ((rc = corr_check_scalars(ncols, iw, itheta, ndim, min_corr, max_lag)) != MCE_OK) return rc;
     if (n < 1) return fail(MCE_ERR_INVALID, "chain corr: no rows");
-    const CorrLayout L = corr_layout(n, nparts, ndim, max_lag);
+    const CorrWs L(n, nparts, ndim, max_lag, ws);
     if (ws_bytes < L.total) return fail(MCE_ERR_WORKSPACE, "chain corr: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
     if ((rc = prep_need_device()) != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -87,22 +92,20 @@ int mce_chain_corr_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncol
     for (int32_t j = 0; j < ndim; ++j) { length[j] = 0.0; cut[j] = 0; }
 
     // ---- units: the weights, their prefix sums and the rule, as for thinlen = 2 ----------------------------------------------------------
-    char* sel = prep_at<char>(ws, L.off_sel);
-    const PrepLayout PL = prep_layout(n, nparts);
+    const PrepWs PL(n, nparts, L.sel);
     double totals[5];
-    rc = mce_chain_weights_dev(parts, nparts, ncols, iw, mce_corr::kCorrRuleThinlen, rule, totals, sel, PL.total, stream);
+    rc = mce_chain_weights_dev(parts, nparts, ncols, iw, mce_corr::kCorrRuleThinlen, rule, totals, L.sel, L.sel_bytes, stream);
     if (rc != MCE_OK) return rc;
     if (*rule < 0) return MCE_OK;                                  // a decline: the caller words it
     const int integer = *rule == mce_prep::kRuleInteger ? 1 : 0;
-    const PrepPart* d_prep = reinterpret_cast<const PrepPart*>(sel + PL.off_parts);
-    const long long* d_c = reinterpret_cast<const long long*>(sel + PL.off_c);
+    const PrepPart* d_prep = PL.parts;
+    const long long* d_c = PL.c;
     const int np = (int)table.size();
     std::vector<long long> ends((size_t)np, 0);
     if (integer) {
-        long long* d_ends = prep_at<long long>(ws, L.off_ends);
-        hipLaunchKernelGGL(corr_ends_kernel, dim3((np + kCorrThreads - 1) / kCorrThreads), dim3(kCorrThreads), 0, st, d_prep, np, d_c, d_ends);
+        hipLaunchKernelGGL(corr_ends_kernel, dim3((np + kCorrThreads - 1) / kCorrThreads), dim3(kCorrThreads), 0, st, d_prep, np, d_c, L.ends);
         MCE_HIP(hipGetLastError());
-        MCE_HIP(hipMemcpyAsync(ends.data(), d_ends, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+        MCE_HIP(hipMemcpyAsync(ends.data(), L.ends, (size_t)np * 8, hipMemcpyDeviceToHost, st));
         MCE_HIP(hipStreamSynchronize(st));
     }
     const int64_t cpp = corr_chunks_per_part(nparts);
@@ -137,28 +140,20 @@ int mce_chain_corr_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncol
     }
 
     // ---- (a) the centring values -----------------------------------------------------------------------------------------------------------
-    CorrPart* d_parts = prep_at<CorrPart>(ws, L.off_parts);
-    double* d_mtiles = prep_at<double>(ws, L.off_mtiles);
-    double* d_mean = prep_at<double>(ws, L.off_mean);
-    double* d_ntau = prep_at<double>(ws, L.off_ntau);
-    double* d_S = prep_at<double>(ws, L.off_S);
-    double* d_rho = prep_at<double>(ws, L.off_rho);
-    CorrState* d_state = prep_at<CorrState>(ws, L.off_state);
-    double* d_partial = prep_at<double>(ws, L.off_partial);
     std::vector<double> ntau((size_t)L.lag_rows, 0.0);
     for (int64_t t = 0; t < L.lag_rows; ++t) {
         int64_t cnt = 0;
         for (int p = 0; p < np; ++p) cnt += std::max<int64_t>(part_units[(size_t)p] - t, 0);
         ntau[(size_t)t] = (double)cnt;
     }
-    MCE_HIP(hipMemcpyAsync(d_parts, cp.data(), cp.size() * sizeof(CorrPart), hipMemcpyHostToDevice, st));
-    MCE_HIP(hipMemcpyAsync(d_ntau, ntau.data(), ntau.size() * 8, hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemcpyAsync(L.parts, cp.data(), cp.size() * sizeof(CorrPart), hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemcpyAsync(L.ntau, ntau.data(), ntau.size() * 8, hipMemcpyHostToDevice, st));
     int cl = 1;
     while (cl < ndim) cl <<= 1;
-    hipLaunchKernelGGL(corr_mean_tile_kernel, dim3((unsigned)mchunks), dim3(kCorrThreads), 0, st, d_parts, np, ncols, (int)iw, (int)itheta, (int)ndim, cl, integer,
-                       d_mtiles);
-    hipLaunchKernelGGL(corr_mean_final_kernel, dim3((unsigned)(((int64_t)np * ndim + kCorrThreads - 1) / kCorrThreads)), dim3(kCorrThreads), 0, st, d_parts, np,
-                       (int)ndim, d_mtiles, d_mean);
+    hipLaunchKernelGGL(corr_mean_tile_kernel, dim3((unsigned)mchunks), dim3(kCorrThreads), 0, st, L.parts, np, ncols, (int)iw, (int)itheta, (int)ndim, cl, integer,
+                       L.mtiles);
+    hipLaunchKernelGGL(corr_mean_final_kernel, dim3((unsigned)(((int64_t)np * ndim + kCorrThreads - 1) / kCorrThreads)), dim3(kCorrThreads), 0, st, L.parts, np,
+                       (int)ndim, L.mtiles, L.mean);
     MCE_HIP(hipGetLastError());
 
     // ---- (b), (c): windows of lags until every column has its cut --------------------------------------------------------------------------
@@ -174,14 +169,14 @@ int mce_chain_corr_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncol
         for (int64_t t = tau0; t <= tau1; t += kCorrMaxLaunchLags) {          // (the last launch may run up to 255 lags past the cap: summed, not used)
             const int nsub = (int)std::min<int64_t>(kCorrMaxLaunchLags / kCorrWin, (tau1 + 1 - t + kCorrWin - 1) / kCorrWin);
             const int nlag = nsub * kCorrWin;
-            hipLaunchKernelGGL(corr_lag_kernel, dim3((unsigned)nchunks, colgroups, (unsigned)nsub), dim3(kCorrThreads), 0, st, d_parts, np, d_c, integer, ncols,
-                               (int)itheta, (int)ndim, d_mean, t, nlag, d_partial);
-            hipLaunchKernelGGL(corr_reduce_kernel, dim3((unsigned)(((int64_t)ndim * nlag + kCorrThreads - 1) / kCorrThreads)), dim3(kCorrThreads), 0, st, d_partial,
-                               nchunks, (int)ndim, nlag, t, d_S);
+            hipLaunchKernelGGL(corr_lag_kernel, dim3((unsigned)nchunks, colgroups, (unsigned)nsub), dim3(kCorrThreads), 0, st, L.parts, np, d_c, integer, ncols,
+                               (int)itheta, (int)ndim, L.mean, t, nlag, L.partial);
+            hipLaunchKernelGGL(corr_reduce_kernel, dim3((unsigned)(((int64_t)ndim * nlag + kCorrThreads - 1) / kCorrThreads)), dim3(kCorrThreads), 0, st, L.partial,
+                               nchunks, (int)ndim, nlag, t, L.S);
         }
-        hipLaunchKernelGGL(corr_scan_kernel, dim3(1), dim3(kCorrThreads), 0, st, d_S, d_ntau, (int)ndim, tau0, tau1, min_corr, d_rho, d_state);
+        hipLaunchKernelGGL(corr_scan_kernel, dim3(1), dim3(kCorrThreads), 0, st, L.S, L.ntau, (int)ndim, tau0, tau1, min_corr, L.rho, L.state);
         MCE_HIP(hipGetLastError());
-        MCE_HIP(hipMemcpyAsync(state.data(), d_state, state.size() * sizeof(CorrState), hipMemcpyDeviceToHost, st));
+        MCE_HIP(hipMemcpyAsync(state.data(), L.state, state.size() * sizeof(CorrState), hipMemcpyDeviceToHost, st));
         MCE_HIP(hipStreamSynchronize(st));
         *rho_rows = tau1 + 1;
         for (int32_t j = 0; j < ndim; ++j) { s0[(size_t)j] = state[(size_t)j].s0; cuts[(size_t)j] = state[(size_t)j].cut; }
@@ -199,7 +194,7 @@ int mce_chain_corr_dev(const mce_chain_part* parts, int32_t nparts, int64_t ncol
         length[j] = mce_corr::corr_length(col);
     }
     if (rho) {
-        MCE_HIP(hipMemcpyAsync(rho, d_rho, (size_t)*rho_rows * ndim * 8, hipMemcpyDeviceToHost, st));
+        MCE_HIP(hipMemcpyAsync(rho, L.rho, (size_t)*rho_rows * ndim * 8, hipMemcpyDeviceToHost, st));
         MCE_HIP(hipStreamSynchronize(st));
     }
     return MCE_OK;

@@ -296,26 +296,27 @@ int mce_chain_farm_stats(void* handle, double* stats, int32_t nstats)
 // ---- preparation of the unthinned roots of a wave -------------------------------------------------------------------------------------
 namespace {
 
-struct FarmPrepLayout {
-    int64_t nrows = 0, ntiles = 0;
-    size_t off_tab = 0, ntab = 0, off_tile[3] = {0, 0, 0}, off_red = 0, total = 0;
+// the workspace of nroots roots of nparts parts and nrows rows in all.  The tables take 6 (nroots + 1) + 3 nparts words; a root of n
+// rows has ceil(n / 512) tiles: at most nrows / 512 + nroots in all
+struct FarmPrepWs {
+    int64_t* tab;
+    double *tile_max, *tile_sumw;
+    long long* tile_bad;
+    double* red;
+    size_t total;
+    int64_t ntiles;
+    FarmPrepWs(int32_t nroots, int32_t nparts, int64_t nrows, void* ws = nullptr)
+    {
+        ntiles = nrows / mce::kPrepTile + nroots;
+        WsPlan P(ws);
+        tab = P.take<int64_t>((size_t)6 * ((size_t)nroots + 1) + (size_t)3 * (size_t)nparts);
+        tile_max = P.take<double>((size_t)ntiles);
+        tile_sumw = P.take<double>((size_t)ntiles);
+        tile_bad = P.take<long long>((size_t)ntiles);
+        red = P.take<double>((size_t)nroots * 4);
+        total = P.total;
+    }
 };
-
-// the tables take 6 (nroots + 1) + 3 nparts words; a root of n rows has ceil(n / 512) tiles: at most nrows / 512 + nroots in all
-FarmPrepLayout farm_prep_layout(int32_t nroots, int32_t nparts, int64_t nrows)
-{
-    FarmPrepLayout L;
-    L.nrows = nrows;
-    L.ntiles = nrows / mce::kPrepTile + nroots;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += prep_align(bytes); return at; };
-    L.ntab = (size_t)6 * ((size_t)nroots + 1) + (size_t)3 * (size_t)nparts;
-    L.off_tab = take(L.ntab * 8);
-    for (int k = 0; k < 3; ++k) L.off_tile[k] = take((size_t)L.ntiles * 8);
-    L.off_red = take((size_t)nroots * 4 * sizeof(double));
-    L.total = off;
-    return L;
-}
 
 constexpr int32_t kFarmMaxRoots = 1 << 20;
 
@@ -326,7 +327,7 @@ extern "C" {
 size_t mce_chain_farm_prep_workspace_bytes(int32_t nroots, int32_t nparts, int64_t nrows)
 {
     if (nroots < 1 || nroots > kFarmMaxRoots || nparts < 1 || nparts > kFarmMaxFiles || nrows < 0) return 0;
-    return farm_prep_layout(nroots, nparts, nrows).total;
+    return FarmPrepWs(nroots, nparts, nrows).total;
 }
 
 int mce_chain_farm_prep_dev(const int32_t* root_nparts, const int64_t* root_ncols, int32_t nroots, const mce_chain_part* parts, int32_t nparts, int32_t iw,
@@ -367,23 +368,21 @@ int mce_chain_farm_prep_dev(const int32_t* root_nparts, const int64_t* root_ncol
         param0[r + 1] = param0[r] + n * (nc - itheta);
     }
     if (p != nparts) return fail(MCE_ERR_INVALID, "chain farm prep: the roots own %lld of %d parts", (long long)p, nparts);
-    const FarmPrepLayout L = farm_prep_layout(nroots, nparts, row0[nroots]);
+    const FarmPrepWs L(nroots, nparts, row0[nroots], ws);
     if (ws_bytes < L.total) return fail(MCE_ERR_WORKSPACE, "chain farm prep: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
     if (tile0[nroots] > L.ntiles) return fail(MCE_ERR_INVALID, "chain farm prep: %lld tiles, room for %lld", (long long)tile0[nroots], (long long)L.ntiles);
     int rc = prep_need_device();
     if (rc != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int64_t* d_tab = prep_at<int64_t>(ws, L.off_tab);
+    int64_t* const d_tab = L.tab;
     MCE_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     FarmTables t;
     t.row0 = d_tab; t.tile0 = d_tab + R; t.part0 = d_tab + 2 * R; t.elem0 = d_tab + 3 * R; t.param0 = d_tab + 4 * R; t.ncols = d_tab + 5 * R;
     t.part_first = d_tab + 6 * R; t.part_rows = t.part_first + nparts;
     t.part_ptr = reinterpret_cast<const double* const*>(t.part_rows + nparts);
     t.nroots = nroots; t.nparts = nparts;
-    double* tile_max = prep_at<double>(ws, L.off_tile[0]);
-    double* tile_sumw = prep_at<double>(ws, L.off_tile[1]);
-    long long* tile_bad = prep_at<long long>(ws, L.off_tile[2]);
-    double* red = prep_at<double>(ws, L.off_red);
+    double *const tile_max = L.tile_max, *const tile_sumw = L.tile_sumw, *const red = L.red;
+    long long* const tile_bad = L.tile_bad;
     hipLaunchKernelGGL(farm_gather_kernel, dim3(prep_grid(elem0[nroots], kPrepThreads)), dim3(kPrepThreads), 0, st, t, iw, ilike, itheta, d_params, d_w, d_like);
     hipLaunchKernelGGL(farm_like_tile_kernel, dim3(prep_grid(tile0[nroots], 1)), dim3(kPrepThreads), 0, st, t, d_like, d_w, pos_lnp ? 1 : 0, tile_max, tile_sumw, tile_bad);
     hipLaunchKernelGGL(farm_like_final_kernel, dim3(prep_grid(nroots, 1)), dim3(kPrepThreads), 0, st, t, tile_max, tile_sumw, tile_bad, red);

@@ -9,25 +9,26 @@
 
 namespace {
 
-struct JackLayout {
-    size_t off_partial = 0, off_flags = 0, off_cnt = 0, off_off = 0, off_bad = 0, total = 0;
-    int64_t nblocks = 0;
+// the workspace of nq queries, G groups and kmax columns
+struct JackWs {
+    double* partial;
+    int *flags, *cnt;
+    int64_t* boff;
+    int* bad;
+    size_t total;
+    int64_t nblocks;
+    JackWs(int64_t nq, int32_t G, int32_t kmax, void* ws = nullptr)
+    {
+        nblocks = std::max<int64_t>((nq + mce::kRedThreads - 1) / mce::kRedThreads, 1);
+        WsPlan P(ws);
+        partial = P.take<double>((size_t)nblocks * (size_t)(G + 1) * (size_t)kmax);
+        flags = P.take<int>((size_t)std::max<int64_t>(nq, 1));
+        cnt = P.take<int>((size_t)nblocks);
+        boff = P.take<int64_t>((size_t)nblocks);
+        bad = P.take<int>(1);
+        total = P.total;
+    }
 };
-
-JackLayout jack_layout(int64_t nq, int32_t G, int32_t kmax)
-{
-    JackLayout L;
-    L.nblocks = std::max<int64_t>((nq + mce::kRedThreads - 1) / mce::kRedThreads, 1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes, 256); return at; };
-    L.off_partial = take((size_t)L.nblocks * (size_t)(G + 1) * (size_t)kmax * sizeof(double));
-    L.off_flags = take((size_t)std::max<int64_t>(nq, 1) * sizeof(int));
-    L.off_cnt = take((size_t)L.nblocks * sizeof(int));
-    L.off_off = take((size_t)L.nblocks * sizeof(int64_t));
-    L.off_bad = take(sizeof(int));
-    L.total = off;
-    return L;
-}
 
 int jack_check_scalars(int64_t nq, int32_t L, int64_t nr, int32_t G, int32_t k0, int32_t kmax, int32_t d)
 {
@@ -47,7 +48,7 @@ extern "C" {
 size_t mce_jack_workspace_bytes(int64_t nq, int32_t G, int32_t kmax)
 {
     if (nq < 1 || G < 2 || G > MCE_JACK_MAX_GROUPS || kmax < 1 || kmax > MCE_MAX_K + 1) return 0;
-    return jack_layout(nq, G, kmax).total;
+    return JackWs(nq, G, kmax).total;
 }
 
 int mce_jack_dotp_dev(const double* d_dist, const int64_t* d_idx, int64_t nq, int32_t L, const int64_t* d_qid, const int32_t* d_gq,
@@ -60,37 +61,32 @@ int mce_jack_dotp_dev(const double* d_dist, const int64_t* d_idx, int64_t nq, in
         return fail(MCE_ERR_INVALID, "null pointer argument");
     int rc = jack_check_scalars(nq, L, nr, G, k0, kmax, d);
     if (rc != MCE_OK) return rc;
-    const JackLayout lay = jack_layout(nq, G, kmax);
+    const JackWs lay(nq, G, kmax, ws);
     if (ws_bytes < lay.total) return fail(MCE_ERR_WORKSPACE, "jackknife: workspace of %zu bytes, %zu needed", ws_bytes, lay.total);
     if ((rc = prep_need_device()) != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    double* partial = prep_at<double>(ws, lay.off_partial);
-    int* flags = prep_at<int>(ws, lay.off_flags);
-    int* cnt = prep_at<int>(ws, lay.off_cnt);
-    int64_t* boff = prep_at<int64_t>(ws, lay.off_off);
-    int* bad = prep_at<int>(ws, lay.off_bad);
 
-    MCE_HIP(zero_async(bad, sizeof(int), st));
-    hipLaunchKernelGGL(jack_check_groups_kernel, dim3((unsigned)lay.nblocks), dim3(kRedThreads), 0, st, d_gq, nq, (int)G, bad);
-    hipLaunchKernelGGL(jack_check_groups_kernel, dim3((unsigned)((nr + kRedThreads - 1) / kRedThreads)), dim3(kRedThreads), 0, st, d_gr, nr, (int)G, bad);
+    MCE_HIP(zero_async(lay.bad, sizeof(int), st));
+    hipLaunchKernelGGL(jack_check_groups_kernel, dim3((unsigned)lay.nblocks), dim3(kRedThreads), 0, st, d_gq, nq, (int)G, lay.bad);
+    hipLaunchKernelGGL(jack_check_groups_kernel, dim3((unsigned)((nr + kRedThreads - 1) / kRedThreads)), dim3(kRedThreads), 0, st, d_gr, nr, (int)G, lay.bad);
     MCE_HIP(hipGetLastError());
     int bad_h = 0;
-    MCE_HIP(hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    MCE_HIP(hipMemcpyAsync(&bad_h, lay.bad, sizeof(int), hipMemcpyDeviceToHost, st));
     MCE_HIP(hipStreamSynchronize(st));
     if (bad_h) return fail(MCE_ERR_INVALID, "jackknife: a group id outside 0 .. %d", G - 1);
 
     const dim3 grid((unsigned)lay.nblocks), block(kRedThreads);
     if (L <= kJackRegL)
         hipLaunchKernelGGL((jack_partial_kernel<true>), grid, block, 0, st, d_dist, d_idx, nq, (int)L, d_qid, d_gq, d_gr, nr, (int)G, (int)k0, (int)kmax,
-                           (int)d, ln_unit_ball(d), d_w, d_fs, partial, flags, cnt);
+                           (int)d, ln_unit_ball(d), d_w, d_fs, lay.partial, lay.flags, lay.cnt);
     else
         hipLaunchKernelGGL((jack_partial_kernel<false>), grid, block, 0, st, d_dist, d_idx, nq, (int)L, d_qid, d_gq, d_gr, nr, (int)G, (int)k0, (int)kmax,
-                           (int)d, ln_unit_ball(d), d_w, d_fs, partial, flags, cnt);
+                           (int)d, ln_unit_ball(d), d_w, d_fs, lay.partial, lay.flags, lay.cnt);
     MCE_HIP(hipGetLastError());
-    hipLaunchKernelGGL(jack_final_kernel, dim3((unsigned)((G + 1) * kmax)), block, 0, st, partial, lay.nblocks, (int)(G + 1), (int)k0, (int)kmax,
+    hipLaunchKernelGGL(jack_final_kernel, dim3((unsigned)((G + 1) * kmax)), block, 0, st, lay.partial, lay.nblocks, (int)(G + 1), (int)k0, (int)kmax,
                        d_dotp_full, d_dotp_groups);
-    hipLaunchKernelGGL(jack_scan_kernel, dim3(1), block, 0, st, cnt, lay.nblocks, boff, d_nshort);
-    hipLaunchKernelGGL(jack_compact_kernel, grid, block, 0, st, flags, nq, d_qid, boff, d_short_rows);
+    hipLaunchKernelGGL(jack_scan_kernel, dim3(1), block, 0, st, lay.cnt, lay.nblocks, lay.boff, d_nshort);
+    hipLaunchKernelGGL(jack_compact_kernel, grid, block, 0, st, lay.flags, nq, d_qid, lay.boff, d_short_rows);
     MCE_HIP(hipGetLastError());
     MCE_HIP(hipStreamSynchronize(st));
     return MCE_OK;

@@ -6,6 +6,7 @@
 // group ids are checked on the device, in the first pass over them.
 #pragma once
 
+#include "capi_seg.hpp"
 #include "jack_group_kernels.hpp"
 #include "jack_groups.hpp"
 
@@ -13,38 +14,34 @@ namespace {
 
 constexpr int32_t kJgMaxSegs = 1 << 20;
 
-struct JgLayout {
-    size_t off_segs = 0, off_tile0 = 0, off_sums = 0, off_part = 0, off_sys = 0, off_res = 0, total = 0;
-    int64_t max_tiles = 0;
+// the workspace of a call of nseg segments with nrows rows in all and at most Gmax groups.  res: one block per slot of every system,
+// packed, and the flag of the group ids behind them
+struct JgWs {
+    mce::JgSeg* segs;
+    int64_t* tile0;
+    double *sums, *part, *sys, *res;
+    size_t total;
+    JgWs(int64_t nrows, int32_t nseg, int32_t Gmax, void* ws = nullptr)
+    {
+        const size_t S = (size_t)nseg, T = (size_t)mce_seg::seg_max_tiles(nrows, nseg), B = (size_t)Gmax + 1;
+        WsPlan P(ws);
+        segs = P.take<mce::JgSeg>(S);
+        tile0 = P.take<int64_t>(S);
+        sums = P.take<double>(T * B * mce::kJgTileSums);
+        part = P.take<double>(T * B);
+        sys = P.take<double>(S * B * mce::kJgSys);
+        res = P.take<double>(S * B * mce_jg::kJgOut + 1);
+        total = P.total;
+    }
 };
 
-// res: one block per slot of every system, packed, and the flag of the group ids behind them
-JgLayout jg_layout(int64_t nrows, int32_t nseg, int32_t Gmax)
-{
-    JgLayout L;
-    L.max_tiles = nrows / mce::kJgTileRows + nseg;
-    const size_t S = (size_t)nseg, T = (size_t)L.max_tiles, B = (size_t)Gmax + 1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += prep_align(bytes); return at; };
-    L.off_segs = take(S * sizeof(mce::JgSeg));
-    L.off_tile0 = take(S * sizeof(int64_t));
-    L.off_sums = take(T * B * mce::kJgTileSums * 8);
-    L.off_part = take(T * B * 8);
-    L.off_sys = take(S * B * mce::kJgSys * 8);
-    L.off_res = take((S * B * mce_jg::kJgOut + 1) * 8);
-    L.total = off;
-    return L;
-}
-
 // the argument checks of both forms, and the tables
-int jg_tables(const mce_jack_leave_out_seg* segs, int32_t nseg, std::vector<mce::JgSeg>& table, std::vector<int64_t>& tile0, int64_t& nrows, int64_t& ntiles,
-              int32_t& Gmax, int64_t& nslots_total)
+int jg_tables(const mce_jack_leave_out_seg* segs, int32_t nseg, std::vector<mce::JgSeg>& table, mce_seg::SegTable& tiles, int32_t& Gmax, int64_t& nslots_total)
 {
     if (!segs) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (nseg < 1 || nseg > kJgMaxSegs) return fail(MCE_ERR_INVALID, "jackknife leave-out: %d segments (1 .. %d expected)", nseg, kJgMaxSegs);
     table.assign((size_t)nseg, mce::JgSeg{nullptr, nullptr, nullptr, 0, 0, 0});
-    tile0.assign((size_t)nseg, 0);
-    nrows = ntiles = nslots_total = 0;
+    nslots_total = 0;
     Gmax = 0;
     for (int32_t s = 0; s < nseg; ++s) {
         const mce_jack_leave_out_seg& g = segs[s];
@@ -52,13 +49,11 @@ int jg_tables(const mce_jack_leave_out_seg* segs, int32_t nseg, std::vector<mce:
         if (g.n < 0 || g.n > (int64_t)1 << 40 || (g.n > 0 && (!g.w || !g.g)))
             return fail(MCE_ERR_INVALID, "jackknife leave-out: segment %d has %lld rows at w %s, g %s", s, (long long)g.n, g.w ? "valid" : "null", g.g ? "valid" : "null");
         table[(size_t)s] = mce::JgSeg{g.w, g.fs, g.g, g.n, g.G, (int32_t)nslots_total};
-        tile0[(size_t)s] = ntiles;
-        ntiles += (g.n + mce::kJgTileRows - 1) / mce::kJgTileRows;
-        nrows += g.n;
+        tiles.add(g.n);
         nslots_total += g.G + 1;
         Gmax = std::max(Gmax, g.G);
     }
-    if (ntiles > 0x7fffffffLL) return fail(MCE_ERR_INVALID, "jackknife leave-out: %lld rows in one call", (long long)nrows);
+    if (!tiles.fits()) return fail(MCE_ERR_INVALID, "jackknife leave-out: %lld rows in one call", (long long)tiles.nrows);
     return MCE_OK;
 }
 
@@ -121,7 +116,7 @@ int mce_jack_groups_dev(const mce_jack_groups_seg* segs, int32_t nseg, void* str
 size_t mce_jack_leave_out_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t Gmax)
 {
     if (nrows_total < 0 || nseg < 1 || nseg > kJgMaxSegs || Gmax < 2 || Gmax > MCE_JACK_MAX_GROUPS) return 0;
-    return jg_layout(nrows_total, nseg, Gmax).total;
+    return JgWs(nrows_total, nseg, Gmax).total;
 }
 
 int mce_jack_leave_out_dev(const mce_jack_leave_out_seg* segs, int32_t nseg, double* out, void* ws, size_t ws_bytes, void* stream)
@@ -129,39 +124,29 @@ int mce_jack_leave_out_dev(const mce_jack_leave_out_seg* segs, int32_t nseg, dou
     using namespace mce;
     if (!out) return fail(MCE_ERR_INVALID, "null pointer argument");
     std::vector<JgSeg> table;
-    std::vector<int64_t> tile0;
-    int64_t nrows = 0, ntiles = 0, nslots_total = 0;
+    mce_seg::SegTable tiles;
+    int64_t nslots_total = 0;
     int32_t Gmax = 0;
-    int rc = jg_tables(segs, nseg, table, tile0, nrows, ntiles, Gmax, nslots_total);
+    int rc = jg_tables(segs, nseg, table, tiles, Gmax, nslots_total);
     if (rc != MCE_OK) return rc;
     if (!ws) return fail(MCE_ERR_INVALID, "null pointer argument");
-    const JgLayout L = jg_layout(nrows, nseg, Gmax);
-    if (ws_bytes < L.total) return fail(MCE_ERR_WORKSPACE, "jackknife leave-out: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
-    if ((rc = prep_need_device()) != MCE_OK) return rc;
+    const JgWs W(tiles.nrows, nseg, Gmax, ws);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = seg_dev_begin("jackknife leave-out", ws_bytes, W.total, table, tiles.tile0, W.segs, W.tile0, st)) != MCE_OK) return rc;
 
-    JgSeg* d_segs = prep_at<JgSeg>(ws, L.off_segs);
-    int64_t* d_tile0 = prep_at<int64_t>(ws, L.off_tile0);
-    double* d_sums = prep_at<double>(ws, L.off_sums);
-    double* d_part = prep_at<double>(ws, L.off_part);
-    double* d_sys = prep_at<double>(ws, L.off_sys);
-    double* d_res = prep_at<double>(ws, L.off_res);
     const size_t nres = (size_t)nslots_total * mce_jg::kJgOut;    // the flag of the group ids sits behind the blocks
     const int nslots = Gmax + 1;
     bool moments = false;
     for (const JgSeg& g : table) moments = moments || (g.fs != nullptr && g.n > 0);
-
-    MCE_HIP(hipMemcpyAsync(d_segs, table.data(), table.size() * sizeof(JgSeg), hipMemcpyHostToDevice, st));
-    MCE_HIP(hipMemcpyAsync(d_tile0, tile0.data(), tile0.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    MCE_HIP(zero_async(d_res + nres, sizeof(double), st));
-    const dim3 tb(kJgThreads), per_slot((unsigned)nseg, (unsigned)nslots);
-    if (ntiles > 0) hipLaunchKernelGGL(jg_sum_tile_kernel, dim3((unsigned)ntiles), tb, 0, st, d_segs, d_tile0, (int)nseg, nslots, d_sums, d_res + nres);
-    hipLaunchKernelGGL(jg_centre_kernel, per_slot, tb, 0, st, d_segs, d_tile0, nslots, d_sums, d_sys);
-    if (ntiles > 0 && moments) hipLaunchKernelGGL(jg_var_tile_kernel, dim3((unsigned)ntiles), tb, 0, st, d_segs, d_tile0, (int)nseg, nslots, d_sys, d_part);
-    hipLaunchKernelGGL(jg_result_kernel, per_slot, tb, 0, st, d_segs, d_tile0, nslots, d_sys, d_part, d_res);
+    MCE_HIP(zero_async(W.res + nres, sizeof(double), st));
+    const dim3 tb(kJgThreads), per_tile((unsigned)tiles.ntiles), per_slot((unsigned)nseg, (unsigned)nslots);
+    if (tiles.ntiles > 0) hipLaunchKernelGGL(jg_sum_tile_kernel, per_tile, tb, 0, st, W.segs, W.tile0, (int)nseg, nslots, W.sums, W.res + nres);
+    hipLaunchKernelGGL(jg_centre_kernel, per_slot, tb, 0, st, W.segs, W.tile0, nslots, W.sums, W.sys);
+    if (tiles.ntiles > 0 && moments) hipLaunchKernelGGL(jg_var_tile_kernel, per_tile, tb, 0, st, W.segs, W.tile0, (int)nseg, nslots, W.sys, W.part);
+    hipLaunchKernelGGL(jg_result_kernel, per_slot, tb, 0, st, W.segs, W.tile0, nslots, W.sys, W.part, W.res);
     MCE_HIP(hipGetLastError());
     std::vector<double> host(nres + 1);
-    MCE_HIP(hipMemcpyAsync(host.data(), d_res, (nres + 1) * 8, hipMemcpyDeviceToHost, st));
+    MCE_HIP(hipMemcpyAsync(host.data(), W.res, (nres + 1) * 8, hipMemcpyDeviceToHost, st));
     MCE_HIP(hipStreamSynchronize(st));                            // the one wait
     if (host[nres] != 0.0) return fail(MCE_ERR_INVALID, "jackknife: a group id outside 0 .. G - 1");
     std::copy(host.begin(), host.begin() + (ptrdiff_t)nres, out);
@@ -172,30 +157,22 @@ int mce_jack_leave_out_f64(const mce_jack_leave_out_seg* segs, int32_t nseg, dou
 {
     if (!out) return fail(MCE_ERR_INVALID, "null pointer argument");
     std::vector<mce::JgSeg> table;
-    std::vector<int64_t> tile0;
-    int64_t nrows = 0, ntiles = 0, nslots_total = 0;
+    mce_seg::SegTable tiles;
+    int64_t nslots_total = 0;
     int32_t Gmax = 0;
-    int rc = jg_tables(segs, nseg, table, tile0, nrows, ntiles, Gmax, nslots_total);
+    int rc = jg_tables(segs, nseg, table, tiles, Gmax, nslots_total);
     if (rc != MCE_OK) return rc;
     if ((rc = select_device(device)) != MCE_OK) return rc;
-    DevBuf cols, ids, ws;
-    MCE_HIP(cols.alloc((size_t)std::max<int64_t>(nrows, 1) * 2 * sizeof(double)));
-    MCE_HIP(ids.alloc((size_t)std::max<int64_t>(nrows, 1) * sizeof(int32_t)));
-    std::vector<mce_jack_leave_out_seg> dsegs((size_t)nseg);
-    int64_t at = 0;
-    for (int32_t s = 0; s < nseg; ++s) {
-        const int64_t n = segs[s].n;
-        double* d_w = cols.as<double>() + 2 * at;
-        int32_t* d_g = ids.as<int32_t>() + at;
-        dsegs[(size_t)s] = mce_jack_leave_out_seg{n > 0 ? d_w : nullptr, (n > 0 && segs[s].fs) ? d_w + n : nullptr, n > 0 ? d_g : nullptr, n, segs[s].G};
-        if (n > 0) {
-            MCE_HIP(hipMemcpy(d_w, segs[s].w, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-            if (segs[s].fs) MCE_HIP(hipMemcpy(d_w + n, segs[s].fs, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-            MCE_HIP(hipMemcpy(d_g, segs[s].g, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        at += n;
-    }
-    const size_t wsb = mce_jack_leave_out_workspace_bytes(nrows, nseg, Gmax);
+    SegStage cols;
+    DevBuf ws;
+    size_t bytes = 0;
+    for (int32_t s = 0; s < nseg; ++s) bytes += (size_t)segs[s].n * 2 * sizeof(double) + seg_stage_bytes((size_t)segs[s].n * sizeof(int32_t));
+    if ((rc = cols.alloc(bytes)) != MCE_OK) return rc;
+    std::vector<mce_jack_leave_out_seg> dsegs(segs, segs + nseg);
+    for (mce_jack_leave_out_seg& g : dsegs)
+        if ((rc = cols.put(g.w, (size_t)g.n, g.w)) != MCE_OK || (rc = cols.put(g.fs, (size_t)g.n, g.fs)) != MCE_OK || (rc = cols.put(g.g, (size_t)g.n, g.g)) != MCE_OK)
+            return rc;
+    const size_t wsb = mce_jack_leave_out_workspace_bytes(tiles.nrows, nseg, Gmax);
     MCE_HIP(ws.alloc(wsb));
     return mce_jack_leave_out_dev(dsegs.data(), nseg, out, ws.p, wsb, nullptr);
 }

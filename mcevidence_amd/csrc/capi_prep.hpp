@@ -15,28 +15,51 @@ constexpr int32_t kPrepMaxParts = 65536;
 
 size_t prep_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
-struct PrepLayout {
-    int64_t n = 0, ntl = 0;
-    size_t off_parts = 0, off_tot = 0, off_w = 0, off_c = 0, off_cand = 0, off_tile[7] = {0, 0, 0, 0, 0, 0, 0}, total = 0;
-};
-enum { kTileSum = 0, kTileMax, kTileBad, kTileBase, kTileFrac, kTileCnt, kTileOut };
+template <class T> T* prep_at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
 
-PrepLayout prep_layout(int64_t n, int32_t nparts)
-{
-    PrepLayout L;
-    L.n = n;
-    L.ntl = (n + 1 + mce::kPrepTile - 1) / mce::kPrepTile;          // (the candidates of the bin rule: up to n + 1 bins)
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += prep_align(bytes); return at; };
-    L.off_parts = take((size_t)nparts * sizeof(mce::PrepPart));
-    L.off_tot = take(sizeof(mce::PrepTotals));
-    L.off_w = take((size_t)n * sizeof(double));
-    L.off_c = take((size_t)n * sizeof(long long));
-    L.off_cand = take((size_t)(n + 1) * sizeof(long long));
-    for (int k = 0; k < 7; ++k) L.off_tile[k] = take((size_t)L.ntl * 8);
-    L.total = off;
-    return L;
-}
+// a workspace, declared ONCE as a row of take()s: every array starts on a multiple of 256 bytes.  Over no workspace (ws = null) the
+// row only counts -- `total` is what a *_workspace_bytes function returns --, over a workspace it also hands out the typed pointers,
+// so the size and the pointers cannot disagree.
+struct WsPlan {
+    char* base;
+    size_t total = 0;
+    explicit WsPlan(void* ws) : base(static_cast<char*>(ws)) {}
+    template <class T> T* take(size_t count) { return take_bytes<T>(count * sizeof(T)); }
+    template <class T> T* take_bytes(size_t bytes)
+    {
+        T* const p = base ? reinterpret_cast<T*>(base + total) : nullptr;
+        total += prep_align(bytes);
+        return p;
+    }
+};
+
+// the select workspace of a chain of n rows in nparts parts: the parts, the totals, the weights, their prefix sums, the candidates
+// (the bin rule: up to n + 1 bins) and seven per-tile arrays
+struct PrepWs {
+    mce::PrepPart* parts;
+    mce::PrepTotals* tot;
+    double *w, *tile_frac;
+    long long *c, *cand, *tile_sum, *tile_max, *tile_bad, *tile_base, *tile_cnt, *tile_out;
+    size_t total;
+    PrepWs(int64_t n, int32_t nparts, void* ws = nullptr)
+    {
+        const size_t ntl = (size_t)((n + 1 + mce::kPrepTile - 1) / mce::kPrepTile);
+        WsPlan P(ws);
+        parts = P.take<mce::PrepPart>((size_t)nparts);
+        tot = P.take<mce::PrepTotals>(1);
+        w = P.take<double>((size_t)n);
+        c = P.take<long long>((size_t)n);
+        cand = P.take<long long>((size_t)(n + 1));
+        tile_sum = P.take<long long>(ntl);
+        tile_max = P.take<long long>(ntl);
+        tile_bad = P.take<long long>(ntl);
+        tile_base = P.take<long long>(ntl);
+        tile_frac = P.take<double>(ntl);
+        tile_cnt = P.take<long long>(ntl);
+        tile_out = P.take<long long>(ntl);
+        total = P.total;
+    }
+};
 
 // one entry of a part table (`who`: the caller's prefix): rows at a null pointer, negative rows, rows beyond 2^40
 int prep_check_part(const char* who, long long p, const mce_chain_part& part)
@@ -70,16 +93,14 @@ int prep_need_device()
     return MCE_OK;
 }
 
-template <class T> T* prep_at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
-
-int prep_select_args(int64_t n, int32_t nparts, int32_t rule, double thinlen, void* ws, size_t ws_bytes, PrepLayout& L)
+int prep_select_args(int64_t n, int32_t nparts, int32_t rule, double thinlen, void* ws, size_t ws_bytes)
 {
     if (!ws) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (n < 1 || nparts < 1 || nparts > kPrepMaxParts) return fail(MCE_ERR_INVALID, "chain prep: n=%lld nparts=%d", (long long)n, nparts);
     if (rule != mce_prep::kRuleInteger && rule != mce_prep::kRuleBin) return fail(MCE_ERR_INVALID, "chain prep: rule %d selects nothing", rule);
     if (!(thinlen > 1.0)) return fail(MCE_ERR_INVALID, "chain prep: thinlen=%g", thinlen);
-    L = prep_layout(n, nparts);
-    if (ws_bytes < L.total) return fail(MCE_ERR_WORKSPACE, "chain prep: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+    const size_t need = PrepWs(n, nparts).total;
+    if (ws_bytes < need) return fail(MCE_ERR_WORKSPACE, "chain prep: workspace of %zu bytes, %zu needed", ws_bytes, need);
     return MCE_OK;
 }
 
@@ -90,7 +111,7 @@ extern "C" {
 size_t mce_chain_select_workspace_bytes(int64_t n, int32_t nparts)
 {
     if (n < 0 || nparts < 1 || nparts > kPrepMaxParts) return 0;
-    return prep_layout(n, nparts).total;
+    return PrepWs(n, nparts).total;
 }
 
 size_t mce_chain_gather_workspace_bytes(int32_t nparts)
@@ -117,28 +138,25 @@ int mce_chain_weights_dev(const mce_chain_part* parts, int32_t nparts, int64_t n
     if (rc != MCE_OK) return rc;
     if (iw < 0 || iw >= ncols) return fail(MCE_ERR_INVALID, "chain prep: weight column %d of %lld", iw, (long long)ncols);
     if (n < 1) return fail(MCE_ERR_INVALID, "chain prep: no rows");
-    const PrepLayout L = prep_layout(n, nparts);
-    if (ws_bytes < L.total) return fail(MCE_ERR_WORKSPACE, "chain prep: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+    const PrepWs W(n, nparts, ws);
+    if (ws_bytes < W.total) return fail(MCE_ERR_WORKSPACE, "chain prep: workspace of %zu bytes, %zu needed", ws_bytes, W.total);
     if ((rc = prep_need_device()) != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    PrepPart* d_parts = prep_at<PrepPart>(ws, L.off_parts);
-    PrepTotals* d_tot = prep_at<PrepTotals>(ws, L.off_tot);
-    double* d_w = prep_at<double>(ws, L.off_w);
     const int64_t nt = (n + kPrepTile - 1) / kPrepTile;
-    MCE_HIP(hipMemcpyAsync(d_parts, table.data(), table.size() * sizeof(PrepPart), hipMemcpyHostToDevice, st));
-    MCE_HIP(hipMemsetAsync(d_tot, 0, sizeof(PrepTotals), st));
-    hipLaunchKernelGGL(prep_weights_kernel, dim3(prep_grid(n, kPrepThreads)), dim3(kPrepThreads), 0, st, d_parts, (int)table.size(), n, ncols, (int)iw, d_w);
-    hipLaunchKernelGGL(prep_tile_kernel, dim3(prep_grid(nt, 1)), dim3(kPrepThreads), 0, st, d_w, n, nt, prep_at<long long>(ws, L.off_tile[kTileSum]),
-                       prep_at<long long>(ws, L.off_tile[kTileMax]), prep_at<double>(ws, L.off_tile[kTileFrac]), prep_at<long long>(ws, L.off_tile[kTileBad]));
-    hipLaunchKernelGGL(prep_scan_kernel, dim3(1), dim3(kPrepScanThreads), 0, st, prep_at<long long>(ws, L.off_tile[kTileSum]), nt,
-                       prep_at<long long>(ws, L.off_tile[kTileBase]), &d_tot->sum_int);
-    hipLaunchKernelGGL(prep_totals_kernel, dim3(1), dim3(kPrepThreads), 0, st, prep_at<long long>(ws, L.off_tile[kTileMax]), prep_at<double>(ws, L.off_tile[kTileFrac]),
-                       prep_at<long long>(ws, L.off_tile[kTileBad]), nt, d_tot);
-    hipLaunchKernelGGL(prep_cum_kernel, dim3(prep_grid(nt, 1)), dim3(kPrepThreads), 0, st, d_w, n, nt, prep_at<long long>(ws, L.off_tile[kTileBase]),
-                       prep_at<long long>(ws, L.off_c));
+    MCE_HIP(hipMemcpyAsync(W.parts, table.data(), table.size() * sizeof(PrepPart), hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemsetAsync(W.tot, 0, sizeof(PrepTotals), st));
+    hipLaunchKernelGGL(prep_weights_kernel, dim3(prep_grid(n, kPrepThreads)), dim3(kPrepThreads), 0, st, W.parts, (int)table.size(), n, ncols, (int)iw, W.w);
+    hipLaunchKernelGGL(prep_tile_kernel, dim3(prep_grid(nt, 1)), dim3(kPrepThreads), 0, st, W.w, n, nt, W.tile_sum,
+                       W.tile_max, W.tile_frac, W.tile_bad);
+    hipLaunchKernelGGL(prep_scan_kernel, dim3(1), dim3(kPrepScanThreads), 0, st, W.tile_sum, nt,
+                       W.tile_base, &W.tot->sum_int);
+    hipLaunchKernelGGL(prep_totals_kernel, dim3(1), dim3(kPrepThreads), 0, st, W.tile_max, W.tile_frac,
+                       W.tile_bad, nt, W.tot);
+    hipLaunchKernelGGL(prep_cum_kernel, dim3(prep_grid(nt, 1)), dim3(kPrepThreads), 0, st, W.w, n, nt, W.tile_base,
+                       W.c);
     MCE_HIP(hipGetLastError());
     PrepTotals tot;
-    MCE_HIP(hipMemcpyAsync(&tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    MCE_HIP(hipMemcpyAsync(&tot, W.tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     MCE_HIP(hipStreamSynchronize(st));
     mce_prep::WeightTotals t;
     t.sum_int = tot.sum_int; t.max_int = tot.max_int; t.frac = tot.frac; t.bad = tot.bad;
@@ -152,18 +170,18 @@ int mce_chain_select_count_dev(int64_t n, int32_t nparts, int32_t rule, double t
 {
     using namespace mce;
     if (!n_out) return fail(MCE_ERR_INVALID, "null pointer argument");
-    PrepLayout L;
-    int rc = prep_select_args(n, nparts, rule, thinlen, ws, ws_bytes, L);
+    int rc = prep_select_args(n, nparts, rule, thinlen, ws, ws_bytes);
     if (rc != MCE_OK) return rc;
+    const PrepWs W(n, nparts, ws);
     if (rule == mce_prep::kRuleBin && (!d_edges || nedges < 1 || nedges > n + 1))
         return fail(MCE_ERR_INVALID, "chain prep: the bin rule needs 1 .. n + 1 edges on the device (got %lld)", (long long)nedges);
     if ((rc = prep_need_device()) != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    PrepTotals* d_tot = prep_at<PrepTotals>(ws, L.off_tot);
+    PrepTotals* d_tot = W.tot;
     PrepTotals tot;
     MCE_HIP(hipMemcpyAsync(&tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     MCE_HIP(hipStreamSynchronize(st));
-    long long* cand = prep_at<long long>(ws, L.off_cand);
+    long long* cand = W.cand;
     int64_t len = n;
     if (rule == mce_prep::kRuleInteger) {
         const long long factor = (long long)thinlen;
@@ -171,16 +189,16 @@ int mce_chain_select_count_dev(int64_t n, int32_t nparts, int32_t rule, double t
             *n_out = tot.sum_int / factor;
             return MCE_OK;
         }
-        hipLaunchKernelGGL(prep_flag_kernel, dim3(prep_grid(n, kPrepThreads)), dim3(kPrepThreads), 0, st, prep_at<long long>(ws, L.off_c), n, factor, cand);
+        hipLaunchKernelGGL(prep_flag_kernel, dim3(prep_grid(n, kPrepThreads)), dim3(kPrepThreads), 0, st, W.c, n, factor, cand);
     } else {
         len = nedges;
-        hipLaunchKernelGGL(prep_bin_kernel, dim3(prep_grid(nedges, kPrepThreads / 64)), dim3(kPrepThreads), 0, st, prep_at<double>(ws, L.off_w), n, d_edges,
+        hipLaunchKernelGGL(prep_bin_kernel, dim3(prep_grid(nedges, kPrepThreads / 64)), dim3(kPrepThreads), 0, st, W.w, n, d_edges,
                            nedges, cand);
     }
     const int64_t nt = (len + kPrepTile - 1) / kPrepTile;
-    hipLaunchKernelGGL(prep_count_kernel, dim3(prep_grid(nt, 1)), dim3(kPrepThreads), 0, st, cand, len, nt, prep_at<long long>(ws, L.off_tile[kTileCnt]));
-    hipLaunchKernelGGL(prep_scan_kernel, dim3(1), dim3(kPrepScanThreads), 0, st, prep_at<long long>(ws, L.off_tile[kTileCnt]), nt,
-                       prep_at<long long>(ws, L.off_tile[kTileOut]), &d_tot->n_out);
+    hipLaunchKernelGGL(prep_count_kernel, dim3(prep_grid(nt, 1)), dim3(kPrepThreads), 0, st, cand, len, nt, W.tile_cnt);
+    hipLaunchKernelGGL(prep_scan_kernel, dim3(1), dim3(kPrepScanThreads), 0, st, W.tile_cnt, nt,
+                       W.tile_out, &d_tot->n_out);
     MCE_HIP(hipGetLastError());
     MCE_HIP(hipMemcpyAsync(&tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     MCE_HIP(hipStreamSynchronize(st));
@@ -193,28 +211,28 @@ int mce_chain_select_fill_dev(int64_t n, int32_t nparts, int32_t rule, double th
 {
     using namespace mce;
     if (!d_src || !d_new_w) return fail(MCE_ERR_INVALID, "null pointer argument");
-    PrepLayout L;
-    int rc = prep_select_args(n, nparts, rule, thinlen, ws, ws_bytes, L);
+    int rc = prep_select_args(n, nparts, rule, thinlen, ws, ws_bytes);
     if (rc != MCE_OK) return rc;
+    const PrepWs W(n, nparts, ws);
     if (n_out < 1) return fail(MCE_ERR_INVALID, "chain prep: n_out=%lld", (long long)n_out);
     if (rule == mce_prep::kRuleBin && (nedges < 1 || nedges > n + 1)) return fail(MCE_ERR_INVALID, "chain prep: %lld edges", (long long)nedges);
     if ((rc = prep_need_device()) != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     PrepTotals tot;
-    MCE_HIP(hipMemcpyAsync(&tot, prep_at<PrepTotals>(ws, L.off_tot), sizeof(tot), hipMemcpyDeviceToHost, st));
+    MCE_HIP(hipMemcpyAsync(&tot, W.tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     MCE_HIP(hipStreamSynchronize(st));
     const long long factor = (long long)thinlen;
-    const double* d_w = prep_at<double>(ws, L.off_w);
+    const double* d_w = W.w;
     if (rule == mce_prep::kRuleInteger && factor < tot.max_int) {
         if (n_out != tot.sum_int / factor) return fail(MCE_ERR_INVALID, "chain prep: n_out=%lld, the count call said %lld", (long long)n_out, tot.sum_int / factor);
-        hipLaunchKernelGGL(prep_search_kernel, dim3(prep_grid(n_out, kPrepThreads)), dim3(kPrepThreads), 0, st, prep_at<long long>(ws, L.off_c), n, factor, n_out,
+        hipLaunchKernelGGL(prep_search_kernel, dim3(prep_grid(n_out, kPrepThreads)), dim3(kPrepThreads), 0, st, W.c, n, factor, n_out,
                            d_w, reinterpret_cast<long long*>(d_src), d_new_w);
     } else {
         if (n_out != tot.n_out) return fail(MCE_ERR_INVALID, "chain prep: n_out=%lld, the count call said %lld", (long long)n_out, tot.n_out);
         const int64_t len = rule == mce_prep::kRuleInteger ? n : nedges;
         const int64_t nt = (len + kPrepTile - 1) / kPrepTile;
-        hipLaunchKernelGGL(prep_fill_kernel, dim3(prep_grid(nt, 1)), dim3(kPrepThreads), 0, st, prep_at<long long>(ws, L.off_cand), len, nt,
-                           prep_at<long long>(ws, L.off_tile[kTileOut]), d_w, rule == mce_prep::kRuleInteger ? 1 : 0, n_out, reinterpret_cast<long long*>(d_src),
+        hipLaunchKernelGGL(prep_fill_kernel, dim3(prep_grid(nt, 1)), dim3(kPrepThreads), 0, st, W.cand, len, nt,
+                           W.tile_out, d_w, rule == mce_prep::kRuleInteger ? 1 : 0, n_out, reinterpret_cast<long long*>(d_src),
                            d_new_w);
     }
     MCE_HIP(hipGetLastError());

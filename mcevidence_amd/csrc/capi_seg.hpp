@@ -1,0 +1,51 @@
+// capi_seg.hpp -- part of capi.hip (one translation unit): what the host sides of the segment-tile families (capi_moments.hpp,
+// capi_jackres.hpp, capi_summary.hpp; the scheme: seg_tiles.hpp) share: the opening of their _dev forms and the staging of their
+// host-pointer forms.  Each family keeps its own argument checks and error texts.
+#pragma once
+
+#include "seg_tiles.hpp"
+
+namespace {
+
+// the opening of a _dev form, after the argument checks: the workspace holds the plan, a device is there, and the segment table and the
+// first tiles are on their way to it
+template <class Seg>
+int seg_dev_begin(const char* who, size_t ws_bytes, size_t need, const std::vector<Seg>& table, const std::vector<int64_t>& tile0, Seg* d_segs, int64_t* d_tile0,
+                  hipStream_t st)
+{
+    if (ws_bytes < need) return fail(MCE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+    const int rc = prep_need_device();
+    if (rc != MCE_OK) return rc;
+    MCE_HIP(hipMemcpyAsync(d_segs, table.data(), table.size() * sizeof(Seg), hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemcpyAsync(d_tile0, tile0.data(), tile0.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    return MCE_OK;
+}
+
+// a host-pointer form stages the columns of all its segments in ONE device buffer, one behind the other, and hands the device form
+// their addresses: alloc() the bytes of all columns (seg_stage_bytes each), then put() them in any order
+size_t seg_stage_bytes(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+
+struct SegStage {
+    DevBuf buf;
+    char* at = nullptr;
+    int alloc(size_t bytes)
+    {
+        MCE_HIP(buf.alloc(bytes));
+        at = buf.as<char>();
+        return MCE_OK;
+    }
+    // `rows` rows of `width` values of T, `ld` values apart on the host (null, or no rows: no column) -> packed on the device; dev:
+    // its address there (null)
+    template <class T> int put(const T* src, size_t rows, const T*& dev, size_t width = 1, size_t ld = 1)
+    {
+        dev = nullptr;
+        if (!src || rows == 0) return MCE_OK;
+        if (ld == width) MCE_HIP(hipMemcpy(at, src, rows * width * sizeof(T), hipMemcpyHostToDevice));
+        else MCE_HIP(hipMemcpy2D(at, width * sizeof(T), src, ld * sizeof(T), width * sizeof(T), rows, hipMemcpyHostToDevice));
+        dev = reinterpret_cast<const T*>(at);
+        at += seg_stage_bytes(rows * width * sizeof(T));
+        return MCE_OK;
+    }
+};
+
+}  // namespace

@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "chain_conv.hpp"
+#include "seg_tiles.hpp"
 
 namespace mce {
 
@@ -53,13 +54,7 @@ struct ConvSys {
 // the segment that owns tile k (tile0 ascending; a segment without rows owns none)
 __device__ __forceinline__ int conv_seg_of(const ConvSeg* __restrict__ segs, int nseg, int64_t k)
 {
-    int lo = 0, hi = nseg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (segs[mid].tile0 <= k) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
+    return mce_seg::last_at_or_below(nseg, k, [segs](int i) { return segs[i].tile0; });
 }
 
 // grid: the tiles.  Thread (rs, j): column j of the rows rs, rs + RS, .. of the tile, RS = 256 / CL row lanes, CL = the power of two

@@ -25,6 +25,7 @@
 
 #include "chain_corr.hpp"
 #include "chain_prep_kernels.hpp"
+#include "seg_tiles.hpp"
 
 namespace mce {
 
@@ -59,13 +60,7 @@ struct CorrState {
 // the part that owns chunk k (parts[p].chunk0 ascending from 0; mean = the mean pass's numbering)
 __device__ __forceinline__ int corr_part_of(const CorrPart* __restrict__ parts, int nparts, int64_t k, bool mean)
 {
-    int lo = 0, hi = nparts - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((mean ? parts[mid].mchunk0 : parts[mid].chunk0) <= k) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
+    return mce_seg::last_at_or_below(nparts, k, [parts, mean](int i) { return mean ? parts[i].mchunk0 : parts[i].chunk0; });
 }
 
 __global__ __launch_bounds__(kCorrThreads) void corr_ends_kernel(const PrepPart* __restrict__ parts, int nparts, const long long* __restrict__ c,

@@ -33,6 +33,8 @@
 
 #include <vector>
 
+#include "seg_tiles.hpp"
+
 namespace mce {
 
 enum : int { kByteOther = 0, kByteSpace = 1, kByteTerm = 2, kByteHash = 3 };
@@ -68,16 +70,10 @@ inline bool layout_ok(const int64_t* file_off, const int64_t* file_len, int64_t 
     return true;
 }
 
-// the last f in [0, n) with base[f] <= x; base[0] <= x is the caller's promise (base is non-decreasing)
+// the last f in [0, n) with base[f] <= x; base[0] <= x is the caller's promise (base is non-decreasing): seg_tiles.hpp's search
 MCE_HD inline int64_t last_at_or_below(const int64_t* base, int64_t n, int64_t x)
 {
-    int64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (base[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
+    return mce_seg::last_at_or_below(n, x, [base](int64_t i) { return base[i]; });
 }
 
 // file_tile0[f] = file_off[f] / kTileBytes

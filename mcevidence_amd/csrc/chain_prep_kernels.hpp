@@ -27,6 +27,7 @@
 
 #include "chain_kernels.hpp"
 #include "chain_prep.hpp"
+#include "seg_tiles.hpp"
 
 namespace mce {
 
@@ -49,12 +50,7 @@ struct PrepTotals {
 // row g of the concatenated numbering (0 <= g < n; parts are non-empty, parts[0].first = 0, firsts ascending)
 __device__ __forceinline__ const double* prep_row(const PrepPart* __restrict__ parts, int nparts, int64_t g, int64_t ncols)
 {
-    int lo = 0, hi = nparts - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (parts[mid].first <= g) lo = mid;
-        else hi = mid - 1;
-    }
+    const int lo = mce_seg::last_at_or_below(nparts, g, [parts](int i) { return parts[i].first; });
     return parts[lo].rows + (g - parts[lo].first) * ncols;
 }
 

@@ -1,10 +1,7 @@
 // jack_group_kernels.hpp -- the bookkeeping of the delete-a-group jackknife for chains that stay on the device (mce_jack_groups_dev,
 // mce_jack_leave_out_dev: capi_jackres.hpp).  The rule is jack_groups.hpp's; this file arranges it into launches that serve any number
-// of systems (one system = the s1 partition of one root), after the pattern of like_moments_kernels.hpp.  fp64 throughout, no
-// floating-point atomics, plain C++ stores only, 64-bit row indices.  A tile is kJgTileRows = 512 rows of ONE segment, counted from the
-// segment's first row, so a tile never spans two systems and every sum is formed in an order that the system's own row count fixes: two
-// runs give the same bits, and a system's bits do not depend on its neighbours, its position or the call.  The tile -> segment lookup is
-// chain_farm.hpp's "last entry at or below the key" over the segments' first tiles (a segment without rows owns no tile).
+// of systems (one system = the s1 partition of one root) by the segment-tile scheme of seg_tiles.hpp, which states the invariant these
+// launches keep; it holds per (system, slot).  Plain C++ stores only.
 //
 // A thread holds the two rows t and t + 256 of its tile in registers; the loop over the slots b = -1, 0 .. G - 1 is wave-uniform, as in
 // jack_partial_kernel, and a row enters slot b's sums by compare-and-select (g != b): no indexed private array, no scratch.  Every
@@ -24,15 +21,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "chain_farm.hpp"
+#include "block_reduce.hpp"
 #include "jack_groups.hpp"
 #include "like_moments.hpp"
-#include "reduce_kernels.hpp"
+#include "seg_tiles.hpp"
 
 namespace mce {
 
 constexpr int kJgThreads = kRedThreads;
-constexpr int kJgTileRows = 512;
+constexpr int kJgTileRows = mce_seg::kSegTileRows;
 constexpr int kJgTileSums = 6;                                  // per tile and slot: rows, sum a, sum a f, sum a^2, used rows, refused rows
 constexpr int kJgSys = 6;                                       // per system and slot after step 1: rows, W, c, A2, used rows, status
 static_assert(kJgTileRows == 2 * kJgThreads, "a thread holds two rows of its tile");
@@ -75,14 +72,14 @@ struct JgRows {
 
 __device__ __forceinline__ int64_t jg_load_rows(const JgSeg* __restrict__ segs, const int64_t* __restrict__ tile0, int nseg, int64_t tile, JgRows& r)
 {
-    const int64_t s = mce_farm::last_at_or_below(tile0, nseg, tile);
-    const int64_t n = segs[s].n;
+    int64_t r0, r1;
+    const int64_t s = mce_seg::seg_tile_rows(segs, tile0, nseg, tile, r0, r1);
     const double* __restrict__ w = segs[s].w;
     const double* __restrict__ fs = segs[s].fs;
     const int32_t* __restrict__ g = segs[s].g;
-    const int64_t i0 = (tile - tile0[s]) * kJgTileRows + threadIdx.x, i1 = i0 + kJgThreads;
-    r.live0 = i0 < n;
-    r.live1 = i1 < n;
+    const int64_t i0 = r0 + threadIdx.x, i1 = i0 + kJgThreads;
+    r.live0 = i0 < r1;
+    r.live1 = i1 < r1;
     r.a0 = r.live0 ? w[i0] : 0.0;
     r.a1 = r.live1 ? w[i1] : 0.0;
     r.g0 = r.live0 ? (int)g[i0] : -2;
@@ -91,21 +88,6 @@ __device__ __forceinline__ int64_t jg_load_rows(const JgSeg* __restrict__ segs, 
     r.f0 = (fs && r.live0 && mce_mom::mom_used(r.a0)) ? fs[i0] : 0.0;
     r.f1 = (fs && r.live1 && mce_mom::mom_used(r.a1)) ? fs[i1] : 0.0;
     return s;
-}
-
-// OR over the workgroup, valid in every thread.  `red64` = kJgThreads / 64 words of LDS.
-__device__ __forceinline__ unsigned long long block_or(unsigned long long v, unsigned long long* red64)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v |= __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red64[wv] = v;
-    __syncthreads();
-    unsigned long long m = 0;
-#pragma unroll
-    for (int i = 0; i < kJgThreads / 64; ++i) m |= red64[i];
-    return m;
 }
 
 // grid: the tiles.  sums[tile][Gmax + 1][kJgTileSums]; *bad_ids = 1.0 where a group id lies outside [0, G)
@@ -166,14 +148,8 @@ __global__ __launch_bounds__(kJgThreads) void jg_centre_kernel(const JgSeg* __re
     __shared__ double red[kJgThreads / 64];
     const int y = blockIdx.x, slot = blockIdx.y;
     if (slot > segs[y].G) return;
-    const int64_t t0 = tile0[y], nt = (segs[y].n + kJgTileRows - 1) / kJgTileRows;
-    double acc[kJgTileSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int64_t k = threadIdx.x; k < nt; k += kJgThreads)
-#pragma unroll
-        for (int j = 0; j < kJgTileSums; ++j) acc[j] += sums[((t0 + k) * nslots + slot) * kJgTileSums + j];
     double tot[kJgTileSums];
-#pragma unroll
-    for (int j = 0; j < kJgTileSums; ++j) tot[j] = block_sum(acc[j], red);
+    block_fold<kJgTileSums>(sums + (tile0[y] * nslots + slot) * kJgTileSums, mce_seg::seg_ntiles(segs[y].n), (int64_t)nslots * kJgTileSums, tot, red);
     if (threadIdx.x == 0) {
         const double W = tot[1];
         double* out = sys + ((int64_t)y * nslots + slot) * kJgSys;
@@ -214,11 +190,8 @@ __global__ __launch_bounds__(kJgThreads) void jg_result_kernel(const JgSeg* __re
     const int y = blockIdx.x, slot = blockIdx.y;
     if (slot > segs[y].G) return;
     const bool moments = segs[y].fs != nullptr;
-    const int64_t t0 = tile0[y], nt = (segs[y].n + kJgTileRows - 1) / kJgTileRows;
-    double acc = 0.0;
-    if (moments)
-        for (int64_t k = threadIdx.x; k < nt; k += kJgThreads) acc += part[(t0 + k) * nslots + slot];
-    const double V = block_sum(acc, red);
+    double V;                                                            // (no moments: no tile is read)
+    block_fold<1>(part + tile0[y] * nslots + slot, moments ? mce_seg::seg_ntiles(segs[y].n) : 0, nslots, &V, red);
     if (threadIdx.x == 0) {
         const double* in = sys + ((int64_t)y * nslots + slot) * kJgSys;
         mce_jg::jg_pack(moments, in[0], in[1], (int)in[5], in[1], in[2], V / in[1], in[3], in[4], res + ((int64_t)segs[y].slot0 + slot) * mce_jg::kJgOut);

@@ -17,8 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_reduce.hpp"
 #include "jack.hpp"
-#include "reduce_kernels.hpp"
 
 namespace mce {
 

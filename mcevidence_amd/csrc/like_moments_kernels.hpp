@@ -1,11 +1,7 @@
 // like_moments_kernels.hpp -- the weighted moments of the likelihood column behind information= (mce_like_moments_dev,
 // capi_moments.hpp) for columns that are already on the device.  The rule is like_moments.hpp's; this file arranges it into four
-// launches that serve any number of systems (one system = one (fs, w, n) segment: the s1 partition of one root).  fp64 throughout,
-// no floating-point atomics, plain C++ stores only, 64-bit row indices.  A tile is kMomTileRows = 512 rows of ONE segment, counted from
-// the segment's first row, so a tile never spans two systems and every sum is formed in an order that the system's own row count
-// fixes: two runs give the same bits, and a system's bits do not depend on its neighbours, its position or the call.  The tile ->
-// segment lookup is chain_farm.hpp's "last entry at or below the key" over the segments' first tiles (a segment without rows owns no
-// tile and is never the answer).
+// launches that serve any number of systems (one system = one (fs, w, n) segment: the s1 partition of one root) by the segment-tile
+// scheme of seg_tiles.hpp, which states the invariant these launches keep.  Plain C++ stores only.
 //
 //   mom_sum_tile_kernel      step 1, per tile: sum a, sum a f, sum a^2, the used rows, the rows status 3 refuses -- five block_sums
 //   mom_centre_kernel        one workgroup per system: its tiles, thread t taking t, t + 256, .., then block_sum: W, c = S / W, the status
@@ -17,14 +13,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "chain_farm.hpp"
+#include "block_reduce.hpp"
 #include "like_moments.hpp"
-#include "reduce_kernels.hpp"
+#include "seg_tiles.hpp"
 
 namespace mce {
 
 constexpr int kMomThreads = kRedThreads;
-constexpr int kMomTileRows = 512;
+constexpr int kMomTileRows = mce_seg::kSegTileRows;
 constexpr int kMomTileSums = 5;                                 // per tile: sum a, sum a f, sum a^2, used rows, refused rows
 constexpr int kMomSys = 5;                                      // per system after step 1: W, c, A2, used rows, status
 
@@ -34,17 +30,6 @@ struct MomSeg {
     int64_t n;
 };
 
-// the rows [r0, r1) of tile `tile`, and its segment
-__device__ __forceinline__ int64_t mom_tile_rows(const MomSeg* __restrict__ segs, const int64_t* __restrict__ tile0, int nseg, int64_t tile, int64_t& r0,
-                                                 int64_t& r1)
-{
-    const int64_t s = mce_farm::last_at_or_below(tile0, nseg, tile);
-    const int64_t n = segs[s].n;
-    r0 = (tile - tile0[s]) * kMomTileRows;
-    r1 = r0 + kMomTileRows < n ? r0 + kMomTileRows : n;
-    return s;
-}
-
 // grid: the tiles.  sums[tile][kMomTileSums]
 __global__ __launch_bounds__(kMomThreads) void mom_sum_tile_kernel(const MomSeg* __restrict__ segs, const int64_t* __restrict__ tile0, int nseg,
                                                                    double* __restrict__ sums)
@@ -52,7 +37,7 @@ __global__ __launch_bounds__(kMomThreads) void mom_sum_tile_kernel(const MomSeg*
     __shared__ double red[kMomThreads / 64];
     const int64_t tile = blockIdx.x;
     int64_t r0, r1;
-    const int64_t s = mom_tile_rows(segs, tile0, nseg, tile, r0, r1);
+    const int64_t s = mce_seg::seg_tile_rows(segs, tile0, nseg, tile, r0, r1);
     const double* __restrict__ fs = segs[s].fs;
     const double* __restrict__ w = segs[s].w;
     double sa = 0.0, saf = 0.0, saa = 0.0, cnt = 0.0, bad = 0.0;
@@ -80,14 +65,8 @@ __global__ __launch_bounds__(kMomThreads) void mom_centre_kernel(const MomSeg* _
 {
     __shared__ double red[kMomThreads / 64];
     const int y = blockIdx.x;
-    const int64_t t0 = tile0[y], nt = (segs[y].n + kMomTileRows - 1) / kMomTileRows;
-    double acc[kMomTileSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int64_t k = threadIdx.x; k < nt; k += kMomThreads)
-#pragma unroll
-        for (int j = 0; j < kMomTileSums; ++j) acc[j] += sums[(t0 + k) * kMomTileSums + j];
     double tot[kMomTileSums];
-#pragma unroll
-    for (int j = 0; j < kMomTileSums; ++j) tot[j] = block_sum(acc[j], red);
+    block_fold<kMomTileSums>(sums + tile0[y] * kMomTileSums, mce_seg::seg_ntiles(segs[y].n), kMomTileSums, tot, red);
     if (threadIdx.x == 0) {
         const double W = tot[0];
         double* out = sys + (int64_t)y * kMomSys;
@@ -106,7 +85,7 @@ __global__ __launch_bounds__(kMomThreads) void mom_var_tile_kernel(const MomSeg*
     __shared__ double red[kMomThreads / 64];
     const int64_t tile = blockIdx.x;
     int64_t r0, r1;
-    const int64_t s = mom_tile_rows(segs, tile0, nseg, tile, r0, r1);
+    const int64_t s = mce_seg::seg_tile_rows(segs, tile0, nseg, tile, r0, r1);
     const double* __restrict__ fs = segs[s].fs;
     const double* __restrict__ w = segs[s].w;
     const double c = sys[s * kMomSys + 1];
@@ -125,10 +104,8 @@ __global__ __launch_bounds__(kMomThreads) void mom_result_kernel(const MomSeg* _
 {
     __shared__ double red[kMomThreads / 64];
     const int y = blockIdx.x;
-    const int64_t t0 = tile0[y], nt = (segs[y].n + kMomTileRows - 1) / kMomTileRows;
-    double acc = 0.0;
-    for (int64_t k = threadIdx.x; k < nt; k += kMomThreads) acc += part[t0 + k];
-    const double V = block_sum(acc, red);
+    double V;
+    block_fold<1>(part + tile0[y], mce_seg::seg_ntiles(segs[y].n), 1, &V, red);
     if (threadIdx.x == 0) {
         const double* in = sys + (int64_t)y * kMomSys;
         mce_mom::mom_pack((int)in[4], in[0], in[1], V / in[0], in[2], in[3], res + (int64_t)y * mce_mom::kMomOut);

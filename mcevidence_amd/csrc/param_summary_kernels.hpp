@@ -1,11 +1,8 @@
 // param_summary_kernels.hpp -- the posterior summary behind summary= (mce_param_summary_dev, capi_summary.hpp) for chains that are
 // already on the device.  The rule is param_summary.hpp's; this file arranges it into launches that serve any number of systems (one
-// system = one (x, ld, n, d, w, fs) segment: the s1 partition of one root).  fp64 throughout, no floating-point atomics, plain C++
-// stores only, 64-bit row indices.  A tile is kSumTileRows = 512 rows of ONE segment, counted from the segment's first row, so a tile
-// never spans two systems and every sum is formed in an order that the system's own row count fixes: two runs give the same bits, and
-// a system's bits do not depend on its neighbours, its position, the call or the size of a sort pass.  The tile -> segment lookup is
-// chain_farm.hpp's "last entry at or below the key" over the segments' first tiles (a segment without rows owns no tile and is never
-// the answer).  A RUN is one (system, column): the n values of the column with their weights.
+// system = one (x, ld, n, d, w, fs) segment: the s1 partition of one root) by the segment-tile scheme of seg_tiles.hpp, which states
+// the invariant these launches keep; here a system's bits do not depend on the size of a sort pass either.  Plain C++ stores only.
+// A RUN is one (system, column): the n values of the column with their weights.
 //
 //   sum_tile_kernel      per tile: sum a, sum a^2, the used rows, the rows with a bad weight / a NaN f, the (max f, lowest row) pair;
 //                        per tile and column: sum a x, min, max, the rows with a value that is not finite
@@ -25,15 +22,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "chain_farm.hpp"
+#include "block_reduce.hpp"
 #include "param_summary.hpp"
-#include "reduce_kernels.hpp"
+#include "seg_tiles.hpp"
 
 namespace mce {
 
 constexpr int kPsumThreads = kRedThreads;
-constexpr int kSumWaves = kPsumThreads / 64;
-constexpr int kSumTileRows = 512;
+constexpr int kSumWaves = kRedWaves;
+constexpr int kSumTileRows = mce_seg::kSegTileRows;
+static_assert(kSumTileRows == 2 * kPsumThreads, "a thread holds two rows of its tile");
 constexpr int kSumScanTile = 1024;                              // sorted elements per scan tile: 4 per thread
 constexpr int kSumTileHead = 7;                                 // per tile: sum a, sum a^2, used, bad weights, bad f, best f, best row
 constexpr int kSumTileCol = 4;                                  // per tile and column: sum a x, min, max, bad values
@@ -57,77 +55,6 @@ struct SumRun {
     int32_t seg, col;
 };
 
-__device__ __forceinline__ double wave_min(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const double u = __shfl_down(v, o, 64); v = u < v ? u : v; }
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const double u = __shfl_down(v, o, 64); v = u > v ? u : v; }
-    return v;
-}
-// the better of the pairs of a wave, in lane 0
-__device__ __forceinline__ void wave_best(double& f, long long& row)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double uf = __shfl_down(f, o, 64);
-        const long long ur = __shfl_down(row, o, 64);
-        if (mce_sum::sum_better(uf, ur, f, row)) { f = uf; row = ur; }
-    }
-}
-// the best pair of the workgroup, in thread 0.  bf, br: kSumWaves entries of LDS each
-__device__ __forceinline__ void block_best(double& f, long long& row, double* bf, long long* br)
-{
-    wave_best(f, row);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) { bf[w] = f; br[w] = row; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        f = bf[0];
-        row = br[0];
-        for (int i = 1; i < kSumWaves; ++i)
-            if (mce_sum::sum_better(bf[i], br[i], f, row)) { f = bf[i]; row = br[i]; }
-    }
-}
-__device__ __forceinline__ double block_min(double v, double* red)
-{
-    v = wave_min(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int i = 1; i < kSumWaves; ++i) s = red[i] < s ? red[i] : s;
-    return s;
-}
-__device__ __forceinline__ double block_max(double v, double* red)
-{
-    v = wave_max(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int i = 1; i < kSumWaves; ++i) s = red[i] > s ? red[i] : s;
-    return s;
-}
-
-// the rows [r0, r1) of tile `tile`, and its segment
-__device__ __forceinline__ int64_t sum_tile_rows(const SumSeg* __restrict__ segs, const int64_t* __restrict__ tile0, int nseg, int64_t tile, int64_t& r0,
-                                                 int64_t& r1)
-{
-    const int64_t s = mce_farm::last_at_or_below(tile0, nseg, tile);
-    const int64_t n = segs[s].n;
-    r0 = (tile - tile0[s]) * kSumTileRows;
-    r1 = r0 + kSumTileRows < n ? r0 + kSumTileRows : n;
-    return s;
-}
-
 // grid: the tiles.  head[tile][kSumTileHead], cols[tile][kSumTileCol][dmax].  Thread t owns the rows r0 + t and r0 + t + 256 of the
 // tile (a row past the tile's end, in the last tile of a segment, is treated as a row that is not used); per column the wave's 128 rows
 // are combined by shuffles, the four waves in wave order.
@@ -140,7 +67,7 @@ __global__ __launch_bounds__(kPsumThreads) void sum_tile_kernel(const SumSeg* __
     __shared__ double part[kSumWaves][kSumTileCol][mce_sum::kSumMaxDim + 1];
     const int64_t tile = blockIdx.x;
     int64_t r0, r1;
-    const int64_t s = sum_tile_rows(segs, tile0, nseg, tile, r0, r1);
+    const int64_t s = mce_seg::seg_tile_rows(segs, tile0, nseg, tile, r0, r1);
     const SumSeg g = segs[s];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t ra = r0 + threadIdx.x, rb = ra + kPsumThreads;
@@ -159,7 +86,7 @@ __global__ __launch_bounds__(kPsumThreads) void sum_tile_kernel(const SumSeg* __
         const double v = block_sum(t[k], red);
         if (threadIdx.x == 0) head[tile * kSumTileHead + k] = v;
     }
-    block_best(bestf, bestr, bf, br);
+    block_best(bestf, bestr, bf, br, mce_sum::sum_better);
     if (threadIdx.x == 0) {
         head[tile * kSumTileHead + 5] = bestf;
         head[tile * kSumTileHead + 6] = (double)bestr;
@@ -202,7 +129,8 @@ __global__ __launch_bounds__(kPsumThreads) void sum_sys_kernel(const SumSeg* __r
     __shared__ double bf[kSumWaves];
     __shared__ long long br[kSumWaves];
     const int y = blockIdx.x;
-    const int64_t t0 = tile0[y], nt = (segs[y].n + kSumTileRows - 1) / kSumTileRows;
+    // (block_fold's order, written out: the best pair shares the one pass over the tiles with the five sums)
+    const int64_t t0 = tile0[y], nt = mce_seg::seg_ntiles(segs[y].n);
     double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     double bestf = 0.0;
     long long bestr = -1;
@@ -216,7 +144,7 @@ __global__ __launch_bounds__(kPsumThreads) void sum_sys_kernel(const SumSeg* __r
     double tot[5];
 #pragma unroll
     for (int j = 0; j < 5; ++j) tot[j] = block_sum(acc[j], red);
-    block_best(bestf, bestr, bf, br);
+    block_best(bestf, bestr, bf, br, mce_sum::sum_better);
     if (threadIdx.x == 0) {
         double* out = sys + (int64_t)y * kSumSys;
         out[0] = tot[0];
@@ -235,7 +163,8 @@ __global__ __launch_bounds__(kPsumThreads) void sum_col_kernel(const SumSeg* __r
     __shared__ double red[kSumWaves];
     const int64_t r = blockIdx.x;
     const int y = runs[r].seg, j = runs[r].col;
-    const int64_t t0 = tile0[y], nt = (segs[y].n + kSumTileRows - 1) / kSumTileRows;
+    // (block_fold's order, written out: the extremes share the one pass over the tiles with the two sums)
+    const int64_t t0 = tile0[y], nt = mce_seg::seg_ntiles(segs[y].n);
     const double INF = __builtin_huge_val();
     double sx = 0.0, mn = INF, mx = -INF, bad = 0.0;
     for (int64_t k = threadIdx.x; k < nt; k += kPsumThreads) {
@@ -266,7 +195,7 @@ __global__ __launch_bounds__(kPsumThreads) void sum_var_tile_kernel(const SumSeg
     __shared__ double lds[kSumWaves][mce_sum::kSumMaxDim + 1];
     const int64_t tile = blockIdx.x;
     int64_t r0, r1;
-    const int64_t s = sum_tile_rows(segs, tile0, nseg, tile, r0, r1);
+    const int64_t s = mce_seg::seg_tile_rows(segs, tile0, nseg, tile, r0, r1);
     const SumSeg g = segs[s];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t ra = r0 + threadIdx.x, rb = ra + kPsumThreads;
@@ -297,10 +226,8 @@ __global__ __launch_bounds__(kPsumThreads) void sum_var_col_kernel(const SumSeg*
     __shared__ double red[kSumWaves];
     const int64_t r = blockIdx.x;
     const int y = runs[r].seg, j = runs[r].col;
-    const int64_t t0 = tile0[y], nt = (segs[y].n + kSumTileRows - 1) / kSumTileRows;
-    double acc = 0.0;
-    for (int64_t k = threadIdx.x; k < nt; k += kPsumThreads) acc += part[(t0 + k) * dmax + j];
-    const double V = block_sum(acc, red);
+    double V;
+    block_fold<1>(part + tile0[y] * dmax + j, mce_seg::seg_ntiles(segs[y].n), dmax, &V, red);
     if (threadIdx.x == 0) col[r * kSumCol + 1] = V / sys[(int64_t)y * kSumSys + 0];
 }
 
@@ -308,13 +235,7 @@ __global__ __launch_bounds__(kPsumThreads) void sum_var_col_kernel(const SumSeg*
 // next run and is never the answer)
 template <bool BY_TILE> __device__ __forceinline__ int sum_run_of(const SumRun* __restrict__ runs, int nruns, int64_t e)
 {
-    int lo = 0, hi = nruns - 1;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if ((BY_TILE ? runs[mid].tile0 : runs[mid].begin) <= e) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
+    return mce_seg::last_at_or_below(nruns, e, [runs](int i) { return BY_TILE ? runs[i].tile0 : runs[i].begin; });
 }
 
 // grid: the elements of the pass, one thread each.  keys[e], wts[e]

@@ -9,32 +9,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "reduce_kernels.hpp"
+#include "block_reduce.hpp"
 
 namespace mce {
 
 constexpr int kPrefixThreads = 256;
 constexpr int kPrefixMaxRows = 4 * kPrefixThreads;      // rows of logl per workgroup of prefix_max_kernel
 constexpr int kMaxPrefix = 256;                         // == MCE_MAX_PREFIX
-static_assert(kPrefixThreads == kRedThreads, "block_sum's tree is kRedThreads wide");
-
-// maximum and "a NaN was seen" over the workgroup; result valid in thread 0.  fmax drops NaNs, so they travel in the flag.
-__device__ __forceinline__ void block_max_nan(double& m, int& nan, double* red_m, int* red_n)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        m = fmax(m, __shfl_down(m, o, 64));
-        nan |= __shfl_down(nan, o, 64);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) { red_m[w] = m; red_n[w] = nan; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 1; i < kPrefixThreads / 64; ++i) { m = fmax(m, red_m[i]); nan |= red_n[i]; }
-    }
-}
+static_assert(kPrefixThreads == kRedThreads, "block_sum's and block_max_nan's trees are kRedThreads wide");
 
 // Workgroup j reads the rows [j R, min((j + 1) R, p_max)), R = kPrefixMaxRows, once, and writes for every segment
 // s = [p_{s-1}, p_s) that meets them blkmax[s][j] = the maximum over the rows of both (NaN if one of them is NaN).  A segment s

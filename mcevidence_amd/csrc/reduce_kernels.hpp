@@ -14,37 +14,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_reduce.hpp"  // kRedThreads, wave_sum, block_sum
 #include "sym_types.hpp"
 #include "f16_filter.hpp"   // list_insert
 
 namespace mce {
 
-constexpr int kRedThreads = 256;
 constexpr int kMaxK = 32;        // == MCE_MAX_K
 constexpr int kMaxLists = 16;    // reference splits merged per query
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// sum over the workgroup; result valid in thread 0.  `red` = kRedThreads/64 doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double* red)
-{
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < kRedThreads / 64; ++i) s += red[i];
-    }
-    return s;
-}
 
 // ---------------------------------------------------------------------------
 // merge_lists: one thread per query merges its L sorted per-split lists into the K best

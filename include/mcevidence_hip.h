@@ -629,6 +629,32 @@ int mce_param_summary_dev(const mce_summary_seg* segs, int32_t nseg, const doubl
                           void* stream);
 int mce_param_summary_f64(const mce_summary_seg* segs, int32_t nseg, const double* q, int32_t nq, int64_t pass_elems, double* out, int32_t device);
 
+/* The weighted parameter covariance behind covariance= (the weighted mean and the covariance matrix of the first d parameter columns),
+ * for MANY systems (the ready roots of a farm wave) in one call.  The rule is stated in csrc/param_cov.hpp and docs/design/tension.md.
+ * One system is one segment: x[n][ld] the RAW rows (the first d columns are measured) and w[n] the weights of the s1 partition the
+ * estimator sums over; segments may differ in d and ld.  A row with w == 0 is skipped and nothing of it is read into a result.
+ * out (HOST, packed in segment order, mce_param_cov_out_doubles(d) doubles per system) = {W, A2 = sum w^2, rows used, status, column,
+ * reserved x 3} then mean[d] (bit for bit mce_param_summary_dev's mean of the same segment) and cov[d (d + 1) / 2], the packed upper
+ * triangle, row-major, i <= j: C_ij = sum w (x_i - m_i)(x_j - m_j) / W about the computed mean.  status 0 ok (column -1); 3 a weight
+ * that is negative or not finite (column -1), else a used row with a value that is not finite (column: the lowest such); 5 W is not
+ * > 0.  With a status other than 0 every value is NaN; a failing system fails alone.  A system's bits depend on its own rows alone:
+ * not on its neighbours, its position or the number of systems.  Everything runs on `stream` with one host wait; the number of
+ * launches does not depend on nseg.  Segments and workspace (mce_param_cov_workspace_bytes(rows of all segments, nseg, the largest d))
+ * are the caller's.  mce_param_cov_f64 takes HOST segments, uploads them to `device` and calls the device form.  Argument errors (d
+ * outside 1 .. 127, ld < d, negative sizes, null pointers): MCE_ERR_INVALID (no device needed); no visible device: MCE_ERR_NO_DEVICE. */
+#define MCE_COV_HEAD 8
+typedef struct mce_cov_seg {
+    const double* x;
+    int64_t ld;
+    int64_t n;
+    int32_t d;
+    const double* w;
+} mce_cov_seg;
+size_t mce_param_cov_out_doubles(int32_t d);
+size_t mce_param_cov_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t dmax);
+int mce_param_cov_dev(const mce_cov_seg* segs, int32_t nseg, double* out, void* ws, size_t ws_bytes, void* stream);
+int mce_param_cov_f64(const mce_cov_seg* segs, int32_t nseg, double* out, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

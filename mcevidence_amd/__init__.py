@@ -9,8 +9,9 @@ from .chains import MCSamples
 from .evidence import HipBackend, MCEvidence, evidence_many
 from .resident import ResidentChains, evidence_from_files
 from .farm import evidence_many_from_files, farm_waves
+from .tension import evidence_tension
 from .prior import cosmo_params_list, get_prior_volume, iscosmo_param, params_info
 
-__all__ = ["MCEvidence", "evidence_many", "MCSamples", "HipBackend", "ResidentChains", "evidence_from_files", "evidence_many_from_files", "farm_waves", "params_info", "get_prior_volume", "iscosmo_param",
+__all__ = ["MCEvidence", "evidence_many", "MCSamples", "HipBackend", "ResidentChains", "evidence_from_files", "evidence_many_from_files", "farm_waves", "evidence_tension", "params_info", "get_prior_volume", "iscosmo_param",
            "cosmo_params_list"]
 __version__ = "0.1.0"

@@ -197,6 +197,19 @@ SIGNATURES["mce_param_summary_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.
 SIGNATURES["mce_param_summary_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int64, _P, _P, _c.c_size_t, _P])
 SIGNATURES["mce_param_summary_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int64, _P, _c.c_int32])
 
+
+class CovSeg(ctypes.Structure):
+    """``mce_cov_seg``: one system of ``mce_param_cov_*`` -- its raw rows (address, row stride in doubles, rows, measured columns) and
+    the address of its w column"""
+    _fields_ = [("x", _P), ("ld", _c.c_int64), ("n", _c.c_int64), ("d", _c.c_int32), ("w", _P)]
+
+
+MCE_COV_HEAD = 8
+SIGNATURES["mce_param_cov_out_doubles"] = (_c.c_size_t, [_c.c_int32])
+SIGNATURES["mce_param_cov_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_cov_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_param_cov_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
+
 class JackGroupsSeg(ctypes.Structure):
     """``mce_jack_groups_seg``: one system of ``mce_jack_groups_dev`` (rows / src / out: device addresses; part_first: a host array)."""
     _fields_ = [("rows", _P), ("src", _P), ("part_first", _P), ("nparts", _c.c_int64), ("n", _c.c_int64), ("N", _c.c_int64), ("G", _c.c_int32),
@@ -728,6 +741,51 @@ def param_summary(systems, q, device=0, pass_elems=0):
     segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0, f.ctypes.data if f is not None and f.size else 0)
             for x, d, w, f in keep]
     return _param_summary(load().mce_param_summary_f64, segs, q, pass_elems, (int(device),))
+
+
+def param_cov_out_doubles(d):
+    return int(load().mce_param_cov_out_doubles(int(d)))
+
+
+def param_cov_workspace_bytes(nrows_total, nseg, dmax):
+    return int(load().mce_param_cov_workspace_bytes(int(nrows_total), int(nseg), int(dmax)))
+
+
+def cov_block_doubles(d):
+    """doubles of one system's result block: MCE_COV_HEAD + d + d (d + 1) / 2"""
+    return MCE_COV_HEAD + int(d) + int(d) * (int(d) + 1) // 2
+
+
+def _param_cov(call, segs, tail):
+    arr = (CovSeg * max(len(segs), 1))()
+    for i, (x, ld, n, d, w) in enumerate(segs):
+        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w = x or None, int(ld), int(n), int(d), w or None
+    sizes = [cov_block_doubles(d) if 1 <= int(d) <= 127 else 0 for _, _, _, d, _ in segs]
+    out = np.full(max(sum(sizes), 1), np.nan)
+    check(call(_c.cast(arr, _P), len(segs), out.ctypes.data, *tail))
+    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
+    return [out[at[i]:at[i + 1]] for i in range(len(segs))]
+
+
+def param_cov_dev(segs, ws, ws_bytes, stream=0):
+    """mce_param_cov_dev: the weighted mean and covariance of ``len(segs)`` systems that are on the device -> one float64 block per
+    system (``covariance.from_block`` reads it); ``segs``: [(device address of the rows, row stride in doubles, rows, measured columns,
+    device address of w)]"""
+    return _param_cov(load().mce_param_cov_dev, segs, (ws or None, int(ws_bytes), stream or None))
+
+
+def param_cov(systems, device=0):
+    """mce_param_cov_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
+    keep = []
+    for x, d, w in systems:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if x.shape[0] != w.size:
+            raise ValueError("param cov: rows and w of one length expected")
+        keep.append((x, int(d), w))
+    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
+    return _param_cov(load().mce_param_cov_f64, segs, (int(device),))
 
 
 def jack_groups_dev(segs, stream=0):

@@ -65,6 +65,12 @@ def build_parser(prog=None):
                    help="print the weighted mean, standard deviation, equal-tailed limits (probabilities P ...; default 0.68 0.95) and the "
                         "best-fit sample of every parameter used, after the information lines and before the ln(B) lines: logged with them "
                         "at -vb 1, printed where the ln(B) lines are printed (--farm, --jackknife) at -vb 0; write it after root_name")
+    p.add_argument("--tension", dest="tension", nargs=2, default=None, metavar=("ROOT_A", "ROOT_B"),
+                   help="tension between the data sets of the roots ROOT_A and ROOT_B under one model, root_name being their JOINT run: the three "
+                        "roots in one batched GPU pass (mcevidence_amd.tension), then ln R, ln I, the suspiciousness ln S, the dimensionality d "
+                        "with its p-value, and the Gaussian parameter shift in the parameters A and B share; composes with --jackknife, --burn, "
+                        "--thin, --thin-corr, -k, --cross, --converge and --summary (all three roots take them), not with --farm or --resident; write it "
+                        "after root_name")
     return p
 
 
@@ -178,6 +184,44 @@ def farm_main(args):
     return outs
 
 
+def tension_main(args):
+    """``--tension ROOT_A ROOT_B``: the three roots as ``--farm`` prints roots, then the tension lines and their footnote.  ``--cross``,
+    ``--converge`` and ``--summary`` go to all three roots (``--information`` is always set); ``--farm`` and ``--resident`` name another
+    route for ``root_name`` and are refused"""
+    import copy
+    from . import tension
+    roots = [args.tension[0], args.tension[1], args.root_name]
+    pvols, ndims = [], []
+    for r in roots:
+        a = copy.copy(args)
+        a.root_name = r
+        pvols.append(prior.get_prior_volume(a, cosmo=not args.allparams))      # (sets a.ndim, as for one root)
+        ndims.append(a.ndim)
+    logging.getLogger("mcevidence_amd").setLevel(
+        logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
+    ea, eb, eab, info = tension.evidence_tension(roots[0], roots[1], roots[2], kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen,
+                                                 thinlen=args.thinlen, idchain=args.idchain, split=args.cross, **_thin_kw(args), **_converge_kw(args),
+                                                 **_summary_kw(args), **_jackknife_kw(args), **_backend_kw(args))
+    note = None
+    for r, mle, inf in zip(roots, (ea, eb, eab), info["roots"]):
+        print()
+        print("Using file: ", r)
+        _print_converge(inf)
+        _print_information(inf)
+        _print_summary(inf)
+        note = _print_lnb(mle, inf) or note
+    print()
+    print("Tension of {} and {} (joint run: {})".format(*roots))
+    for line in tension.lines(info["tension"]):
+        print(line)
+    if note:
+        _print_jackknife_note(note)
+    print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
+    print(tension.FOOTNOTE)
+    print("")
+    return ea, eb, eab, info
+
+
 def main(argv=None):
     args = build_parser(prog="MCEvidence.py").parse_args(argv)
     if args.paramsfile:
@@ -187,6 +231,10 @@ def main(argv=None):
         for n in new:
             if n not in prior.cosmo_params_list:
                 prior.cosmo_params_list.append(n)
+    if args.tension is not None:
+        if args.farm or args.resident:
+            build_parser(prog="MCEvidence.py").error("--tension runs its three roots in one batched pass: it does not combine with --farm or --resident")
+        return tension_main(args)
     if args.farm:
         return farm_main(args)
     prior_volume = prior.get_prior_volume(args, cosmo=not args.allparams)

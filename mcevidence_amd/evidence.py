@@ -29,6 +29,7 @@ import numpy as np
 
 from . import information as _information
 from . import summary as _summary
+from . import covariance as _covariance
 from .chains import MCSamples, rank0_draw
 from .resident import mle_from_sums
 
@@ -207,7 +208,9 @@ class MCEvidence(object):
         Bayesian model dimensionality in ``info["information"]`` (information.py; docs/design/information.md) -- and ``summary`` -- None,
         True (68 % and 95 %) or up to 7 probabilities: ``evidence()`` then also stores the weighted means, standard deviations,
         equal-tailed limits and the best-fit sample of the first ``ndim`` parameters in ``info["summary"]`` and in
-        ``self.param_summary`` (summary.py; docs/design/summary.md; ``self.summary()`` stays the reference's printing method).
+        ``self.param_summary`` (summary.py; docs/design/summary.md; ``self.summary()`` stays the reference's printing method) -- and
+        ``covariance`` -- None or True: ``evidence()`` then also stores the weighted mean and covariance matrix of the first ``ndim``
+        parameters in ``info["covariance"]`` and in ``self.param_cov`` (covariance.py; docs/design/tension.md).
 
         method      chain root name / file name(s), or list/tuple/dict of chain arrays
                     (columns: weight, -lnL, parameters...)
@@ -236,6 +239,11 @@ class MCEvidence(object):
         # (what the last evidence() found is kept as ``param_summary``: ``summary`` is the reference's method of this class)
         self.param_summary = None
         _summary.refuse(self.summary_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
+        # the weighted mean and covariance matrix of the parameters with every evidence() call (docs/design/tension.md): None (off:
+        # nothing changes) or True; consumed here for the same reason
+        self.covariance = gdkwargs.pop("covariance", None)
+        self.param_cov = None
+        _covariance.refuse(self.covariance, brange=brange, nbatch=nbatch, isfunc=isfunc)
         self.logger = logger
         self.verbose = verbose
         self.debug = bool(debug or verbose > 1)
@@ -490,9 +498,21 @@ class MCEvidence(object):
                                _summary.targets(probs))
         self.param_summary = self.info["summary"] = _summary.build(blk, probs, logLmax, _summary.param_names(self.fname, self.ndim))
 
+    def _fill_covariance(self):
+        """``info["covariance"]`` of this call (the constructor's ``covariance`` keyword; unset: nothing happens): the rule of
+        covariance.py on s1's weights and its raw first ``ndim`` columns, on the host -- under a process group every rank computes its
+        own, no collective"""
+        if _covariance.spec(self.covariance) is None:
+            return
+        _covariance.refuse(self.covariance, brange=self.brange, nbatch=self.nbatch)
+        samples, _, _ = self.gd.arrays("s1")
+        blk = _covariance.measure(self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim])
+        self.param_cov = self.info["covariance"] = _covariance.build(blk, _covariance.param_names(self.fname, self.ndim))
+
     def _report(self, MLE, verbose, info, pos_lnp=False):
         self._fill_information(MLE, pos_lnp)
         self._fill_summary(pos_lnp)
+        self._fill_covariance()
         if verbose > 0 and "information" in self.info and _information.wanted(self.information):
             for line in _information.lines(self.info["information"]):
                 self.logger.info(line)

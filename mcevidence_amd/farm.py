@@ -22,6 +22,7 @@ import numpy as np
 from . import information as _information
 from . import resident as _res
 from . import summary as _summary
+from . import covariance as _covariance
 
 logger = logging.getLogger("mcevidence_amd")
 
@@ -215,7 +216,7 @@ class _Root(object):
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
                              require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto",
-                             information=None, jackknife=None, summary=None):
+                             information=None, jackknife=None, summary=None, covariance=None):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -241,7 +242,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     roots one probability each; a list of such entries of another length, or a mixture, is a ``ValueError`` before any work): the
     weighted means, standard deviations, equal-tailed limits and the best-fit sample of every such root's first ``ndim`` parameters in
     ``info["summary"]`` -- ONE ``mce_param_summary_dev`` call per wave (and per set of probabilities) over all its ready roots, thinned
-    and unthinned alike, before the feed.  Without a GPU: ``RuntimeError``."""
+    and unthinned alike, before the feed.  ``covariance`` (one value or one per root: None or True): the weighted mean and covariance matrix
+    of every such root's first ``ndim`` parameters in ``info["covariance"]`` -- ONE ``mce_param_cov_dev`` call per wave over all its ready
+    roots that ask, thinned and unthinned alike, before the feed.  Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
     roots = list(roots)
@@ -260,11 +263,15 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     jack_kw = [{} if v is None or v is False else {"jackknife": v} for v in jacks]
     sums = _per_root_summary(summary, n)
     sum_kw = [{"summary": v} if _summary.wanted(v) else {} for v in sums]
+    covs = _per_root(covariance, n, "covariance")
+    for v in covs:
+        _covariance.spec(v)
+    cov_kw = [{"covariance": v} if _covariance.wanted(v) else {} for v in covs]
     common = dict(kmax=kmax, idchain=idchain, idpattern=idpattern, iw=iw, ilike=ilike, itheta=itheta)
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **sum_kw[i], **extra)
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **sum_kw[i], **cov_kw[i], **extra)
                 for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
@@ -290,7 +297,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
         if reason == _res.RESIDENT:
             try:
                 reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i],
-                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i])
+                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i], covariance=covs[i])
             except ValueError as e:                # (thin_corr together with thinlen; a converge or jackknife value no route takes)
                 fail(i, e)
                 continue
@@ -451,6 +458,11 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                     sblks.update(zip((r.index for r in sasked),
                                      _res.summary_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9], r.problem[10]) for r in sasked],
                                                               _summary.targets(probs), device, stream.cuda_stream)))
+                # covariance: the ready roots that ask for it in one call, while the gathered rows are raw
+                casked = [r for r in ready if _covariance.wanted(covs[r.index])]
+                cblks = dict(zip((r.index for r in casked),
+                                 _res.covariance_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in casked],
+                                                             device, stream.cuda_stream))) if casked else {}
                 # jackknife: the group ids of the ready roots that ask for it in one call, their leave-one-group-out blocks in another
                 # (src: the kept rows of a thinned root; fs only where the deleted sets' moments are wanted)
                 jasked = [r for r in ready if r.jack is not None]
@@ -490,6 +502,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                         if r.index in sblks:
                             inf["summary"] = _summary.build(sblks[r.index], _summary.spec(sums[r.index]), r.scal[0],
                                                             _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
+                        if r.index in cblks:
+                            inf["covariance"] = _covariance.build(cblks[r.index],
+                                                                  _covariance.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
                         if r.jack is not None:
                             pending.append((r, out, inf))
                             continue
@@ -522,6 +537,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             kw.update(info_kw[i])
             kw.update(jack_kw[i])
             kw.update(sum_kw[i])
+            kw.update(cov_kw[i])
             if covtype != "all":
                 kw["covtype"] = covtype
             if backend is not None:

@@ -25,6 +25,7 @@ import numpy as np
 from . import chains as _chains
 from . import information as _information
 from . import summary as _summary
+from . import covariance as _covariance
 
 logger = logging.getLogger("mcevidence_amd")
 
@@ -69,7 +70,7 @@ class ResidentDecline(Exception):
 
 def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all", split=False, ndim=None, nparam=None,
          distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None, converge=None, converge_by="auto", jackknife=None, nchains=None,
-         summary=None):
+         summary=None, covariance=None):
     """``"resident"`` or the reason why the route declines.  A pure function of the call's keywords and of what is known
     about the data at the time (``ncols``: the files' column counts, ``nrows``: rows left after burn-in / thinning,
     ``nparam``: parameter columns; None: not known yet).  ``thin_corr`` (thinning by the measured autocorrelation length) is resident
@@ -78,8 +79,10 @@ def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all"
     is the ValueError every route raises.  ``jackknife`` (the delete-a-group error bars; ``nchains``: the chains, where known) is resident
     work for an auto evidence; with a split it declines to the host route, which whitens s1 and s2 there; a number of groups or a
     ``by`` it cannot take is the ValueError every route raises.  ``summary`` (the posterior summary of the parameters) is resident work
-    and declines nothing; a value it cannot take is the ValueError every route raises."""
+    and declines nothing; a value it cannot take is the ValueError every route raises.  ``covariance`` (the weighted mean and covariance
+    matrix of the parameters) is resident work too: it is validated and declines nothing."""
     _summary.spec(summary)
+    _covariance.spec(covariance)
     if not ischain:
         return REASONS["ischain"]
     _chains.thin_corr_scale(thin_corr, thinlen)
@@ -232,6 +235,17 @@ def summary_measure_dev(systems, q, device, stream, pass_elems=0):
     return [_summary.from_block(b, s[3], len(q)) for b, s in zip(blocks, systems)]
 
 
+def covariance_measure_dev(systems, device, stream):
+    """ONE ``mce_param_cov_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured columns,
+    device address of w)] -> one ``covariance.measure`` dict per system"""
+    import torch
+    from . import _capi
+    wsb = _capi.param_cov_workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems))
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
+    blocks = _capi.param_cov_dev(systems, ws.data_ptr(), wsb, stream)
+    return [_covariance.from_block(b, s[3]) for b, s in zip(blocks, systems)]
+
+
 # ---- the jackknife of a chain that stays on the device (docs/design/jackknife_resident.md; this module and farm.py) -----------------
 def jack_spec(jackknife, nchains=None):
     """None, or dict(groups, by, G) of the ``jackknife`` keyword: G is the number of groups (None while ``by="chains"`` does not
@@ -337,6 +351,7 @@ class ResidentChains(object):
         self.converge = None
         self.information = None                            # (what the last evidence(information=True) found)
         self.summary = None                                # (what the last evidence(summary=..) found)
+        self.covariance = None                             # (what the last evidence(covariance=..) found)
         self.names_root = None                             # (the root whose .paramnames file names the parameters, where there is one)
         self.jackknife = None                              # (what the last evidence(jackknife=...) found,
         self.jackknife_block = None                        #  and its leave-one-group-out block: _capi.JACK_LEAVE_OUT_FIELDS per slot)
@@ -557,7 +572,7 @@ class ResidentChains(object):
 
     # -- the estimator ---------------------------------------------------------------------------------------------------
     def evidence(self, kmax=5, ndim=None, priorvolume=1, covtype="all", pos_lnp=False, split=False, s1frac=0.5, split_rows=None,
-                 info=False, backend=None, information=None, jackknife=None, summary=None):
+                 info=False, backend=None, information=None, jackknife=None, summary=None, covariance=None):
         """ln E as ``MCEvidence(...).evidence(...)`` returns it (``MLE[1:]``, and the info dict if ``info=True``; it
         carries ``info["route"] = "resident"``).  ``split=True``: the reference's random split, drawn on the host with the
         call ``MCSamples.chain_split`` makes (same RNG consumption); ``split_rows=(s1, s2)``: ``set_split``.
@@ -569,7 +584,9 @@ class ResidentChains(object):
         tensors and ONE ``mce_jack_leave_out_dev`` call gives S_b, SumW_b and, with ``information``, the deleted sets' moments.
         ``summary`` (None, True or up to 7 probabilities): the weighted means, standard deviations, equal-tailed limits and the best-fit
         sample of the first ``ndim`` parameters in ``info["summary"]``, from one ``mce_param_summary_dev`` call on the gathered rows,
-        weights and fs -- BEFORE the feed and the jackknife ladder, while the rows are certainly raw (the ladder whitens them)."""
+        weights and fs -- BEFORE the feed and the jackknife ladder, while the rows are certainly raw (the ladder whitens them).
+        ``covariance`` (None or True): the weighted mean and covariance matrix of the first ``ndim`` parameters in ``info["covariance"]``,
+        from one ``mce_param_cov_dev`` call on the gathered rows and weights, made at the same place for the same reason."""
         from . import _capi
         from .evidence import HipBackend
         backend = backend or HipBackend()
@@ -582,6 +599,7 @@ class ResidentChains(object):
             raise ResidentDecline(reason)
         jspec = jack_spec(jackknife, self.nchains)
         probs = _summary.spec(summary)
+        want_cov = _covariance.spec(covariance) is not None
         torch = self._torch
         ms = self.stats["ms"]
         with torch.cuda.device(self.device):
@@ -612,6 +630,11 @@ class ResidentChains(object):
                 sblk, = summary_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr(), fs.data_ptr())], _summary.targets(probs),
                                             self.device, self._stream())
                 ms["summary"] = _ms(t0)
+            cblk = None
+            if want_cov:
+                t0 = time.perf_counter()
+                cblk, = covariance_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())], self.device, self._stream())
+                ms["covariance"] = _ms(t0)
             t0 = time.perf_counter()
             with backend._scoped():
                 dotp, jac, _, _ = _capi.evidence_feed_part_dev(s1["params"].data_ptr(), n1, self.nparam, s2["params"].data_ptr() if cross else 0, n2,
@@ -633,6 +656,7 @@ class ResidentChains(object):
         out = mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, math.log(priorvolume), cross)[1:]
         self.information = None if mom is None else _information.build(mom, logLmax, out)
         self.summary = None if sblk is None else _summary.build(sblk, probs, logLmax, _summary.param_names(self.names_root, nd))
+        self.covariance = None if cblk is None else _covariance.build(cblk, _covariance.param_names(self.names_root, nd))
         self.jackknife_block = jblock
         self.jackknife = None if jrun is None else jack_result(jrun, jblock, jspec, SumW, logLmax, n1, kmax, math.log(priorvolume))
         if self.jackknife is not None and self.information is not None:
@@ -650,6 +674,8 @@ class ResidentChains(object):
             inf["jackknife"] = self.jackknife
         if self.summary is not None:
             inf["summary"] = self.summary
+        if self.covariance is not None:
+            inf["covariance"] = self.covariance
         return out, inf
 
 
@@ -683,13 +709,14 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     split = bool(ctor.get("split", False))
     _information.refuse(ctor.get("information"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _summary.refuse(ctor.get("summary"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
+    _covariance.refuse(ctor.get("covariance"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     reason = RESIDENT if _is_file_root(root) else REASONS["not_files"]
     if reason == RESIDENT:
         reason = plan(thinlen=ctor.get("thinlen", 0.0), isfunc=ctor.get("isfunc"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1),
                       verbose=max(ctor.get("verbose", 1), 2 if ctor.get("debug") else 0), covtype=covtype, split=split, ndim=None,
                       distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"),
                       converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"), jackknife=ctor.get("jackknife"),
-                      summary=ctor.get("summary"))
+                      summary=ctor.get("summary"), covariance=ctor.get("covariance"))
     if reason == RESIDENT:
         level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
         if not logging.getLogger().handlers:
@@ -707,7 +734,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
             got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,
                               backend=ctor.get("backend"), information=ctor.get("information"), jackknife=ctor.get("jackknife"),
-                              summary=ctor.get("summary"))
+                              summary=ctor.get("summary"), covariance=ctor.get("covariance"))
             mle, inf = got
             if ctor.get("verbose", 1) > 0:
                 log_information(inf)

@@ -1,0 +1,243 @@
+"""Tension statistics between two data sets A and B under one model, from three runs: A alone, B alone and the joint run AB.
+
+Each run gives ln E[k], ``info["information"]`` (<ln L>_P, D_KL[k], the Bayesian model dimensionality) and ``info["covariance"]`` (the
+weighted mean and covariance of the parameters).  ``combine`` is host arithmetic on those (docs/design/tension.md):
+
+    ln R[k] = ln E_AB[k] - ln E_A[k] - ln E_B[k]                      the evidence ratio: > 0 agreement, < 0 tension, prior dependent
+    ln I[k] = D_KL_A[k] + D_KL_B[k] - D_KL_AB[k]                      the information ratio
+    ln S    = <ln L>_AB - <ln L>_A - <ln L>_B  ( = ln R[k] - ln I[k] for every k: the prior volume cancels)   the suspiciousness
+    d       = d_A + d_B - d_AB                                        the dimensionality both data sets constrain
+    p       = Q(d / 2, (d - 2 ln S) / 2)                              d - 2 ln S is chi^2_d distributed for Gaussian posteriors
+    sigma_equiv = -ndtri(p / 2)                                       the two-sided Gaussian equivalent of p
+
+(Handley & Lemos 2019, arXiv:1902.04029), Q the regularised upper incomplete gamma function; p = 1 where d - 2 ln S <= 0.  Where d <= 0
+the chains do not show a shared constrained direction: p and sigma_equiv are NaN, ``status`` is 1 and one WARNING is logged.  ``status``
+2: a value of an input is not finite (an input's own status was not 0).
+
+The parameter shift in the parameters both runs share:  Delta = m_A - m_B,  C = C_A[sh, sh] + C_B[sh, sh],  chi^2 = Delta^T C^-1 Delta
+by Cholesky factorisation and solve, dof = len(sh), p = Q(dof / 2, chi^2 / 2).  C_A + C_B is the covariance of the difference ONLY for
+independent data sets, and chi^2 is chi^2_dof distributed ONLY for Gaussian posteriors: both are assumed, neither is checked.
+``shift.status`` 1: C is not positive definite (every value NaN, one WARNING); 2: a mean or covariance entry is not finite.
+
+ln R is only meaningful when the three runs share the prior on the shared parameters and each ln E carries its own full prior volume
+(``priorvolume``); nothing here can check that.
+
+With ``jackknife`` set on all three runs, ``sigma`` holds the root-sum-square of the three runs' jackknife sigmas of ln E[k], <ln L> and
+d: the three chains are independent; like every jackknife sigma here it is conservative.
+"""
+from __future__ import annotations
+
+import logging
+import math
+
+import numpy as np
+
+logger = logging.getLogger("mcevidence_amd")
+
+__all__ = ["combine", "evidence_tension", "lines", "shared_parameters", "p_value", "sigma_equivalent", "FOOTNOTE"]
+
+OK, NO_DIMENSION, NOT_FINITE = 0, 1, 2
+SHIFT_OK, SHIFT_NOT_POSITIVE, SHIFT_NOT_FINITE = 0, 1, 2
+FOOTNOTE = ("* tension: p and sigma of ln S assume Gaussian posteriors (d - 2 ln S ~ chi^2_d); the parameter shift assumes Gaussian posteriors and "
+            "independent data sets (C = C_A + C_B); ln R depends on the prior volume the three runs share.")
+
+
+def _gammaincc_large(a, x):
+    """Q(a, x) for a > 20 by the series of P below x = a + 1 and by the continued fraction of Q (modified Lentz) above it: there
+    ``torch.special.gammaincc`` switches to an asymptotic expansion that is good to 1e-9 only (Q(63.5, 75) = 0.0799419870175 against its
+    0.0799419871053), this is good to 1e-12"""
+    front = math.exp(-x + a * math.log(x) - math.lgamma(a))
+    if x < a + 1.0:
+        ap, term = a, 1.0 / a
+        total = term
+        for _ in range(100000):
+            ap += 1.0
+            term *= x / ap
+            total += term
+            if abs(term) < abs(total) * 1e-17:
+                break
+        return 1.0 - total * front
+    tiny = 1e-300
+    b = x + 1.0 - a
+    c, d = 1.0 / tiny, 1.0 / b
+    h = d
+    for i in range(1, 100000):
+        an = -i * (i - a)
+        b += 2.0
+        d = an * d + b
+        d = tiny if abs(d) < tiny else d
+        c = b + an / c
+        c = tiny if abs(c) < tiny else c
+        d = 1.0 / d
+        step = d * c
+        h *= step
+        if abs(step - 1.0) < 1e-16:
+            break
+    return front * h
+
+
+def p_value(dof, chi2):
+    """Q(dof / 2, chi2 / 2) in fp64 (``torch.special.gammaincc``; above dof = 40 ``_gammaincc_large``); 1 where chi2 <= 0; NaN where dof
+    is not > 0 or an argument is NaN"""
+    import torch
+    dof, chi2 = float(dof), float(chi2)
+    if not dof > 0.0 or math.isnan(chi2):
+        return float("nan")
+    if chi2 <= 0.0:
+        return 1.0
+    # (a = dof / 2 > 20 is where torch's implementation takes its asymptotic branch)
+    if dof > 40.0 and math.isfinite(dof) and math.isfinite(chi2):
+        return min(max(_gammaincc_large(0.5 * dof, 0.5 * chi2), 0.0), 1.0)
+    return float(torch.special.gammaincc(torch.tensor(0.5 * dof, dtype=torch.float64), torch.tensor(0.5 * chi2, dtype=torch.float64)))
+
+
+def sigma_equivalent(p):
+    """-ndtri(p / 2): the lower tail, so that a small p keeps its digits (``torch.special.ndtri`` in fp64)"""
+    import torch
+    p = float(p)
+    if math.isnan(p):
+        return float("nan")
+    return -float(torch.special.ndtri(torch.tensor(0.5 * p, dtype=torch.float64))) + 0.0
+
+
+def _default_names(names):
+    return list(names) == ["p%d" % j for j in range(len(names))]
+
+
+def shared_parameters(names_a, names_b, shared=None):
+    """-> (names, columns in A, columns in B).  None: the names A and B have in common, in A's order -- both sides must have names from a
+    ``.paramnames`` file (names other than p0, p1, ..); a count: that many leading columns of both; a list: those names on both sides"""
+    names_a, names_b = list(names_a), list(names_b)
+    if shared is None:
+        if _default_names(names_a) or _default_names(names_b):
+            raise ValueError("tension: shared= is required (names, or a count of leading columns) where a run has no .paramnames file")
+        shared = [n for n in names_a if n in names_b]
+    if isinstance(shared, (int, np.integer)) and not isinstance(shared, bool):
+        k = int(shared)
+        if not 1 <= k <= min(len(names_a), len(names_b)):
+            raise ValueError("tension: shared=%d leading columns of %d and %d parameters" % (k, len(names_a), len(names_b)))
+        return names_a[:k], list(range(k)), list(range(k))
+    shared = [str(n) for n in shared]
+    missing = [n for n in shared if n not in names_a or n not in names_b]
+    if missing or not shared or len(set(shared)) != len(shared):
+        raise ValueError("tension: shared=%r: %s" % (shared, "not a parameter of both runs: %r" % missing if missing else "one or more distinct names expected"))
+    return shared, [names_a.index(n) for n in shared], [names_b.index(n) for n in shared]
+
+
+def _shift(cov_a, cov_b, shared):
+    names, ia, ib = shared_parameters(cov_a["names"], cov_b["names"], shared)
+    nan = float("nan")
+    delta = np.asarray(cov_a["mean"], dtype=np.float64)[ia] - np.asarray(cov_b["mean"], dtype=np.float64)[ib]
+    C = np.asarray(cov_a["cov"], dtype=np.float64)[np.ix_(ia, ia)] + np.asarray(cov_b["cov"], dtype=np.float64)[np.ix_(ib, ib)]
+    out = {"names": names, "delta": delta, "chi2": nan, "dof": len(names), "p": nan, "sigma_equiv": nan, "status": SHIFT_OK}
+    if not (np.isfinite(delta).all() and np.isfinite(C).all()):
+        out["status"] = SHIFT_NOT_FINITE
+        out["delta"] = np.full(len(names), nan)
+        logger.warning("tension: shift status %d (a mean or a covariance entry of a run is not finite): every value is NaN" % SHIFT_NOT_FINITE)
+        return out
+    try:
+        L = np.linalg.cholesky(C)
+    except np.linalg.LinAlgError:
+        out["status"] = SHIFT_NOT_POSITIVE
+        logger.warning("tension: shift status %d (C_A + C_B is not positive definite in the shared parameters): every value is NaN" % SHIFT_NOT_POSITIVE)
+        return out
+    z = np.linalg.solve(L, delta)                          # (L is triangular: chi^2 = |L^-1 Delta|^2)
+    out["chi2"] = float(z @ z)
+    out["p"] = p_value(out["dof"], out["chi2"])
+    out["sigma_equiv"] = sigma_equivalent(out["p"])
+    return out
+
+
+def _rss(*xs):
+    return np.sqrt(sum(np.asarray(x, dtype=np.float64) ** 2 for x in xs))
+
+
+def combine(a, b, ab, shared=None):
+    """``a``, ``b``, ``ab``: (lnE[kmax - 1], info) of the runs on A, on B and on both, each with ``info["information"]`` and
+    ``info["covariance"]`` -> dict(lnR[k], lnI[k], lnS, d, p, sigma_equiv, shift{names, delta, chi2, dof, p, sigma_equiv, status},
+    status) and, with ``info["jackknife"]`` in all three, sigma{lnR[k], lnS, d}.  The module's docstring has the definitions and the
+    assumptions (Gaussian posteriors; independent data sets for the shift)."""
+    runs = []
+    for name, (lnE, info) in (("a", a), ("b", b), ("ab", ab)):
+        if "information" not in info or "covariance" not in info:
+            raise ValueError("tension: run %s has no info[%r]: run it with information=True, covariance=True" % (name, "information" if "information" not in info else "covariance"))
+        runs.append((np.atleast_1d(np.asarray(lnE, dtype=np.float64)), info))
+    (ea, ia), (eb, ib), (eab, iab) = runs
+    if not ea.shape == eb.shape == eab.shape:
+        raise ValueError("tension: ln E of %d, %d and %d columns" % (ea.size, eb.size, eab.size))
+    fa, fb, fab = ia["information"], ib["information"], iab["information"]
+    with np.errstate(all="ignore"):
+        lnR = eab - ea - eb
+        lnI = np.asarray(fa["D_KL"], dtype=np.float64) + np.asarray(fb["D_KL"], dtype=np.float64) - np.asarray(fab["D_KL"], dtype=np.float64)
+        lnS = float(fab["mean_logL"]) - float(fa["mean_logL"]) - float(fb["mean_logL"])
+        d = float(fa["bmd"]) + float(fb["bmd"]) - float(fab["bmd"])
+    out = {"lnR": lnR, "lnI": lnI, "lnS": lnS, "d": d, "p": float("nan"), "sigma_equiv": float("nan"), "status": OK}
+    if not (math.isfinite(lnS) and math.isfinite(d)):
+        out["status"] = NOT_FINITE
+        logger.warning("tension: status %d (<ln L> or the dimensionality of a run is not finite): p is NaN" % NOT_FINITE)
+    elif not d > 0.0:
+        out["status"] = NO_DIMENSION
+        logger.warning("tension: status %d (d = d_A + d_B - d_AB = %g is not > 0): p is NaN" % (NO_DIMENSION, d))
+    else:
+        out["p"] = p_value(d, d - 2.0 * lnS)
+        out["sigma_equiv"] = sigma_equivalent(out["p"])
+    out["shift"] = _shift(ia["covariance"], ib["covariance"], shared)
+    jks = [i.get("jackknife") for i in (ia, ib, iab)]
+    sgs = [f.get("sigma") for f in (fa, fb, fab)]
+    if all(j is not None for j in jks) and all(s is not None for s in sgs):
+        out["sigma"] = {"lnR": _rss(*[j["sigma"] for j in jks]), "lnS": float(_rss(*[s["mean_logL"] for s in sgs])), "d": float(_rss(*[s["bmd"] for s in sgs]))}
+    return out
+
+
+def lines(t):
+    """the lines printed after the three roots: ln R / ln I per k, ln S, d, p and its sigma, then the shift; +- where the jackknife ran"""
+    sg = t.get("sigma")
+    pm = (lambda key, k=None: " ± {}".format(sg[key] if k is None else sg[key][k])) if sg else (lambda key, k=None: "")
+    out = []
+    for k in range(len(t["lnR"])):
+        out.append("   ln R[k={}] = {}{}   ln I[k={}] = {}".format(k + 1, t["lnR"][k], pm("lnR", k), k + 1, t["lnI"][k]))
+    out.append("   ln S = {}{}".format(t["lnS"], pm("lnS")))
+    out.append("   d = {}{}".format(t["d"], pm("d")))
+    out.append("   p = {}   sigma = {}".format(t["p"], t["sigma_equiv"]))
+    s = t["shift"]
+    out.append("   shift ({}): chi2 = {}  dof = {}  p = {}   sigma = {}".format(", ".join(s["names"]), s["chi2"], s["dof"], s["p"], s["sigma_equiv"]))
+    return out
+
+
+_FARM_ONLY = ("device", "wave_bytes", "return_exceptions", "require_resident")
+
+
+def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", **kw):
+    """The three runs and their tension: ``route="farm"``: ``evidence_many_from_files([root_a, root_b, root_ab], information=True,
+    covariance=True, info=True, **kw)`` (a root the farm does not cover takes its per-root route); ``route="host"``: three
+    ``MCEvidence(root, information=True, covariance=True, **kw).evidence(info=True)``.  ``kw``: the farm's keywords (``kmax``, ``ndim``,
+    ``priorvolume``, ``burnlen``, ``thinlen``, ``thin_corr``, ``jackknife``, ..; the four of them that may be sequences have one entry per
+    root, in the order A, B, AB).  Returns (lnE_a, lnE_b, lnE_ab, info): ``info["tension"]`` is ``combine``'s dict, ``info["roots"]`` the
+    three runs' info dicts, ``info["route"]`` the route asked for.  The assumptions are ``combine``'s."""
+    if route not in ("farm", "host"):
+        raise ValueError("tension: route=%r: 'farm' or 'host' expected" % (route,))
+    roots = [root_a, root_b, root_ab]
+    for k in ("information", "covariance", "info"):
+        if k in kw:
+            raise ValueError("tension: %s is set by evidence_tension" % k)
+    if route == "farm":
+        from .farm import evidence_many_from_files
+        outs = evidence_many_from_files(roots, information=True, covariance=True, info=True, **kw)
+    else:
+        from .evidence import MCEvidence
+        from .farm import _per_root
+        kw = {k: v for k, v in kw.items() if k not in _FARM_ONLY}
+        call = {k: kw.pop(k) for k in ("pos_lnp",) if k in kw}
+        if kw.get("covtype", "all") != "all":
+            call["covtype"] = kw["covtype"]
+        if kw.get("thin_corr", None) in (None, False):
+            for k in ("thin_corr", "corr_min", "corr_max_lag"):
+                kw.pop(k, None)
+        if kw.get("converge", None) in (None, False):
+            for k in ("converge", "converge_by"):
+                kw.pop(k, None)
+        per = {k: _per_root(kw.pop(k), 3, k) for k in ("ndim", "priorvolume", "burnlen", "thinlen") if k in kw}
+        kw.setdefault("verbose", 0)
+        outs = [MCEvidence(r, information=True, covariance=True, **{k: v[i] for k, v in per.items()}, **kw).evidence(info=True, **call) for i, r in enumerate(roots)]
+    t = combine(outs[0], outs[1], outs[2], shared=shared)
+    return outs[0][0], outs[1][0], outs[2][0], {"tension": t, "roots": [o[1] for o in outs], "route": route}

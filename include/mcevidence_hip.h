@@ -655,6 +655,46 @@ size_t mce_param_cov_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t 
 int mce_param_cov_dev(const mce_cov_seg* segs, int32_t nseg, double* out, void* ws, size_t ws_bytes, void* stream);
 int mce_param_cov_f64(const mce_cov_seg* segs, int32_t nseg, double* out, int32_t device);
 
+/* The non-Gaussian parameter shift behind shift="kde" (--shift-kde): a leave-one-out Gaussian kernel density estimate on the whitened rows
+ * of a parameter-DIFFERENCE chain, and the weight of the rows whose density lies above the density at a point, for MANY systems in one
+ * call.  The rule is stated in csrc/kde_shift.hpp and docs/design/shift_kde.md.  One system is one segment: x[n][ld] the rows (the first
+ * d columns are measured, 1 <= d <= MCE_KDE_MAX_DIM) and w[n] their weights, on the DEVICE (mce_kde_shift_f64: on the host); linv[d * d]
+ * (row-major, the lower triangle of the inverse Cholesky factor of the rows' covariance; what lies above the diagonal is not read),
+ * mean[d] and point[d] are HOST arrays in both forms; c = 1 / (2 h^2) > 0.  z = linv (x - mean);  for a used row i,
+ * S_i = sum over used j != i of w_j exp(-c max(0, |z_i - z_j|^2)) and t_i = S_i / (W - w_i);  at z_0 = linv (point - mean), over all used
+ * j, S_0 = sum w_j K_0j, Q_0 = sum w_j^2 K_0j^2, t_0 = S_0 / W, s_0 = sqrt(Q_0) / W.  A kernel value exp(-a) with a >= 746 is +0.0 (its
+ * exact value is below 0.17 * 2^-1074).  A row with w == 0 is skipped and nothing of it is
+ * read into a result.
+ * out (HOST, MCE_KDE_OUT doubles per system, in segment order) = {W, A2 = sum w^2, rows used, status, column, c, S_0, Q_0, M(t_0),
+ * M(t_0 - s_0), M(t_0 + s_0), M_eq, reserved x 4}, M(tau) = sum over used i of w_i [t_i > tau], M_eq = sum w_i [t_i == t_0].
+ * dens (optional; device, or host for _f64): n + 1 doubles, t_i (NaN for a row that is not used), t_0 last.  zout (optional, likewise):
+ * the whitened rows [n][d], zeros for a row that is not used.  status 0 ok; 3 a weight that is negative or not finite; 4 a used row
+ * with a value that is not finite (column: the lowest such); 5 W is not > 0; 6 fewer than 2 used rows.  With a status other than 0
+ * every value is NaN; a failing system fails alone.  A system's bits depend on its own rows, d and c alone: not on its neighbours, its
+ * position or the number of systems; two runs give the same bits.  Everything runs on `stream` with one host wait; five launches,
+ * whatever nseg is.  Workspace: mce_kde_shift_workspace_bytes(rows of all segments, nseg, the largest d).  Argument errors (d outside
+ * 1 .. 64, ld < d, negative sizes, c not positive and finite, null pointers): MCE_ERR_INVALID (no device needed); no visible device:
+ * MCE_ERR_NO_DEVICE. */
+#define MCE_KDE_OUT 16
+#define MCE_KDE_MAX_DIM 64
+typedef struct mce_kde_seg {
+    const double* x;
+    int64_t ld;
+    int64_t n;
+    int32_t d;
+    const double* w;
+    const double* linv;
+    const double* mean;
+    const double* point;
+    double c;
+    double* dens;
+    double* zout;
+} mce_kde_seg;
+size_t mce_kde_shift_out_doubles(void);
+size_t mce_kde_shift_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t dmax);
+int mce_kde_shift_dev(const mce_kde_seg* segs, int32_t nseg, double* out, void* ws, size_t ws_bytes, void* stream);
+int mce_kde_shift_f64(const mce_kde_seg* segs, int32_t nseg, double* out, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

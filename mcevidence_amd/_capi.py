@@ -210,6 +210,22 @@ SIGNATURES["mce_param_cov_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_in
 SIGNATURES["mce_param_cov_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_size_t, _P])
 SIGNATURES["mce_param_cov_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
 
+
+class KdeSeg(ctypes.Structure):
+    """``mce_kde_seg``: one system of ``mce_kde_shift_*`` -- its rows (address, row stride in doubles, rows, measured columns), the address
+    of its w column, the HOST addresses of linv[d * d], mean[d] and point[d], c = 1 / (2 h^2), and the optional addresses of the densities
+    [n + 1] and of the whitened rows [n, d]"""
+    _fields_ = [("x", _P), ("ld", _c.c_int64), ("n", _c.c_int64), ("d", _c.c_int32), ("w", _P), ("linv", _P), ("mean", _P), ("point", _P),
+                ("c", _c.c_double), ("dens", _P), ("zout", _P)]
+
+
+MCE_KDE_OUT = 16
+MCE_KDE_MAX_DIM = 64
+SIGNATURES["mce_kde_shift_out_doubles"] = (_c.c_size_t, [])
+SIGNATURES["mce_kde_shift_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_kde_shift_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_kde_shift_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
+
 class JackGroupsSeg(ctypes.Structure):
     """``mce_jack_groups_seg``: one system of ``mce_jack_groups_dev`` (rows / src / out: device addresses; part_first: a host array)."""
     _fields_ = [("rows", _P), ("src", _P), ("part_first", _P), ("nparts", _c.c_int64), ("n", _c.c_int64), ("N", _c.c_int64), ("G", _c.c_int32),
@@ -786,6 +802,58 @@ def param_cov(systems, device=0):
         keep.append((x, int(d), w))
     segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
     return _param_cov(load().mce_param_cov_f64, segs, (int(device),))
+
+
+def kde_shift_out_doubles():
+    return int(load().mce_kde_shift_out_doubles())
+
+
+def kde_shift_workspace_bytes(nrows_total, nseg, dmax):
+    return int(load().mce_kde_shift_workspace_bytes(int(nrows_total), int(nseg), int(dmax)))
+
+
+def _kde_shift(call, segs, tail):
+    """``segs``: [(x, ld, n, d, w, linv, mean, point, c, dens, zout)], linv / mean / point host arrays (or None), the rest addresses"""
+    arr = (KdeSeg * max(len(segs), 1))()
+    keep = []
+    for i, (x, ld, n, d, w, linv, mean, point, c, dens, zout) in enumerate(segs):
+        host = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (linv, mean, point)]
+        if 1 <= int(d) <= MCE_KDE_MAX_DIM and any(a is not None and a.size != k for a, k in zip(host, (int(d) * int(d), int(d), int(d)))):
+            raise ValueError("kde shift: segment %d: linv[d * d], mean[d] and point[d] expected" % i)
+        keep.append(host)
+        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w = x or None, int(ld), int(n), int(d), w or None
+        arr[i].linv, arr[i].mean, arr[i].point = [None if a is None else a.ctypes.data for a in host]
+        arr[i].c, arr[i].dens, arr[i].zout = float(c), dens or None, zout or None
+    out = np.full(max(len(segs), 1) * MCE_KDE_OUT, np.nan)
+    check(call(_c.cast(arr, _P), len(segs), out.ctypes.data, *tail))
+    return [out[i * MCE_KDE_OUT:(i + 1) * MCE_KDE_OUT] for i in range(len(segs))]
+
+
+def kde_shift_dev(segs, ws, ws_bytes, stream=0):
+    """mce_kde_shift_dev: the leave-one-out kernel density sums of ``len(segs)`` systems that are on the device -> one float64 block of
+    MCE_KDE_OUT doubles per system (``shift_kde.from_block`` reads it); ``segs``: [(device address of the rows, row stride in doubles,
+    rows, measured columns, device address of w, linv, mean, point (host arrays), c, device address of the densities or 0, of the
+    whitened rows or 0)]"""
+    return _kde_shift(load().mce_kde_shift_dev, segs, (ws or None, int(ws_bytes), stream or None))
+
+
+def kde_shift(systems, device=0, want_dens=False, want_z=False):
+    """mce_kde_shift_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w, linv, mean, point, c)], uploaded by the library ->
+    [(block, dens[n + 1] or None, z[n, d] or None)]"""
+    keep, segs = [], []
+    for x, d, w, linv, mean, point, c in systems:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if x.shape[0] != w.size:
+            raise ValueError("kde shift: rows and w of one length expected")
+        dens = np.full(w.size + 1, np.nan) if want_dens else None
+        z = np.zeros((w.size, max(int(d), 1))) if want_z else None
+        keep.append((x, w, dens, z))
+        segs.append((x.ctypes.data if x.size else 0, x.shape[1], w.size, int(d), w.ctypes.data if w.size else 0, linv, mean, point, c,
+                     0 if dens is None else dens.ctypes.data, 0 if z is None else z.ctypes.data))
+    blocks = _kde_shift(load().mce_kde_shift_f64, segs, (int(device),))
+    return [(b, k[2], k[3]) for b, k in zip(blocks, keep)]
 
 
 def jack_groups_dev(segs, stream=0):

@@ -71,6 +71,13 @@ def build_parser(prog=None):
                         "with its p-value, and the Gaussian parameter shift in the parameters A and B share; composes with --jackknife, --burn, "
                         "--thin, --thin-corr, -k, --cross, --converge and --summary (all three roots take them), not with --farm or --resident; write it "
                         "after root_name")
+    p.add_argument("--shift-kde", dest="shift_kde", nargs="?", const=1, default=None, type=int, metavar="BOOST",
+                   help="with --tension: the non-Gaussian parameter shift too -- the posterior mass of the parameter difference above the density "
+                        "at no difference, by a leave-one-out kernel density estimate on the difference chain (mcevidence_amd.shift_kde); BOOST "
+                        "(default 1) pairs every row of A with that many rows of B; one more line after the Gaussian shift: p [p_lo, p_hi], "
+                        "sigma, n_local, rows and the bandwidth h")
+    p.add_argument("--shift-bandwidth", dest="shift_bandwidth", default=None, type=float, metavar="SCALE",
+                   help="with --shift-kde: the bandwidth as a multiple of Silverman's rule (default 1; raise it where n_local is small)")
     return p
 
 
@@ -184,6 +191,13 @@ def farm_main(args):
     return outs
 
 
+def _shift_kw(args):
+    """--shift-kde / --shift-bandwidth, where the first was given"""
+    if args.shift_kde is None:
+        return {}
+    return {"shift": "both", "boost": args.shift_kde, "bandwidth_scale": 1.0 if args.shift_bandwidth is None else args.shift_bandwidth}
+
+
 def tension_main(args):
     """``--tension ROOT_A ROOT_B``: the three roots as ``--farm`` prints roots, then the tension lines and their footnote.  ``--cross``,
     ``--converge`` and ``--summary`` go to all three roots (``--information`` is always set); ``--farm`` and ``--resident`` name another
@@ -201,7 +215,7 @@ def tension_main(args):
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
     ea, eb, eab, info = tension.evidence_tension(roots[0], roots[1], roots[2], kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen,
                                                  thinlen=args.thinlen, idchain=args.idchain, split=args.cross, **_thin_kw(args), **_converge_kw(args),
-                                                 **_summary_kw(args), **_jackknife_kw(args), **_backend_kw(args))
+                                                 **_summary_kw(args), **_jackknife_kw(args), **_backend_kw(args), **_shift_kw(args))
     note = None
     for r, mle, inf in zip(roots, (ea, eb, eab), info["roots"]):
         print()
@@ -218,6 +232,8 @@ def tension_main(args):
         _print_jackknife_note(note)
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
     print(tension.FOOTNOTE)
+    if args.shift_kde is not None:
+        print(tension.FOOTNOTE_KDE)
     print("")
     return ea, eb, eab, info
 
@@ -231,6 +247,14 @@ def main(argv=None):
         for n in new:
             if n not in prior.cosmo_params_list:
                 prior.cosmo_params_list.append(n)
+    if (args.shift_kde is not None or args.shift_bandwidth is not None) and args.tension is None:
+        build_parser(prog="MCEvidence.py").error("--shift-kde and --shift-bandwidth belong to --tension ROOT_A ROOT_B")
+    if args.shift_bandwidth is not None and args.shift_kde is None:
+        build_parser(prog="MCEvidence.py").error("--shift-bandwidth belongs to --shift-kde")
+    if args.shift_kde is not None and args.shift_kde < 1:
+        build_parser(prog="MCEvidence.py").error("--shift-kde BOOST: a positive number of offsets expected")
+    if args.shift_bandwidth is not None and not args.shift_bandwidth > 0.0:
+        build_parser(prog="MCEvidence.py").error("--shift-bandwidth SCALE: a positive number expected")
     if args.tension is not None:
         if args.farm or args.resident:
             build_parser(prog="MCEvidence.py").error("--tension runs its three roots in one batched pass: it does not combine with --farm or --resident")

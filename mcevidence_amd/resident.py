@@ -522,6 +522,12 @@ class ResidentChains(object):
         with self._torch.cuda.device(self.device):
             return self._gather(None, want=("w",))["w"].cpu().numpy()
 
+    def rows(self):
+        """(params [nrows, nparam], w [nrows]): the kept rows' parameter columns and weights as device tensors, from one gather pass"""
+        with self._torch.cuda.device(self.device):
+            out = self._gather(None, want=("params", "w"))
+        return out["params"], out["w"]
+
     def _gather(self, rows, want):
         """one gather pass -> dict of device tensors among params / w / like / full; ``rows``: int64 device tensor or None"""
         from . import _capi

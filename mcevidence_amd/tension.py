@@ -19,6 +19,11 @@ by Cholesky factorisation and solve, dof = len(sh), p = Q(dof / 2, chi^2 / 2).  
 independent data sets, and chi^2 is chi^2_dof distributed ONLY for Gaussian posteriors: both are assumed, neither is checked.
 ``shift.status`` 1: C is not positive definite (every value NaN, one WARNING); 2: a mean or covariance entry is not finite.
 
+The Gaussian assumption of the shift can be dropped: ``parameter_shift_kde`` (``evidence_tension(shift="kde" | "both")``, shift_kde.py)
+estimates the posterior mass of the parameter DIFFERENCE above the density at "no difference" by a leave-one-out kernel density estimate
+on the difference chain (Raveri & Doux 2021, arXiv:2105.03324) and puts its dict into ``t["shift_kde"]``; independent data sets stay
+assumed.
+
 ln R is only meaningful when the three runs share the prior on the shared parameters and each ln E carries its own full prior volume
 (``priorvolume``); nothing here can check that.
 
@@ -34,12 +39,15 @@ import numpy as np
 
 logger = logging.getLogger("mcevidence_amd")
 
-__all__ = ["combine", "evidence_tension", "lines", "shared_parameters", "p_value", "sigma_equivalent", "FOOTNOTE"]
+__all__ = ["combine", "evidence_tension", "lines", "shared_parameters", "p_value", "sigma_equivalent", "parameter_shift_kde", "FOOTNOTE", "FOOTNOTE_KDE"]
 
 OK, NO_DIMENSION, NOT_FINITE = 0, 1, 2
 SHIFT_OK, SHIFT_NOT_POSITIVE, SHIFT_NOT_FINITE = 0, 1, 2
 FOOTNOTE = ("* tension: p and sigma of ln S assume Gaussian posteriors (d - 2 ln S ~ chi^2_d); the parameter shift assumes Gaussian posteriors and "
             "independent data sets (C = C_A + C_B); ln R depends on the prior volume the three runs share.")
+
+
+from .shift_kde import FOOTNOTE as FOOTNOTE_KDE  # noqa: E402  (the second footnote sentence, printed where the KDE shift was asked for)
 
 
 def _gammaincc_large(a, x):
@@ -152,11 +160,23 @@ def _rss(*xs):
     return np.sqrt(sum(np.asarray(x, dtype=np.float64) ** 2 for x in xs))
 
 
-def combine(a, b, ab, shared=None):
+def parameter_shift_kde(rows_a, w_a, rows_b, w_b, boost=1, bandwidth_scale=1.0, max_rows=262144, device=None, names=None):
+    """The non-Gaussian parameter shift of two runs from their rows in the SHARED columns (``rows_a`` [nA, d], ``rows_b`` [nB, d]) and
+    their weights: NumPy arrays (uploaded by the library to ``device``, 0 when None) or torch tensors of one device.  The difference chain
+    pairs row i of the one with row i + o_s of the other for ``boost`` offsets o_s, is thinned to at most ``max_rows`` rows and whitened by
+    its own covariance; the density of every row and of "no difference" is a leave-one-out Gaussian KDE of bandwidth ``bandwidth_scale``
+    times Silverman's.  -> dict(names, p, p_lo, p_hi, sigma_p, sigma_equiv, limit, n_local, ess_eff, ess, rows, h, t0, bandwidth_scale,
+    boost, dof, status, column); shift_kde.py has the rule, the statuses and the assumptions (independent data sets and rows)."""
+    from . import shift_kde
+    return shift_kde.estimate(rows_a, w_a, rows_b, w_b, boost=boost, bandwidth_scale=bandwidth_scale, max_rows=max_rows, device=device, names=names)
+
+
+def combine(a, b, ab, shared=None, shift_kde=None):
     """``a``, ``b``, ``ab``: (lnE[kmax - 1], info) of the runs on A, on B and on both, each with ``info["information"]`` and
     ``info["covariance"]`` -> dict(lnR[k], lnI[k], lnS, d, p, sigma_equiv, shift{names, delta, chi2, dof, p, sigma_equiv, status},
     status) and, with ``info["jackknife"]`` in all three, sigma{lnR[k], lnS, d}.  The module's docstring has the definitions and the
-    assumptions (Gaussian posteriors; independent data sets for the shift)."""
+    assumptions (Gaussian posteriors; independent data sets for the shift).  ``shift_kde``: ``parameter_shift_kde``'s dict, which goes
+    into ``t["shift_kde"]`` as it is."""
     runs = []
     for name, (lnE, info) in (("a", a), ("b", b), ("ab", ab)):
         if "information" not in info or "covariance" not in info:
@@ -186,11 +206,14 @@ def combine(a, b, ab, shared=None):
     sgs = [f.get("sigma") for f in (fa, fb, fab)]
     if all(j is not None for j in jks) and all(s is not None for s in sgs):
         out["sigma"] = {"lnR": _rss(*[j["sigma"] for j in jks]), "lnS": float(_rss(*[s["mean_logL"] for s in sgs])), "d": float(_rss(*[s["bmd"] for s in sgs]))}
+    if shift_kde is not None:
+        out["shift_kde"] = shift_kde
     return out
 
 
 def lines(t):
-    """the lines printed after the three roots: ln R / ln I per k, ln S, d, p and its sigma, then the shift; +- where the jackknife ran"""
+    """the lines printed after the three roots: ln R / ln I per k, ln S, d, p and its sigma, then the shift (and the KDE shift where it was
+    asked for); +- where the jackknife ran"""
     sg = t.get("sigma")
     pm = (lambda key, k=None: " ± {}".format(sg[key] if k is None else sg[key][k])) if sg else (lambda key, k=None: "")
     out = []
@@ -201,21 +224,57 @@ def lines(t):
     out.append("   p = {}   sigma = {}".format(t["p"], t["sigma_equiv"]))
     s = t["shift"]
     out.append("   shift ({}): chi2 = {}  dof = {}  p = {}   sigma = {}".format(", ".join(s["names"]), s["chi2"], s["dof"], s["p"], s["sigma_equiv"]))
+    if t.get("shift_kde") is not None:
+        from . import shift_kde
+        out.extend(shift_kde.lines(t["shift_kde"]))
     return out
 
 
 _FARM_ONLY = ("device", "wave_bytes", "return_exceptions", "require_resident")
 
 
-def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", **kw):
+def _host_rows(m):
+    """(rows, weights) of the s1 partition of an ``MCEvidence`` object: what ``covariance=`` measures"""
+    part = m.gd.data["s1"]
+    return np.asarray(part.samples, dtype=np.float64)[:, :m.ndim], np.asarray(part.adjusted_weights, dtype=np.float64)
+
+
+def _farm_rows(root, ndim, kw, i):
+    """the rows and weights of root ``i`` (0: A, 1: B) read once more, on the device where the resident route takes the root, else on the
+    host; the per-root keywords are the farm's"""
+    from . import resident as _res
+    from .farm import _per_root
+    one = lambda k, default: _per_root(kw[k], 3, k)[i] if k in kw else default          # noqa: E731
+    read = {k: kw[k] for k in ("idchain", "idpattern", "iw", "ilike", "itheta") if k in kw}
+    corr = {}
+    if one("thin_corr", None) not in (None, False):
+        corr = {"thin_corr": one("thin_corr", None), **{k: kw[k] for k in ("corr_min", "corr_max_lag") if kw.get(k) is not None}}
+    try:
+        rc = _res.ResidentChains.from_files(root, burnlen=one("burnlen", 0), thinlen=one("thinlen", 0), device=kw.get("device", 0), ndim=one("ndim", None),
+                                            **read, **corr)
+        x, w = rc.rows()
+        return x[:, :ndim], w
+    except _res.ResidentDecline:
+        from .evidence import MCEvidence
+        m = MCEvidence(root, ndim=one("ndim", None), burnlen=one("burnlen", 0), thinlen=one("thinlen", 0), verbose=0, **read, **corr)
+        return _host_rows(m)
+
+
+def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", shift="gaussian", boost=1, bandwidth_scale=1.0, **kw):
     """The three runs and their tension: ``route="farm"``: ``evidence_many_from_files([root_a, root_b, root_ab], information=True,
     covariance=True, info=True, **kw)`` (a root the farm does not cover takes its per-root route); ``route="host"``: three
     ``MCEvidence(root, information=True, covariance=True, **kw).evidence(info=True)``.  ``kw``: the farm's keywords (``kmax``, ``ndim``,
     ``priorvolume``, ``burnlen``, ``thinlen``, ``thin_corr``, ``jackknife``, ..; the four of them that may be sequences have one entry per
     root, in the order A, B, AB).  Returns (lnE_a, lnE_b, lnE_ab, info): ``info["tension"]`` is ``combine``'s dict, ``info["roots"]`` the
-    three runs' info dicts, ``info["route"]`` the route asked for.  The assumptions are ``combine``'s."""
+    three runs' info dicts, ``info["route"]`` the route asked for.  The assumptions are ``combine``'s.  ``shift``: "gaussian" (the dict and
+    the lines as they are without the keyword), "kde" or "both": ``parameter_shift_kde`` with ``boost`` and ``bandwidth_scale`` on the rows
+    and weights ``covariance=`` measured in A and B, in ``info["tension"]["shift_kde"]`` -- the Gaussian shift stays in either case.  The
+    host route uses its three objects' rows (``mce_kde_shift_f64``); the farm route reads A and B once more after the farm pass
+    (``ResidentChains.from_files(...).rows()``, the sums by ``mce_kde_shift_dev``; a root the resident plan declines: its host rows)."""
     if route not in ("farm", "host"):
         raise ValueError("tension: route=%r: 'farm' or 'host' expected" % (route,))
+    if shift not in ("gaussian", "kde", "both"):
+        raise ValueError("tension: shift=%r: 'gaussian', 'kde' or 'both' expected" % (shift,))
     roots = [root_a, root_b, root_ab]
     for k in ("information", "covariance", "info"):
         if k in kw:
@@ -223,6 +282,7 @@ def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", **kw):
     if route == "farm":
         from .farm import evidence_many_from_files
         outs = evidence_many_from_files(roots, information=True, covariance=True, info=True, **kw)
+        rows = (lambda i, nd: _farm_rows(roots[i], nd, kw, i)) if shift != "gaussian" else None
     else:
         from .evidence import MCEvidence
         from .farm import _per_root
@@ -238,6 +298,21 @@ def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", **kw):
                 kw.pop(k, None)
         per = {k: _per_root(kw.pop(k), 3, k) for k in ("ndim", "priorvolume", "burnlen", "thinlen") if k in kw}
         kw.setdefault("verbose", 0)
-        outs = [MCEvidence(r, information=True, covariance=True, **{k: v[i] for k, v in per.items()}, **kw).evidence(info=True, **call) for i, r in enumerate(roots)]
-    t = combine(outs[0], outs[1], outs[2], shared=shared)
+        outs, ms = [], []
+        for i, r in enumerate(roots):
+            m = MCEvidence(r, information=True, covariance=True, **{k: v[i] for k, v in per.items()}, **kw)
+            outs.append(m.evidence(info=True, **call))
+            if shift != "gaussian" and i < 2:                   # (A and B are kept for their rows; otherwise one object at a time, as before)
+                ms.append(m)
+            del m
+        rows = lambda i, nd: _host_rows(ms[i])                                     # noqa: E731
+    kde = None
+    if shift != "gaussian":
+        ca, cb = outs[0][1]["covariance"], outs[1][1]["covariance"]
+        names, ia, ib = shared_parameters(ca["names"], cb["names"], shared)
+        (xa, wa), (xb, wb) = rows(0, len(ca["names"])), rows(1, len(cb["names"]))
+        if type(xa) is not type(xb):                            # (one root on the device, one on the host: both on the host)
+            xa, wa, xb, wb = [v.cpu().numpy() if hasattr(v, "cpu") else v for v in (xa, wa, xb, wb)]
+        kde = parameter_shift_kde(xa[:, ia], wa, xb[:, ib], wb, boost=boost, bandwidth_scale=bandwidth_scale, device=kw.get("device", None), names=names)
+    t = combine(outs[0], outs[1], outs[2], shared=shared, shift_kde=kde)
     return outs[0][0], outs[1][0], outs[2][0], {"tension": t, "roots": [o[1] for o in outs], "route": route}

@@ -695,6 +695,37 @@ size_t mce_kde_shift_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t 
 int mce_kde_shift_dev(const mce_kde_seg* segs, int32_t nseg, double* out, void* ws, size_t ws_bytes, void* stream);
 int mce_kde_shift_f64(const mce_kde_seg* segs, int32_t nseg, double* out, int32_t device);
 
+/* The 1-D marginal posterior densities behind marginals= (a Gaussian kernel density estimate of each of the first d parameter columns
+ * on a regular grid, its mode and its highest-posterior-density regions), for MANY systems (the ready roots of a farm wave) in one
+ * call.  The rule is stated in csrc/param_marginals.hpp and docs/design/marginals.md.  One system is one mce_summary_seg: x[n][ld] the
+ * RAW rows and w[n] the weights of the s1 partition the estimator sums over (fs is not read); segments may differ in d and ld.  A row
+ * with w == 0 is skipped and nothing of it is read into a result.  probs[np]: 1 .. MCE_MARGINALS_MAX_P probabilities in (0, 1); grid:
+ * 64, 128, 256, 512 or 1024 points; scale: the factor on the normal-reference bandwidth, finite and > 0.  With W, A2, m, v, min, max as
+ * mce_param_summary_dev forms them (bit for bit): ess = W W / A2, h = (scale sqrt(v)) pow(4 / (3 ess), 0.2), c = 1 / (2 h h),
+ * lo = min - 3 h, step = (max + 3 h - lo) / (grid - 1), g_k = lo + k step (two roundings), rho_k = sum over used i of w_i K(c (g_k -
+ * x_i)^2) / (W h sqrt(2 pi)) with K(a) = a >= 746 ? +0.0 : exp(-a).  The mode is the grid point of the largest rho (the lowest k among
+ * equals).  For a probability p the grid points are ordered by rho descending, then k ascending, and rho is accumulated serially in that
+ * order to Z; the region is the positions up to and including the first whose running sum is >= p Z.
+ * out (HOST, packed in segment order, mce_param_marginals_out_doubles(d, np, grid) doubles per system) = {W, A2, rows used, status,
+ * column, grid, np, reserved}, then the rows mean[d], var[d], sd[d], h[d], c[d], lo[d], step[d], mode[d], mode_density[d],
+ * col_status[d], then per probability lower[d], upper[d], pieces[d] (the maximal runs of consecutive selected grid points), edge[d] (1
+ * where the first or the last grid point is selected), then density[d][grid].  status 0 ok; 3 and 5 as mce_param_summary_dev (column
+ * likewise); 6 fewer than 2 used rows: every value is NaN and that system fails alone.  col_status 0 ok; 7: sd is 0, or h, c or step
+ * is not finite and > 0: that column is NaN with pieces -1, and the other columns do not notice.  A system's bits depend on its own rows,
+ * probs, grid and scale alone: not on its neighbours, its position or the number of systems; two runs give the same bits; fp64, sums in
+ * a fixed order, no floating-point atomics, plain stores, 64-bit row indices.  Ten launches whatever nseg is, on the caller's stream,
+ * which this library synchronises once, on return.  Workspace: mce_param_marginals_workspace_bytes(rows of all segments, nseg, the
+ * largest d, np, grid).  mce_param_marginals_f64 takes HOST segments, uploads them to `device` and calls the device form.  Argument
+ * errors (d outside 1 .. 127, np outside 1 .. 7, a p outside (0, 1), another grid, a scale that is not finite and > 0, ld < d, negative
+ * sizes, null pointers): MCE_ERR_INVALID (no device needed); no visible device: MCE_ERR_NO_DEVICE. */
+#define MCE_MARGINALS_HEAD 8
+#define MCE_MARGINALS_MAX_P 7
+size_t mce_param_marginals_out_doubles(int32_t d, int32_t np, int32_t grid);
+size_t mce_param_marginals_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t dmax, int32_t np, int32_t grid);
+int mce_param_marginals_dev(const mce_summary_seg* segs, int32_t nseg, const double* probs, int32_t np, int32_t grid, double scale, double* out, void* ws,
+                            size_t ws_bytes, void* stream);
+int mce_param_marginals_f64(const mce_summary_seg* segs, int32_t nseg, const double* probs, int32_t np, int32_t grid, double scale, double* out, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

@@ -226,6 +226,14 @@ SIGNATURES["mce_kde_shift_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_in
 SIGNATURES["mce_kde_shift_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_size_t, _P])
 SIGNATURES["mce_kde_shift_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
 
+MCE_MARGINALS_HEAD = 8
+MCE_MARGINALS_MAX_P = 7
+SIGNATURES["mce_param_marginals_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_marginals_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_marginals_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_param_marginals_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _c.c_int32])
+
+
 class JackGroupsSeg(ctypes.Structure):
     """``mce_jack_groups_seg``: one system of ``mce_jack_groups_dev`` (rows / src / out: device addresses; part_first: a host array)."""
     _fields_ = [("rows", _P), ("src", _P), ("part_first", _P), ("nparts", _c.c_int64), ("n", _c.c_int64), ("N", _c.c_int64), ("G", _c.c_int32),
@@ -854,6 +862,54 @@ def kde_shift(systems, device=0, want_dens=False, want_z=False):
                      0 if dens is None else dens.ctypes.data, 0 if z is None else z.ctypes.data))
     blocks = _kde_shift(load().mce_kde_shift_f64, segs, (int(device),))
     return [(b, k[2], k[3]) for b, k in zip(blocks, keep)]
+
+
+def param_marginals_out_doubles(d, np_, grid):
+    return int(load().mce_param_marginals_out_doubles(int(d), int(np_), int(grid)))
+
+
+def param_marginals_workspace_bytes(nrows_total, nseg, dmax, np_, grid):
+    return int(load().mce_param_marginals_workspace_bytes(int(nrows_total), int(nseg), int(dmax), int(np_), int(grid)))
+
+
+def marginals_block_doubles(d, np_, grid):
+    """doubles of one system's result block: MCE_MARGINALS_HEAD + d * (10 + 4 np + grid)"""
+    return MCE_MARGINALS_HEAD + int(d) * (10 + 4 * int(np_) + int(grid))
+
+
+def _param_marginals(call, segs, probs, grid, scale, tail):
+    arr = (SummarySeg * max(len(segs), 1))()
+    for i, (x, ld, n, d, w) in enumerate(segs):
+        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, None
+    probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    npr, grid = probs.size, int(grid)
+    shape_ok = 1 <= npr <= MCE_MARGINALS_MAX_P and grid in (64, 128, 256, 512, 1024)
+    sizes = [marginals_block_doubles(d, npr, grid) if shape_ok and 1 <= int(d) <= 127 else 0 for _, _, _, d, _ in segs]
+    out = np.full(max(sum(sizes), 1), np.nan)
+    check(call(_c.cast(arr, _P), len(segs), probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
+    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
+    return [out[at[i]:at[i + 1]] for i in range(len(segs))]
+
+
+def param_marginals_dev(segs, probs, grid, scale, ws, ws_bytes, stream=0):
+    """mce_param_marginals_dev: the 1-D marginal densities, modes and HPD regions of ``len(segs)`` systems that are on the device -> one
+    float64 block per system (``marginals.from_block`` reads it); ``segs``: [(device address of the rows, row stride in doubles, rows,
+    measured columns, device address of w)]"""
+    return _param_marginals(load().mce_param_marginals_dev, segs, probs, grid, scale, (ws or None, int(ws_bytes), stream or None))
+
+
+def param_marginals(systems, probs, grid, scale, device=0):
+    """mce_param_marginals_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
+    keep = []
+    for x, d, w in systems:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if x.shape[0] != w.size:
+            raise ValueError("param marginals: rows and w of one length expected")
+        keep.append((x, int(d), w))
+    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
+    return _param_marginals(load().mce_param_marginals_f64, segs, probs, grid, scale, (int(device),))
 
 
 def jack_groups_dev(segs, stream=0):

@@ -65,6 +65,16 @@ def build_parser(prog=None):
                    help="print the weighted mean, standard deviation, equal-tailed limits (probabilities P ...; default 0.68 0.95) and the "
                         "best-fit sample of every parameter used, after the information lines and before the ln(B) lines: logged with them "
                         "at -vb 1, printed where the ln(B) lines are printed (--farm, --jackknife) at -vb 0; write it after root_name")
+    p.add_argument("--marginals", dest="marginals", nargs="*", default=None, type=float, metavar="P",
+                   help="print the mode, the highest-posterior-density limits with their number of pieces (probabilities P ...; default 0.68 "
+                        "0.95) and the bandwidth h of the 1-D marginal density of every parameter used, after the summary lines and before "
+                        "the ln(B) lines; write it after root_name")
+    p.add_argument("--marginals-grid", dest="marginals_grid", default=None, type=int, metavar="G", choices=(64, 128, 256, 512, 1024),
+                   help="with --marginals: the grid points of a density (default 512)")
+    p.add_argument("--marginals-scale", dest="marginals_scale", default=None, type=float, metavar="S",
+                   help="with --marginals: the bandwidth as a multiple of the normal-reference rule (default 1)")
+    p.add_argument("--marginals-out", dest="marginals_out", default=None, metavar="FILE.npz",
+                   help="with --marginals: write the names, the grid points and the densities of every parameter to FILE.npz, one set per root")
     p.add_argument("--tension", dest="tension", nargs=2, default=None, metavar=("ROOT_A", "ROOT_B"),
                    help="tension between the data sets of the roots ROOT_A and ROOT_B under one model, root_name being their JOINT run: the three "
                         "roots in one batched GPU pass (mcevidence_amd.tension), then ln R, ln I, the suspiciousness ln S, the dimensionality d "
@@ -86,6 +96,35 @@ def _summary_kw(args):
     if args.summary is None:
         return {}
     return {"summary": tuple(args.summary) if args.summary else True}
+
+
+def _marginals_kw(args):
+    """--marginals / --marginals-grid / --marginals-scale, where the first was given"""
+    if args.marginals is None:
+        return {}
+    if args.marginals_grid is None and args.marginals_scale is None:
+        return {"marginals": tuple(args.marginals) if args.marginals else True}
+    kw = {"probs": tuple(args.marginals) if args.marginals else True}
+    if args.marginals_grid is not None:
+        kw["grid"] = args.marginals_grid
+    if args.marginals_scale is not None:
+        kw["scale"] = args.marginals_scale
+    return {"marginals": kw}
+
+
+def _print_marginals(info, logged=False):
+    """the marginals lines, after the summary lines and before the ln(B) lines; ``logged``: the route has logged them already"""
+    from .marginals import lines
+    if (info or {}).get("marginals") and not logged:
+        for line in lines(info["marginals"]):
+            print(line)
+
+
+def _save_marginals(args, roots, infos):
+    """--marginals-out, where it was given"""
+    if args.marginals_out is not None:
+        from .marginals import save
+        save(args.marginals_out, roots, infos)
 
 
 def _print_summary(info, logged=False):
@@ -170,10 +209,10 @@ def farm_main(args):
         ndims.append(a.ndim)
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
-    want_info = args.converge is not None or args.information or args.jackknife is not None or args.summary is not None
+    want_info = args.converge is not None or args.information or args.jackknife is not None or args.summary is not None or args.marginals is not None
     outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
                                     idchain=args.idchain, split=args.cross, info=want_info, **_thin_kw(args), **_converge_kw(args),
-                                    **_information_kw(args), **_summary_kw(args), **_jackknife_kw(args), **_backend_kw(args))
+                                    **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_jackknife_kw(args), **_backend_kw(args))
     infos = [o[1] for o in outs] if want_info else [None] * len(outs)
     outs = [o[0] for o in outs] if want_info else outs
     note = None
@@ -183,7 +222,9 @@ def farm_main(args):
         _print_converge(inf)
         _print_information(inf)
         _print_summary(inf)
+        _print_marginals(inf)
         note = _print_lnb(mle, inf) or note
+    _save_marginals(args, roots, infos)
     if note:
         _print_jackknife_note(note)
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
@@ -200,7 +241,7 @@ def _shift_kw(args):
 
 def tension_main(args):
     """``--tension ROOT_A ROOT_B``: the three roots as ``--farm`` prints roots, then the tension lines and their footnote.  ``--cross``,
-    ``--converge`` and ``--summary`` go to all three roots (``--information`` is always set); ``--farm`` and ``--resident`` name another
+    ``--converge``, ``--summary`` and ``--marginals`` go to all three roots (``--information`` is always set); ``--farm`` and ``--resident`` name another
     route for ``root_name`` and are refused"""
     import copy
     from . import tension
@@ -215,7 +256,7 @@ def tension_main(args):
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
     ea, eb, eab, info = tension.evidence_tension(roots[0], roots[1], roots[2], kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen,
                                                  thinlen=args.thinlen, idchain=args.idchain, split=args.cross, **_thin_kw(args), **_converge_kw(args),
-                                                 **_summary_kw(args), **_jackknife_kw(args), **_backend_kw(args), **_shift_kw(args))
+                                                 **_summary_kw(args), **_marginals_kw(args), **_jackknife_kw(args), **_backend_kw(args), **_shift_kw(args))
     note = None
     for r, mle, inf in zip(roots, (ea, eb, eab), info["roots"]):
         print()
@@ -223,7 +264,9 @@ def tension_main(args):
         _print_converge(inf)
         _print_information(inf)
         _print_summary(inf)
+        _print_marginals(inf)
         note = _print_lnb(mle, inf) or note
+    _save_marginals(args, roots, info["roots"])
     print()
     print("Tension of {} and {} (joint run: {})".format(*roots))
     for line in tension.lines(info["tension"]):
@@ -255,6 +298,8 @@ def main(argv=None):
         build_parser(prog="MCEvidence.py").error("--shift-kde BOOST: a positive number of offsets expected")
     if args.shift_bandwidth is not None and not args.shift_bandwidth > 0.0:
         build_parser(prog="MCEvidence.py").error("--shift-bandwidth SCALE: a positive number expected")
+    if (args.marginals_grid is not None or args.marginals_scale is not None or args.marginals_out is not None) and args.marginals is None:
+        build_parser(prog="MCEvidence.py").error("--marginals-grid, --marginals-scale and --marginals-out belong to --marginals")
     if args.tension is not None:
         if args.farm or args.resident:
             build_parser(prog="MCEvidence.py").error("--tension runs its three roots in one batched pass: it does not combine with --farm or --resident")
@@ -268,12 +313,17 @@ def main(argv=None):
     print("Using file: ", args.root_name)
     if args.resident:
         from .resident import evidence_from_files
+        want_info = args.jackknife is not None or args.marginals_out is not None
         out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
-                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, info=args.jackknife is not None,
-                                  **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_jackknife_kw(args), **_backend_kw(args))
-        if args.jackknife is not None:
+                                  kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, info=want_info,
+                                  **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_jackknife_kw(args),
+                                  **_backend_kw(args))
+        if want_info:
             out, inf = out
+            _save_marginals(args, [args.root_name], [inf])
+        if args.jackknife is not None:
             _print_summary(inf, logged=args.verbose >= 1)
+            _print_marginals(inf, logged=args.verbose >= 1)
             jk = _print_lnb(out, inf)
             if jk:
                 _print_jackknife_note(jk)
@@ -282,7 +332,7 @@ def main(argv=None):
         return out
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
-                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_backend_kw(args))
+                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_backend_kw(args))
     _print_converge(getattr(mce, "info", None))
     if args.jackknife is not None:
         mce.jackknife = {"groups": args.jackknife, "by": args.jackknife_by}
@@ -290,11 +340,13 @@ def main(argv=None):
         jk = mce.info["jackknife"]
         _print_information(mce.info)
         _print_summary(mce.info, logged=args.verbose >= 1)
+        _print_marginals(mce.info, logged=args.verbose >= 1)
         for k in range(1, len(jk["lnE"]) + 1):
             print("   ln(B)[k={}] = {} \u00b1 {}".format(k, jk["lnE"][k - 1], jk["sigma"][k - 1]))
         print("* \u00b1: delete-a-group jackknife over {} {} (conservative, not a calibrated 1 sigma).".format(jk["groups"], jk["by"]))
     else:
         out = mce.evidence()
+    _save_marginals(args, [args.root_name], [getattr(mce, "info", None)])
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
     print("")
     return out

@@ -1,0 +1,183 @@
+// capi_marginals.hpp -- part of capi.hip (one translation unit): mce_param_marginals_out_doubles / mce_param_marginals_workspace_bytes /
+// mce_param_marginals_dev / mce_param_marginals_f64: the 1-D marginal densities, modes and highest-density regions of the parameter
+// columns of MANY systems (the ready roots of a farm wave) that are on the device, in one call (param_marginals_kernels.hpp has the
+// launches, param_marginals.hpp the rule).  Everything is enqueued on the caller's stream; the host waits once, for one block of
+// results.  Argument checks come before any device call.  Ten launches, whatever the number of systems.
+#pragma once
+
+#include "capi_seg.hpp"
+#include "param_marginals.hpp"
+#include "param_marginals_kernels.hpp"
+
+namespace {
+
+constexpr int32_t kMarMaxSegs = 1 << 16;
+constexpr int64_t kMarMaxRows = 0x7fffffffLL;
+
+// no table of nseg segments with nrows rows has more (system, part) pairs than this
+size_t mar_max_parts(int64_t nrows_total, int32_t nseg)
+{
+    return (size_t)std::min<int64_t>((int64_t)mce_mar::kMarMaxParts * nseg, mce_seg::seg_max_tiles(nrows_total, nseg));
+}
+
+// the workspace of a call: nrows_total rows in nseg segments, at most dmax columns, np probabilities, G grid points
+struct MarWs {
+    mce::SumSeg* segs;
+    int64_t* tile0;
+    double *head, *cols, *part, *sys, *col, *prm, *probs, *S, *res;
+    mce::SumRun* runs;
+    mce::MarSeg* msegs;
+    size_t total;
+    MarWs(int64_t nrows_total, int32_t nseg, int32_t dmax, int32_t np, int32_t G, void* ws = nullptr)
+    {
+        const size_t Sg = (size_t)nseg, T = (size_t)mce_seg::seg_max_tiles(nrows_total, nseg), R = Sg * (size_t)dmax, D = (size_t)dmax;
+        WsPlan P(ws);
+        segs = P.take<mce::SumSeg>(Sg);
+        tile0 = P.take<int64_t>(Sg);
+        head = P.take<double>(T * mce::kSumTileHead);
+        cols = P.take<double>(T * mce::kSumTileCol * D);
+        part = P.take<double>(T * D);
+        sys = P.take<double>(Sg * mce::kSumSys);
+        col = P.take<double>(R * mce::kSumCol);
+        runs = P.take<mce::SumRun>(R);
+        msegs = P.take<mce::MarSeg>(Sg);
+        prm = P.take<double>(R * mce::kMarPrm);
+        probs = P.take<double>((size_t)mce_mar::kMarMaxP + 1);
+        S = P.take<double>(mar_max_parts(nrows_total, nseg) * D * (size_t)G);
+        res = P.take<double>(Sg * (size_t)mce_mar::mar_out_doubles(dmax, np, G));
+        total = P.total;
+    }
+};
+
+struct MarTables {
+    std::vector<mce::SumSeg> segs;
+    std::vector<mce::MarSeg> msegs;
+    mce_seg::SegTable tiles;
+    std::vector<mce::SumRun> runs;
+    int64_t out_doubles = 0, parts = 0;
+    int32_t dmax = 1, max_parts = 0;
+};
+
+bool mar_shape_ok(int32_t nseg, int32_t dmax, int32_t np, int32_t G)
+{
+    return nseg >= 1 && nseg <= kMarMaxSegs && dmax >= 1 && dmax <= mce_mar::kMarMaxDim && np >= 1 && np <= mce_mar::kMarMaxP && mce_mar::mar_grid_ok(G);
+}
+
+// the argument checks of both forms, and the tables
+int mar_tables(const mce_summary_seg* segs, int32_t nseg, const double* probs, int32_t np, int32_t G, double scale, MarTables& T)
+{
+    if (!segs || !probs) return fail(MCE_ERR_INVALID, "null pointer argument");
+    if (nseg < 1 || nseg > kMarMaxSegs) return fail(MCE_ERR_INVALID, "param marginals: %d segments (1 .. %d expected)", nseg, kMarMaxSegs);
+    if (np < 1 || np > mce_mar::kMarMaxP) return fail(MCE_ERR_INVALID, "param marginals: %d probabilities (1 .. %d expected)", np, mce_mar::kMarMaxP);
+    for (int32_t t = 0; t < np; ++t)
+        if (!(probs[t] > 0.0 && probs[t] < 1.0)) return fail(MCE_ERR_INVALID, "param marginals: probability %d is %g (0 < p < 1 expected)", t, probs[t]);
+    if (!mce_mar::mar_grid_ok(G)) return fail(MCE_ERR_INVALID, "param marginals: grid=%d (64, 128, 256, 512 or 1024 expected)", G);
+    if (!mce_mar::mar_pos_finite(scale)) return fail(MCE_ERR_INVALID, "param marginals: scale=%g (finite and > 0 expected)", scale);
+    T.segs.assign((size_t)nseg, mce::SumSeg{});
+    T.msegs.assign((size_t)nseg, mce::MarSeg{});
+    for (int32_t s = 0; s < nseg; ++s) {
+        const mce_summary_seg& g = segs[s];
+        if (g.d < 1 || g.d > mce_mar::kMarMaxDim) return fail(MCE_ERR_INVALID, "param marginals: segment %d has d=%d (1 .. %d expected)", s, g.d, mce_mar::kMarMaxDim);
+        if (g.n < 0 || g.n > kMarMaxRows || g.ld < g.d || (g.n > 0 && (!g.x || !g.w)))
+            return fail(MCE_ERR_INVALID, "param marginals: segment %d has %lld rows, ld=%lld, d=%d at x %s, w %s", s, (long long)g.n, (long long)g.ld, g.d,
+                        g.x ? "valid" : "null", g.w ? "valid" : "null");
+        mce::SumSeg& o = T.segs[(size_t)s];
+        o.x = g.x; o.w = g.w; o.fs = nullptr; o.ld = g.ld; o.n = g.n; o.d = g.d; o.pad = 0;
+        o.out_off = T.out_doubles;
+        o.col0 = (int64_t)T.runs.size();
+        T.msegs[(size_t)s] = mce::MarSeg{T.parts, T.out_doubles};
+        const int nparts = mce_mar::mar_nparts(g.n);
+        T.parts += (int64_t)nparts * g.d;
+        T.max_parts = std::max(T.max_parts, (int32_t)nparts);
+        T.out_doubles += mce_mar::mar_out_doubles(g.d, np, G);
+        T.tiles.add(g.n);
+        T.dmax = std::max(T.dmax, g.d);
+        for (int32_t j = 0; j < g.d; ++j) T.runs.push_back(mce::SumRun{0, 0, s, j});
+    }
+    if (!T.tiles.fits()) return fail(MCE_ERR_INVALID, "param marginals: %lld rows in one call", (long long)T.tiles.nrows);
+    return MCE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mce_param_marginals_out_doubles(int32_t d, int32_t np, int32_t grid)
+{
+    if (!mar_shape_ok(1, d, np, grid)) return 0;
+    return (size_t)mce_mar::mar_out_doubles(d, np, grid);
+}
+
+size_t mce_param_marginals_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t dmax, int32_t np, int32_t grid)
+{
+    if (nrows_total < 0 || !mar_shape_ok(nseg, dmax, np, grid)) return 0;
+    return MarWs(nrows_total, nseg, dmax, np, grid).total;
+}
+
+int mce_param_marginals_dev(const mce_summary_seg* segs, int32_t nseg, const double* probs, int32_t np, int32_t grid, double scale, double* out, void* ws,
+                            size_t ws_bytes, void* stream)
+{
+    using namespace mce;
+    if (!out) return fail(MCE_ERR_INVALID, "null pointer argument");
+    MarTables T;
+    int rc = mar_tables(segs, nseg, probs, np, grid, scale, T);
+    if (rc != MCE_OK) return rc;
+    if (!ws) return fail(MCE_ERR_INVALID, "null pointer argument");
+    if ((rc = prep_need_device()) != MCE_OK) return rc;
+    const MarWs W(T.tiles.nrows, nseg, T.dmax, np, grid, ws);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = seg_dev_begin("param marginals", ws_bytes, W.total, T.segs, T.tiles.tile0, W.segs, W.tile0, st)) != MCE_OK) return rc;
+    if ((size_t)T.parts > mar_max_parts(T.tiles.nrows, nseg) * (size_t)T.dmax) return fail(MCE_ERR_WORKSPACE, "param marginals: %lld parts, fewer planned", (long long)T.parts);
+    const int dmax = T.dmax, G = grid, nblk = mce_mar::mar_nblocks(G);
+    const int64_t R = (int64_t)T.runs.size();
+    if (R * nblk > mce_seg::kSegMaxTiles) return fail(MCE_ERR_INVALID, "param marginals: %lld columns in one call", (long long)R);
+    MCE_HIP(hipMemcpyAsync(W.runs, T.runs.data(), T.runs.size() * sizeof(SumRun), hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemcpyAsync(W.msegs, T.msegs.data(), T.msegs.size() * sizeof(MarSeg), hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemcpyAsync(W.probs, probs, (size_t)np * 8, hipMemcpyHostToDevice, st));
+    const dim3 tb(kPsumThreads);
+    const unsigned ntiles = (unsigned)T.tiles.ntiles;
+    // the moments, by summary's kernels as they stand
+    if (ntiles > 0) hipLaunchKernelGGL(sum_tile_kernel, dim3(ntiles), tb, 0, st, W.segs, W.tile0, (int)nseg, dmax, W.head, W.cols);
+    hipLaunchKernelGGL(sum_sys_kernel, dim3((unsigned)nseg), tb, 0, st, W.segs, W.tile0, W.head, W.sys);
+    hipLaunchKernelGGL(sum_col_kernel, dim3((unsigned)R), tb, 0, st, W.segs, W.tile0, W.runs, dmax, W.cols, W.sys, W.col);
+    if (ntiles > 0) hipLaunchKernelGGL(sum_var_tile_kernel, dim3(ntiles), tb, 0, st, W.segs, W.tile0, (int)nseg, dmax, W.col, W.part);
+    hipLaunchKernelGGL(sum_var_col_kernel, dim3((unsigned)R), tb, 0, st, W.segs, W.tile0, W.runs, dmax, W.part, W.sys, W.col);
+    // the bandwidths and grids; the kernel sums per part; the fold; the decisions; the blocks
+    const dim3 mt(kMarThreads);
+    hipLaunchKernelGGL(mar_prep_kernel, dim3((unsigned)((R + kMarThreads - 1) / kMarThreads)), mt, 0, st, W.segs, W.runs, R, W.sys, W.col, G, scale, W.prm);
+    if (T.max_parts > 0)
+        hipLaunchKernelGGL(mar_density_kernel, dim3((unsigned)(R * nblk), (unsigned)T.max_parts), mt, 0, st, W.segs, W.msegs, W.runs, W.prm, G, nblk, W.S);
+    hipLaunchKernelGGL(mar_fold_kernel, dim3((unsigned)(R * nblk)), mt, 0, st, W.segs, W.msegs, W.runs, W.prm, W.sys, G, nblk, (int)np, W.S, W.res);
+    hipLaunchKernelGGL(mar_hpd_kernel, dim3((unsigned)R), mt, 0, st, W.segs, W.msegs, W.runs, W.prm, W.probs, (int)np, G, W.res);
+    hipLaunchKernelGGL(mar_result_kernel, dim3((unsigned)nseg), mt, 0, st, W.segs, W.msegs, W.sys, W.col, W.prm, G, (int)np, W.res);
+    MCE_HIP(hipGetLastError());
+    MCE_HIP(hipMemcpyAsync(out, W.res, (size_t)T.out_doubles * 8, hipMemcpyDeviceToHost, st));
+    MCE_HIP(hipStreamSynchronize(st));                            // the one wait
+    return MCE_OK;
+}
+
+int mce_param_marginals_f64(const mce_summary_seg* segs, int32_t nseg, const double* probs, int32_t np, int32_t grid, double scale, double* out, int32_t device)
+{
+    if (!out) return fail(MCE_ERR_INVALID, "null pointer argument");
+    MarTables T;
+    int rc = mar_tables(segs, nseg, probs, np, grid, scale, T);
+    if (rc != MCE_OK) return rc;
+    if ((rc = select_device(device)) != MCE_OK) return rc;
+    size_t elems = 0;
+    for (int32_t s = 0; s < nseg; ++s) elems += (size_t)segs[s].n * ((size_t)segs[s].d + 1);
+    SegStage data;
+    DevBuf ws;
+    if ((rc = data.alloc(elems * sizeof(double))) != MCE_OK) return rc;
+    std::vector<mce_summary_seg> dsegs(segs, segs + nseg);
+    for (mce_summary_seg& g : dsegs) {
+        // the d measured columns, packed: ld = d on the device; the likelihood column is not an input
+        if ((rc = data.put(g.x, (size_t)g.n, g.x, (size_t)g.d, (size_t)g.ld)) != MCE_OK || (rc = data.put(g.w, (size_t)g.n, g.w)) != MCE_OK) return rc;
+        g.ld = g.d;
+        g.fs = nullptr;
+    }
+    const size_t wsb = mce_param_marginals_workspace_bytes(T.tiles.nrows, nseg, T.dmax, np, grid);
+    MCE_HIP(ws.alloc(wsb));
+    return mce_param_marginals_dev(dsegs.data(), nseg, probs, np, grid, scale, out, ws.p, wsb, nullptr);
+}
+
+}  // extern "C"

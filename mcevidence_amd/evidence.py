@@ -29,6 +29,7 @@ import numpy as np
 
 from . import information as _information
 from . import summary as _summary
+from . import marginals as _marginals
 from . import covariance as _covariance
 from .chains import MCSamples, rank0_draw
 from .resident import mle_from_sums
@@ -210,7 +211,10 @@ class MCEvidence(object):
         equal-tailed limits and the best-fit sample of the first ``ndim`` parameters in ``info["summary"]`` and in
         ``self.param_summary`` (summary.py; docs/design/summary.md; ``self.summary()`` stays the reference's printing method) -- and
         ``covariance`` -- None or True: ``evidence()`` then also stores the weighted mean and covariance matrix of the first ``ndim``
-        parameters in ``info["covariance"]`` and in ``self.param_cov`` (covariance.py; docs/design/tension.md).
+        parameters in ``info["covariance"]`` and in ``self.param_cov`` (covariance.py; docs/design/tension.md) -- and ``marginals`` -- None,
+        True, up to 7 probabilities or dict(probs, grid, scale): ``evidence()`` then also stores the 1-D marginal density of each of the
+        first ``ndim`` parameters on a grid, its mode and its highest-posterior-density regions in ``info["marginals"]`` and in
+        ``self.param_marginals`` (marginals.py; docs/design/marginals.md).
 
         method      chain root name / file name(s), or list/tuple/dict of chain arrays
                     (columns: weight, -lnL, parameters...)
@@ -239,6 +243,11 @@ class MCEvidence(object):
         # (what the last evidence() found is kept as ``param_summary``: ``summary`` is the reference's method of this class)
         self.param_summary = None
         _summary.refuse(self.summary_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
+        # the 1-D marginal densities, modes and HPD regions with every evidence() call (docs/design/marginals.md): None (off: nothing
+        # changes), True, the probabilities, or a dict of probs, grid and scale; consumed here for the same reason
+        self.marginals_spec = gdkwargs.pop("marginals", None)
+        self.param_marginals = None
+        _marginals.refuse(self.marginals_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
         # the weighted mean and covariance matrix of the parameters with every evidence() call (docs/design/tension.md): None (off:
         # nothing changes) or True; consumed here for the same reason
         self.covariance = gdkwargs.pop("covariance", None)
@@ -498,6 +507,24 @@ class MCEvidence(object):
                                _summary.targets(probs))
         self.param_summary = self.info["summary"] = _summary.build(blk, probs, logLmax, _summary.param_names(self.fname, self.ndim))
 
+    def _fill_marginals(self):
+        """``info["marginals"]`` of this call (the constructor's ``marginals`` keyword; unset: nothing happens): the rule of marginals.py
+        on s1's weights and its raw first ``ndim`` columns -- by ``mce_param_marginals_f64`` where the HIP backend is in use, otherwise
+        in NumPy; under a process group every rank computes its own, no collective"""
+        sp = _marginals.spec(self.marginals_spec)
+        if sp is None:
+            return
+        _marginals.refuse(self.marginals_spec, brange=self.brange, nbatch=self.nbatch)
+        samples, _, _ = self.gd.arrays("s1")
+        a, x = self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim]
+        if getattr(self.backend, "name", None) == "hip":
+            import torch
+            devs = getattr(self.backend, "devices", None)
+            blk = _marginals.measure_native(a, x, *sp, device=devs[0] if devs else (torch.cuda.current_device() if torch.cuda.is_available() else 0))
+        else:
+            blk = _marginals.measure(a, x, *sp)
+        self.param_marginals = self.info["marginals"] = _marginals.build(blk, sp, _summary.param_names(self.fname, self.ndim))
+
     def _fill_covariance(self):
         """``info["covariance"]`` of this call (the constructor's ``covariance`` keyword; unset: nothing happens): the rule of
         covariance.py on s1's weights and its raw first ``ndim`` columns, on the host -- under a process group every rank computes its
@@ -512,12 +539,16 @@ class MCEvidence(object):
     def _report(self, MLE, verbose, info, pos_lnp=False):
         self._fill_information(MLE, pos_lnp)
         self._fill_summary(pos_lnp)
+        self._fill_marginals()
         self._fill_covariance()
         if verbose > 0 and "information" in self.info and _information.wanted(self.information):
             for line in _information.lines(self.info["information"]):
                 self.logger.info(line)
         if verbose > 0 and "summary" in self.info and _summary.wanted(self.summary_spec):
             for line in _summary.lines(self.info["summary"]):
+                self.logger.info(line)
+        if verbose > 0 and "marginals" in self.info and _marginals.wanted(self.marginals_spec):
+            for line in _marginals.lines(self.info["marginals"]):
                 self.logger.info(line)
         if verbose > 0:
             for k in range(1, self.kmax):

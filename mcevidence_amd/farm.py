@@ -22,6 +22,7 @@ import numpy as np
 from . import information as _information
 from . import resident as _res
 from . import summary as _summary
+from . import marginals as _marginals
 from . import covariance as _covariance
 
 logger = logging.getLogger("mcevidence_amd")
@@ -142,6 +143,20 @@ def _per_root_summary(value, n):
     return [value] * n
 
 
+def _per_root_marginals(value, n):
+    """``marginals`` of the farm -> one value per root, by ``_per_root_summary``'s rule with a dict as one more kind of entry: a dict, or a
+    sequence of bare numbers, is ONE value for every root; a list / tuple whose entries are all None, a bool, a sequence or a dict is one
+    entry per root"""
+    if isinstance(value, (list, tuple, np.ndarray)) and len(value) > 0:
+        slot = [v is None or isinstance(v, (bool, np.bool_, list, tuple, np.ndarray, dict)) for v in value]
+        if all(slot):
+            return _per_root(list(value), n, "marginals")
+        if any(slot):
+            raise ValueError("marginals=%r: either one value for every root or one entry per root (None, True, a sequence of probabilities or a "
+                             "dict each), not a mixture" % (value,))
+    return [value] * n
+
+
 def _parse_wave(pool, device, wave_bytes, paths, lens, ms):
     """one wave: the files read into the staging buffer, uploaded and parsed -> (the C array of per-file results, the device tensor
     global token k is written to, {path: exception} of the files that could not be read)"""
@@ -216,7 +231,7 @@ class _Root(object):
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
                              require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto",
-                             information=None, jackknife=None, summary=None, covariance=None):
+                             information=None, jackknife=None, summary=None, covariance=None, marginals=None):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -244,7 +259,10 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     ``info["summary"]`` -- ONE ``mce_param_summary_dev`` call per wave (and per set of probabilities) over all its ready roots, thinned
     and unthinned alike, before the feed.  ``covariance`` (one value or one per root: None or True): the weighted mean and covariance matrix
     of every such root's first ``ndim`` parameters in ``info["covariance"]`` -- ONE ``mce_param_cov_dev`` call per wave over all its ready
-    roots that ask, thinned and unthinned alike, before the feed.  Without a GPU: ``RuntimeError``."""
+    roots that ask, thinned and unthinned alike, before the feed.  ``marginals`` (one value or one per root, by ``summary``'s rule; a dict is
+    one value): the 1-D marginal densities, modes and HPD regions of every such root's first ``ndim`` parameters in ``info["marginals"]`` --
+    ONE ``mce_param_marginals_dev`` call per wave and per distinct (probs, grid, scale) over all its ready roots that ask, before the feed.
+    Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
     roots = list(roots)
@@ -263,6 +281,10 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     jack_kw = [{} if v is None or v is False else {"jackknife": v} for v in jacks]
     sums = _per_root_summary(summary, n)
     sum_kw = [{"summary": v} if _summary.wanted(v) else {} for v in sums]
+    mars = _per_root_marginals(marginals, n)
+    for v in mars:
+        _marginals.spec(v)
+    mar_kw = [{"marginals": v} if _marginals.wanted(v) else {} for v in mars]
     covs = _per_root(covariance, n, "covariance")
     for v in covs:
         _covariance.spec(v)
@@ -271,7 +293,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **sum_kw[i], **cov_kw[i], **extra)
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **sum_kw[i], **mar_kw[i], **cov_kw[i], **extra)
                 for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
@@ -297,7 +319,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
         if reason == _res.RESIDENT:
             try:
                 reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i],
-                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i], covariance=covs[i])
+                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i], covariance=covs[i], marginals=mars[i])
             except ValueError as e:                # (thin_corr together with thinlen; a converge or jackknife value no route takes)
                 fail(i, e)
                 continue
@@ -458,6 +480,13 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                     sblks.update(zip((r.index for r in sasked),
                                      _res.summary_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9], r.problem[10]) for r in sasked],
                                                               _summary.targets(probs), device, stream.cuda_stream)))
+                # marginals: the ready roots that ask for them in one call per distinct (probs, grid, scale), while the gathered rows are raw
+                mblks = {}
+                for msp in sorted(set(_marginals.spec(mars[r.index]) for r in ready if _marginals.wanted(mars[r.index]))):
+                    masked = [r for r in ready if _marginals.wanted(mars[r.index]) and _marginals.spec(mars[r.index]) == msp]
+                    mblks.update(zip((r.index for r in masked),
+                                     _res.marginals_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in masked],
+                                                                msp, device, stream.cuda_stream)))
                 # covariance: the ready roots that ask for it in one call, while the gathered rows are raw
                 casked = [r for r in ready if _covariance.wanted(covs[r.index])]
                 cblks = dict(zip((r.index for r in casked),
@@ -502,6 +531,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                         if r.index in sblks:
                             inf["summary"] = _summary.build(sblks[r.index], _summary.spec(sums[r.index]), r.scal[0],
                                                             _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
+                        if r.index in mblks:
+                            inf["marginals"] = _marginals.build(mblks[r.index], _marginals.spec(mars[r.index]),
+                                                                _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
                         if r.index in cblks:
                             inf["covariance"] = _covariance.build(cblks[r.index],
                                                                   _covariance.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
@@ -537,6 +569,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             kw.update(info_kw[i])
             kw.update(jack_kw[i])
             kw.update(sum_kw[i])
+            kw.update(mar_kw[i])
             kw.update(cov_kw[i])
             if covtype != "all":
                 kw["covtype"] = covtype

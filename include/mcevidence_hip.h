@@ -726,6 +726,37 @@ int mce_param_marginals_dev(const mce_summary_seg* segs, int32_t nseg, const dou
                             size_t ws_bytes, void* stream);
 int mce_param_marginals_f64(const mce_summary_seg* segs, int32_t nseg, const double* probs, int32_t np, int32_t grid, double scale, double* out, int32_t device);
 
+/* The 2-D joint posterior densities behind contours= (a product-Gaussian kernel density estimate of every pair of chosen parameter
+ * columns on a regular grid x grid, its mode and its credible regions), for MANY systems in one call.  The rule is stated in
+ * csrc/param_contours.hpp and docs/design/contours.md.  One system is one mce_summary_seg as for mce_param_marginals_dev.  cols[nc]: a
+ * strictly increasing list of 2 .. MCE_CONTOURS_MAX_COLS columns, every one below every segment's d; the pairs are (cols[s], cols[t]),
+ * s < t, in the order (0,1), (0,2), .., (nc-2, nc-1), P = nc (nc - 1) / 2 of them, the first column of a pair its x axis.  probs[np]:
+ * 1 .. MCE_MARGINALS_MAX_P probabilities in (0, 1); grid: 32 or 64; scale: finite and > 0.  With the moments as mce_param_summary_dev
+ * forms them (bit for bit): h = (scale sqrt(v)) pow(1 / ess, 1 / 6), c = 1 / (2 h h), lo = min - 3 h, step = (max + 3 h - lo) /
+ * (grid - 1), E_j[r][k] = K(c_j (g_jk - x_rj)^2) with K(a) = a >= 746 ? +0.0 : exp(-a), rho[kx][ky] = sum over used r of (w_r E_i[r][kx])
+ * E_j[r][ky] / (W h_i h_j 2 pi).  The mode is the cell of the largest rho (the lowest kx * grid + ky among equals).  For a probability p
+ * the cells are ordered by rho descending, then flat index ascending, and rho is accumulated serially in that order to Z; the region is
+ * the positions up to and including the first whose running sum is >= p Z.
+ * out (HOST, packed in segment order, mce_param_contours_out_doubles(nc, np, grid) doubles per system) = {W, A2, rows used, status,
+ * column, grid, np, nc}, then the rows col[nc], mean, var, sd, h, c, lo, step, col_status, then mode_x[P], mode_y, mode_density,
+ * pair_status, then per probability level[P] (the contour height), cells, lower_x, upper_x, lower_y, upper_y (the bounding box in grid
+ * points), edge (1 where a selected cell lies on the grid's border), then density[P][grid][grid], kx the slow index.  status 0 ok; 3, 5
+ * and 6 as mce_param_marginals_dev: every value is NaN and that system fails alone.  col_status 7 as there, on this rule's h, c and
+ * step; a pair with such a column has pair_status 7, NaN values and cells -1, and the other pairs do not notice.  A pair's bits depend
+ * on its system's rows, its two columns, grid and scale alone; two runs give the same bits; fp64, sums in a fixed order, no
+ * floating-point atomics, plain stores, 64-bit row indices.  Ten launches whatever nseg is, on the caller's stream, which this library
+ * synchronises once, on return.  Workspace: mce_param_contours_workspace_bytes(rows of all segments, nseg, the largest d, nc, np, grid).
+ * mce_param_contours_f64 takes HOST segments, uploads them to `device` and calls the device form.  Argument errors: MCE_ERR_INVALID (no
+ * device needed); no visible device: MCE_ERR_NO_DEVICE. */
+#define MCE_CONTOURS_HEAD 8
+#define MCE_CONTOURS_MAX_COLS 32
+size_t mce_param_contours_out_doubles(int32_t nc, int32_t np, int32_t grid);
+size_t mce_param_contours_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t dmax, int32_t nc, int32_t np, int32_t grid);
+int mce_param_contours_dev(const mce_summary_seg* segs, int32_t nseg, const int32_t* cols, int32_t nc, const double* probs, int32_t np, int32_t grid, double scale,
+                           double* out, void* ws, size_t ws_bytes, void* stream);
+int mce_param_contours_f64(const mce_summary_seg* segs, int32_t nseg, const int32_t* cols, int32_t nc, const double* probs, int32_t np, int32_t grid, double scale,
+                           double* out, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

@@ -228,10 +228,16 @@ SIGNATURES["mce_kde_shift_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32])
 
 MCE_MARGINALS_HEAD = 8
 MCE_MARGINALS_MAX_P = 7
+MCE_CONTOURS_HEAD = 8
+MCE_CONTOURS_MAX_COLS = 32
 SIGNATURES["mce_param_marginals_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int32])
 SIGNATURES["mce_param_marginals_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32])
 SIGNATURES["mce_param_marginals_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _P, _c.c_size_t, _P])
 SIGNATURES["mce_param_marginals_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _c.c_int32])
+SIGNATURES["mce_param_contours_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_contours_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_contours_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_param_contours_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _c.c_int32])
 
 
 class JackGroupsSeg(ctypes.Structure):
@@ -910,6 +916,55 @@ def param_marginals(systems, probs, grid, scale, device=0):
         keep.append((x, int(d), w))
     segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
     return _param_marginals(load().mce_param_marginals_f64, segs, probs, grid, scale, (int(device),))
+
+
+def param_contours_out_doubles(nc, np_, grid):
+    return int(load().mce_param_contours_out_doubles(int(nc), int(np_), int(grid)))
+
+
+def param_contours_workspace_bytes(nrows_total, nseg, dmax, nc, np_, grid):
+    return int(load().mce_param_contours_workspace_bytes(int(nrows_total), int(nseg), int(dmax), int(nc), int(np_), int(grid)))
+
+
+def contours_block_doubles(nc, np_, grid):
+    """doubles of one system's result block: MCE_CONTOURS_HEAD + 9 nc + P (4 + 7 np + grid^2), P = nc (nc - 1) / 2"""
+    nc, grid = int(nc), int(grid)
+    return MCE_CONTOURS_HEAD + 9 * nc + (nc * (nc - 1) // 2) * (4 + 7 * int(np_) + grid * grid)
+
+
+def _param_contours(call, segs, cols, probs, grid, scale, tail):
+    arr = (SummarySeg * max(len(segs), 1))()
+    for i, (x, ld, n, d, w) in enumerate(segs):
+        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, None
+    cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    npr, grid = probs.size, int(grid)
+    shape_ok = 1 <= npr <= MCE_MARGINALS_MAX_P and grid in (32, 64) and 2 <= cols.size <= MCE_CONTOURS_MAX_COLS
+    size = contours_block_doubles(cols.size, npr, grid) if shape_ok else 0
+    out = np.full(max(size * len(segs), 1), np.nan)
+    check(call(_c.cast(arr, _P), len(segs), cols.ctypes.data, cols.size, probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
+    return [out[i * size:(i + 1) * size] for i in range(len(segs))]
+
+
+def param_contours_dev(segs, cols, probs, grid, scale, ws, ws_bytes, stream=0):
+    """mce_param_contours_dev: the 2-D joint densities, modes and credible regions of every pair of the columns ``cols`` of ``len(segs)``
+    systems that are on the device -> one float64 block per system (``contours.from_block`` reads it); ``segs``: [(device address of the
+    rows, row stride in doubles, rows, measured columns, device address of w)]"""
+    return _param_contours(load().mce_param_contours_dev, segs, cols, probs, grid, scale, (ws or None, int(ws_bytes), stream or None))
+
+
+def param_contours(systems, cols, probs, grid, scale, device=0):
+    """mce_param_contours_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
+    keep = []
+    for x, d, w in systems:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if x.shape[0] != w.size:
+            raise ValueError("param contours: rows and w of one length expected")
+        keep.append((x, int(d), w))
+    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
+    return _param_contours(load().mce_param_contours_f64, segs, cols, probs, grid, scale, (int(device),))
 
 
 def jack_groups_dev(segs, stream=0):

@@ -75,6 +75,17 @@ def build_parser(prog=None):
                    help="with --marginals: the bandwidth as a multiple of the normal-reference rule (default 1)")
     p.add_argument("--marginals-out", dest="marginals_out", default=None, metavar="FILE.npz",
                    help="with --marginals: write the names, the grid points and the densities of every parameter to FILE.npz, one set per root")
+    p.add_argument("--contours", dest="contours", nargs="*", default=None, type=float, metavar="P",
+                   help="also report the 2-D joint posterior density of every pair of the chosen parameters: its mode and, per probability P "
+                        "(default 0.68 0.95), the contour level and the number of grid cells it encloses")
+    p.add_argument("--contours-params", dest="contours_params", nargs="+", default=None, metavar="NAME",
+                   help="with --contours: the parameters (names or column indices, 2 to 32; default: all of the parameters used, at most 32)")
+    p.add_argument("--contours-grid", dest="contours_grid", default=None, type=int, metavar="G", choices=(32, 64),
+                   help="with --contours: the grid points per axis (default 64)")
+    p.add_argument("--contours-scale", dest="contours_scale", default=None, type=float, metavar="S",
+                   help="with --contours: the bandwidth as a multiple of the normal-reference rule (default 1)")
+    p.add_argument("--contours-out", dest="contours_out", default=None, metavar="FILE.npz",
+                   help="with --contours: write the names, the pairs, the two grid axes, the densities and the levels of every pair to FILE.npz, one set per root")
     p.add_argument("--tension", dest="tension", nargs=2, default=None, metavar=("ROOT_A", "ROOT_B"),
                    help="tension between the data sets of the roots ROOT_A and ROOT_B under one model, root_name being their JOINT run: the three "
                         "roots in one batched GPU pass (mcevidence_amd.tension), then ln R, ln I, the suspiciousness ln S, the dimensionality d "
@@ -110,6 +121,37 @@ def _marginals_kw(args):
     if args.marginals_scale is not None:
         kw["scale"] = args.marginals_scale
     return {"marginals": kw}
+
+
+def _contours_kw(args):
+    """--contours / --contours-params / --contours-grid / --contours-scale, where the first was given"""
+    if args.contours is None:
+        return {}
+    if args.contours_params is None and args.contours_grid is None and args.contours_scale is None:
+        return {"contours": tuple(args.contours) if args.contours else True}
+    kw = {"probs": tuple(args.contours) if args.contours else True}
+    if args.contours_params is not None:
+        kw["params"] = [int(v) if v.isdigit() else v for v in args.contours_params]
+    if args.contours_grid is not None:
+        kw["grid"] = args.contours_grid
+    if args.contours_scale is not None:
+        kw["scale"] = args.contours_scale
+    return {"contours": kw}
+
+
+def _print_contours(info, logged=False):
+    """the contours lines, after the marginals lines and before the ln(B) lines; ``logged``: the route has logged them already"""
+    from .contours import lines
+    if (info or {}).get("contours") and not logged:
+        for line in lines(info["contours"]):
+            print(line)
+
+
+def _save_contours(args, roots, infos):
+    """--contours-out, where it was given"""
+    if args.contours_out is not None:
+        from .contours import save
+        save(args.contours_out, roots, infos)
 
 
 def _print_marginals(info, logged=False):
@@ -209,10 +251,12 @@ def farm_main(args):
         ndims.append(a.ndim)
     logging.getLogger("mcevidence_amd").setLevel(
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
-    want_info = args.converge is not None or args.information or args.jackknife is not None or args.summary is not None or args.marginals is not None
+    want_info = args.converge is not None or args.information or args.jackknife is not None or args.summary is not None or args.marginals is not None or \
+        args.contours is not None
     outs = evidence_many_from_files(roots, kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen, thinlen=args.thinlen,
                                     idchain=args.idchain, split=args.cross, info=want_info, **_thin_kw(args), **_converge_kw(args),
-                                    **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_jackknife_kw(args), **_backend_kw(args))
+                                    **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_contours_kw(args), **_jackknife_kw(args),
+                                    **_backend_kw(args))
     infos = [o[1] for o in outs] if want_info else [None] * len(outs)
     outs = [o[0] for o in outs] if want_info else outs
     note = None
@@ -223,8 +267,10 @@ def farm_main(args):
         _print_information(inf)
         _print_summary(inf)
         _print_marginals(inf)
+        _print_contours(inf)
         note = _print_lnb(mle, inf) or note
     _save_marginals(args, roots, infos)
+    _save_contours(args, roots, infos)
     if note:
         _print_jackknife_note(note)
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
@@ -256,7 +302,8 @@ def tension_main(args):
         logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
     ea, eb, eab, info = tension.evidence_tension(roots[0], roots[1], roots[2], kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen,
                                                  thinlen=args.thinlen, idchain=args.idchain, split=args.cross, **_thin_kw(args), **_converge_kw(args),
-                                                 **_summary_kw(args), **_marginals_kw(args), **_jackknife_kw(args), **_backend_kw(args), **_shift_kw(args))
+                                                 **_summary_kw(args), **_marginals_kw(args), **_contours_kw(args), **_jackknife_kw(args), **_backend_kw(args),
+                                                 **_shift_kw(args))
     note = None
     for r, mle, inf in zip(roots, (ea, eb, eab), info["roots"]):
         print()
@@ -265,8 +312,10 @@ def tension_main(args):
         _print_information(inf)
         _print_summary(inf)
         _print_marginals(inf)
+        _print_contours(inf)
         note = _print_lnb(mle, inf) or note
     _save_marginals(args, roots, info["roots"])
+    _save_contours(args, roots, info["roots"])
     print()
     print("Tension of {} and {} (joint run: {})".format(*roots))
     for line in tension.lines(info["tension"]):
@@ -300,6 +349,8 @@ def main(argv=None):
         build_parser(prog="MCEvidence.py").error("--shift-bandwidth SCALE: a positive number expected")
     if (args.marginals_grid is not None or args.marginals_scale is not None or args.marginals_out is not None) and args.marginals is None:
         build_parser(prog="MCEvidence.py").error("--marginals-grid, --marginals-scale and --marginals-out belong to --marginals")
+    if (args.contours_params is not None or args.contours_grid is not None or args.contours_scale is not None or args.contours_out is not None) and args.contours is None:
+        build_parser(prog="MCEvidence.py").error("--contours-params, --contours-grid, --contours-scale and --contours-out belong to --contours")
     if args.tension is not None:
         if args.farm or args.resident:
             build_parser(prog="MCEvidence.py").error("--tension runs its three roots in one batched pass: it does not combine with --farm or --resident")
@@ -313,17 +364,19 @@ def main(argv=None):
     print("Using file: ", args.root_name)
     if args.resident:
         from .resident import evidence_from_files
-        want_info = args.jackknife is not None or args.marginals_out is not None
+        want_info = args.jackknife is not None or args.marginals_out is not None or args.contours_out is not None
         out = evidence_from_files(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume, idchain=args.idchain,
                                   kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen, thinlen=args.thinlen, info=want_info,
-                                  **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_jackknife_kw(args),
-                                  **_backend_kw(args))
+                                  **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_contours_kw(args),
+                                  **_jackknife_kw(args), **_backend_kw(args))
         if want_info:
             out, inf = out
             _save_marginals(args, [args.root_name], [inf])
+            _save_contours(args, [args.root_name], [inf])
         if args.jackknife is not None:
             _print_summary(inf, logged=args.verbose >= 1)
             _print_marginals(inf, logged=args.verbose >= 1)
+            _print_contours(inf, logged=args.verbose >= 1)
             jk = _print_lnb(out, inf)
             if jk:
                 _print_jackknife_note(jk)
@@ -332,7 +385,8 @@ def main(argv=None):
         return out
     mce = MCEvidence(args.root_name, split=args.cross, ndim=args.ndim, priorvolume=prior_volume,
                      idchain=args.idchain, kmax=args.kmax, verbose=args.verbose, burnlen=args.burnlen,
-                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_backend_kw(args))
+                     thinlen=args.thinlen, **_thin_kw(args), **_converge_kw(args), **_information_kw(args), **_summary_kw(args), **_marginals_kw(args), **_contours_kw(args),
+                     **_backend_kw(args))
     _print_converge(getattr(mce, "info", None))
     if args.jackknife is not None:
         mce.jackknife = {"groups": args.jackknife, "by": args.jackknife_by}
@@ -341,12 +395,14 @@ def main(argv=None):
         _print_information(mce.info)
         _print_summary(mce.info, logged=args.verbose >= 1)
         _print_marginals(mce.info, logged=args.verbose >= 1)
+        _print_contours(mce.info, logged=args.verbose >= 1)
         for k in range(1, len(jk["lnE"]) + 1):
             print("   ln(B)[k={}] = {} \u00b1 {}".format(k, jk["lnE"][k - 1], jk["sigma"][k - 1]))
         print("* \u00b1: delete-a-group jackknife over {} {} (conservative, not a calibrated 1 sigma).".format(jk["groups"], jk["by"]))
     else:
         out = mce.evidence()
     _save_marginals(args, [args.root_name], [getattr(mce, "info", None)])
+    _save_contours(args, [args.root_name], [getattr(mce, "info", None)])
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
     print("")
     return out

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import information as _information
 from . import summary as _summary
+from . import contours as _contours
 from . import marginals as _marginals
 from . import covariance as _covariance
 from .chains import MCSamples, rank0_draw
@@ -214,7 +215,10 @@ class MCEvidence(object):
         parameters in ``info["covariance"]`` and in ``self.param_cov`` (covariance.py; docs/design/tension.md) -- and ``marginals`` -- None,
         True, up to 7 probabilities or dict(probs, grid, scale): ``evidence()`` then also stores the 1-D marginal density of each of the
         first ``ndim`` parameters on a grid, its mode and its highest-posterior-density regions in ``info["marginals"]`` and in
-        ``self.param_marginals`` (marginals.py; docs/design/marginals.md).
+        ``self.param_marginals`` (marginals.py; docs/design/marginals.md) -- and ``contours`` -- None, True, up to 7 probabilities or
+        dict(probs, grid, scale, params): ``evidence()`` then also stores the 2-D joint density of every pair of the chosen parameters
+        (default: all of the first ``ndim``, at most 32) on a grid, its mode and the levels and regions of the probabilities in
+        ``info["contours"]`` and in ``self.param_contours`` (contours.py; docs/design/contours.md).
 
         method      chain root name / file name(s), or list/tuple/dict of chain arrays
                     (columns: weight, -lnL, parameters...)
@@ -248,6 +252,11 @@ class MCEvidence(object):
         self.marginals_spec = gdkwargs.pop("marginals", None)
         self.param_marginals = None
         _marginals.refuse(self.marginals_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
+        # the 2-D joint densities, modes and credible levels of the parameter pairs with every evidence() call
+        # (docs/design/contours.md): None (off: nothing changes), True, the probabilities, or a dict of probs, grid, scale and params
+        self.contours_spec = gdkwargs.pop("contours", None)
+        self.param_contours = None
+        _contours.refuse(self.contours_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
         # the weighted mean and covariance matrix of the parameters with every evidence() call (docs/design/tension.md): None (off:
         # nothing changes) or True; consumed here for the same reason
         self.covariance = gdkwargs.pop("covariance", None)
@@ -525,6 +534,26 @@ class MCEvidence(object):
             blk = _marginals.measure(a, x, *sp)
         self.param_marginals = self.info["marginals"] = _marginals.build(blk, sp, _summary.param_names(self.fname, self.ndim))
 
+    def _fill_contours(self):
+        """``info["contours"]`` of this call (the constructor's ``contours`` keyword; unset: nothing happens): the rule of contours.py on
+        s1's weights and its raw first ``ndim`` columns -- by ``mce_param_contours_f64`` where the HIP backend is in use, otherwise in
+        NumPy; under a process group every rank computes its own, no collective"""
+        if not _contours.wanted(self.contours_spec):
+            return
+        _contours.refuse(self.contours_spec, brange=self.brange, nbatch=self.nbatch)
+        names = _summary.param_names(self.fname, self.ndim)
+        sp = _contours.spec(self.contours_spec, ndim=self.ndim, names=names)
+        probs, grid, scale, cols = sp
+        samples, _, _ = self.gd.arrays("s1")
+        a, x = self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim]
+        if getattr(self.backend, "name", None) == "hip":
+            import torch
+            devs = getattr(self.backend, "devices", None)
+            blk = _contours.measure_native(a, x, cols, probs, grid, scale, device=devs[0] if devs else (torch.cuda.current_device() if torch.cuda.is_available() else 0))
+        else:
+            blk = _contours.measure(a, x, cols, probs, grid, scale)
+        self.param_contours = self.info["contours"] = _contours.build(blk, sp, names)
+
     def _fill_covariance(self):
         """``info["covariance"]`` of this call (the constructor's ``covariance`` keyword; unset: nothing happens): the rule of
         covariance.py on s1's weights and its raw first ``ndim`` columns, on the host -- under a process group every rank computes its
@@ -540,6 +569,7 @@ class MCEvidence(object):
         self._fill_information(MLE, pos_lnp)
         self._fill_summary(pos_lnp)
         self._fill_marginals()
+        self._fill_contours()
         self._fill_covariance()
         if verbose > 0 and "information" in self.info and _information.wanted(self.information):
             for line in _information.lines(self.info["information"]):
@@ -549,6 +579,9 @@ class MCEvidence(object):
                 self.logger.info(line)
         if verbose > 0 and "marginals" in self.info and _marginals.wanted(self.marginals_spec):
             for line in _marginals.lines(self.info["marginals"]):
+                self.logger.info(line)
+        if verbose > 0 and "contours" in self.info and _contours.wanted(self.contours_spec):
+            for line in _contours.lines(self.info["contours"]):
                 self.logger.info(line)
         if verbose > 0:
             for k in range(1, self.kmax):

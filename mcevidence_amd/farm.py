@@ -22,6 +22,7 @@ import numpy as np
 from . import information as _information
 from . import resident as _res
 from . import summary as _summary
+from . import contours as _contours
 from . import marginals as _marginals
 from . import covariance as _covariance
 
@@ -231,7 +232,7 @@ class _Root(object):
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
                              require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto",
-                             information=None, jackknife=None, summary=None, covariance=None, marginals=None):
+                             information=None, jackknife=None, summary=None, covariance=None, marginals=None, contours=None):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -262,6 +263,8 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     roots that ask, thinned and unthinned alike, before the feed.  ``marginals`` (one value or one per root, by ``summary``'s rule; a dict is
     one value): the 1-D marginal densities, modes and HPD regions of every such root's first ``ndim`` parameters in ``info["marginals"]`` --
     ONE ``mce_param_marginals_dev`` call per wave and per distinct (probs, grid, scale) over all its ready roots that ask, before the feed.
+    ``contours`` (by the same rule): the 2-D joint densities, modes and credible levels of the pairs of every such root's chosen parameters
+    in ``info["contours"]`` -- ONE ``mce_param_contours_dev`` call per wave and per distinct (probs, grid, scale, columns), at the same place.
     Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
@@ -285,6 +288,10 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     for v in mars:
         _marginals.spec(v)
     mar_kw = [{"marginals": v} if _marginals.wanted(v) else {} for v in mars]
+    cons = _per_root_marginals(contours, n)
+    for v in cons:
+        _contours.spec(v)
+    con_kw = [{"contours": v} if _contours.wanted(v) else {} for v in cons]
     covs = _per_root(covariance, n, "covariance")
     for v in covs:
         _covariance.spec(v)
@@ -293,7 +300,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **sum_kw[i], **mar_kw[i], **cov_kw[i], **extra)
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **sum_kw[i], **mar_kw[i], **con_kw[i], **cov_kw[i], **extra)
                 for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
@@ -319,7 +326,8 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
         if reason == _res.RESIDENT:
             try:
                 reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i],
-                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i], covariance=covs[i], marginals=mars[i])
+                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i], covariance=covs[i], marginals=mars[i],
+                                   contours=cons[i])
             except ValueError as e:                # (thin_corr together with thinlen; a converge or jackknife value no route takes)
                 fail(i, e)
                 continue
@@ -487,6 +495,21 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                     mblks.update(zip((r.index for r in masked),
                                      _res.marginals_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in masked],
                                                                 msp, device, stream.cuda_stream)))
+                # contours: likewise, one call per distinct (probs, grid, scale, columns); a root whose ``params`` do not fit its own
+                # parameters fails alone, with the ValueError of ``contours.spec``
+                conblks, cspecs = {}, {}
+                for r in [r for r in ready if _contours.wanted(cons[r.index])]:
+                    try:
+                        cspecs[r.index] = _contours.spec(cons[r.index], ndim=r.problem[6],
+                                                         names=_summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
+                    except ValueError as e:
+                        fail(r.index, e)
+                ready = [r for r in ready if not (_contours.wanted(cons[r.index]) and r.index not in cspecs)]
+                for csp in sorted(set(cspecs.values())):
+                    cwho = [r for r in ready if cspecs.get(r.index) == csp]
+                    conblks.update(zip((r.index for r in cwho),
+                                       _res.contours_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in cwho],
+                                                                 csp, device, stream.cuda_stream)))
                 # covariance: the ready roots that ask for it in one call, while the gathered rows are raw
                 casked = [r for r in ready if _covariance.wanted(covs[r.index])]
                 cblks = dict(zip((r.index for r in casked),
@@ -534,6 +557,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                         if r.index in mblks:
                             inf["marginals"] = _marginals.build(mblks[r.index], _marginals.spec(mars[r.index]),
                                                                 _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
+                        if r.index in conblks:
+                            inf["contours"] = _contours.build(conblks[r.index], cspecs[r.index],
+                                                              _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
                         if r.index in cblks:
                             inf["covariance"] = _covariance.build(cblks[r.index],
                                                                   _covariance.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
@@ -570,6 +596,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             kw.update(jack_kw[i])
             kw.update(sum_kw[i])
             kw.update(mar_kw[i])
+            kw.update(con_kw[i])
             kw.update(cov_kw[i])
             if covtype != "all":
                 kw["covtype"] = covtype

@@ -25,6 +25,7 @@ import numpy as np
 from . import chains as _chains
 from . import information as _information
 from . import summary as _summary
+from . import contours as _contours
 from . import marginals as _marginals
 from . import covariance as _covariance
 
@@ -71,7 +72,7 @@ class ResidentDecline(Exception):
 
 def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all", split=False, ndim=None, nparam=None,
          distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None, converge=None, converge_by="auto", jackknife=None, nchains=None,
-         summary=None, covariance=None, marginals=None):
+         summary=None, covariance=None, marginals=None, contours=None):
     """``"resident"`` or the reason why the route declines.  A pure function of the call's keywords and of what is known
     about the data at the time (``ncols``: the files' column counts, ``nrows``: rows left after burn-in / thinning,
     ``nparam``: parameter columns; None: not known yet).  ``thin_corr`` (thinning by the measured autocorrelation length) is resident
@@ -81,9 +82,11 @@ def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all"
     work for an auto evidence; with a split it declines to the host route, which whitens s1 and s2 there; a number of groups or a
     ``by`` it cannot take is the ValueError every route raises.  ``summary`` (the posterior summary of the parameters) is resident work
     and declines nothing; a value it cannot take is the ValueError every route raises.  ``covariance`` (the weighted mean and covariance
-    matrix of the parameters) is resident work too: it is validated and declines nothing; so is ``marginals`` (the 1-D marginal densities)."""
+    matrix of the parameters) is resident work too: it is validated and declines nothing; so is ``marginals`` (the 1-D marginal densities), and so is
+    ``contours`` (the 2-D joint densities of the parameter pairs)."""
     _summary.spec(summary)
     _marginals.spec(marginals)
+    _contours.spec(contours)
     _covariance.spec(covariance)
     if not ischain:
         return REASONS["ischain"]
@@ -237,6 +240,18 @@ def summary_measure_dev(systems, q, device, stream, pass_elems=0):
     return [_summary.from_block(b, s[3], len(q)) for b, s in zip(blocks, systems)]
 
 
+def contours_measure_dev(systems, spec, device, stream):
+    """ONE ``mce_param_contours_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
+    columns, device address of w)] and ``spec`` = (probs, grid, scale, cols) -> one ``contours.measure`` dict per system"""
+    import torch
+    from . import _capi
+    probs, grid, scale, cols = spec
+    wsb = _capi.param_contours_workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(cols), len(probs), grid)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
+    blocks = _capi.param_contours_dev(systems, cols, probs, grid, scale, ws.data_ptr(), wsb, stream)
+    return [_contours.from_block(b, len(cols), len(probs), grid) for b in blocks]
+
+
 def marginals_measure_dev(systems, spec, device, stream):
     """ONE ``mce_param_marginals_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
     columns, device address of w)] and ``spec`` = (probs, grid, scale) -> one ``marginals.measure`` dict per system"""
@@ -366,6 +381,7 @@ class ResidentChains(object):
         self.information = None                            # (what the last evidence(information=True) found)
         self.summary = None                                # (what the last evidence(summary=..) found)
         self.marginals = None                              # (what the last evidence(marginals=..) found)
+        self.contours = None                               # (what the last evidence(contours=..) found)
         self.covariance = None                             # (what the last evidence(covariance=..) found)
         self.names_root = None                             # (the root whose .paramnames file names the parameters, where there is one)
         self.jackknife = None                              # (what the last evidence(jackknife=...) found,
@@ -593,7 +609,8 @@ class ResidentChains(object):
 
     # -- the estimator ---------------------------------------------------------------------------------------------------
     def evidence(self, kmax=5, ndim=None, priorvolume=1, covtype="all", pos_lnp=False, split=False, s1frac=0.5, split_rows=None,
-                 info=False, backend=None, information=None, jackknife=None, summary=None, covariance=None, marginals=None):
+                 info=False, backend=None, information=None, jackknife=None, summary=None, covariance=None, marginals=None,
+                 contours=None):
         """ln E as ``MCEvidence(...).evidence(...)`` returns it (``MLE[1:]``, and the info dict if ``info=True``; it
         carries ``info["route"] = "resident"``).  ``split=True``: the reference's random split, drawn on the host with the
         call ``MCSamples.chain_split`` makes (same RNG consumption); ``split_rows=(s1, s2)``: ``set_split``.
@@ -609,7 +626,10 @@ class ResidentChains(object):
         ``covariance`` (None or True): the weighted mean and covariance matrix of the first ``ndim`` parameters in ``info["covariance"]``,
         from one ``mce_param_cov_dev`` call on the gathered rows and weights, made at the same place for the same reason.
         ``marginals`` (None, True, probabilities or dict(probs, grid, scale)): the 1-D marginal densities, modes and HPD regions of the
-        first ``ndim`` parameters in ``info["marginals"]`` (and ``self.marginals``), from one ``mce_param_marginals_dev`` call there too."""
+        first ``ndim`` parameters in ``info["marginals"]`` (and ``self.marginals``), from one ``mce_param_marginals_dev`` call there too.
+        ``contours`` (None, True, probabilities or dict(probs, grid, scale, params)): the 2-D joint densities, modes and credible levels
+        of the pairs of the chosen parameters in ``info["contours"]`` (and ``self.contours``), from one ``mce_param_contours_dev`` call
+        at the same place."""
         from . import _capi
         from .evidence import HipBackend
         backend = backend or HipBackend()
@@ -624,6 +644,8 @@ class ResidentChains(object):
         probs = _summary.spec(summary)
         want_cov = _covariance.spec(covariance) is not None
         mspec = _marginals.spec(marginals)
+        cnames = _summary.param_names(self.names_root, nd) if _contours.wanted(contours) else None
+        cspec = _contours.spec(contours, ndim=nd, names=cnames)
         torch = self._torch
         ms = self.stats["ms"]
         with torch.cuda.device(self.device):
@@ -659,6 +681,11 @@ class ResidentChains(object):
                 t0 = time.perf_counter()
                 mblk, = marginals_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())], mspec, self.device, self._stream())
                 ms["marginals"] = _ms(t0)
+            conblk = None
+            if cspec is not None:
+                t0 = time.perf_counter()
+                conblk, = contours_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())], cspec, self.device, self._stream())
+                ms["contours"] = _ms(t0)
             cblk = None
             if want_cov:
                 t0 = time.perf_counter()
@@ -686,6 +713,7 @@ class ResidentChains(object):
         self.information = None if mom is None else _information.build(mom, logLmax, out)
         self.summary = None if sblk is None else _summary.build(sblk, probs, logLmax, _summary.param_names(self.names_root, nd))
         self.marginals = None if mblk is None else _marginals.build(mblk, mspec, _summary.param_names(self.names_root, nd))
+        self.contours = None if conblk is None else _contours.build(conblk, cspec, cnames)
         self.covariance = None if cblk is None else _covariance.build(cblk, _covariance.param_names(self.names_root, nd))
         self.jackknife_block = jblock
         self.jackknife = None if jrun is None else jack_result(jrun, jblock, jspec, SumW, logLmax, n1, kmax, math.log(priorvolume))
@@ -706,13 +734,15 @@ class ResidentChains(object):
             inf["summary"] = self.summary
         if self.marginals is not None:
             inf["marginals"] = self.marginals
+        if self.contours is not None:
+            inf["contours"] = self.contours
         if self.covariance is not None:
             inf["covariance"] = self.covariance
         return out, inf
 
 
 def log_information(inf):
-    """the information lines, then the summary lines, then the marginals lines, before the ln(B) lines"""
+    """the information lines, then the summary lines, then the marginals lines, then the contours lines, before the ln(B) lines"""
     if (inf or {}).get("information"):
         for line in _information.lines(inf["information"]):
             logger.info(line)
@@ -721,6 +751,9 @@ def log_information(inf):
             logger.info(line)
     if (inf or {}).get("marginals"):
         for line in _marginals.lines(inf["marginals"]):
+            logger.info(line)
+    if (inf or {}).get("contours"):
+        for line in _contours.lines(inf["contours"]):
             logger.info(line)
 
 
@@ -745,6 +778,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     _information.refuse(ctor.get("information"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _summary.refuse(ctor.get("summary"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _marginals.refuse(ctor.get("marginals"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
+    _contours.refuse(ctor.get("contours"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _covariance.refuse(ctor.get("covariance"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     reason = RESIDENT if _is_file_root(root) else REASONS["not_files"]
     if reason == RESIDENT:
@@ -752,7 +786,8 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
                       verbose=max(ctor.get("verbose", 1), 2 if ctor.get("debug") else 0), covtype=covtype, split=split, ndim=None,
                       distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"),
                       converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"), jackknife=ctor.get("jackknife"),
-                      summary=ctor.get("summary"), covariance=ctor.get("covariance"), marginals=ctor.get("marginals"))
+                      summary=ctor.get("summary"), covariance=ctor.get("covariance"), marginals=ctor.get("marginals"),
+                      contours=ctor.get("contours"))
     if reason == RESIDENT:
         level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
         if not logging.getLogger().handlers:
@@ -770,7 +805,8 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
             got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,
                               backend=ctor.get("backend"), information=ctor.get("information"), jackknife=ctor.get("jackknife"),
-                              summary=ctor.get("summary"), covariance=ctor.get("covariance"), marginals=ctor.get("marginals"))
+                              summary=ctor.get("summary"), covariance=ctor.get("covariance"), marginals=ctor.get("marginals"),
+                              contours=ctor.get("contours"))
             mle, inf = got
             if ctor.get("verbose", 1) > 0:
                 log_information(inf)

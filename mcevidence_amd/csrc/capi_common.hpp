@@ -57,6 +57,8 @@ std::atomic<int> g_prune_mode{0};
 //   MCE_RSPLIT=n                 reference splits of the exhaustive sweep (the model's choice)
 //   MCE_TAIL_SPLIT=0             keep a search with a nearly empty last round of workgroups in one launch
 //   MCE_WIDE=0                   exhaustive one-k-step sweep: two query tiles per wave also where four would be taken (A/B)
+//   MCE_PANEL_QT=2|4             symmetric sweep on the panel kernel: query tiles per wave (the plan's choice by block count; 4 only
+//                                where the shape has it: one GPU, one pass, no chains, one or two k-steps)
 //   MCE_PANEL_DEBUG=bits         knn_panel.hpp test hooks (8: every candidate through the redo list, 16: waves give up waiting)
 //   MCE_PRUNE_HEAVY="<waves>,<S>"|auto|0   pruned walk over one set: the first waves served by S workgroups each (off)
 //   MCE_PRUNE_LISTS=long         pruned walk, K <= 10: the full-length list kernel instead of the short-list one (A/B)
@@ -74,7 +76,7 @@ std::atomic<int> g_prune_mode{0};
 struct Tuning {
     bool sym_kernel_f16 = false, tail_split = true, prune_prof = false, wide = true;
     int spin_limit = 1 << 21, sym_bucket = 0, sym_panel = 0, sym_seed_rows = 0, sym_seed_share = 2, sym_seed_mode = -1;
-    int f16_seed_rows = -1, f16_seed_share = -1, f16_seed_tg = -1, rsplit = 0, panel_debug = 0, sym_chains = 0;
+    int f16_seed_rows = -1, f16_seed_share = -1, f16_seed_tg = -1, rsplit = 0, panel_debug = 0, sym_chains = 0, panel_qt = 0;
     size_t feed_wave_bytes = 0;
 };
 Tuning read_tuning()
@@ -97,6 +99,7 @@ Tuning read_tuning()
     t.tail_split = num("MCE_TAIL_SPLIT", 1) != 0;
     t.wide = num("MCE_WIDE", 1) != 0;
     t.panel_debug = num("MCE_PANEL_DEBUG", 0);
+    t.panel_qt = num("MCE_PANEL_QT", 0);
     t.prune_prof = getenv("MCE_PRUNE_PROF") != nullptr;
     if ((e = getenv("MCE_FEED_WAVE_BYTES"))) t.feed_wave_bytes = (size_t)std::strtoull(e, nullptr, 10);
     return t;

@@ -27,6 +27,11 @@ constexpr int kPruneHeavyMinBlocks = 64, kPruneHeavyCount = 700, kPruneHeavyMaxS
 constexpr double kPruneHeavyFullRounds = 10.0;
 constexpr int kPruneHeavySplit = 4, kPruneHeavyMaxSplit = 8;
 constexpr int kPruneWaveQueries = mce::kHQT * 32;     // list columns per workgroup of the walk
+// plan blocks (512 rows) from which the symmetric sweep takes its four-tile form (knn_panel.hpp, QT = 4; MCE_PANEL_QT overrides).  Its
+// units are twice as long, so smaller sets pay in tail.  Same box, parent | QT = 4, five alternations of 20 steps, d = 27, kmax = 10, ms
+// per step (mean +- s.d.): 147 k rows 2.45 | 3.68, 262 k 4.06 | 5.54, 524 k 12.45 +- 0.02 | 12.06 +- 0.22 (no win by three s.d.),
+// 1 M 37.87 +- 0.13 | 36.02 +- 0.56 (profiles/r07_wide/ab.txt): from the 1954 blocks of a million rows.
+constexpr int kPanelWideMinBlocks = 1954;
 constexpr int kWideMinBlocks = 480;                    // query blocks from which the exhaustive one-k-step sweep takes its wide form (make_plan):
                                                        // ~one full round of the wider workgroups (two ranks' and four ranks' shards of C4: 977, 489 blocks)
 // side lists for split waves are part of a plan only when the split can happen (44 % of the list arrays: ~630 MB at C5)
@@ -61,6 +66,7 @@ struct Plan {
     int ksel = 0;                             // fp64 sweep: entries kept per list -- K + kRefineMargin (capped at MCE_MAX_K): the lists are chosen on
                                               // GEMM-form keys, the final K among them on EXACT distances (reduce_kernels.hpp, REFINE); 0: K
     bool twopass = false;                     // fp16 filter, 16 < K <= 32: two sweeps of 16-entry lists (knn_f16.hpp, LOWER)
+    bool panel_wide_ok = false;               // the symmetric sweep may run four query tiles per wave (knn_panel.hpp, QT = 4): it has the kernel, rows fit 24 bits
     bool wide_ok = false;                     // the exhaustive sweep may run four query tiles per wave (knn_f16.hpp, QTT = 4): nqblk is even
     bool prune = false;                       // fp16 filter walking k-d ordered chunk lists (prune.hpp)
     bool kd_ready = false;                    // ... whose k-d order is in the workspace already (mce_prune_part_prepare_dev on every rank + the all-reduce
@@ -276,10 +282,14 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
     // agree; which sweep runs (pruned walk, symmetric, exhaustive) is settled later -- only the exhaustive one has a wide form.
     p.wide_ok = f16 && !p.twopass && p.KST == 1 && p.vh->launch_wide && p.nqblk >= kWideMinBlocks && nr <= ((int64_t)1 << 25) && read_tuning().wide;
     if (p.wide_ok && (p.nqblk & 1)) p.nqblk += 1;
+    // The symmetric sweep's four-tile form (knn_panel.hpp, QT = 4) serves TWO query blocks per workgroup as well, but takes an odd
+    // block count as it is (the last workgroup's second half idles): the layout is the same whatever MCE_PANEL_QT says.
+    const bool panel_wide_shape = f16 && !p.twopass && nq == nr && p.vh->launch_panel_wide && p.vh->launch_sym && p.nqblk >= 2;
     p.nq_pad = (int64_t)p.nqblk * qpb;
     const int64_t rows_per_chunk = (int64_t)p.CT * rows_per_tile;
     p.nchunk = (nr + rows_per_chunk - 1) / rows_per_chunk;
     p.nrow_pad = p.nchunk * rows_per_chunk;
+    p.panel_wide_ok = panel_wide_shape && p.nrow_pad <= ((int64_t)1 << (mce::kHSymRowBits - 1));      // (queue words: 7 query-local bits, the row flag, 24 bits of row)
 
     if (f16 && !p.twopass && p.KST == 1 && d <= mce::kPruneMaxDim && p.vh->launch_prune && nq > 0 &&
         p.nrow_pad <= ((int64_t)1 << mce::kHRelBits) && (int64_t)p.nqblk * p.nchunk <= mce::kPruneMaxPairs) {

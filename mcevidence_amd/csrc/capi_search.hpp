@@ -370,9 +370,11 @@ int sym_units_and_flops(const Plan& p, const mce::PanelGeom& g, bool panel_kerne
 {
     int units = mce::sym_unit_count(p.nqblk, mce::kHWaves * mce::kHQT, panel * p.CT, (int)((nr + 31) / 32) + (int)(((nr + 31) / 32) & 1));
     double tiles = 0.0;
+    double qtiles = 16.0;       // query tiles a unit multiplies every reference tile with
     if (panel_kernel) {
         units = mce::panel_unit_count(g);
-        // executed MFMA flops: every unit's tiles x 16 query tiles x (32 x 32 x 16 KST) multiply-adds -- a figure for
+        qtiles = g.tpb;         // (the geometry actually launched: 32 with four query tiles per wave)
+        // executed MFMA flops: every unit's tiles x 16 | 32 query tiles x (32 x 32 x 16 KST) multiply-adds -- a figure for
         // mce_last_search_stats(), counted only while profiling is on (the loop is O(units x panels): seconds of host
         // time per search near the row limit)
         for (int u = 0; g_prof_on && u < units; ++u) {
@@ -385,7 +387,7 @@ int sym_units_and_flops(const Plan& p, const mce::PanelGeom& g, bool panel_kerne
         const double tpb = mce::kHWaves * mce::kHQT, T = (double)((nr + 31) / 32);
         for (int b = 0; b < p.nqblk; ++b) tiles += std::min(tpb * (b + 1), T);
     }
-    g_last_flops_main = tiles * 16.0 * 1024.0 * 32.0 * p.KST;        // (a two-pass search: the first pass's sweep, which the event bracket times)
+    g_last_flops_main = tiles * qtiles * 1024.0 * 32.0 * p.KST;        // (a two-pass search: the first pass's sweep, which the event bracket times)
     return units;
 }
 
@@ -446,6 +448,11 @@ int Search::symmetric()
         }
     }
     const bool unit_table = apo || geom.nsplit > 1;
+    // four query tiles per wave (knn_panel.hpp, QT = 4): one GPU, one pass, units from the geometry; a workgroup then serves two of
+    // the plan's blocks -- the geometry counts 1024-row blocks, everything else here stays keyed by the plan's
+    const bool panel_wide = panel_kernel && p.panel_wide_ok && p.nparts == 1 && !p.twopass && !unit_table &&
+                            (tun.panel_qt == 4 || (tun.panel_qt != 2 && p.nqblk >= kPanelWideMinBlocks));
+    if (panel_wide) { geom.tpb = 2 * mce::kHWaves * mce::kHQT; geom.qb_lo = 0; geom.qb_hi = (p.nqblk + 1) / 2; }
     // 16 < K <= 32 (round 5): TWO symmetric passes over 16-entry lists, as the exhaustive sweep does it (knn_f16.hpp, LOWER) --
     // the first finds every row's 16 nearest (lists A), the second the next K - 16 beyond them (lists B: knn_panel.hpp,
     // LOWER); the merge takes the K best of A and B.  The second pass needs bounds on the K-th distance: a prepass
@@ -497,7 +504,7 @@ int Search::symmetric()
                 }
                 pa.units = tab;
             }
-            MCE_HIP((lower ? p.vh->launch_panel_lower : p.vh->launch_panel)(pa, st));
+            MCE_HIP((lower ? p.vh->launch_panel_lower : (panel_wide ? p.vh->launch_panel_wide : p.vh->launch_panel))(pa, st));
         } else {
             MCE_HIP(p.vh->launch_sym(a, st));
         }
@@ -516,7 +523,7 @@ int Search::symmetric()
     g_last_flops_all = g_last_flops_main + (double)(seed_used & 0xffff) * p.CT * (double)(qb_hi - qb_lo) * 16.0 * 1024.0 * 32.0 * p.KST;
     snprintf(g_last_kernel, sizeof(g_last_kernel), "%s symmetric%s%s%s grid=%d block=%d lds=%zu qt=%d ct=%d panel=%d seed=%dx%d/%d bucket=%d", p.vh->name, panel_kernel ? " panel-kernel" : "",
              p.twopass ? " two passes" : "", geom.blk_stride > 1 ? " pairs-once" : (geom.nsplit > 1 ? " chains" : ""), sym_units,
-             mce::kHThreads, panel_kernel ? p.vh->lds_bytes_panel : p.vh->lds_bytes_sym, p.QT, p.CT, a.sym.panel, seed_used & 0xffff, (seed_used >> 16) & 0xfff, (seed_used >> 28) & 3, p.sl.cap);
+             mce::kHThreads, panel_wide ? p.vh->lds_bytes_panel_wide : (panel_kernel ? p.vh->lds_bytes_panel : p.vh->lds_bytes_sym), panel_wide ? 2 * p.QT : p.QT, p.CT, a.sym.panel, seed_used & 0xffff, (seed_used >> 16) & 0xfff, (seed_used >> 28) & 3, p.sl.cap);
     return MCE_OK;
 }
 

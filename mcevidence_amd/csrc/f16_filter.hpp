@@ -221,11 +221,12 @@ __device__ __forceinline__ bool sym_slot_insert(PS slots, PT thr, PR rrow, PF rt
 // waiting; returns the accumulators NOT handled because the queue was full.
 // The gate's own first-level minima say which triples of accumulators hold something: 6 wave-wide compares, then 3 for each
 // triple that does (usually one) -- 9 instead of 16.
-template <bool ROWFLAG>
+// (ROWBIT: where the row flag sits -- the panel sweep's four-tile form keeps 7 query-local bits above a 24-bit row field)
+template <bool ROWFLAG, int ROWBIT = kHSymRowBits>
 __device__ __forceinline__ unsigned f16_event(const v16f& c, const float (&l1)[5], const unsigned lanew, const float g, const bool rowflag, const int jb0,
                                               const unsigned todo, const int qlimit, int* const wq, int& qcount)
 {
-    const unsigned wbase = (lanew + (unsigned)jb0) | (ROWFLAG && rowflag ? (1u << kHSymRowBits) : 0u);
+    const unsigned wbase = (lanew + (unsigned)jb0) | (ROWFLAG && rowflag ? (1u << ROWBIT) : 0u);
     unsigned rem = 0;
 #define MCE_HIT(R_, P_, S_)                                                                                               \
     if ((S_) != 0 && (todo & (1u << (R_)))) {                                                                             \

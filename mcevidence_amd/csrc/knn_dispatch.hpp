@@ -102,6 +102,8 @@ struct KnnF16Variant {
     knn_panel_launch_fn launch_panel_lower;
     knn_f16_launch_fn launch_sym_repair_lower;
     knn_f16_launch_fn launch_sym_pre32;
+    knn_panel_launch_fn launch_panel_wide;  // knn_panel_kernel<.., QT = 4>: four query tiles per wave, a workgroup = two query blocks (KST = 2), else null
+    size_t lds_bytes_panel_wide;
 };
 // ---- deep fp16-filter variants (knn_deep.hpp): 64 <= d <= 127, KST = 5, 6 or 8 sixteen-wide k-steps, K <= 16 ----
 struct DeepArgs;                   // knn_deep.hpp

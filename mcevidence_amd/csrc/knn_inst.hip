@@ -78,14 +78,14 @@ hipError_t launch_f16_variant(const KnnF16Args& a, hipStream_t st)
 #endif
 
 #if MCE_INST_F16 || MCE_INST_PANEL
-template <int KST, int KCAP, bool LOWER = false>
+template <int KST, int KCAP, bool LOWER = false, int QT = 2>
 hipError_t launch_panel_variant(const PanelArgs& a, hipStream_t st)
 #if MCE_INST_PANEL
 {
-    constexpr size_t LDS = panel_lds_bytes(KST);
+    constexpr size_t LDS = panel_lds_bytes(KST, QT);
     static_assert(LDS <= 160 * 1024, "LDS budget");
     static bool attr_set[kMaxDevices] = {};
-    auto kern = knn_panel_kernel<KST, KCAP, LOWER>;
+    auto kern = knn_panel_kernel<KST, KCAP, LOWER, QT>;
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev >= kMaxDevices || !attr_set[dev]) {
@@ -93,6 +93,7 @@ hipError_t launch_panel_variant(const PanelArgs& a, hipStream_t st)
         if (e != hipSuccess) return e;
         if (dev < kMaxDevices) attr_set[dev] = true;
     }
+    if (a.geom.tpb != 8 * QT) return hipErrorInvalidValue;       // (the geometry counts blocks of 8 waves x QT tiles)
     const int units = panel_unit_count(a.geom);
     if (units <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3((unsigned)units), dim3(kHThreads), LDS, st, a);
@@ -102,6 +103,8 @@ template hipError_t launch_panel_variant<1, MCE_KCAP>(const PanelArgs&, hipStrea
 template hipError_t launch_panel_variant<2, MCE_KCAP>(const PanelArgs&, hipStream_t);
 template hipError_t launch_panel_variant<3, MCE_KCAP>(const PanelArgs&, hipStream_t);
 template hipError_t launch_panel_variant<4, MCE_KCAP>(const PanelArgs&, hipStream_t);
+template hipError_t launch_panel_variant<1, MCE_KCAP, false, 4>(const PanelArgs&, hipStream_t);
+template hipError_t launch_panel_variant<2, MCE_KCAP, false, 4>(const PanelArgs&, hipStream_t);
 #if MCE_KCAP == 16
 template hipError_t launch_panel_variant<1, MCE_KCAP, true>(const PanelArgs&, hipStream_t);
 template hipError_t launch_panel_variant<2, MCE_KCAP, true>(const PanelArgs&, hipStream_t);
@@ -114,6 +117,8 @@ extern template hipError_t launch_panel_variant<1, MCE_KCAP>(const PanelArgs&, h
 extern template hipError_t launch_panel_variant<2, MCE_KCAP>(const PanelArgs&, hipStream_t);
 extern template hipError_t launch_panel_variant<3, MCE_KCAP>(const PanelArgs&, hipStream_t);
 extern template hipError_t launch_panel_variant<4, MCE_KCAP>(const PanelArgs&, hipStream_t);
+extern template hipError_t launch_panel_variant<1, MCE_KCAP, false, 4>(const PanelArgs&, hipStream_t);
+extern template hipError_t launch_panel_variant<2, MCE_KCAP, false, 4>(const PanelArgs&, hipStream_t);
 #if MCE_KCAP == 16
 extern template hipError_t launch_panel_variant<1, MCE_KCAP, true>(const PanelArgs&, hipStream_t);
 extern template hipError_t launch_panel_variant<2, MCE_KCAP, true>(const PanelArgs&, hipStream_t);
@@ -182,11 +187,13 @@ extern const KnnVariant MCE_CAT(g_knn_kcap, MCE_KCAP)[kMaxKS] = {
 #else
 #define MCE_F16_WIDE(KST) nullptr, 0
 #endif
+// the panel sweep with four query tiles per wave: one and two k-steps (with three and four the B fragments alone are 48 and 64 registers)
+#define MCE_PANEL_WIDE(KST) ((KST) <= 2 ? &launch_panel_variant<((KST) <= 2 ? (KST) : 2), MCE_KCAP, false, 4> : (knn_panel_launch_fn) nullptr), ((KST) <= 2 ? panel_lds_bytes(KST, 4) : 0)
 #define MCE_F16_VARIANT(KST, PRUNE_FN)                                                                   \
     {&launch_f16_variant<KST, MCE_KCAP, false>, PRUNE_FN, MCE_F16_LOWER(KST), &launch_f16_variant<KST, MCE_KCAP, false, false, 1>, \
      &launch_f16_variant<KST, MCE_KCAP, false, false, 2>, &launch_f16_variant<KST, MCE_KCAP, false, false, 3>, &launch_panel_variant<KST, MCE_KCAP>, panel_lds_bytes(KST), \
      f16_lds_bytes(KST, MCE_KCAP, true), KST, MCE_KCAP, f16_qt(MCE_KCAP), f16_chunk_tiles(KST), \
-     f16_lds_bytes(KST, MCE_KCAP), "knn_f16_kernel<KST=" #KST ",KCAP=" MCE_STR(MCE_KCAP) ">", MCE_F16_SHORT(KST), MCE_F16_WIDE(KST), MCE_F16_SYM_LOWER(KST)}
+     f16_lds_bytes(KST, MCE_KCAP), "knn_f16_kernel<KST=" #KST ",KCAP=" MCE_STR(MCE_KCAP) ">", MCE_F16_SHORT(KST), MCE_F16_WIDE(KST), MCE_F16_SYM_LOWER(KST), MCE_PANEL_WIDE(KST)}
 extern const KnnF16Variant MCE_CAT(g_knn_f16_kcap, MCE_KCAP)[kMaxKST] = {
     MCE_F16_VARIANT(1, (&launch_f16_variant<1, MCE_KCAP, true>)), MCE_F16_VARIANT(2, nullptr), MCE_F16_VARIANT(3, nullptr),
     MCE_F16_VARIANT(4, nullptr),
@@ -238,6 +245,8 @@ template __global__ void knn_panel_kernel<1, MCE_KCAP>(PanelArgs);
 template __global__ void knn_panel_kernel<2, MCE_KCAP>(PanelArgs);
 template __global__ void knn_panel_kernel<3, MCE_KCAP>(PanelArgs);
 template __global__ void knn_panel_kernel<4, MCE_KCAP>(PanelArgs);
+template __global__ void knn_panel_kernel<1, MCE_KCAP, false, 4>(PanelArgs);
+template __global__ void knn_panel_kernel<2, MCE_KCAP, false, 4>(PanelArgs);
 #if MCE_KCAP == 16
 template __global__ void knn_panel_kernel<1, MCE_KCAP, true>(PanelArgs);
 template __global__ void knn_panel_kernel<2, MCE_KCAP, true>(PanelArgs);

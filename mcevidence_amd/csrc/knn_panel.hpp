@@ -72,13 +72,16 @@ struct PanelArgs {
 // 32-row reference tiles per staged chunk (tile = KST KB): even, and a whole number of 16-byte vectors per thread
 __host__ __device__ constexpr int panel_chunk_tiles(int KST) { return MCE_PANEL_STAGE_KB / KST / 2 * 2; }
 constexpr int kPanelQueue = MCE_PANEL_QUEUE;
-__host__ __device__ constexpr size_t panel_lds_bytes(int KST)
+// candidate queue entries per wave.  Four query tiles per wave: heads, bounds and the redo list double, and the queue gives way
+// to stay within 160 KB -- 448 -> 384 entries (KST = 1: 158.1 KB, KST = 2: 155.1 KB)
+__host__ __device__ constexpr int panel_queue(int QT) { return QT == 4 ? (kPanelQueue < 384 ? kPanelQueue : 384) : kPanelQueue; }
+__host__ __device__ constexpr size_t panel_lds_bytes(int KST, int QT = kHQT)
 {
     return (size_t)2 * panel_chunk_tiles(KST) * KST * 1024           // staging
-           + (size_t)kHWaves * kPanelQueue * 16                        // queues: d2 (8) + packed (4) + next (4)
-           + (size_t)kHWaves * kHQT * 32 * 4 + 128                     // chain heads + votes
-           + (size_t)kHWaves * kHQT * 32 * 4                           // K-th bound per query as of the last drain (float, rounded up)
-           + (size_t)kHWaves * panel_chunk_tiles(KST) * kHQT * 4;      // redo list
+           + (size_t)kHWaves * panel_queue(QT) * 16                    // queues: d2 (8) + packed (4) + next (4)
+           + (size_t)kHWaves * QT * 32 * 4 + 128                       // chain heads + votes
+           + (size_t)kHWaves * QT * 32 * 4                             // K-th bound per query as of the last drain (float, rounded up)
+           + (size_t)kHWaves * panel_chunk_tiles(KST) * QT * 4;        // redo list
 }
 
 // pointers read out of the argument block are generic to the compiler; these say what they are (global memory), so that
@@ -105,19 +108,30 @@ __device__ __forceinline__ float vmaxf(float a, float b)       // v_max_f32 with
 // row side (the same test with the roles exchanged, against j's first list) in phase R.  Thresholds, slots and published bounds
 // then speak of the (K - 16)-th entry beyond the cut, i.e. of the K-th neighbour; the prepass that seeds them bounds the K-th
 // distance (capi_search.hpp).  The first 16 still pass the fp16 gate and are evaluated again -- the price of lists that hold 16.
-template <int KST, int KCAP, bool LOWER = false>
+//
+// QT (round 7): 32-query tiles per wave.  2: a workgroup serves one 512-row block of the plan.  4: a wave owns 128 queries (lane l
+// the queries l and l + 64), a workgroup TWO plan blocks (geom.tpb = 32: qblk, qb_lo, qb_hi count 1024-row blocks), and every A
+// fragment read from LDS feeds eight MFMAs -- in two halves: the gate of the query tiles (0, 1) runs under the MFMAs of (2, 3) of
+// the same reference tile, that of (2, 3) under the next tile's (0, 1), so ONE reference tile is in flight and the accumulators
+// stay at 64 registers.  What the rest of the search keys by block -- buckets, bucket_flag, the repair launch, the merge -- stays
+// keyed by the plan's 512-row blocks (kPanelPlanRows).  Queue words: query-local (7 bits) << 25 | row flag << 24 | row (24 bits).
+constexpr int kPanelPlanRows = kHWaves * 64;
+template <int KST, int KCAP, bool LOWER = false, int QT = 2>
 __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_by_value)
 {
-    static_assert(kHQT == 2 && kHNL == 1, "8 waves x 2 query tiles, one list per owner lane");
-    constexpr int QT = 2;
-    constexpr int QPW = 64;                              // queries per wave
-    constexpr int QPB = kHWaves * QPW;                   // 512
+    static_assert(QT == 2 || QT == 4, "two or four query tiles per wave");
+    constexpr int NL = QT / 2;                           // queries a lane owns
+    constexpr int QPW = 32 * QT;                         // queries per wave
+    constexpr int QPB = kHWaves * QPW;                   // 512 | 1024
+    constexpr int PBW = QPB / kPanelPlanRows;            // plan blocks per workgroup
     constexpr int TPB = QPB / 32;
+    constexpr int RELB = QT == 4 ? 25 : kHRelBits;       // queue word: query-local << RELB | row flag << ROWB | row
+    constexpr int ROWB = RELB - 1;
     constexpr int CT = panel_chunk_tiles(KST);
     constexpr int CHUNK_BYTES = CT * KST * 1024;
     constexpr int VPT = CHUNK_BYTES / 16 / kHThreads;
     static_assert(CHUNK_BYTES % (16 * kHThreads) == 0 && CT % 2 == 0, "chunk geometry");
-    constexpr int QN = kPanelQueue;
+    constexpr int QN = panel_queue(QT);
     // The only explicit kernel argument is the struct, so it sits at offset 0 of the kernarg segment.  It is read through
     // this pointer, laundered before every cold use: the loads then happen THERE (scalar loads from constant memory)
     // instead of at kernel entry with the values held -- or spilled -- across the tile loop.
@@ -191,16 +205,41 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         }
     };
     const int64_t qwave0 = (int64_t)qblk * QPB + wave * QPW;     // first query of this wave
+    // QT = 4 with an ODD number of plan blocks: the launch's last workgroup has only its first plan block.  The waves of the missing one
+    // (wave-uniform: a plan block is four whole waves) stage chunks and keep the barriers like everybody, with gates that never
+    // pass, and touch no per-query or per-block memory: every such access below is guarded by wave_live or by q < nq (<= nq_pad).
+    const bool wave_live = PBW == 1 || qwave0 < MCE_ARGS()->nq_pad;
 
-    whead[lane] = -1;
+#pragma unroll
+    for (int nl = 0; nl < NL; ++nl) whead[nl * 64 + lane] = -1;
     if (tid < 3) wvote[tid] = 0;
 
-    // lane l OWNS wave-local query l: its sorted top-KCAP list lives here
-    double own_d[KCAP];
-    int own_i[KCAP];
+    // Lane l OWNS the wave-local queries l (and l + 64, QT = 4).  Their sorted top-KCAP lists live in MEMORY for the whole unit -- in part_d / part_i, where it
+    // travels from unit to unit anyway -- and is in registers only inside a drain (loaded before phase A, folded in phase B, stored
+    // after it): the tile loop needs G, cR and sthr, not the 3 KCAP registers of a list.  Two wave-uniform flags say what the
+    // memory copy is worth (docs/design/panel_kernel.md, "Lists out of registers"):
+    //   list_in_mem  the wave's lists in memory are this chain's: handed over by the previous unit, or stored by a drain of this one;
+    //                otherwise a drain starts from empty lists (a block's first unit before its first drain)
+    //   trusted      nobody else writes these lists while the unit runs.  A wave that gave up waiting, or whose block is flagged,
+    //                runs beside other units of its block: it NEVER stores (every drain of it starts from empty lists; the block
+    //                is searched again by the repair launch, which starts from empty lists and writes all of them), so that a
+    //                trusted wave of the same block never reads back anything but its own stores.
+    // (LMEM: only the four-tile form, which does not fit otherwise.  At QT = 2 the lists stay in registers from the prologue to the
+    //  epilogue, as before: with them in memory the flagship ran 37.80 +- 0.14 ms per step against 37.33 +- 0.07, same box, five
+    //  alternations -- the registers freed buy a two-tile loop nothing, and every drain pays the stores.)
+    constexpr bool LMEM = QT == 4;
+    bool list_in_mem = false, trusted = true;
+    double reg_d[NL][KCAP];
+    int reg_i[NL][KCAP];
+    if constexpr (!LMEM) {
 #pragma unroll
-    for (int k = 0; k < KCAP; ++k) { own_d[k] = INF; own_i[k] = -1; }
-    double seed_thr = INF;          // bound on the final K-th squared distance known from elsewhere (prepass, row side)
+        for (int k = 0; k < KCAP; ++k) { reg_d[0][k] = INF; reg_i[0][k] = -1; }
+    }
+    const int k_last = MCE_ARGS()->ksel - 1;
+    double list_kth[NL];            // the K-th entry of the list handed over (units after a block's first)
+    double seed_thr[NL];            // bound on the final K-th squared distance known from elsewhere (prepass, row side)
+#pragma unroll
+    for (int nl = 0; nl < NL; ++nl) { list_kth[nl] = INF; seed_thr[nl] = INF; }
 
     // A block's lists travel from one of its units to the next through the list arrays.  Units are dispatched in number
     // order, panel by panel, so the previous unit of this block started a whole panel's worth of units ago and the wait
@@ -228,24 +267,35 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             // A block in which some unit has given up is being searched by units that no longer run one after the other:
-            // two of them may write the lists at the same time, and what a later unit would load can hold the same row
-            // twice -- a K-th entry BELOW the true K-th distance, which would be published as a bound (and the repair launch
-            // starts from the published bounds).  Such a block is flagged already (the flag is set before the sweep of the
-            // unit that gave up, and this unit has seen all its predecessors finish): its units start from empty lists.
-            if (ok && gptr(a->sym.bucket_flag)[qblk] != 0) ok = false;
-            if (ok) {
-                const int64_t q = qwave0 + lane;
-                const int64_t np = a->nq_pad;
-                const auto pd = gptr(a->part_d) + list_off;
-                const auto pi = gptr(a->part_i) + list_off;
+            // what a later unit would load can be a mix of two units' stores and hold the same row twice -- a K-th entry
+            // BELOW the true K-th distance, which would be published as a bound (and the repair launch starts from the
+            // published bounds).  Such a block is flagged already (the flag is set before the sweep of the unit that gave
+            // up, and this unit has seen all its predecessors finish): its units start every drain from empty lists.
+            // (QT = 4: either plan block of the workgroup)
 #pragma unroll
-                for (int k = 0; k < KCAP; ++k) {
-                    own_d[k] = pd[(int64_t)k * np + q];
-                    own_i[k] = pi[(int64_t)k * np + q];
+            for (int h = 0; h < PBW; ++h)
+                if (ok && (PBW == 1 || (int64_t)(qblk * PBW + h) * kPanelPlanRows < a->nq_pad) && gptr(a->sym.bucket_flag)[qblk * PBW + h] != 0) ok = false;
+            // (the same address in every lane: wave-uniform, and said so -- the drain branches on it)
+            ok = __builtin_amdgcn_readfirstlane((int)ok) != 0;
+            if (ok) {
+                list_in_mem = true;
+                if constexpr (!LMEM) {
+                    const int64_t q = qwave0 + lane;
+                    const int64_t np = a->nq_pad;
+                    const auto pd = gptr(a->part_d) + list_off;
+                    const auto pi = gptr(a->part_i) + list_off;
+#pragma unroll
+                    for (int k = 0; k < KCAP; ++k) {
+                        reg_d[0][k] = pd[(int64_t)k * np + q];
+                        reg_i[0][k] = pi[(int64_t)k * np + q];
+                    }
                 }
-            } else if (lane == 0) {
+#pragma unroll
+                for (int nl = 0; nl < NL; ++nl) list_kth[nl] = (!LMEM || !wave_live) ? INF : (gptr(a->part_d) + list_off)[(int64_t)k_last * a->nq_pad + qwave0 + nl * 64 + lane];
+            } else {
+                trusted = false;
                 // (every WAVE waits on its own and may be the only one of its workgroup to give up: each flags the block)
-                gptr_w(a->sym.bucket_flag)[qblk] = 1;
+                if (lane < PBW && (PBW == 1 || (int64_t)(qblk * PBW + lane) * kPanelPlanRows < a->nq_pad)) gptr_w(a->sym.bucket_flag)[qblk * PBW + lane] = 1;
             }
         }
     }
@@ -253,8 +303,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
     // ---- B fragments (fp16 query rows) + per-query gate constants ---------------------------------------------------
     v8h b[QT][KST];
     float G[QT], cR[QT];
-    unsigned lanew[QT];             // queue word of the lane's query: query-local << kHRelBits | 4 (lane >> 5)
-    const int k_last = MCE_ARGS()->ksel - 1;
+    unsigned lanew[QT];             // queue word of the lane's query: query-local << RELB | 4 (lane >> 5)
     {
         const ArgsPtr a = MCE_ARGS();
         const auto Xh = gptr(a->Xh);
@@ -262,9 +311,11 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         for (int qt = 0; qt < QT; ++qt) {
             const int64_t q = qwave0 + qt * 32 + (lane & 31);
 #pragma unroll
-            for (int ks = 0; ks < KST; ++ks)
-                b[qt][ks] = *(const __attribute__((address_space(1))) v8h*)(Xh + q * (int64_t)(16 * KST) + 16 * ks + 8 * (lane >> 5));
-            lanew[qt] = ((unsigned)(qt * 32 + (lane & 31)) << kHRelBits) | (unsigned)(4 * (lane >> 5));
+            for (int ks = 0; ks < KST; ++ks) {
+                const v8h zero = {0, 0, 0, 0, 0, 0, 0, 0};
+                b[qt][ks] = wave_live ? *(const __attribute__((address_space(1))) v8h*)(Xh + q * (int64_t)(16 * KST) + 16 * ks + 8 * (lane >> 5)) : zero;
+            }
+            lanew[qt] = ((unsigned)(qt * 32 + (lane & 31)) << RELB) | (unsigned)(4 * (lane >> 5));
             cR[qt] = -__builtin_huge_valf();
             G[qt] = -__builtin_huge_valf();
         }
@@ -273,7 +324,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
     // a round trip per refresh): for the lane's two gated queries gq_a = e_x + max e_y (+ slack) and gq_c = eps - |x^|^2
     // (-inf: padding query), for the query the lane OWNS own_a = the same sum; and the launch's scale^2 and the row gate's
     // additive term.  See f16_filter.hpp for the bound.
-    double gq_a[QT], gq_c[QT], own_a = 0.0, s2c, rowc;
+    double gq_a[QT], gq_c[QT], own_a[NL], s2c, rowc;
     {
         const ArgsPtr a = MCE_ARGS();
         const auto params = gptr(a->params);
@@ -292,30 +343,40 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
                 gq_c[qt] = t.c;
             }
         }
-        {
-            const int64_t q = qwave0 + lane;
-            if (q < a->nq) own_a = f16_gate_a(qinfo[2 * q], p_ey, KST);
+#pragma unroll
+        for (int nl = 0; nl < NL; ++nl) {
+            const int64_t q = qwave0 + nl * 64 + lane;
+            own_a[nl] = 0.0;
+            if (q < a->nq) own_a[nl] = f16_gate_a(qinfo[2 * q], p_ey, KST);
         }
     }
     // gate of query (qt, lane & 31) from a bound `thr` on its K-th squared distance (input units)
     auto gate_of = [&](double thr, int qt) __attribute__((always_inline)) -> float { return f16_gate(thr, s2c, gq_a[qt], gq_c[qt]); };
     // row-side gate constant R of the OWNED query from the bound on its K-th squared distance
-    auto own_row_gate = [&](double thr) __attribute__((always_inline)) -> float { return f16_row_gate(thr, s2c, own_a, rowc); };
+    auto own_row_gate = [&](double thr, int nl) __attribute__((always_inline)) -> float { return f16_row_gate(thr, s2c, own_a[nl], rowc); };
     {
         const ArgsPtr a = MCE_ARGS();
-        const int64_t q = qwave0 + lane;
-        double t0 = INF;
-        if (sym_on) t0 = __longlong_as_double((long long)__hip_atomic_load(gptr(a->sym.thr) + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        else if (a->sym.thr) t0 = __longlong_as_double((long long)gptr(a->sym.thr)[q]);       // bounds of a prepass (plain array)
-        seed_thr = t0;
-        // (the list may already hold a tighter K-th: units after the first)
-        double tl = own_d[KCAP - 1];
+        double t0[NL];
 #pragma unroll
-        for (int k = 0; k < KCAP - 1; ++k) tl = (k == k_last) ? own_d[k] : tl;
-        t0 = fmin(t0, tl);
-        sthr[lane] = __double2float_ru(t0);
+        for (int nl = 0; nl < NL; ++nl) {
+            const int64_t q = qwave0 + nl * 64 + lane;
+            t0[nl] = INF;
+            if (!wave_live) t0[nl] = INF;
+            else if (sym_on) t0[nl] = __longlong_as_double((long long)__hip_atomic_load(gptr(a->sym.thr) + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            else if (a->sym.thr) t0[nl] = __longlong_as_double((long long)gptr(a->sym.thr)[q]);       // bounds of a prepass (plain array)
+            seed_thr[nl] = t0[nl];
+            // (the list may already hold a tighter K-th: units after the first)
+            if constexpr (!LMEM) {
+                double tl = reg_d[0][KCAP - 1];
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) G[qt] = gate_of(__shfl(t0, qt * 32 + (lane & 31), 64), qt);
+                for (int k = 0; k < KCAP - 1; ++k) tl = (k == k_last) ? reg_d[0][k] : tl;
+                list_kth[nl] = tl;
+            }
+            t0[nl] = fmin(t0[nl], list_kth[nl]);
+            sthr[nl * 64 + lane] = __double2float_ru(t0[nl]);
+        }
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) G[qt] = gate_of(__shfl(t0[qt / 2], (qt & 1) * 32 + (lane & 31), 64), qt);
         if (sym_on) {
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) cR[qt] = gq_c[qt] > -INF ? f16_round_up(gq_c[qt]) : -__builtin_huge_valf();
@@ -343,6 +404,34 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         const int self_exclude = a->self_exclude;
         const int64_t self_offset = a->self_offset;
         const auto rperm = gptr(a->rperm);
+        // the owner lane's list: its loads go out here and are consumed in phase B -- one L2 round trip under phases A and R.
+        // (Agent-scope loads: within a unit the lane reads back its own stores, which program order alone guarantees; a plain
+        //  load, though, the compiler may satisfy from the registers of the last store, i.e. keep the list live across the tile loop.)
+        double loc_d[NL][KCAP];
+        int loc_i[NL][KCAP];
+        double (&own_d)[NL][KCAP] = *(LMEM ? &loc_d : &reg_d);
+        int (&own_i)[NL][KCAP] = *(LMEM ? &loc_i : &reg_i);
+        int chain_;
+        int64_t list_off;
+        chain_of(chain_, list_off);
+        const int64_t own_o = list_off + qwave0 + lane;
+        const int64_t npad = a->nq_pad;
+        auto list_load = [&](const int nl) __attribute__((always_inline)) {
+            if constexpr (!LMEM) return;
+            if (list_in_mem && wave_live) {
+                const auto pd = (const __attribute__((address_space(1))) unsigned long long*)(a->part_d) + own_o + nl * 64;
+                const auto pi = gptr(a->part_i) + own_o + nl * 64;
+#pragma unroll
+                for (int k = 0; k < KCAP; ++k) {
+                    own_d[nl][k] = __longlong_as_double((long long)__hip_atomic_load(pd + (int64_t)k * npad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                    own_i[nl][k] = __hip_atomic_load(pi + (int64_t)k * npad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < KCAP; ++k) { own_d[nl][k] = INF; own_i[nl][k] = -1; }
+            }
+        };
+        list_load(0);
         {
             // phase A: 8 lanes share one queued pair and read the two rows in 64-byte segments; all loads of a group of
             // NPASS * 8 pairs are issued before the first use (the gather is latency-bound)
@@ -362,8 +451,8 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
                     const bool valid = e < qcount;
                     if (valid) {
                         const unsigned ent = (unsigned)wq[e];
-                        ql = (int)(ent >> kHRelBits);
-                        j = (int)(ent & ((1u << kHSymRowBits) - 1u));
+                        ql = (int)(ent >> RELB);
+                        j = (int)(ent & ((1u << ROWB) - 1u));
                     }
                     qlp[u] = ql;
                     const int64_t q = qwave0 + ql;
@@ -401,7 +490,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
                                 const int64_t o = (int64_t)(KCAP - 1) * a->nq_pad + qwave0 + qlp[u];
                                 const double ld = gptr(a->lo_d)[o];
                                 const int li = gptr(a->lo_i)[o];
-                                const int jr = (int)((unsigned)wq[ep[u]] & ((1u << kHSymRowBits) - 1u));
+                                const int jr = (int)((unsigned)wq[ep[u]] & ((1u << ROWB) - 1u));
                                 const int jc = rperm ? rperm[jr] : jr;
                                 col = a0 > ld || (a0 == ld && jc > li);
                             }
@@ -435,15 +524,15 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
                 const int e = e0 + lane;
                 const bool valid = e < qcount;
                 const unsigned ent = valid ? (unsigned)wq[e] : 0u;
-                const int ql = (int)(ent >> kHRelBits);
-                const int j = (int)(ent & ((1u << kHSymRowBits) - 1u));
-                const bool rowflag = (ent >> kHSymRowBits) & 1u;        // the lane passed the row gate on this tile: only then can the pair matter to row j
+                const int ql = (int)(ent >> RELB);
+                const int j = (int)(ent & ((1u << ROWB) - 1u));
+                const bool rowflag = (ent >> ROWB) & 1u;        // the lane passed the row gate on this tile: only then can the pair matter to row j
                 const double d2 = valid ? wqd[e] : -1.0;
                 const bool ok = valid && d2 >= 0.0;
                 const int oj = ok ? (rperm ? rperm[j] : j) : -1;
                 bool rs = ok && rowflag;          // (the row flag is raised only on tiles that carry the row-side gate)
                 if (rs) {
-                    const int jb = j / QPB;
+                    const int jb = j / kPanelPlanRows;          // (buckets and flags: the plan's 512-row blocks, whatever QT)
                     rs = d2 <= __longlong_as_double((long long)__hip_atomic_load(sp_thr + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                     if constexpr (LOWER) {
                         if (rs) {       // beyond the 16th entry of row j's first list?  (what j is offered is the QUERY's row)
@@ -475,59 +564,78 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         const long long t_dR = clock64();
         st_tR += t_dR - t_dA;
 #endif
-        // ---- phase B: every owner lane folds its chain into its register list ----------
-        {
-            int cur = whead[lane];
-            whead[lane] = -1;
+        // ---- phase B: every owner lane folds its chain(s) into its list(s), one list after the other; each goes back to memory --
+        // read again by this lane's next drain, or (the unit's last drain) by the block's next unit -- and leaves its K-th entry
+        double thr_own[NL];
+#pragma unroll
+        for (int nl = 0; nl < NL; ++nl) {
+            if (nl + 1 < NL) list_load(nl + 1);         // (in flight under this list's fold)
+            int cur = whead[nl * 64 + lane];
+            whead[nl * 64 + lane] = -1;
             while (__any(cur >= 0)) {
                 const bool on = cur >= 0;
                 const int ce = on ? cur : 0;
                 const double d2 = on ? wqd[ce] : INF;
                 const int j = wq[ce];
                 cur = on ? wnx[ce] : -1;
-                list_insert<KCAP>(own_d, own_i, d2, j);
+                list_insert<KCAP>(own_d[nl], own_i[nl], d2, j);
             }
+            if (LMEM && trusted && wave_live) {
+                const auto pd = gptr_w(a->part_d) + own_o + nl * 64;
+                const auto pi = gptr_w(a->part_i) + own_o + nl * 64;
+#pragma unroll
+                for (int k = 0; k < KCAP; ++k) {
+                    pd[(int64_t)k * npad] = own_d[nl][k];
+                    pi[(int64_t)k * npad] = own_i[nl][k];
+                }
+            }
+            double t = own_d[nl][KCAP - 1];
+#pragma unroll
+            for (int k = 0; k < KCAP - 1; ++k) t = (k == k_last) ? own_d[nl][k] : t;
+            thr_own[nl] = fmin(t, seed_thr[nl]);
+            seed_thr[nl] = thr_own[nl];      // (a wave that is not trusted starts its next drain from an empty list: what it knew stays known)
         }
+        if (trusted) list_in_mem = true;
         qcount = 0;
         // ---- refresh the gates; symmetric sweep: publish the bound and take back what the row side knows ----------
-        double thr_own = own_d[KCAP - 1];
-#pragma unroll
-        for (int k = 0; k < KCAP - 1; ++k) thr_own = (k == k_last) ? own_d[k] : thr_own;
-        thr_own = fmin(thr_own, seed_thr);
         if (sym_on) {
             const auto sp_thr = gptr_w(a->sym.thr);
             const auto sp_rrow = gptr_w(a->sym.rrow);
             const auto sp_rtile = gptr_w(a->sym.rtile);
-            const int64_t q = qwave0 + lane;
-            double t = thr_own;
-            float R = 0.0f;
-            if (q < nq) {
-                if (t < INF) {
-                    // both fetch-mins in flight together: the row constant is formed from the list's own bound; whoever
-                    // published a tighter bound on this row published the matching constant with it, and it comes back here
-                    const unsigned long long mb = (unsigned long long)__double_as_longlong(t);
-                    const unsigned rb = __float_as_uint(own_row_gate(t));
-                    const unsigned long long ob = __hip_atomic_fetch_min(sp_thr + q, mb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned orb = __hip_atomic_fetch_min(sp_rrow + q, rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    t = fmin(t, __longlong_as_double((long long)ob));
-                    R = __uint_as_float(rb < orb ? rb : orb);
-                } else {
-                    t = __longlong_as_double((long long)__hip_atomic_load(sp_thr + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    const unsigned rb = __float_as_uint(own_row_gate(t));
-                    const unsigned orb = __hip_atomic_fetch_min(sp_rrow + q, rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    R = __uint_as_float(rb < orb ? rb : orb);
+#pragma unroll
+            for (int nl = 0; nl < NL; ++nl) {
+                const int64_t q = qwave0 + nl * 64 + lane;
+                double t = thr_own[nl];
+                float R = 0.0f;
+                if (q < nq) {
+                    if (t < INF) {
+                        // both fetch-mins in flight together: the row constant is formed from the list's own bound; whoever
+                        // published a tighter bound on this row published the matching constant with it, and it comes back here
+                        const unsigned long long mb = (unsigned long long)__double_as_longlong(t);
+                        const unsigned rb = __float_as_uint(own_row_gate(t, nl));
+                        const unsigned long long ob = __hip_atomic_fetch_min(sp_thr + q, mb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const unsigned orb = __hip_atomic_fetch_min(sp_rrow + q, rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        t = fmin(t, __longlong_as_double((long long)ob));
+                        R = __uint_as_float(rb < orb ? rb : orb);
+                    } else {
+                        t = __longlong_as_double((long long)__hip_atomic_load(sp_thr + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                        const unsigned rb = __float_as_uint(own_row_gate(t, nl));
+                        const unsigned orb = __hip_atomic_fetch_min(sp_rrow + q, rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        R = __uint_as_float(rb < orb ? rb : orb);
+                    }
                 }
+                thr_own[nl] = t;
+                seed_thr[nl] = t;
+                float m = R;
+#pragma unroll
+                for (int o = 16; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+                if ((lane & 31) == 0 && wave_live) __hip_atomic_store(sp_rtile + ((qwave0 + nl * 64 + lane) >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            thr_own = t;
-            seed_thr = t;
-            float m = R;
-#pragma unroll
-            for (int o = 16; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-            if ((lane & 31) == 0) __hip_atomic_store(sp_rtile + ((qwave0 + lane) >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        sthr[lane] = __double2float_ru(thr_own);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) G[qt] = gate_of(__shfl(thr_own, qt * 32 + (lane & 31), 64), qt);
+        for (int nl = 0; nl < NL; ++nl) sthr[nl * 64 + lane] = __double2float_ru(thr_own[nl]);
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) G[qt] = gate_of(__shfl(thr_own[qt / 2], (qt & 1) * 32 + (lane & 31), 64), qt);
 #if MCE_PANEL_STATS
         st_tD += clock64() - t_d0;
 #endif
@@ -540,26 +648,27 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
     // raised while a wave sweeps and dropped inside its candidate tiles and drains, or the other way round: +1.0 % / +0.15 %,
     // profiles/r06_mid/panel_dynamic_priority_ab.txt.)
     auto event = [&](const v16f& c, const float (&l1)[5], const int qt, const float gq, const bool rowflag, const int jb0, const unsigned todo, const int qlimit) __attribute__((always_inline)) -> unsigned {
-        return f16_event<true>(c, l1, lanew[qt], gq, rowflag, jb0, todo, qlimit, wq, qcount);
+        return f16_event<true, ROWB>(c, l1, lanew[qt], gq, rowflag, jb0, todo, qlimit, wq, qcount);
     };
 
     // ---- staging (global_load_lds DMA, linear image) + A fragments + MFMA -----------------------------------------
     const auto Yh_bytes = (const __attribute__((address_space(1))) char*)MCE_ARGS()->Yh;
     auto stage_async = [&](int64_t c, int buf) { f16_stage_chunk<VPT>(Yh_bytes + c * (int64_t)CHUNK_BYTES, stage0 + buf * CHUNK_BYTES, tid, wave); };
     auto load_a = [&](const char* lp, v8h (&a)[KST]) { f16_load_a<KST>(lp, a); };
-    // one 32-row tile = QT chains of KST MFMAs, issued k-step by k-step (the dependent ones one apart)
-    auto mfma_first = [&](const v8h (&a)[KST], v16f (&acc)[QT]) __attribute__((always_inline)) {
+    // one 32-row tile x TWO query tiles (q0, q0 + 1: all of a wave's at QT = 2, one half of them at QT = 4) = 2 chains of KST
+    // MFMAs, issued k-step by k-step (the dependent ones one apart)
+    auto mfma_first = [&](const v8h (&a)[KST], v16f (&acc)[2], const int q0) __attribute__((always_inline)) {
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
+        for (int qt = 0; qt < 2; ++qt) {
             v16f z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[qt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[qt][0], z, 0, 0, 0);
+            acc[qt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[q0 + qt][0], z, 0, 0, 0);
         }
     };
-    auto mfma_rest = [&](const v8h (&a)[KST], v16f (&acc)[QT]) __attribute__((always_inline)) {
+    auto mfma_rest = [&](const v8h (&a)[KST], v16f (&acc)[2], const int q0) __attribute__((always_inline)) {
 #pragma unroll
         for (int ks = 1; ks < KST; ++ks)
 #pragma unroll
-            for (int qt = 0; qt < QT; ++qt) acc[qt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[ks], b[qt][ks], acc[qt], 0, 0, 0);
+            for (int qt = 0; qt < 2; ++qt) acc[qt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[ks], b[q0 + qt][ks], acc[qt], 0, 0, 0);
     };
     // The gate reads the accumulators through inline asm (v_min3_f32), which neither the compiler's hazard recogniser nor
     // its scheduler knows to keep away from the MFMAs that write them.  The result of an 8-pass MFMA may be read 11 wait
@@ -571,34 +680,34 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
 #else
 #define MCE_ORDER(GATED_, NEXT_) do {} while (0)
 #endif
-    // gate of one finished tile (both query tiles): ONE branch per tile, so that the tile's MFMAs and the gate's VALU work
-    // share a basic block and interleave; tix: the tile's index in its chunk (for a redo); gq / rg: the lane's gates for
+    // gate of one finished tile (the query tiles q0, q0 + 1): ONE branch per tile, so that the tile's MFMAs and the gate's VALU
+    // work share a basic block and interleave; tix: the tile's index in its chunk (for a redo); gq / rg: the lane's gates for
     // the PAIR of tiles this one belongs to (either side / row side)
-    auto gate_tile = [&](const v16f (&acc)[QT], const int jb0, const float (&gq)[QT], const float (&rg)[QT], const int tix) __attribute__((always_inline)) {
+    auto gate_tile = [&](const v16f (&acc)[2], const int jb0, const float (&gq)[QT], const float (&rg)[QT], const int tix, const int q0) __attribute__((always_inline)) {
 #if MCE_PANEL_ABL == 2      // tools only: no gate at all -- the MFMA + LDS stream alone (results invalid)
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" :: "v"(acc[0]), "v"(acc[1]));
 #endif
         return;
 #endif
-        float l1[QT][5], mm[QT];
-        bool pq[QT];
+        float l1[2][5], mm[2];
+        bool pq[2];
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
+        for (int qt = 0; qt < 2; ++qt) {
             mm[qt] = f16_min16(acc[qt], l1[qt]);
-            pq[qt] = mm[qt] <= gq[qt];
+            pq[qt] = mm[qt] <= gq[q0 + qt];
         }
         if (__any(pq[0] || pq[1])) {
 #pragma unroll
-            for (int qt = 0; qt < QT; ++qt) {
+            for (int qt = 0; qt < 2; ++qt) {
                 if (!__any(pq[qt])) continue;
 #if MCE_PANEL_STATS
                 st_events += 1;
                 const long long t_e0 = clock64();
 #endif
-                const unsigned rem = event(acc[qt], l1[qt], qt, gq[qt], mm[qt] <= rg[qt], jb0, 0xffffu, qlimit_gate);
+                const unsigned rem = event(acc[qt], l1[qt], q0 + qt, gq[q0 + qt], mm[qt] <= rg[q0 + qt], jb0, 0xffffu, qlimit_gate);
                 if (rem) {                                     // queue full: the chunk end multiplies this tile again
-                    if (lane == 0) wredo[nredo] = (int)(rem | ((unsigned)qt << 16) | ((unsigned)tix << 17));
+                    if (lane == 0) wredo[nredo] = (int)(rem | ((unsigned)(q0 + qt) << 16) | ((unsigned)tix << 18));
                     nredo += 1;
                 }
 #if MCE_PANEL_STATS
@@ -628,7 +737,7 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
 #if MCE_PANEL_STATS
     st_tPro = clock64() - t_kernel0;
 #endif
-    v16f accA[QT], accB[QT];
+    v16f accA[2], accB[2];          // QT = 2: two reference tiles in flight; QT = 4: the two halves (query tiles 0, 1 | 2, 3) of one
     for (int k = 0; k < ntot; ++k) {
         const int buf = k & 1;
         const int c = cfirst + k;
@@ -658,14 +767,14 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         const int thi = t_hi - c * CT < CT ? t_hi - c * CT : CT;
         const char* const lbuf = stage0 + buf * CHUNK_BYTES + lane * 16;
         const int jchunk = c * (CT * 32);
-        {
+        if constexpr (QT == 2) {
             // tiles in pairs, software-pipelined one tile deep: the MFMAs of a tile are issued before the gate of the one
             // before it; the gate of the pair's second tile closes the chunk (flush)
             v8h a0[KST], a1[KST];
             load_a(lbuf + (tlo * KST) * 1024, a0);
             load_a(lbuf + ((tlo + 1) * KST) * 1024, a1);
-            mfma_first(a0, accA);
-            mfma_rest(a0, accA);
+            mfma_first(a0, accA, 0);
+            mfma_rest(a0, accA, 0);
             int t = tlo;
             float gqP[QT], rgP[QT];
             _Pragma("unroll 1") for (;;)
@@ -678,23 +787,75 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
                 }
                 const bool more = t + 2 < thi;
                 load_a(lbuf + ((more ? t + 2 : t) * KST) * 1024, a0);        // (last trip: harmless re-read)
-                mfma_first(a1, accB);
+                mfma_first(a1, accB, 0);
                 MCE_ORDER(accA, accB);
-                mfma_rest(a1, accB);
-                gate_tile(accA, jchunk + t * 32, gqP, rgP, t);
+                mfma_rest(a1, accB, 0);
+                gate_tile(accA, jchunk + t * 32, gqP, rgP, t, 0);
                 if (!more) break;
                 load_a(lbuf + ((t + 3) * KST) * 1024, a1);
-                mfma_first(a0, accA);
+                mfma_first(a0, accA, 0);
                 MCE_ORDER(accB, accA);
-                mfma_rest(a0, accA);
-                gate_tile(accB, jchunk + (t + 1) * 32, gqP, rgP, t + 1);
+                mfma_rest(a0, accA, 0);
+                gate_tile(accB, jchunk + (t + 1) * 32, gqP, rgP, t + 1, 0);
                 t += 2;
             }
             {   // the chunk's last tile: no MFMA behind it -- the wait states spelled out, then its gate (flush)
 #if defined(__HIP_DEVICE_COMPILE__)
                 asm volatile("s_nop 15\n\ts_nop 3" : "+v"(accB[0]), "+v"(accB[1]));
 #endif
-                gate_tile(accB, jchunk + (t + 1) * 32, gqP, rgP, t + 1);
+                gate_tile(accB, jchunk + (t + 1) * 32, gqP, rgP, t + 1, 0);
+            }
+        } else {
+            // QT = 4: per reference tile ONE load of the A fragments and eight MFMAs in two halves -- accA: query tiles (0, 1), accB:
+            // (2, 3).  Software-pipelined half a tile deep: MFMAs(0, 1) -> MFMAs(2, 3) with the gate of (0, 1) -> the next tile's
+            // MFMAs(0, 1) with the gate of (2, 3) -> ...  The wait states are those of the two-tile loop: a half's gate comes after
+            // the first two MFMAs of the other half (MCE_ORDER: 16 wait states behind the gated half's last MFMA where 11 are
+            // needed), and it is done reading before the same registers' next MFMAs are issued behind it (program order).  Tiles in
+            // pairs (one row-gate constant per pair; a range of tiles is a whole number of pairs); the gate of the last tile's
+            // second half closes the chunk (flush).
+            v8h a0[KST], a1[KST];
+            load_a(lbuf + (tlo * KST) * 1024, a0);
+            mfma_first(a0, accA, 0);
+            mfma_rest(a0, accA, 0);
+            int t = tlo;
+            float gqP[QT], rgP[QT];
+            _Pragma("unroll 1") for (;;)
+            {
+                const float rP = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(rt_cur), t));
+#pragma unroll
+                for (int qt = 0; qt < QT; ++qt) {
+                    rgP[qt] = rP + cR[qt];
+                    gqP[qt] = vmaxf(G[qt], rgP[qt]);            // either side
+                }
+                // tile t (A fragments in a0)
+                load_a(lbuf + ((t + 1) * KST) * 1024, a1);
+                mfma_first(a0, accB, 2);
+                MCE_ORDER(accA, accB);
+                mfma_rest(a0, accB, 2);
+                gate_tile(accA, jchunk + t * 32, gqP, rgP, t, 0);
+                mfma_first(a1, accA, 0);
+                MCE_ORDER(accB, accA);
+                mfma_rest(a1, accA, 0);
+                gate_tile(accB, jchunk + t * 32, gqP, rgP, t, 2);
+                // tile t + 1 (A fragments in a1)
+                const bool more = t + 2 < thi;
+                load_a(lbuf + ((more ? t + 2 : t) * KST) * 1024, a0);        // (last trip: harmless re-read)
+                mfma_first(a1, accB, 2);
+                MCE_ORDER(accA, accB);
+                mfma_rest(a1, accB, 2);
+                gate_tile(accA, jchunk + (t + 1) * 32, gqP, rgP, t + 1, 0);
+                if (!more) break;
+                mfma_first(a0, accA, 0);
+                MCE_ORDER(accB, accA);
+                mfma_rest(a0, accA, 0);
+                gate_tile(accB, jchunk + (t + 1) * 32, gqP, rgP, t + 1, 2);
+                t += 2;
+            }
+            {   // the second half of the chunk's last tile: no MFMA behind it -- the wait states spelled out, then its gate (flush)
+#if defined(__HIP_DEVICE_COMPILE__)
+                asm volatile("s_nop 15\n\ts_nop 3" : "+v"(accB[0]), "+v"(accB[1]));
+#endif
+                gate_tile(accB, jchunk + (t + 1) * 32, gqP, rgP, t + 1, 2);
             }
         }
         // ---- chunk end: the deferred tiles and the drain (ONE copy of it in the code) ------------------------------
@@ -707,31 +868,41 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
             for (int i = 0; i < n; ++i) {
                 const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(wredo[i]);
                 const unsigned todo = w & 0xffffu;
-                const int qt = (int)((w >> 16) & 1u), t = (int)(w >> 17);
+                const int qt = (int)((w >> 16) & 3u), t = (int)(w >> 18);
                 const float Rt = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(rt_cur), t));
                 v8h at[KST];
                 load_a(lbuf + (t * KST) * 1024, at);
                 v16f z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 v16f r_ = z;
                 // (wave-uniform choice of the query tile: a branch, not sixteen selects)
+                float cRq = cR[0], Gq = G[0];
                 if (qt == 0) {
 #pragma unroll
                     for (int ks = 0; ks < KST; ++ks) r_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(at[ks], b[0][ks], r_, 0, 0, 0);
-                } else {
+                } else if (QT == 2 || qt == 1) {
 #pragma unroll
                     for (int ks = 0; ks < KST; ++ks) r_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(at[ks], b[1][ks], r_, 0, 0, 0);
+                    cRq = cR[1]; Gq = G[1];
+                } else if (qt == 2) {
+#pragma unroll
+                    for (int ks = 0; ks < KST; ++ks) r_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(at[ks], b[QT - 2][ks], r_, 0, 0, 0);
+                    cRq = cR[QT - 2]; Gq = G[QT - 2];
+                } else {
+#pragma unroll
+                    for (int ks = 0; ks < KST; ++ks) r_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(at[ks], b[QT - 1][ks], r_, 0, 0, 0);
+                    cRq = cR[QT - 1]; Gq = G[QT - 1];
                 }
 #if defined(__HIP_DEVICE_COMPILE__)
                 asm volatile("s_nop 15\n\ts_nop 3" : "+v"(r_));
 #endif
                 float l1[5];
                 const float mm = f16_min16(r_, l1);
-                const float rg = Rt + (qt ? cR[1] : cR[0]);
-                const float gq = vmaxf(qt ? G[1] : G[0], rg);
+                const float rg = Rt + cRq;
+                const float gq = vmaxf(Gq, rg);
                 unsigned rem = 0;
                 if (__any(mm <= gq)) rem = event(r_, l1, qt, gq, mm <= rg, jchunk + t * 32, todo, QN - 64);
                 if (rem) {
-                    if (lane == 0) wredo[nredo] = (int)(rem | ((unsigned)qt << 16) | ((unsigned)t << 17));
+                    if (lane == 0) wredo[nredo] = (int)(rem | ((unsigned)qt << 16) | ((unsigned)t << 18));
                     nredo += 1;
                 }
 #if MCE_PANEL_STATS
@@ -751,20 +922,22 @@ __global__ __launch_bounds__(kHThreads, 2) void knn_panel_kernel(PanelArgs args_
         o2[0] = (double)st_tA; o2[1] = (double)st_tR; o2[2] = (double)(st_tD - st_tA - st_tR); o2[3] = (double)st_tB; o2[4] = 0; o2[5] = 0; o2[6] = 0; o2[7] = 0;
     }
 #endif
-    // ---- write the lists (lane l owns wave-local query l: coalesced) and hand them to the block's next unit ------------
+    // ---- hand the lists to the block's next unit: the unit's last chunk ended with a drain, which stored them ------------
     {
         const ArgsPtr a = MCE_ARGS();
-        const int64_t q = qwave0 + lane;
-        const int64_t np = a->nq_pad;
         int chain;
         int64_t list_off;
         chain_of(chain, list_off);
-        const auto pd = gptr_w(a->part_d) + list_off;
-        const auto pi = gptr_w(a->part_i) + list_off;
+        if constexpr (!LMEM) {      // (lane l owns wave-local query l: coalesced)
+            const int64_t q = qwave0 + lane;
+            const int64_t np = a->nq_pad;
+            const auto pd = gptr_w(a->part_d) + list_off;
+            const auto pi = gptr_w(a->part_i) + list_off;
 #pragma unroll
-        for (int k = 0; k < KCAP; ++k) {
-            pd[(int64_t)k * np + q] = own_d[k];
-            pi[(int64_t)k * np + q] = own_i[k];
+            for (int k = 0; k < KCAP; ++k) {
+                pd[(int64_t)k * np + q] = reg_d[0][k];
+                pi[(int64_t)k * np + q] = reg_i[0][k];
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();

@@ -726,6 +726,26 @@ int mce_param_marginals_dev(const mce_summary_seg* segs, int32_t nseg, const dou
                             size_t ws_bytes, void* stream);
 int mce_param_marginals_f64(const mce_summary_seg* segs, int32_t nseg, const double* probs, int32_t np, int32_t grid, double scale, double* out, int32_t device);
 
+/* mce_param_marginals_dev for parameters with hard prior bounds (marginals= with bounds=): the grid ends on a bound it would cross, the
+ * density is Jones' linear boundary kernel in its positive form, and a grid that ends on a bound counts half a cell there in the HPD
+ * sums.  The rule is stated in csrc/param_marginals_bounds.hpp and docs/design/marginals_bounds.md.  bounds: a HOST array, 2 d doubles
+ * per segment in segment order, lo[d] then hi[d]; -inf / +inf: that side is open; lo < hi, neither NaN.  Everything else is taken as
+ * mce_param_marginals_dev takes it.  out (HOST, mce_param_marginals_bounded_out_doubles(d, np, grid) doubles per system) = that call's
+ * head with 1 in the reserved slot, then its ten per-column rows and bound_lo[d], bound_hi[d], at_lo[d], at_hi[d] (1 where the grid
+ * ends on the bound), then the rows per probability and density[d][grid] as there.  col_status 8: a used value lies outside the column's
+ * bounds; that column is NaN with pieces -1, and the other columns do not notice.  A column whose two sides are open has the bits
+ * mce_param_marginals_dev gives it.  A system's bits depend on its own rows, bounds, probs, grid and scale alone.  Ten launches whatever
+ * nseg is, on the caller's stream, which this library synchronises once, on return.  Workspace:
+ * mce_param_marginals_bounded_workspace_bytes(rows of all segments, nseg, the largest d, np, grid).  mce_param_marginals_bounded_f64
+ * takes HOST segments.  Argument errors (those of mce_param_marginals_dev, a null bounds, a pair of bounds that is not lo < hi):
+ * MCE_ERR_INVALID (no device needed). */
+size_t mce_param_marginals_bounded_out_doubles(int32_t d, int32_t np, int32_t grid);
+size_t mce_param_marginals_bounded_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t dmax, int32_t np, int32_t grid);
+int mce_param_marginals_bounded_dev(const mce_summary_seg* segs, int32_t nseg, const double* bounds, const double* probs, int32_t np, int32_t grid, double scale,
+                                    double* out, void* ws, size_t ws_bytes, void* stream);
+int mce_param_marginals_bounded_f64(const mce_summary_seg* segs, int32_t nseg, const double* bounds, const double* probs, int32_t np, int32_t grid, double scale,
+                                    double* out, int32_t device);
+
 /* The 2-D joint posterior densities behind contours= (a product-Gaussian kernel density estimate of every pair of chosen parameter
  * columns on a regular grid x grid, its mode and its credible regions), for MANY systems in one call.  The rule is stated in
  * csrc/param_contours.hpp and docs/design/contours.md.  One system is one mce_summary_seg as for mce_param_marginals_dev.  cols[nc]: a

@@ -234,6 +234,10 @@ SIGNATURES["mce_param_marginals_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_
 SIGNATURES["mce_param_marginals_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32])
 SIGNATURES["mce_param_marginals_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _P, _c.c_size_t, _P])
 SIGNATURES["mce_param_marginals_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _c.c_int32])
+SIGNATURES["mce_param_marginals_bounded_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_marginals_bounded_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_marginals_bounded_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_param_marginals_bounded_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _c.c_int32])
 SIGNATURES["mce_param_contours_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int32])
 SIGNATURES["mce_param_contours_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32])
 SIGNATURES["mce_param_contours_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _P, _c.c_size_t, _P])
@@ -916,6 +920,63 @@ def param_marginals(systems, probs, grid, scale, device=0):
         keep.append((x, int(d), w))
     segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
     return _param_marginals(load().mce_param_marginals_f64, segs, probs, grid, scale, (int(device),))
+
+
+def param_marginals_bounded_out_doubles(d, np_, grid):
+    return int(load().mce_param_marginals_bounded_out_doubles(int(d), int(np_), int(grid)))
+
+
+def param_marginals_bounded_workspace_bytes(nrows_total, nseg, dmax, np_, grid):
+    return int(load().mce_param_marginals_bounded_workspace_bytes(int(nrows_total), int(nseg), int(dmax), int(np_), int(grid)))
+
+
+def marginals_bounded_block_doubles(d, np_, grid):
+    """doubles of one system's result block: MCE_MARGINALS_HEAD + d * (14 + 4 np + grid)"""
+    return MCE_MARGINALS_HEAD + int(d) * (14 + 4 * int(np_) + int(grid))
+
+
+def _param_marginals_bounded(call, segs, bounds, probs, grid, scale, tail):
+    """``bounds``: per system (lo[d], hi[d]) -> the HOST array of the call, 2 d doubles per segment"""
+    arr = (SummarySeg * max(len(segs), 1))()
+    for i, (x, ld, n, d, w) in enumerate(segs):
+        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, None
+    if len(bounds) != len(segs):
+        raise ValueError("param marginals: one pair of bounds arrays per system expected")
+    flat = []
+    for (_, _, _, d, _), (lo, hi) in zip(segs, bounds):
+        lo, hi = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (lo, hi))
+        if lo.size != max(int(d), 0) or hi.size != lo.size:
+            raise ValueError("param marginals: %d lower and %d upper bounds for %d columns" % (lo.size, hi.size, d))
+        flat += [lo, hi]
+    flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0))
+    probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    npr, grid = probs.size, int(grid)
+    shape_ok = 1 <= npr <= MCE_MARGINALS_MAX_P and grid in (64, 128, 256, 512, 1024)
+    sizes = [marginals_bounded_block_doubles(d, npr, grid) if shape_ok and 1 <= int(d) <= 127 else 0 for _, _, _, d, _ in segs]
+    out = np.full(max(sum(sizes), 1), np.nan)
+    check(call(_c.cast(arr, _P), len(segs), flat.ctypes.data if flat.size else None, probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
+    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
+    return [out[at[i]:at[i + 1]] for i in range(len(segs))]
+
+
+def param_marginals_bounded_dev(segs, bounds, probs, grid, scale, ws, ws_bytes, stream=0):
+    """mce_param_marginals_bounded_dev: ``param_marginals_dev`` with hard prior bounds, ``bounds`` = [(lo[d], hi[d])] per system (HOST
+    arrays, -inf / +inf: open) -> one float64 block per system (``marginals.from_block_bounded`` reads it)"""
+    return _param_marginals_bounded(load().mce_param_marginals_bounded_dev, segs, bounds, probs, grid, scale, (ws or None, int(ws_bytes), stream or None))
+
+
+def param_marginals_bounded(systems, bounds, probs, grid, scale, device=0):
+    """mce_param_marginals_bounded_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
+    keep = []
+    for x, d, w in systems:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if x.shape[0] != w.size:
+            raise ValueError("param marginals: rows and w of one length expected")
+        keep.append((x, int(d), w))
+    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
+    return _param_marginals_bounded(load().mce_param_marginals_bounded_f64, segs, bounds, probs, grid, scale, (int(device),))
 
 
 def param_contours_out_doubles(nc, np_, grid):

@@ -75,6 +75,9 @@ def build_parser(prog=None):
                    help="with --marginals: the bandwidth as a multiple of the normal-reference rule (default 1)")
     p.add_argument("--marginals-out", dest="marginals_out", default=None, metavar="FILE.npz",
                    help="with --marginals: write the names, the grid points and the densities of every parameter to FILE.npz, one set per root")
+    p.add_argument("--bounds", dest="bounds", nargs="*", default=None, metavar="NAME=LO:HI",
+                   help="with --marginals: honour hard prior bounds in the 1-D densities (a linear boundary kernel; the grid ends on the bound). "
+                        "Without a value: the bounds of the root's .ranges or log.param file; or NAME=LO:HI ..., an empty side or N: open")
     p.add_argument("--contours", dest="contours", nargs="*", default=None, type=float, metavar="P",
                    help="also report the 2-D joint posterior density of every pair of the chosen parameters: its mode and, per probability P "
                         "(default 0.68 0.95), the contour level and the number of grid cells it encloses")
@@ -109,18 +112,34 @@ def _summary_kw(args):
     return {"summary": tuple(args.summary) if args.summary else True}
 
 
+def _bounds_kw(args):
+    """--bounds, where it was given: "ranges", or the mapping of its NAME=LO:HI values"""
+    if getattr(args, "bounds", None) is None:
+        return {}
+    if not args.bounds:
+        return {"bounds": "ranges"}
+    out = {}
+    for item in args.bounds:
+        name, eq, pair = item.partition("=")
+        lo, colon, hi = pair.partition(":")
+        if not name or not eq or not colon:
+            raise ValueError("bounds=%r: NAME=LO:HI expected" % (item,))
+        out[name] = tuple(None if v.strip() in ("", "N", "None") else v.strip() for v in (lo, hi))
+    return {"bounds": out}
+
+
 def _marginals_kw(args):
-    """--marginals / --marginals-grid / --marginals-scale, where the first was given"""
+    """--marginals / --marginals-grid / --marginals-scale, where the first was given, and --bounds with them"""
     if args.marginals is None:
         return {}
     if args.marginals_grid is None and args.marginals_scale is None:
-        return {"marginals": tuple(args.marginals) if args.marginals else True}
+        return dict({"marginals": tuple(args.marginals) if args.marginals else True}, **_bounds_kw(args))
     kw = {"probs": tuple(args.marginals) if args.marginals else True}
     if args.marginals_grid is not None:
         kw["grid"] = args.marginals_grid
     if args.marginals_scale is not None:
         kw["scale"] = args.marginals_scale
-    return {"marginals": kw}
+    return dict({"marginals": kw}, **_bounds_kw(args))
 
 
 def _contours_kw(args):
@@ -349,6 +368,8 @@ def main(argv=None):
         build_parser(prog="MCEvidence.py").error("--shift-bandwidth SCALE: a positive number expected")
     if (args.marginals_grid is not None or args.marginals_scale is not None or args.marginals_out is not None) and args.marginals is None:
         build_parser(prog="MCEvidence.py").error("--marginals-grid, --marginals-scale and --marginals-out belong to --marginals")
+    if args.bounds is not None and args.marginals is None:
+        build_parser(prog="MCEvidence.py").error("--bounds belongs to --marginals")
     if (args.contours_params is not None or args.contours_grid is not None or args.contours_scale is not None or args.contours_out is not None) and args.contours is None:
         build_parser(prog="MCEvidence.py").error("--contours-params, --contours-grid, --contours-scale and --contours-out belong to --contours")
     if args.tension is not None:

@@ -1,0 +1,287 @@
+// param_marginals_bounds_kernels.hpp -- the boundary-corrected 1-D marginal densities behind marginals= with bounds=
+// (mce_param_marginals_bounded_dev, capi_marginals_bounds.hpp) for chains that are already on the device.  The rule is
+// param_marginals_bounds.hpp's; the launches follow param_marginals_kernels.hpp's on the segment-tile scheme of seg_tiles.hpp, and that
+// file's kernels stay as they are (mce_param_marginals_dev keeps its bits and its code).  Plain C++ stores only, no atomics, 64-bit row
+// indices.  A RUN is one (system, column).
+//
+//   (sum_tile / sum_sys / sum_col / sum_var_tile / sum_var_col of param_summary_kernels.hpp, as they stand)
+//   marb_prep_kernel     one thread per run: the system's status, then h, c, step 3' (lo, step, at_lo, at_hi) and the column's status
+//                        (prm[run][kMarbPrm])
+//   marb_density_kernel  the hot path, in mar_density_kernel's shape: a workgroup owns one (run, block of 256 grid points) and one PART of
+//                        the system's tiles, a thread one grid point in a register; the part's tiles go through LDS as (x, a) pairs, 512
+//                        rows at a time, and every thread adds the staged rows in row order, into TWO sums: S += t and R += t (x - g),
+//                        t = a exp(-arg) formed once.  Rows at or above 746 are branched over as there.  S and R are written per part:
+//                        SR[((part0 + col * nparts + part) * 2 + {0, 1}) * G + k]
+//   marb_fold_kernel     per run and grid point: the parts in part order for both sums, then steps 5' and 6', into the result block
+//   marb_hpd_kernel      one workgroup per run: mar_hpd_kernel's sort and cut, the running sums with the end weights of step 8'
+//   marb_result_kernel   one workgroup per system: the head and the per-column rows of the result block
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "block_reduce.hpp"
+#include "param_marginals_bounds.hpp"
+#include "param_marginals_kernels.hpp"
+#include "param_summary_kernels.hpp"
+#include "seg_tiles.hpp"
+
+namespace mce {
+
+constexpr int kMarbPrm = 12;                                    // per run: kMarPrm's h, c, lo, step, sd, status, -, -; then L, U, at_lo, at_hi
+
+__device__ __forceinline__ double* marb_p_rows(double* block, int d) { return block + mce_mar::kMarHead + (int64_t)mce_marb::kMarbPerCol * d; }
+__device__ __forceinline__ double* marb_dens_rows(double* block, int d, int np)
+{
+    return block + mce_mar::kMarHead + (int64_t)(mce_marb::kMarbPerCol + mce_mar::kMarPerP * np) * d;
+}
+
+// grid: the runs, one thread each.  bnd[run][2]: L, U
+__global__ __launch_bounds__(kMarThreads) void marb_prep_kernel(const SumSeg* __restrict__ segs, const SumRun* __restrict__ runs, int64_t nruns,
+                                                               const double* __restrict__ sys, const double* __restrict__ col, const double* __restrict__ bnd,
+                                                               int G, double scale, double* __restrict__ prm)
+{
+    const int64_t r = (int64_t)blockIdx.x * kMarThreads + threadIdx.x;
+    if (r >= nruns) return;
+    const int y = runs[r].seg;
+    const SumSeg& g = segs[y];
+    const double* s = sys + (int64_t)y * kSumSys;
+    int badcol = -1;
+    for (int j = g.d - 1; j >= 0; --j)
+        if (col[(g.col0 + j) * kSumCol + 4] > 0.0) badcol = j;
+    int column;
+    const int status = mce_mar::mar_status(((int)s[3] & 1) != 0, badcol, s[0], s[2], &column);
+    double* out = prm + r * kMarbPrm;
+    const double nan = __builtin_nan("");
+    const double L = bnd[2 * r], U = bnd[2 * r + 1];
+    double sd = nan, h = nan, c = nan, lo = nan, step = nan, at_lo = nan, at_hi = nan;
+    int cs = kMarSysFailed;
+    if (status == mce_mar::kMarOk) {
+        const double* in = col + r * kSumCol;
+        cs = mce_marb::marb_params(s[0], s[1], in[1], in[2], in[3], L, U, scale, G, &sd, &h, &c, &lo, &step, &at_lo, &at_hi);
+    }
+    out[0] = h;
+    out[1] = c;
+    out[2] = lo;
+    out[3] = step;
+    out[4] = sd;
+    out[5] = (double)cs;
+    out[6] = 0.0;
+    out[7] = 0.0;
+    out[8] = L;
+    out[9] = U;
+    out[10] = at_lo;
+    out[11] = at_hi;
+}
+
+// grid: x = run * nblk + block of grid points, y = part
+__global__ __launch_bounds__(kMarThreads) void marb_density_kernel(const SumSeg* __restrict__ segs, const MarSeg* __restrict__ msegs, const SumRun* __restrict__ runs,
+                                                                  const double* __restrict__ prm, int G, int nblk, double* __restrict__ SR)
+{
+    __shared__ double2 stage[mce_seg::kSegTileRows];
+    const int64_t r = blockIdx.x / nblk;
+    const int blk = blockIdx.x % nblk, part = blockIdx.y;
+    const int y = runs[r].seg, j = runs[r].col;
+    const SumSeg g = segs[y];
+    const int nparts = mce_mar::mar_nparts(g.n);
+    if (part >= nparts) return;                                  // (a launch is sized by the call's largest part count)
+    const double* p = prm + r * kMarbPrm;
+    if ((int)p[5] != mce_mar::kMarOk) return;
+    const double c = p[1];
+    const int k = blk * kMarThreads + threadIdx.x;
+    const bool mine = k < G;
+    const double gk = mce_mar::mar_grid_point(p[2], p[3], mine ? k : 0);
+    const int64_t t0 = mce_mar::mar_part_tile(g.n, part), t1 = mce_mar::mar_part_tile(g.n, part + 1);
+    double S = 0.0, R = 0.0;
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t r0 = t * mce_seg::kSegTileRows;
+        const int64_t left = g.n - r0;
+        const int cnt = left < mce_seg::kSegTileRows ? (int)left : mce_seg::kSegTileRows;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int at = threadIdx.x + q * kMarThreads;
+            if (at < cnt) {
+                const int64_t i = r0 + at;
+                const double a = g.w[i];
+                const bool used = mce_sum::sum_used(a);
+                stage[at] = make_double2(used ? g.x[i * g.ld + j] : 0.0, used ? a : 0.0);
+            }
+        }
+        __syncthreads();
+        if (mine) {
+            for (int i = 0; i < cnt; ++i) {
+                const double2 xa = stage[i];
+                mce_marb::marb_term(c, gk, xa.x, xa.y, &S, &R);
+            }
+        }
+    }
+    if (mine) {
+        double* dst = SR + (msegs[y].part0 + (int64_t)j * nparts + part) * 2 * G + k;
+        dst[0] = S;
+        dst[G] = R;
+    }
+}
+
+// grid: run * nblk + block of grid points.  The densities go to the system's result block.
+__global__ __launch_bounds__(kMarThreads) void marb_fold_kernel(const SumSeg* __restrict__ segs, const MarSeg* __restrict__ msegs, const SumRun* __restrict__ runs,
+                                                               const double* __restrict__ prm, const double* __restrict__ sys, int G, int nblk, int np,
+                                                               const double* __restrict__ SR, double* __restrict__ res)
+{
+    const int64_t r = blockIdx.x / nblk;
+    const int k = (int)(blockIdx.x % nblk) * kMarThreads + threadIdx.x;
+    if (k >= G) return;
+    const int y = runs[r].seg, j = runs[r].col;
+    const SumSeg& g = segs[y];
+    const double* p = prm + r * kMarbPrm;
+    double rho = __builtin_nan("");
+    if ((int)p[5] == mce_mar::kMarOk) {
+        const int nparts = mce_mar::mar_nparts(g.n);
+        const double* src = SR + (msegs[y].part0 + (int64_t)j * nparts) * 2 * G + k;
+        double S = 0.0, R = 0.0;
+        for (int q = 0; q < nparts; ++q) {
+            S += src[(int64_t)q * 2 * G];
+            R += src[(int64_t)q * 2 * G + G];
+        }
+        const double h = p[0];
+        const double norm = mce_mar::mar_norm(sys[(int64_t)y * kSumSys + 0], h);
+        double a0, a1, a2, den;
+        mce_marb::marb_consts(mce_mar::mar_grid_point(p[2], p[3], k), p[8], p[9], h, &a0, &a1, &a2, &den);
+        rho = mce_marb::marb_density(mce_marb::marb_t0(S, norm), mce_marb::marb_t1(R, h, norm), a0, a1, a2, den);
+    }
+    marb_dens_rows(res + msegs[y].out_off, g.d, np)[(int64_t)j * G + k] = rho;
+}
+
+// grid: the runs, one workgroup each
+__global__ __launch_bounds__(kMarThreads) void marb_hpd_kernel(const SumSeg* __restrict__ segs, const MarSeg* __restrict__ msegs, const SumRun* __restrict__ runs,
+                                                              const double* __restrict__ prm, const double* __restrict__ probs, int np, int G,
+                                                              double* __restrict__ res)
+{
+    __shared__ double s_rho[mce_mar::kMarMaxGrid];
+    __shared__ double s_cum[mce_mar::kMarMaxGrid];
+    __shared__ int s_k[mce_mar::kMarMaxGrid];
+    __shared__ unsigned char s_sel[mce_mar::kMarMaxGrid];
+    __shared__ double red[kRedWaves];
+    const int64_t r = blockIdx.x;
+    const int y = runs[r].seg, j = runs[r].col;
+    const int d = segs[y].d;
+    double* block = res + msegs[y].out_off;
+    double* colr = mar_col_rows(block);
+    double* pr = marb_p_rows(block, d);
+    const double* p = prm + r * kMarbPrm;
+    const int cs = (int)p[5];
+    const double nan = __builtin_nan("");
+    if (cs != mce_mar::kMarOk) {
+        if (threadIdx.x == 0) {
+            colr[mce_mar::kMarMode * d + j] = nan;
+            colr[mce_mar::kMarModeDensity * d + j] = nan;
+            for (int t = 0; t < np; ++t) {
+                double* o = pr + (int64_t)t * mce_mar::kMarPerP * d + j;
+                o[mce_mar::kMarLower * d] = nan;
+                o[mce_mar::kMarUpper * d] = nan;
+                o[mce_mar::kMarPieces * d] = cs == kMarSysFailed ? nan : -1.0;
+                o[mce_mar::kMarEdge * d] = nan;
+            }
+        }
+        return;
+    }
+    const double lo = p[2], step = p[3];
+    const bool at_lo = p[10] != 0.0, at_hi = p[11] != 0.0;
+    const double* rho = marb_dens_rows(block, d, np) + (int64_t)j * G;
+    for (int k = threadIdx.x; k < G; k += kMarThreads) { s_rho[k] = rho[k]; s_k[k] = k; }
+    __syncthreads();
+    // the bitonic network on mar_before: G is a power of two
+    for (int size = 2; size <= G; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int a = threadIdx.x; a < G; a += kMarThreads) {
+                const int b = a ^ stride;
+                if (b > a) {
+                    const bool up = (a & size) == 0;             // this pair ends in the order of step 8'
+                    const double ra = s_rho[a], rb = s_rho[b];
+                    const int ka = s_k[a], kb = s_k[b];
+                    const bool b_first = mce_mar::mar_before(rb, kb, ra, ka);
+                    if (b_first == up) { s_rho[a] = rb; s_rho[b] = ra; s_k[a] = kb; s_k[b] = ka; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) {
+        double run = 0.0;
+        for (int q = 0; q < G; ++q) { run += mce_marb::marb_weighted(s_rho[q], s_k[q], G, at_lo, at_hi); s_cum[q] = run; }
+        colr[mce_mar::kMarMode * d + j] = mce_mar::mar_grid_point(lo, step, s_k[0]);
+        colr[mce_mar::kMarModeDensity * d + j] = s_rho[0];
+    }
+    __syncthreads();
+    const double Z = s_cum[G - 1];
+    for (int t = 0; t < np; ++t) {
+        const double target = probs[t] * Z;
+        double first = (double)(G - 1);                          // (no position reaches the target: all of them)
+        for (int q = threadIdx.x; q < G; q += kMarThreads)
+            if (s_cum[q] >= target && (double)q < first) first = (double)q;
+        const int cut = (int)block_min(first, red);
+        __syncthreads();
+        for (int q = threadIdx.x; q < G; q += kMarThreads) s_sel[s_k[q]] = q <= cut ? 1 : 0;
+        __syncthreads();
+        double kmin = (double)G, kmax = -1.0, pieces = 0.0;
+        for (int k = threadIdx.x; k < G; k += kMarThreads) {
+            if (!s_sel[k]) continue;
+            kmin = (double)k < kmin ? (double)k : kmin;
+            kmax = (double)k > kmax ? (double)k : kmax;
+            pieces += (k == 0 || !s_sel[k - 1]) ? 1.0 : 0.0;
+        }
+        kmin = block_min(kmin, red);
+        kmax = block_max(kmax, red);
+        pieces = block_sum(pieces, red);
+        if (threadIdx.x == 0) {
+            double* o = pr + (int64_t)t * mce_mar::kMarPerP * d + j;
+            o[mce_mar::kMarLower * d] = mce_mar::mar_grid_point(lo, step, (int)kmin);
+            o[mce_mar::kMarUpper * d] = mce_mar::mar_grid_point(lo, step, (int)kmax);
+            o[mce_mar::kMarPieces * d] = pieces;
+            o[mce_mar::kMarEdge * d] = (s_sel[0] || s_sel[G - 1]) ? 1.0 : 0.0;
+        }
+        __syncthreads();
+    }
+}
+
+// one workgroup per system: the head and the per-column rows
+__global__ __launch_bounds__(kMarThreads) void marb_result_kernel(const SumSeg* __restrict__ segs, const MarSeg* __restrict__ msegs, const double* __restrict__ sys,
+                                                                 const double* __restrict__ col, const double* __restrict__ prm, int G, int np,
+                                                                 double* __restrict__ res)
+{
+    const int y = blockIdx.x;
+    const SumSeg g = segs[y];
+    const double* s = sys + (int64_t)y * kSumSys;
+    double* out = res + msegs[y].out_off;
+    if (threadIdx.x == 0) {
+        int badcol = -1;
+        for (int j = g.d - 1; j >= 0; --j)
+            if (col[(g.col0 + j) * kSumCol + 4] > 0.0) badcol = j;
+        int column;
+        const int status = mce_mar::mar_status(((int)s[3] & 1) != 0, badcol, s[0], s[2], &column);
+        mce_mar::mar_pack_head(status, column, s[0], s[1], s[2], G, np, out);
+        out[mce_mar::kMarReserved] = 1.0;
+    }
+    const double nan = __builtin_nan("");
+    double* c = mar_col_rows(out);
+    for (int j = threadIdx.x; j < g.d; j += kMarThreads) {
+        const double* in = col + (g.col0 + j) * kSumCol;
+        const double* p = prm + (g.col0 + j) * kMarbPrm;
+        const int cs = (int)p[5];
+        const bool ok = cs == mce_mar::kMarOk, sys_ok = cs != kMarSysFailed;
+        c[mce_mar::kMarMean * g.d + j] = ok ? in[0] : nan;
+        c[mce_mar::kMarVar * g.d + j] = ok ? in[1] : nan;
+        c[mce_mar::kMarSd * g.d + j] = ok ? p[4] : nan;
+        c[mce_mar::kMarH * g.d + j] = ok ? p[0] : nan;
+        c[mce_mar::kMarC * g.d + j] = ok ? p[1] : nan;
+        c[mce_mar::kMarLo * g.d + j] = ok ? p[2] : nan;
+        c[mce_mar::kMarStep * g.d + j] = ok ? p[3] : nan;
+        c[mce_mar::kMarColStatus * g.d + j] = sys_ok ? (double)cs : nan;
+        c[mce_marb::kMarbBoundLo * g.d + j] = sys_ok ? p[8] : nan;
+        c[mce_marb::kMarbBoundHi * g.d + j] = sys_ok ? p[9] : nan;
+        c[mce_marb::kMarbAtLo * g.d + j] = ok ? p[10] : nan;
+        c[mce_marb::kMarbAtHi * g.d + j] = ok ? p[11] : nan;
+    }
+}
+
+}  // namespace mce

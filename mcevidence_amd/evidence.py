@@ -215,7 +215,9 @@ class MCEvidence(object):
         parameters in ``info["covariance"]`` and in ``self.param_cov`` (covariance.py; docs/design/tension.md) -- and ``marginals`` -- None,
         True, up to 7 probabilities or dict(probs, grid, scale): ``evidence()`` then also stores the 1-D marginal density of each of the
         first ``ndim`` parameters on a grid, its mode and its highest-posterior-density regions in ``info["marginals"]`` and in
-        ``self.param_marginals`` (marginals.py; docs/design/marginals.md) -- and ``contours`` -- None, True, up to 7 probabilities or
+        ``self.param_marginals`` (marginals.py; docs/design/marginals.md), with ``bounds`` -- None, "ranges", a mapping name -> (lo, hi) or one
+        (lo, hi) per parameter -- the hard prior bounds those densities honour (docs/design/marginals_bounds.md) -- and ``contours`` --
+        None, True, up to 7 probabilities or
         dict(probs, grid, scale, params): ``evidence()`` then also stores the 2-D joint density of every pair of the chosen parameters
         (default: all of the first ``ndim``, at most 32) on a grid, its mode and the levels and regions of the probabilities in
         ``info["contours"]`` and in ``self.param_contours`` (contours.py; docs/design/contours.md).
@@ -252,6 +254,10 @@ class MCEvidence(object):
         self.marginals_spec = gdkwargs.pop("marginals", None)
         self.param_marginals = None
         _marginals.refuse(self.marginals_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
+        # the hard prior bounds of the marginals (docs/design/marginals_bounds.md): None (off: nothing changes), "ranges", a mapping
+        # name -> (lo, hi) or one (lo, hi) pair per parameter; resolved against the parameter names when the marginals are formed
+        self.bounds = gdkwargs.pop("bounds", None)
+        _marginals.refuse_bounds(self.bounds, self.marginals_spec, root=method if isinstance(method, str) else None)
         # the 2-D joint densities, modes and credible levels of the parameter pairs with every evidence() call
         # (docs/design/contours.md): None (off: nothing changes), True, the probabilities, or a dict of probs, grid, scale and params
         self.contours_spec = gdkwargs.pop("contours", None)
@@ -526,13 +532,18 @@ class MCEvidence(object):
         _marginals.refuse(self.marginals_spec, brange=self.brange, nbatch=self.nbatch)
         samples, _, _ = self.gd.arrays("s1")
         a, x = self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim]
+        names = _summary.param_names(self.fname, self.ndim)
+        bnd = _marginals.bounds_spec(self.bounds, names=names, root=self.fname if isinstance(self.fname, str) else None, marginals=self.marginals_spec)
+        if bnd is not None:
+            _marginals.note_contours(self.contours_spec)
         if getattr(self.backend, "name", None) == "hip":
             import torch
             devs = getattr(self.backend, "devices", None)
-            blk = _marginals.measure_native(a, x, *sp, device=devs[0] if devs else (torch.cuda.current_device() if torch.cuda.is_available() else 0))
+            device = devs[0] if devs else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+            blk = _marginals.measure_native(a, x, *sp, device=device) if bnd is None else _marginals.measure_bounded_native(a, x, bnd, *sp, device=device)
         else:
-            blk = _marginals.measure(a, x, *sp)
-        self.param_marginals = self.info["marginals"] = _marginals.build(blk, sp, _summary.param_names(self.fname, self.ndim))
+            blk = _marginals.measure(a, x, *sp) if bnd is None else _marginals.measure_bounded(a, x, bnd, *sp)
+        self.param_marginals = self.info["marginals"] = _marginals.build(blk, sp, names)
 
     def _fill_contours(self):
         """``info["contours"]`` of this call (the constructor's ``contours`` keyword; unset: nothing happens): the rule of contours.py on

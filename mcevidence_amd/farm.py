@@ -158,6 +158,21 @@ def _per_root_marginals(value, n):
     return [value] * n
 
 
+def _per_root_bounds(value, n):
+    """``bounds`` of the farm -> one value per root, by ``_per_root_marginals``' rule: None, "ranges", a mapping, or a sequence of
+    (lo, hi) pairs is ONE value for every root; a list / tuple whose entries are all None, "ranges", a mapping or a sequence of pairs
+    is one entry per root"""
+    def is_pair(v):
+        return isinstance(v, (list, tuple, np.ndarray)) and len(v) == 2 and not any(isinstance(e, (list, tuple, np.ndarray, dict)) for e in v)
+    if isinstance(value, (list, tuple, np.ndarray)) and len(value) > 0 and not all(is_pair(v) for v in value):
+        slot = [v is None or isinstance(v, (str, dict)) or (isinstance(v, (list, tuple, np.ndarray)) and all(is_pair(e) for e in v)) for v in value]
+        if all(slot):
+            return _per_root(list(value), n, "bounds")
+        raise ValueError("bounds=%r: either one value for every root or one entry per root (None, 'ranges', a mapping or a sequence of (lo, hi) "
+                         "pairs each), not a mixture" % (value,))
+    return [value] * n
+
+
 def _parse_wave(pool, device, wave_bytes, paths, lens, ms):
     """one wave: the files read into the staging buffer, uploaded and parsed -> (the C array of per-file results, the device tensor
     global token k is written to, {path: exception} of the files that could not be read)"""
@@ -232,7 +247,7 @@ class _Root(object):
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
                              idpattern="_?.txt", iw=0, ilike=1, itheta=2, device=0, backend=None, info=False, return_exceptions=False,
                              require_resident=False, wave_bytes=None, split=False, thin_corr=None, corr_min=None, corr_max_lag=None, converge=None, converge_by="auto",
-                             information=None, jackknife=None, summary=None, covariance=None, marginals=None, contours=None):
+                             information=None, jackknife=None, summary=None, covariance=None, marginals=None, contours=None, bounds=None):
     """``[evidence_from_files(root, ...) for root in roots]`` with the files of many roots parsed per wave and the device work of all
     of them in batched calls.  ``ndim``, ``priorvolume``, ``burnlen`` and ``thinlen`` may be sequences, one entry per root.  One result
     per root, in input order, each exactly what ``evidence_from_files(root, ...)`` returns (``MLE[1:]``; with ``info=True`` the same info keys, and
@@ -263,6 +278,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     roots that ask, thinned and unthinned alike, before the feed.  ``marginals`` (one value or one per root, by ``summary``'s rule; a dict is
     one value): the 1-D marginal densities, modes and HPD regions of every such root's first ``ndim`` parameters in ``info["marginals"]`` --
     ONE ``mce_param_marginals_dev`` call per wave and per distinct (probs, grid, scale) over all its ready roots that ask, before the feed.
+    ``bounds`` (one value or one per root, by the same rule: None, "ranges", a mapping name -> (lo, hi) or one (lo, hi) per parameter): the
+    hard prior bounds of such a root's marginals (docs/design/marginals_bounds.md) -- the roots with bounds go through ONE
+    ``mce_param_marginals_bounded_dev`` call per wave and distinct (probs, grid, scale), each with its own bounds; the others as before.
     ``contours`` (by the same rule): the 2-D joint densities, modes and credible levels of the pairs of every such root's chosen parameters
     in ``info["contours"]`` -- ONE ``mce_param_contours_dev`` call per wave and per distinct (probs, grid, scale, columns), at the same place.
     Without a GPU: ``RuntimeError``."""
@@ -287,7 +305,10 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     mars = _per_root_marginals(marginals, n)
     for v in mars:
         _marginals.spec(v)
-    mar_kw = [{"marginals": v} if _marginals.wanted(v) else {} for v in mars]
+    bnds = _per_root_bounds(bounds, n)
+    for v, b, r in zip(mars, bnds, roots):
+        _marginals.refuse_bounds(b, v, root=r if isinstance(r, str) else None)
+    mar_kw = [dict({"marginals": v}, **({} if b is None else {"bounds": b})) if _marginals.wanted(v) else {} for v, b in zip(mars, bnds)]
     cons = _per_root_marginals(contours, n)
     for v in cons:
         _contours.spec(v)
@@ -327,7 +348,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             try:
                 reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i],
                                    converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i], covariance=covs[i], marginals=mars[i],
-                                   contours=cons[i])
+                                   contours=cons[i], bounds=bnds[i])
             except ValueError as e:                # (thin_corr together with thinlen; a converge or jackknife value no route takes)
                 fail(i, e)
                 continue
@@ -489,12 +510,27 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                                      _res.summary_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9], r.problem[10]) for r in sasked],
                                                               _summary.targets(probs), device, stream.cuda_stream)))
                 # marginals: the ready roots that ask for them in one call per distinct (probs, grid, scale), while the gathered rows are raw
-                mblks = {}
+                # (a root with bounds: the bounded call, each root with its own; bounds that do not fit a root's parameters fail it alone)
+                mblks, mbnds = {}, {}
+                for r in [r for r in ready if _marginals.wanted(mars[r.index]) and bnds[r.index] is not None]:
+                    rname = roots[r.index] if isinstance(roots[r.index], str) else None
+                    try:
+                        mbnds[r.index] = _marginals.bounds_spec(bnds[r.index], names=_summary.param_names(rname, r.problem[6]), root=rname, marginals=mars[r.index])
+                        _marginals.note_contours(cons[r.index])
+                    except ValueError as e:
+                        fail(r.index, e)
+                ready = [r for r in ready if not (_marginals.wanted(mars[r.index]) and bnds[r.index] is not None and r.index not in mbnds)]
                 for msp in sorted(set(_marginals.spec(mars[r.index]) for r in ready if _marginals.wanted(mars[r.index]))):
-                    masked = [r for r in ready if _marginals.wanted(mars[r.index]) and _marginals.spec(mars[r.index]) == msp]
-                    mblks.update(zip((r.index for r in masked),
-                                     _res.marginals_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in masked],
-                                                                msp, device, stream.cuda_stream)))
+                    masked = [r for r in ready if _marginals.wanted(mars[r.index]) and _marginals.spec(mars[r.index]) == msp and r.index not in mbnds]
+                    if masked:
+                        mblks.update(zip((r.index for r in masked),
+                                         _res.marginals_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in masked],
+                                                                    msp, device, stream.cuda_stream)))
+                    masked = [r for r in ready if _marginals.wanted(mars[r.index]) and _marginals.spec(mars[r.index]) == msp and r.index in mbnds]
+                    if masked:
+                        mblks.update(zip((r.index for r in masked),
+                                         _res.marginals_bounded_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in masked],
+                                                                            [mbnds[r.index] for r in masked], msp, device, stream.cuda_stream)))
                 # contours: likewise, one call per distinct (probs, grid, scale, columns); a root whose ``params`` do not fit its own
                 # parameters fails alone, with the ValueError of ``contours.spec``
                 conblks, cspecs = {}, {}

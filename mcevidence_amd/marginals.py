@@ -20,10 +20,20 @@ other than 0 every value is NaN.  col_status 7: sd_j is 0, or h_j, c_j or step_j
 pieces -1, and the other columns do not notice.  Either logs one WARNING, raises nothing and leaves ln E alone.  ``measure`` is the rule
 in NumPy, ``from_block`` takes the device's result block (``_capi.param_marginals_dev``), ``build`` makes ``info["marginals"]`` from
 either, ``lines`` the lines that are logged and printed, ``save`` the ``.npz`` file of ``--marginals-out``.
+
+``bounds=`` next to ``marginals=`` (csrc/param_marginals_bounds.hpp; docs/design/marginals_bounds.md) honours hard prior bounds (L, U) of
+a column: a used value outside them is col_status 8; the grid ends on a bound it would cross (at_lo / at_hi); S_jk is joined by
+R_jk = sum a_i K(..) (x_ij - g_k), and with T0 = S / norm, T1 = (R / h) / norm and the moments a0, a1, a2 of the standard normal kernel
+inside the bounds the density is Jones' linear boundary kernel in its positive form, rho = f0 exp(min(f1 / f0, 4) - 1), f0 = T0 / a0,
+f1 = (a2 T0 - a1 T1) / (a0 a2 - a1^2); the HPD sums count half a cell where the grid ends on a bound.  A column without bounds keeps its
+bits.  ``bounds_spec`` resolves the keyword's value, ``measure_bounded`` is the rule in NumPy, ``from_block_bounded`` takes the block of
+``_capi.param_marginals_bounded_dev``.
 """
 from __future__ import annotations
 
 import logging
+import math
+import os
 
 import numpy as np
 
@@ -32,7 +42,8 @@ from . import summary as _summary
 logger = logging.getLogger("mcevidence_amd")
 
 __all__ = ["wanted", "spec", "refuse", "measure", "measure_native", "decide", "hpd_selection", "grid_points", "from_block", "build", "lines", "save", "STATUS_WORDS", "DEFAULT_PROBS",
-           "MAX_PROBS", "GRIDS", "DEFAULT_GRID", "UNDERFLOW"]
+           "MAX_PROBS", "GRIDS", "DEFAULT_GRID", "UNDERFLOW", "bounds_spec", "measure_bounded", "measure_bounded_native", "decide_bounded",
+           "hpd_selection_bounded", "boundary_constants", "boundary_density", "from_block_bounded", "COLUMN_OUTSIDE"]
 
 OK, NOT_FINITE, NO_WEIGHT, FEW_ROWS, COLUMN_BAD = 0, 3, 5, 6, 7
 STATUS_WORDS = dict(_summary.STATUS_WORDS)
@@ -235,23 +246,306 @@ def measure_native(a, x, probs, grid=DEFAULT_GRID, scale=1.0, device=None):
 
 
 def build(blk, spec_, names=None):
-    """``info["marginals"]`` from a block (``measure`` / ``from_block``) and the keyword's ``spec``; a status other than 0, or columns
-    with one, log ONE WARNING"""
+    """``info["marginals"]`` from a block (``measure`` / ``from_block``, or their bounded forms: then with bound_lo, bound_hi, at_lo and
+    at_hi) and the keyword's ``spec``; a status other than 0, or columns with one, log ONE WARNING"""
     probs, grid, scale = spec_
     d = len(blk["mean"])
-    bad = [j for j in range(d) if blk["col_status"][j] == COLUMN_BAD]
+    bad = [j for j in range(d) if blk["col_status"][j] in (COLUMN_BAD, COLUMN_OUTSIDE)]
     if blk["status"] != OK:
         logger.warning("marginals: status %d (%s): every value is NaN" % (blk["status"], STATUS_WORDS[blk["status"]]))
     elif bad:
-        logger.warning("marginals: column status %d (%s) in column%s %s: NaN there" % (COLUMN_BAD, STATUS_WORDS[COLUMN_BAD], "s" if len(bad) > 1 else "",
-                                                                                      ", ".join(str(j) for j in bad)))
+        kinds = sorted(set(int(blk["col_status"][j]) for j in bad))
+        logger.warning("marginals: column status %s (%s) in column%s %s: NaN there" % (
+            ", ".join(str(k) for k in kinds), "; ".join(STATUS_WORDS[k] for k in kinds), "s" if len(bad) > 1 else "", ", ".join(str(j) for j in bad)))
     with np.errstate(all="ignore"):
         ess = blk["W"] * blk["W"] / blk["A2"]
-    return {"probs": tuple(probs), "grid": int(grid), "scale": float(scale), "rows": blk["rows"], "sum_w": blk["W"], "ess": ess,
-            "names": list(names) if names is not None else ["p%d" % j for j in range(d)],
-            "mean": blk["mean"], "sd": blk["sd"], "h": blk["h"], "c": blk["c"], "grid_lo": blk["lo"], "grid_step": blk["step"],
-            "density": blk["density"], "mode": blk["mode"], "mode_density": blk["mode_density"], "lower": blk["lower"], "upper": blk["upper"],
-            "pieces": blk["pieces"], "edge": blk["edge"], "col_status": blk["col_status"], "status": blk["status"], "column": blk["column"]}
+    out = {"probs": tuple(probs), "grid": int(grid), "scale": float(scale), "rows": blk["rows"], "sum_w": blk["W"], "ess": ess,
+           "names": list(names) if names is not None else ["p%d" % j for j in range(d)],
+           "mean": blk["mean"], "sd": blk["sd"], "h": blk["h"], "c": blk["c"], "grid_lo": blk["lo"], "grid_step": blk["step"],
+           "density": blk["density"], "mode": blk["mode"], "mode_density": blk["mode_density"], "lower": blk["lower"], "upper": blk["upper"],
+           "pieces": blk["pieces"], "edge": blk["edge"], "col_status": blk["col_status"], "status": blk["status"], "column": blk["column"]}
+    for k in BOUND_KEYS:
+        if k in blk:
+            out[k] = blk[k]
+    return out
+
+
+# ---- bounds=: hard prior bounds (csrc/param_marginals_bounds.hpp; docs/design/marginals_bounds.md) -------------------------------
+COLUMN_OUTSIDE = 8
+STATUS_WORDS[COLUMN_OUTSIDE] = "a sample lies outside the column's bounds"
+PER_COL_BOUNDED = 14                                   # PER_COL's rows, then bound_lo, bound_hi, at_lo, at_hi
+BOUND_KEYS = ("bound_lo", "bound_hi", "at_lo", "at_hi")
+FAR = 40.0                                             # kMarbFar: phi and psi are 0 from here on
+MAX_SLOPE = 4.0                                        # kMarbMaxSlope: the cap on f1 / f0
+SQRT_2 = 1.4142135623730951
+_BOUNDS_EXPECTED = "None, 'ranges', a mapping name -> (lo, hi) or a sequence of one (lo, hi) pair per parameter expected"
+_erf = np.frompyfunc(math.erf, 1, 1)
+
+
+def _bound_side(v, sign, whole):
+    """one side of a pair: None, 'N' or an infinity: open"""
+    if v is None or (isinstance(v, str) and v.strip() in ("N", "None")):
+        return sign * np.inf
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("bounds=%r: %s" % (whole, _BOUNDS_EXPECTED))
+    if v != v:
+        raise ValueError("bounds=%r: a bound is NaN" % (whole,))
+    return sign * np.inf if np.isinf(v) else v
+
+
+def bounds_spec(bounds, names=None, ndim=None, root=None, marginals=True):
+    """the keyword's value -> (lo[d], hi[d]) float64 arrays (-inf / +inf: that side is open), or None where it is not set.  ``names``: the
+    d parameters in use (None: p0, p1, ..); ``root``: what ``"ranges"`` reads (``prior.bounds``), None on a route without a root name.
+    A name the file or the mapping does not list is unbounded.  ``ValueError`` beginning ``bounds=``: lo >= hi, a NaN, a mapping's name
+    that is not among the parameters in use, a sequence of another length, ``"ranges"`` without a root, ``bounds`` without
+    ``marginals``"""
+    if bounds is None:
+        return None
+    if not wanted(marginals):
+        raise ValueError("bounds=%r without marginals: the bounds are those of the 1-D marginal densities" % (bounds,))
+    if names is None and ndim is None:
+        raise ValueError("bounds=%r: the number of parameters is not known here" % (bounds,))
+    d = len(names) if names is not None else int(ndim)
+    names = list(names) if names is not None else ["p%d" % j for j in range(d)]
+    pairs = [(None, None)] * d
+    if isinstance(bounds, str):
+        if bounds != "ranges":
+            raise ValueError("bounds=%r: %s" % (bounds, _BOUNDS_EXPECTED))
+        if root is None:
+            raise ValueError("bounds='ranges' needs a root name whose .ranges or log.param file lists the bounds: give a mapping or a sequence here")
+        from . import prior
+        try:
+            listed = prior.bounds(root)
+        except ValueError as e:
+            raise ValueError("bounds='ranges': %s" % (str(e).split(": ", 1)[-1],))
+        pairs = [listed.get(n, (None, None)) for n in names]
+        import os
+        if not os.path.isfile(str(root) + ".paramnames") and not any(n in listed for n in names):
+            # (a root without .paramnames: the columns are the listed parameters that are not fixed, in the file's order)
+            free = [p for p in listed.values() if p[0] < p[1]]
+            pairs = [free[j] if j < len(free) else (None, None) for j in range(d)]
+    elif isinstance(bounds, dict):
+        unknown = [k for k in bounds if k not in names]
+        if unknown:
+            raise ValueError("bounds=%r: %s not among the parameters in use (%s)" % (bounds, ", ".join(repr(k) for k in unknown), ", ".join(names)))
+        pairs = [bounds.get(n, (None, None)) for n in names]
+    else:
+        try:
+            pairs = [None if p is None else tuple(p) for p in bounds]
+        except TypeError:
+            raise ValueError("bounds=%r: %s" % (bounds, _BOUNDS_EXPECTED))
+        if len(pairs) != d:
+            raise ValueError("bounds=%r: %d pairs for %d parameters" % (bounds, len(pairs), d))
+    lo, hi = np.full(d, -np.inf), np.full(d, np.inf)
+    for j, p in enumerate(pairs):
+        if p is None:
+            continue
+        if len(p) != 2:
+            raise ValueError("bounds=%r: %s" % (bounds, _BOUNDS_EXPECTED))
+        lo[j], hi[j] = _bound_side(p[0], -1.0, bounds), _bound_side(p[1], +1.0, bounds)
+        if not lo[j] < hi[j]:
+            raise ValueError("bounds=%r: lo >= hi for %s (%r, %r)" % (bounds, names[j], p[0], p[1]))
+    return lo, hi
+
+
+def refuse_bounds(bounds, marginals, root=True):
+    """what every route refuses before any work: ``bounds`` without ``marginals``, a string other than "ranges", "ranges" on a route
+    without a root name (``root=None``)"""
+    if bounds is None:
+        return
+    if not wanted(marginals):
+        raise ValueError("bounds=%r without marginals: the bounds are those of the 1-D marginal densities" % (bounds,))
+    if isinstance(bounds, str):
+        if bounds != "ranges":
+            raise ValueError("bounds=%r: %s" % (bounds, _BOUNDS_EXPECTED))
+        if root is None:
+            raise ValueError("bounds='ranges' needs a root name whose .ranges or log.param file lists the bounds: give a mapping or a sequence here")
+
+
+def note_contours(contours):
+    """marginals with bounds next to contours: ONE INFO line"""
+    if contours is not None and contours is not False:
+        logger.info("contours: the 2-D densities are not boundary-corrected; bounds= applies to the 1-D marginals alone")
+
+
+def _phi(t):
+    with np.errstate(all="ignore"):
+        return np.where(t >= FAR, 0.0, np.exp(-((t * t) / 2.0)) / SQRT_2PI)
+
+
+def _psi(t):
+    with np.errstate(all="ignore"):
+        return np.where(t >= FAR, 0.0, t * _phi(t))
+
+
+def boundary_constants(g, L, U, h):
+    """step 5' at the grid points ``g`` -> (a0, a1, a2, den)"""
+    with np.errstate(all="ignore"):
+        p, q = (g - L) / h, (U - g) / h
+        a0 = 0.5 * (_erf(q / SQRT_2).astype(np.float64) + _erf(p / SQRT_2).astype(np.float64))
+        a1 = _phi(p) - _phi(q)
+        a2 = (a0 - _psi(q)) - _psi(p)
+        return a0, a1, a2, a0 * a2 - a1 * a1
+
+
+def boundary_density(T0, T1, a0, a1, a2, den):
+    """step 6': Jones' linear boundary kernel in its positive form"""
+    with np.errstate(all="ignore"):
+        f0 = T0 / a0
+        f1 = (a2 * T0 - a1 * T1) / den
+        pos = f0 > 0.0
+        slope = np.minimum(np.where(pos, f1 / np.where(pos, f0, 1.0), 0.0), MAX_SLOPE)
+        rho = np.where(pos, f0 * np.exp(slope - 1.0), 0.0)
+        return np.where(pos & ~(np.isfinite(den) & (den > 0.0)), f0, rho)
+
+
+def end_weights(G, at_lo, at_hi):
+    w = np.ones(G)
+    if at_lo:
+        w[0] = 0.5
+    if at_hi:
+        w[G - 1] = 0.5
+    return w
+
+
+def hpd_selection_bounded(rho, probs, at_lo, at_hi):
+    """step 8' on one column's densities -> (order, [the mask of the selected grid points of every p]): ``hpd_selection`` with half a
+    cell where the grid ends on a bound"""
+    rho = np.asarray(rho, dtype=np.float64)
+    G = rho.size
+    order = np.lexsort((np.arange(G), -rho))
+    cum = np.cumsum((end_weights(G, at_lo, at_hi) * rho)[order])
+    masks = []
+    for p in probs:
+        cut = min(int(np.searchsorted(cum, p * cum[-1], side="left")), G - 1)
+        sel = np.zeros(G, dtype=bool)
+        sel[order[:cut + 1]] = True
+        masks.append(sel)
+    return order, masks
+
+
+def decide_bounded(rho, lo, step, probs, at_lo, at_hi):
+    """steps 7' and 8' on one column's densities -> what ``decide`` returns"""
+    rho = np.asarray(rho, dtype=np.float64)
+    G = rho.size
+    order, masks = hpd_selection_bounded(rho, probs, at_lo, at_hi)
+    g = grid_points(lo, step, G)
+    lower, upper, pieces, edge = [], [], [], []
+    for sel in masks:
+        at = np.flatnonzero(sel)
+        lower.append(g[at[0]])
+        upper.append(g[at[-1]])
+        pieces.append(float(np.count_nonzero(sel & ~np.concatenate(([False], sel[:-1])))))
+        edge.append(1.0 if sel[0] or sel[-1] else 0.0)
+    return g[order[0]], rho[order[0]], np.array(lower), np.array(upper), np.array(pieces), np.array(edge)
+
+
+def measure_bounded(a, x, bounds, probs, grid=DEFAULT_GRID, scale=1.0, at=None):
+    """The rule with bounds on host arrays: ``measure``'s arguments and ``bounds`` = (lo[d], hi[d]) (``bounds_spec``) -> ``measure``'s
+    dict with bound_lo, bound_hi, at_lo, at_hi [d] (at_lo / at_hi: 1 where the grid ends on the bound).  col_status 8: a used value
+    outside its bounds.  ``at``: another route's block, whose reported h, c, lo and step are taken, as in ``measure``"""
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    x = np.asarray(x, dtype=np.float64)
+    x = x.reshape(a.size, -1) if x.ndim != 2 else x
+    probs = tuple(float(p) for p in probs)
+    G = int(grid)
+    if x.shape[0] != a.size:
+        raise ValueError("marginals: %d weights, %d rows" % (a.size, x.shape[0]))
+    d, npr = x.shape[1], len(probs)
+    L, U = (np.asarray(v, dtype=np.float64).reshape(-1) for v in bounds)
+    if L.size != d or U.size != d or not np.all(L < U):
+        raise ValueError("bounds=%r: one lo < hi per column expected" % (bounds,))
+    use = a != 0.0
+    a, x = a[use], x[use]
+    with np.errstate(all="ignore"):
+        W = float(np.sum(a))
+        status, column = OK, _summary.COLUMN_NONE
+        badcols = np.flatnonzero(~np.isfinite(x).all(axis=0)) if a.size else np.zeros(0, dtype=int)
+        if not (np.isfinite(a).all() and (a >= 0.0).all()):
+            status = NOT_FINITE
+        elif badcols.size:
+            status, column = NOT_FINITE, int(badcols[0])
+        elif not W > 0.0:
+            status = NO_WEIGHT
+        elif a.size < 2:
+            status = FEW_ROWS
+        out = _nan_block(d, npr, G, a.size, status, column)
+        for k in BOUND_KEYS:
+            out[k] = np.full(d, np.nan)
+        if status != OK:
+            return out
+        out["bound_lo"], out["bound_hi"] = L.copy(), U.copy()
+        A2 = float(np.sum(a * a))
+        out["W"], out["A2"] = W, A2
+        ess = W * W / A2
+        mean = np.sum(a[:, None] * x, axis=0) / W
+        dev = x - mean[None, :]
+        var = np.sum(a[:, None] * (dev * dev), axis=0) / W
+        sd = np.sqrt(var)
+        h = (scale * sd) * np.float64(4.0 / (3.0 * ess)) ** 0.2
+        c = 1.0 / ((2.0 * h) * h)
+        mn, mx = x.min(axis=0), x.max(axis=0)
+        lo, hi = mn - 3.0 * h, mx + 3.0 * h
+        base = (sd > 0.0) & np.isfinite(h) & (h > 0.0) & np.isfinite(c) & (c > 0.0) & np.isfinite((hi - lo) / float(G - 1)) & ((hi - lo) / float(G - 1) > 0.0)
+        outside = (mn < L) | (mx > U)
+        at_lo, at_hi = L >= lo, U <= hi
+        lo, hi = np.where(at_lo, L, lo), np.where(at_hi, U, hi)
+        step = (hi - lo) / float(G - 1)
+        if at is not None:
+            keep = np.asarray(at["col_status"]) == OK
+            h, c, lo, step = (np.where(keep, np.asarray(at[k], dtype=np.float64), v) for k, v in (("h", h), ("c", c), ("lo", lo), ("step", step)))
+            at_lo, at_hi = (np.where(keep, np.asarray(at[k]) == 1.0, v) for k, v in (("at_lo", at_lo), ("at_hi", at_hi)))
+        good = base & ~outside & np.isfinite(step) & (step > 0.0)
+        out["col_status"] = np.where(base, np.where(outside, float(COLUMN_OUTSIDE), np.where(good, float(OK), float(COLUMN_BAD))), float(COLUMN_BAD))
+        rows_at_a_time = max(1, CHUNK_BYTES // (8 * G))
+        for j in range(d):
+            if not good[j]:
+                out["pieces"][:, j] = -1.0
+                continue
+            for k, v in (("mean", mean), ("var", var), ("sd", sd), ("h", h), ("c", c), ("lo", lo), ("step", step)):
+                out[k][j] = v[j]
+            out["at_lo"][j], out["at_hi"][j] = float(at_lo[j]), float(at_hi[j])
+            g = grid_points(lo[j], step[j], G)
+            S, R = np.zeros(G), np.zeros(G)
+            for r0 in range(0, a.size, rows_at_a_time):
+                e = g[None, :] - x[r0:r0 + rows_at_a_time, j][:, None]
+                arg = c[j] * (e * e)
+                t = a[r0:r0 + rows_at_a_time, None] * np.where(arg >= UNDERFLOW, 0.0, np.exp(-arg))
+                S += np.sum(t, axis=0)
+                R += np.sum(t * -e, axis=0)
+            norm = (W * h[j]) * SQRT_2PI
+            rho = boundary_density(S / norm, (R / h[j]) / norm, *boundary_constants(g, L[j], U[j], h[j]))
+            out["density"][j] = rho
+            out["mode"][j], out["mode_density"][j], out["lower"][:, j], out["upper"][:, j], out["pieces"][:, j], out["edge"][:, j] = decide_bounded(
+                rho, lo[j], step[j], probs, bool(at_lo[j]), bool(at_hi[j]))
+        return out
+
+
+def from_block_bounded(block, d, npr, G):
+    """one system's result block of ``mce_param_marginals_bounded_dev`` -> what ``measure_bounded`` returns"""
+    block = np.asarray(block, dtype=np.float64)
+    P = PER_COL_BOUNDED
+    col = block[HEAD:HEAD + P * d].reshape(P, d)
+    per = block[HEAD + P * d:HEAD + (P + PER_P * npr) * d].reshape(npr, PER_P, d)
+    out = dict(W=float(block[0]), A2=float(block[1]), rows=int(block[2]), status=int(block[3]), column=int(block[4]), grid=int(G))
+    for i, k in enumerate(("mean", "var", "sd", "h", "c", "lo", "step", "mode", "mode_density", "col_status") + BOUND_KEYS):
+        out[k] = col[i].copy()
+    for i, k in enumerate(("lower", "upper", "pieces", "edge")):
+        out[k] = per[:, i, :].copy()
+    out["density"] = block[HEAD + (P + PER_P * npr) * d:].reshape(d, G).copy()
+    return out
+
+
+def measure_bounded_native(a, x, bounds, probs, grid=DEFAULT_GRID, scale=1.0, device=None):
+    """``measure_bounded`` by the library from HOST arrays (``mce_param_marginals_bounded_f64``, uploaded to ``device``)"""
+    from . import _capi
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    x = x.reshape(a.size, -1) if x.ndim != 2 else x
+    blk, = _capi.param_marginals_bounded([(x, x.shape[1], a)], [bounds], probs, grid, scale, device=int(device or 0))
+    return from_block_bounded(blk, x.shape[1], len(probs), grid)
 
 
 def lines(m):
@@ -282,4 +576,7 @@ def save(path, roots, infos):
         arrays["names_%d" % r] = np.array(m["names"])
         arrays["grid_%d" % r] = np.stack([grid_points(lo, st, G) for lo, st in zip(m["grid_lo"], m["grid_step"])]) if len(m["names"]) else np.zeros((0, G))
         arrays["density_%d" % r] = np.asarray(m["density"])
+        for k in ("bound_lo", "bound_hi", "at_lo", "at_hi"):   # (with bounds= alone)
+            if k in m:
+                arrays["%s_%d" % (k, r)] = np.asarray(m[k])
     np.savez(path, **arrays)

@@ -83,6 +83,43 @@ def params_info(fname, cosmo=False, volumes={}):
     return par
 
 
+def _side(tok, sign):
+    """one side of a listed bound: 'N', 'None', an empty token or an infinity of either sign: open (-> sign * inf)"""
+    tok = tok.strip().strip("'\"")
+    if tok in ("N", "None", ""):
+        return sign * np.inf
+    v = float(tok)
+    return sign * np.inf if np.isinf(v) else v
+
+
+def bounds(fname):
+    """The hard prior bounds of EVERY parameter ``fname.ranges`` (CosmoMC: ``name min max``) or ``fname/log.param`` (MontePython:
+    ``data.parameters['x'] = [mean, min, max, ...]``) lists -> {name: (lo, hi)}, -inf / +inf where a side is open ('N' / None).  Fixed
+    and derived parameters are listed as the file has them, and an open side never raises; what ``marginals``' ``bounds="ranges"``
+    reads.  Neither file: ``ValueError``."""
+    out = {}
+    if glob.glob("{}*.ranges".format(glob.escape(fname))):
+        with open(fname + ".ranges") as fh:
+            for line in fh:
+                tok = line.split()
+                if len(tok) < 3 or tok[0].startswith("#"):
+                    continue
+                out[tok[0]] = (_side(tok[1], -1.0), _side(tok[2], +1.0))
+    elif glob.glob("{}/log.param".format(glob.escape(fname))):
+        pat = re.compile(r"^\s*data\.parameters\[\s*['\"]([^'\"]+)['\"]\s*\]\s*=\s*\[([^\]]*)\]")
+        with open("{}/log.param".format(fname)) as fh:
+            for line in fh:
+                m = pat.search(line)
+                if not m:
+                    continue
+                arr = m.group(2).split(",")
+                if len(arr) >= 3:
+                    out[m.group(1)] = (_side(arr[1], -1.0), _side(arr[2], +1.0))
+    else:
+        raise ValueError("bounds='ranges': neither %s.ranges nor %s/log.param is there" % (fname, fname))
+    return out
+
+
 def get_prior_volume(args, **kwargs):
     """Prior volume from the chain's range files; also sets ``args.ndim`` (reference
     :1312-1339 -- whose interactive fallback is unreachable, so failures propagate)."""

@@ -72,7 +72,7 @@ class ResidentDecline(Exception):
 
 def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all", split=False, ndim=None, nparam=None,
          distributed=False, ncols=None, nrows=None, ischain=True, thin_corr=None, converge=None, converge_by="auto", jackknife=None, nchains=None,
-         summary=None, covariance=None, marginals=None, contours=None):
+         summary=None, covariance=None, marginals=None, contours=None, bounds=None):
     """``"resident"`` or the reason why the route declines.  A pure function of the call's keywords and of what is known
     about the data at the time (``ncols``: the files' column counts, ``nrows``: rows left after burn-in / thinning,
     ``nparam``: parameter columns; None: not known yet).  ``thin_corr`` (thinning by the measured autocorrelation length) is resident
@@ -83,9 +83,11 @@ def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all"
     ``by`` it cannot take is the ValueError every route raises.  ``summary`` (the posterior summary of the parameters) is resident work
     and declines nothing; a value it cannot take is the ValueError every route raises.  ``covariance`` (the weighted mean and covariance
     matrix of the parameters) is resident work too: it is validated and declines nothing; so is ``marginals`` (the 1-D marginal densities), and so is
-    ``contours`` (the 2-D joint densities of the parameter pairs)."""
+    ``contours`` (the 2-D joint densities of the parameter pairs).  ``bounds`` (the hard prior bounds of the marginals) declines nothing either; without
+    ``marginals`` it is the ValueError every route raises."""
     _summary.spec(summary)
     _marginals.spec(marginals)
+    _marginals.refuse_bounds(bounds, marginals)
     _contours.spec(contours)
     _covariance.spec(covariance)
     if not ischain:
@@ -262,6 +264,18 @@ def marginals_measure_dev(systems, spec, device, stream):
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
     blocks = _capi.param_marginals_dev(systems, probs, grid, scale, ws.data_ptr(), wsb, stream)
     return [_marginals.from_block(b, s[3], len(probs), grid) for b, s in zip(blocks, systems)]
+
+
+def marginals_bounded_measure_dev(systems, bounds, spec, device, stream):
+    """ONE ``mce_param_marginals_bounded_dev`` call for ``systems`` (as ``marginals_measure_dev`` takes them), ``bounds`` = one
+    (lo[d], hi[d]) per system (``marginals.bounds_spec``) and ``spec`` -> one ``marginals.measure_bounded`` dict per system"""
+    import torch
+    from . import _capi
+    probs, grid, scale = spec
+    wsb = _capi.param_marginals_bounded_workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(probs), grid)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
+    blocks = _capi.param_marginals_bounded_dev(systems, bounds, probs, grid, scale, ws.data_ptr(), wsb, stream)
+    return [_marginals.from_block_bounded(b, s[3], len(probs), grid) for b, s in zip(blocks, systems)]
 
 
 def covariance_measure_dev(systems, device, stream):
@@ -610,7 +624,7 @@ class ResidentChains(object):
     # -- the estimator ---------------------------------------------------------------------------------------------------
     def evidence(self, kmax=5, ndim=None, priorvolume=1, covtype="all", pos_lnp=False, split=False, s1frac=0.5, split_rows=None,
                  info=False, backend=None, information=None, jackknife=None, summary=None, covariance=None, marginals=None,
-                 contours=None):
+                 contours=None, bounds=None):
         """ln E as ``MCEvidence(...).evidence(...)`` returns it (``MLE[1:]``, and the info dict if ``info=True``; it
         carries ``info["route"] = "resident"``).  ``split=True``: the reference's random split, drawn on the host with the
         call ``MCSamples.chain_split`` makes (same RNG consumption); ``split_rows=(s1, s2)``: ``set_split``.
@@ -629,7 +643,8 @@ class ResidentChains(object):
         first ``ndim`` parameters in ``info["marginals"]`` (and ``self.marginals``), from one ``mce_param_marginals_dev`` call there too.
         ``contours`` (None, True, probabilities or dict(probs, grid, scale, params)): the 2-D joint densities, modes and credible levels
         of the pairs of the chosen parameters in ``info["contours"]`` (and ``self.contours``), from one ``mce_param_contours_dev`` call
-        at the same place."""
+        at the same place.  ``bounds`` (None, "ranges", a mapping name -> (lo, hi) or one (lo, hi) per parameter): the hard prior bounds
+        of the marginals (docs/design/marginals_bounds.md); then the one call is ``mce_param_marginals_bounded_dev``'s."""
         from . import _capi
         from .evidence import HipBackend
         backend = backend or HipBackend()
@@ -644,6 +659,10 @@ class ResidentChains(object):
         probs = _summary.spec(summary)
         want_cov = _covariance.spec(covariance) is not None
         mspec = _marginals.spec(marginals)
+        _marginals.refuse_bounds(bounds, marginals, root=self.names_root)
+        bnd = _marginals.bounds_spec(bounds, names=_summary.param_names(self.names_root, nd), root=self.names_root, marginals=marginals)
+        if bnd is not None:
+            _marginals.note_contours(contours)
         cnames = _summary.param_names(self.names_root, nd) if _contours.wanted(contours) else None
         cspec = _contours.spec(contours, ndim=nd, names=cnames)
         torch = self._torch
@@ -679,7 +698,11 @@ class ResidentChains(object):
             mblk = None
             if mspec is not None:
                 t0 = time.perf_counter()
-                mblk, = marginals_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())], mspec, self.device, self._stream())
+                msys = [(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())]
+                if bnd is None:
+                    mblk, = marginals_measure_dev(msys, mspec, self.device, self._stream())
+                else:
+                    mblk, = marginals_bounded_measure_dev(msys, [bnd], mspec, self.device, self._stream())
                 ms["marginals"] = _ms(t0)
             conblk = None
             if cspec is not None:
@@ -778,6 +801,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     _information.refuse(ctor.get("information"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _summary.refuse(ctor.get("summary"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _marginals.refuse(ctor.get("marginals"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
+    _marginals.refuse_bounds(ctor.get("bounds"), ctor.get("marginals"), root=root if isinstance(root, str) else None)
     _contours.refuse(ctor.get("contours"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _covariance.refuse(ctor.get("covariance"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     reason = RESIDENT if _is_file_root(root) else REASONS["not_files"]
@@ -787,7 +811,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
                       distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"),
                       converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"), jackknife=ctor.get("jackknife"),
                       summary=ctor.get("summary"), covariance=ctor.get("covariance"), marginals=ctor.get("marginals"),
-                      contours=ctor.get("contours"))
+                      contours=ctor.get("contours"), bounds=ctor.get("bounds"))
     if reason == RESIDENT:
         level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
         if not logging.getLogger().handlers:
@@ -806,7 +830,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,
                               backend=ctor.get("backend"), information=ctor.get("information"), jackknife=ctor.get("jackknife"),
                               summary=ctor.get("summary"), covariance=ctor.get("covariance"), marginals=ctor.get("marginals"),
-                              contours=ctor.get("contours"))
+                              contours=ctor.get("contours"), bounds=ctor.get("bounds"))
             mle, inf = got
             if ctor.get("verbose", 1) > 0:
                 log_information(inf)

@@ -887,16 +887,44 @@ def marginals_block_doubles(d, np_, grid):
     return MCE_MARGINALS_HEAD + int(d) * (10 + 4 * int(np_) + int(grid))
 
 
-def _param_marginals(call, segs, probs, grid, scale, tail):
+def _host_systems(systems, who):
+    """``systems`` = [(x[n, ld], d, w)] host arrays -> (what keeps them alive, [(address of x, ld, n, d, address of w)])"""
+    keep = []
+    for x, d, w in systems:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if x.shape[0] != w.size:
+            raise ValueError("%s: rows and w of one length expected" % who)
+        keep.append((x, int(d), w))
+    return keep, [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
+
+
+def _param_marginals(call, segs, bounds, probs, grid, scale, tail):
+    """``bounds``: None (the plain entry points), or per system (lo[d], hi[d]) -> the HOST array of a bounded call, 2 d doubles per
+    segment, which goes in front of ``probs``"""
     arr = (SummarySeg * max(len(segs), 1))()
     for i, (x, ld, n, d, w) in enumerate(segs):
         arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, None
+    extra = ()
+    if bounds is not None:
+        if len(bounds) != len(segs):
+            raise ValueError("param marginals: one pair of bounds arrays per system expected")
+        flat = []
+        for (_, _, _, d, _), (lo, hi) in zip(segs, bounds):
+            lo, hi = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (lo, hi))
+            if lo.size != max(int(d), 0) or hi.size != lo.size:
+                raise ValueError("param marginals: %d lower and %d upper bounds for %d columns" % (lo.size, hi.size, d))
+            flat += [lo, hi]
+        flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0))
+        extra = (flat.ctypes.data if flat.size else None,)
+    block_doubles = marginals_block_doubles if bounds is None else marginals_bounded_block_doubles
     probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
     npr, grid = probs.size, int(grid)
     shape_ok = 1 <= npr <= MCE_MARGINALS_MAX_P and grid in (64, 128, 256, 512, 1024)
-    sizes = [marginals_block_doubles(d, npr, grid) if shape_ok and 1 <= int(d) <= 127 else 0 for _, _, _, d, _ in segs]
+    sizes = [block_doubles(d, npr, grid) if shape_ok and 1 <= int(d) <= 127 else 0 for _, _, _, d, _ in segs]
     out = np.full(max(sum(sizes), 1), np.nan)
-    check(call(_c.cast(arr, _P), len(segs), probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
+    check(call(_c.cast(arr, _P), len(segs), *extra, probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
     at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
     return [out[at[i]:at[i + 1]] for i in range(len(segs))]
 
@@ -905,21 +933,13 @@ def param_marginals_dev(segs, probs, grid, scale, ws, ws_bytes, stream=0):
     """mce_param_marginals_dev: the 1-D marginal densities, modes and HPD regions of ``len(segs)`` systems that are on the device -> one
     float64 block per system (``marginals.from_block`` reads it); ``segs``: [(device address of the rows, row stride in doubles, rows,
     measured columns, device address of w)]"""
-    return _param_marginals(load().mce_param_marginals_dev, segs, probs, grid, scale, (ws or None, int(ws_bytes), stream or None))
+    return _param_marginals(load().mce_param_marginals_dev, segs, None, probs, grid, scale, (ws or None, int(ws_bytes), stream or None))
 
 
 def param_marginals(systems, probs, grid, scale, device=0):
     """mce_param_marginals_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
-    keep = []
-    for x, d, w in systems:
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
-        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-        if x.shape[0] != w.size:
-            raise ValueError("param marginals: rows and w of one length expected")
-        keep.append((x, int(d), w))
-    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
-    return _param_marginals(load().mce_param_marginals_f64, segs, probs, grid, scale, (int(device),))
+    keep, segs = _host_systems(systems, "param marginals")
+    return _param_marginals(load().mce_param_marginals_f64, segs, None, probs, grid, scale, (int(device),))
 
 
 def param_marginals_bounded_out_doubles(d, np_, grid):
@@ -935,48 +955,16 @@ def marginals_bounded_block_doubles(d, np_, grid):
     return MCE_MARGINALS_HEAD + int(d) * (14 + 4 * int(np_) + int(grid))
 
 
-def _param_marginals_bounded(call, segs, bounds, probs, grid, scale, tail):
-    """``bounds``: per system (lo[d], hi[d]) -> the HOST array of the call, 2 d doubles per segment"""
-    arr = (SummarySeg * max(len(segs), 1))()
-    for i, (x, ld, n, d, w) in enumerate(segs):
-        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, None
-    if len(bounds) != len(segs):
-        raise ValueError("param marginals: one pair of bounds arrays per system expected")
-    flat = []
-    for (_, _, _, d, _), (lo, hi) in zip(segs, bounds):
-        lo, hi = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (lo, hi))
-        if lo.size != max(int(d), 0) or hi.size != lo.size:
-            raise ValueError("param marginals: %d lower and %d upper bounds for %d columns" % (lo.size, hi.size, d))
-        flat += [lo, hi]
-    flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0))
-    probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
-    npr, grid = probs.size, int(grid)
-    shape_ok = 1 <= npr <= MCE_MARGINALS_MAX_P and grid in (64, 128, 256, 512, 1024)
-    sizes = [marginals_bounded_block_doubles(d, npr, grid) if shape_ok and 1 <= int(d) <= 127 else 0 for _, _, _, d, _ in segs]
-    out = np.full(max(sum(sizes), 1), np.nan)
-    check(call(_c.cast(arr, _P), len(segs), flat.ctypes.data if flat.size else None, probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
-    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
-    return [out[at[i]:at[i + 1]] for i in range(len(segs))]
-
-
 def param_marginals_bounded_dev(segs, bounds, probs, grid, scale, ws, ws_bytes, stream=0):
     """mce_param_marginals_bounded_dev: ``param_marginals_dev`` with hard prior bounds, ``bounds`` = [(lo[d], hi[d])] per system (HOST
     arrays, -inf / +inf: open) -> one float64 block per system (``marginals.from_block_bounded`` reads it)"""
-    return _param_marginals_bounded(load().mce_param_marginals_bounded_dev, segs, bounds, probs, grid, scale, (ws or None, int(ws_bytes), stream or None))
+    return _param_marginals(load().mce_param_marginals_bounded_dev, segs, bounds, probs, grid, scale, (ws or None, int(ws_bytes), stream or None))
 
 
 def param_marginals_bounded(systems, bounds, probs, grid, scale, device=0):
     """mce_param_marginals_bounded_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
-    keep = []
-    for x, d, w in systems:
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
-        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-        if x.shape[0] != w.size:
-            raise ValueError("param marginals: rows and w of one length expected")
-        keep.append((x, int(d), w))
-    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
-    return _param_marginals_bounded(load().mce_param_marginals_bounded_f64, segs, bounds, probs, grid, scale, (int(device),))
+    keep, segs = _host_systems(systems, "param marginals")
+    return _param_marginals(load().mce_param_marginals_bounded_f64, segs, bounds, probs, grid, scale, (int(device),))
 
 
 def param_contours_out_doubles(nc, np_, grid):

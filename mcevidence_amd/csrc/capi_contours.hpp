@@ -207,18 +207,11 @@ int mce_param_contours_f64(const mce_summary_seg* segs, int32_t nseg, const int3
     int rc = con_tables(segs, nseg, cols, nc, probs, np, grid, scale, T);
     if (rc != MCE_OK) return rc;
     if ((rc = select_device(device)) != MCE_OK) return rc;
-    size_t elems = 0;
-    for (int32_t s = 0; s < nseg; ++s) elems += (size_t)segs[s].n * ((size_t)segs[s].d + 1);
     SegStage data;
     DevBuf ws;
-    if ((rc = data.alloc(elems * sizeof(double))) != MCE_OK) return rc;
-    std::vector<mce_summary_seg> dsegs(segs, segs + nseg);
-    for (mce_summary_seg& g : dsegs) {
-        // the d measured columns, packed: ld = d on the device
-        if ((rc = data.put(g.x, (size_t)g.n, g.x, (size_t)g.d, (size_t)g.ld)) != MCE_OK || (rc = data.put(g.w, (size_t)g.n, g.w)) != MCE_OK) return rc;
-        g.ld = g.d;
-        g.fs = nullptr;
-    }
+    std::vector<mce_summary_seg> dsegs;
+    if ((rc = seg_stage_xw(segs, nseg, data, dsegs)) != MCE_OK) return rc;
+    for (mce_summary_seg& g : dsegs) g.fs = nullptr;             // (the likelihood column is not an input)
     const size_t wsb = mce_param_contours_workspace_bytes(T.tiles.nrows, nseg, T.dmax, nc, np, grid);
     MCE_HIP(ws.alloc(wsb));
     return mce_param_contours_dev(dsegs.data(), nseg, cols, nc, probs, np, grid, scale, out, ws.p, wsb, nullptr);

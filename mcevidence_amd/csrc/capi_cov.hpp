@@ -139,17 +139,10 @@ int mce_param_cov_f64(const mce_cov_seg* segs, int32_t nseg, double* out, int32_
     int rc = cov_tables(segs, nseg, T);
     if (rc != MCE_OK) return rc;
     if ((rc = select_device(device)) != MCE_OK) return rc;
-    size_t elems = 0;
-    for (int32_t s = 0; s < nseg; ++s) elems += (size_t)segs[s].n * ((size_t)segs[s].d + 1);
     SegStage data;
     DevBuf ws;
-    if ((rc = data.alloc(elems * sizeof(double))) != MCE_OK) return rc;
-    std::vector<mce_cov_seg> dsegs(segs, segs + nseg);
-    for (mce_cov_seg& g : dsegs) {
-        // the d measured columns, packed: ld = d on the device
-        if ((rc = data.put(g.x, (size_t)g.n, g.x, (size_t)g.d, (size_t)g.ld)) != MCE_OK || (rc = data.put(g.w, (size_t)g.n, g.w)) != MCE_OK) return rc;
-        g.ld = g.d;
-    }
+    std::vector<mce_cov_seg> dsegs;
+    if ((rc = seg_stage_xw(segs, nseg, data, dsegs)) != MCE_OK) return rc;
     const size_t wsb = mce_param_cov_workspace_bytes(T.tiles.nrows, nseg, T.dmax);
     MCE_HIP(ws.alloc(wsb));
     return mce_param_cov_dev(dsegs.data(), nseg, out, ws.p, wsb, nullptr);

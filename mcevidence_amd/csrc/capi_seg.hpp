@@ -1,5 +1,5 @@
 // capi_seg.hpp -- part of capi.hip (one translation unit): what the host sides of the segment-tile families (capi_moments.hpp,
-// capi_jackres.hpp, capi_summary.hpp; the scheme: seg_tiles.hpp) share: the opening of their _dev forms and the staging of their
+// capi_jackres.hpp, capi_summary.hpp, capi_cov.hpp, capi_marginals.hpp, capi_contours.hpp; the scheme: seg_tiles.hpp) share: the opening of their _dev forms and the staging of their
 // host-pointer forms.  Each family keeps its own argument checks and error texts.
 #pragma once
 
@@ -47,5 +47,21 @@ struct SegStage {
         return MCE_OK;
     }
 };
+
+// the staging of a host-pointer form whose segments are (x, ld, n, d, w): of every segment the d measured columns packed (ld = d on the
+// device), then the weights, in one buffer of `data`; dsegs: the segments at their device addresses
+template <class Seg> int seg_stage_xw(const Seg* segs, int32_t nseg, SegStage& data, std::vector<Seg>& dsegs)
+{
+    size_t elems = 0;
+    for (int32_t s = 0; s < nseg; ++s) elems += (size_t)segs[s].n * ((size_t)segs[s].d + 1);
+    int rc = data.alloc(elems * sizeof(double));
+    if (rc != MCE_OK) return rc;
+    dsegs.assign(segs, segs + nseg);
+    for (Seg& g : dsegs) {
+        if ((rc = data.put(g.x, (size_t)g.n, g.x, (size_t)g.d, (size_t)g.ld)) != MCE_OK || (rc = data.put(g.w, (size_t)g.n, g.w)) != MCE_OK) return rc;
+        g.ld = g.d;
+    }
+    return MCE_OK;
+}
 
 }  // namespace

@@ -13,7 +13,7 @@
 //                        visits the part's rows in row order, so a pair's bits depend on the system's rows, the two columns, G and scale
 //                        alone.  S[part][pair][G * G] is written per part; the parts' boundaries depend on n alone (con_part_tile).
 //   con_fold_kernel      per (system, pair) and block of 256 cells: the parts in part order, then rho = S / (W h_i h_j 2 pi), into the block
-//   con_region_kernel    one workgroup per (system, pair): a bitonic sort of the (rho, k) pairs in LDS on mar_before, the running sums by
+//   con_region_kernel    one workgroup per (system, pair): density_order.hpp's sort of the (rho, k) pairs in LDS, the running sums by
 //                        ONE thread in sorted order, then per probability the cut by all threads, box and edge by block reductions
 //   con_result_kernel    one workgroup per system: the head and the column rows of the result block
 #pragma once
@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "block_reduce.hpp"
+#include "density_order.hpp"
 #include "param_contours.hpp"
 #include "param_summary_kernels.hpp"
 #include "seg_tiles.hpp"
@@ -274,25 +275,9 @@ __global__ __launch_bounds__(kConThreads) void con_region_kernel(const ConSeg* _
     const double* rho = con_dens_rows(block, nc, np) + (int64_t)p * N;
     for (int k = threadIdx.x; k < N; k += kConThreads) { s_rho[k] = rho[k]; s_k[k] = k; }
     __syncthreads();
-    // the bitonic network on mar_before: N is a power of two
-    for (int size = 2; size <= N; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int a = threadIdx.x; a < N; a += kConThreads) {
-                const int b = a ^ stride;
-                if (b > a) {
-                    const bool up = (a & size) == 0;             // this pair ends in the order of step 6
-                    const double ra = s_rho[a], rb = s_rho[b];
-                    const int ka = s_k[a], kb = s_k[b];
-                    const bool b_first = mce_mar::mar_before(rb, kb, ra, ka);
-                    if (b_first == up) { s_rho[a] = rb; s_rho[b] = ra; s_k[a] = kb; s_k[b] = ka; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    order_sort(s_rho, s_k, N);                                   // (N is a power of two)
     if (threadIdx.x == 0) {
-        double run = 0.0;
-        for (int q = 0; q < N; ++q) { run += s_rho[q]; s_cum[q] = run; }
+        order_running_sum(s_rho, N, s_cum);
         pairr[mce_con::kConModeX * P] = mce_mar::mar_grid_point(lox, stepx, s_k[0] / G);
         pairr[mce_con::kConModeY * P] = mce_mar::mar_grid_point(loy, stepy, s_k[0] % G);
         pairr[mce_con::kConModeDensity * P] = s_rho[0];
@@ -301,11 +286,7 @@ __global__ __launch_bounds__(kConThreads) void con_region_kernel(const ConSeg* _
     __syncthreads();
     const double Z = s_cum[N - 1];
     for (int q = 0; q < np; ++q) {
-        const double target = probs[q] * Z;
-        double first = (double)(N - 1);                          // (no position reaches the target: all of them)
-        for (int i = threadIdx.x; i < N; i += kConThreads)
-            if (s_cum[i] >= target && (double)i < first) first = (double)i;
-        const int cut = (int)block_min(first, red);
+        const int cut = order_cut(s_cum, N, probs[q] * Z, red);
         double x0 = (double)G, x1 = -1.0, y0 = (double)G, y1 = -1.0, edge = 0.0;
         for (int i = threadIdx.x; i <= cut; i += kConThreads) {
             const int kx = s_k[i] / G, ky = s_k[i] % G;

@@ -28,7 +28,8 @@
 //   * mar_before                                                 the order of step 6;
 //   * mar_status, the result block's layout (kMar.., mar_out_doubles);
 //   * mar_decide                                                 steps 5 and 6 on a density array: serial, so bit-reproducible;
-//   * mar_serial                                                 the serial driver: the whole rule on one CPU thread.
+//   * mar_serial                                                 the serial driver: the whole rule on one CPU thread
+//     (both forward to the one text of param_marginals_bounds.hpp, which serves the rule with bounds too).
 #pragma once
 
 #include <stdint.h>
@@ -169,114 +170,25 @@ MCE_HD inline void mar_pack_head(int status, int column, double W, double A2, do
 
 namespace mce_mar {
 
+// The drivers are one text for the rule without and with bounds (param_marginals_bounds.hpp, at the end of this file, has them, behind
+// the pieces of its rule that they call): mar_decide_ends with the end flags of step 8', mar_serial_bounds with bounds that may be null.
+inline void mar_decide_ends(const double* rho, int G, double lo, double step, bool at_lo, bool at_hi, const double* probs, int np, double* mode, double* dec);
+inline void mar_serial_bounds(const double* x, int64_t ld, int64_t n, int d, const double* w, const double* bounds, const double* probs, int np, int G, double scale,
+                              double* out);
+
 // steps 5 and 6 on the G densities of one column: mode[2] = the mode and its density; dec[p * kMarPerP ..]: lower, upper, pieces, edge
 inline void mar_decide(const double* rho, int G, double lo, double step, const double* probs, int np, double* mode, double* dec)
 {
-    std::vector<int> order((size_t)G);
-    for (int k = 0; k < G; ++k) order[(size_t)k] = k;
-    std::sort(order.begin(), order.end(), [rho](int a, int b) { return mar_before(rho[a], a, rho[b], b); });
-    std::vector<double> cum((size_t)G);
-    double run = 0.0;
-    for (int p = 0; p < G; ++p) {
-        run += rho[order[(size_t)p]];
-        cum[(size_t)p] = run;
-    }
-    const double Z = run;
-    mode[0] = mar_grid_point(lo, step, order[0]);
-    mode[1] = rho[order[0]];
-    std::vector<char> sel((size_t)G);
-    for (int t = 0; t < np; ++t) {
-        const double target = probs[t] * Z;
-        int cut = G - 1;
-        for (int p = 0; p < G; ++p)
-            if (cum[(size_t)p] >= target) { cut = p; break; }
-        std::fill(sel.begin(), sel.end(), 0);
-        for (int p = 0; p <= cut; ++p) sel[(size_t)order[(size_t)p]] = 1;
-        int kmin = G, kmax = -1, pieces = 0;
-        for (int k = 0; k < G; ++k) {
-            if (!sel[(size_t)k]) continue;
-            kmin = k < kmin ? k : kmin;
-            kmax = k;
-            pieces += (k == 0 || !sel[(size_t)k - 1]) ? 1 : 0;
-        }
-        dec[t * kMarPerP + kMarLower] = mar_grid_point(lo, step, kmin);
-        dec[t * kMarPerP + kMarUpper] = mar_grid_point(lo, step, kmax);
-        dec[t * kMarPerP + kMarPieces] = (double)pieces;
-        dec[t * kMarPerP + kMarEdge] = (sel[0] || sel[(size_t)G - 1]) ? 1.0 : 0.0;
-    }
+    mar_decide_ends(rho, G, lo, step, false, false, probs, np, mode, dec);
 }
 
 // out: mar_out_doubles(d, np, G) doubles
 inline void mar_serial(const double* x, int64_t ld, int64_t n, int d, const double* w, const double* probs, int np, int G, double scale, double* out)
 {
-    using namespace mce_sum;
-    const double nan = __builtin_nan("");
-    double W = 0.0, A2 = 0.0, rows = 0.0;
-    bool badw = false;
-    int badcol = -1;
-    std::vector<int64_t> used;
-    for (int64_t i = 0; i < n; ++i) {
-        const double a = w[i];
-        if (!sum_used(a)) continue;
-        used.push_back(i);
-        badw = badw || sum_weight_bad(a);
-        for (int j = 0; j < d; ++j)
-            if (sum_value_bad(x[i * ld + j]) && (badcol < 0 || j < badcol)) badcol = j;
-        W += a;
-        A2 += a * a;
-        rows += 1.0;
-    }
-    int column;
-    const int status = mar_status(badw, badcol, W, rows, &column);
-    mar_pack_head(status, column, W, A2, rows, G, np, out);
-    double* col = out + kMarHead;
-    const int64_t total = (int64_t)d * (kMarPerCol + kMarPerP * np + G);
-    for (int64_t k = 0; k < total; ++k) col[k] = nan;
-    if (status != kMarOk) return;
-    double* per_p = col + (int64_t)kMarPerCol * d;
-    double* dens = per_p + (int64_t)kMarPerP * np * d;
-    std::vector<double> dec((size_t)(kMarPerP * (np > 0 ? np : 1)));
-    for (int j = 0; j < d; ++j) {
-        double S = 0.0, mn = HUGE_VAL, mx = -HUGE_VAL;
-        for (int64_t i : used) {
-            const double v = x[i * ld + j];
-            S += w[i] * v;
-            mn = v < mn ? v : mn;
-            mx = v > mx ? v : mx;
-        }
-        const double m = S / W;
-        double V = 0.0;
-        for (int64_t i : used) V += sum_term(w[i], x[i * ld + j], m);
-        double sd, h, c, lo, step;
-        const int cs = mar_params(W, A2, V / W, mn, mx, scale, G, &sd, &h, &c, &lo, &step);
-        col[kMarColStatus * d + j] = (double)cs;
-        if (cs != kMarOk) {
-            for (int t = 0; t < np; ++t) per_p[(t * kMarPerP + kMarPieces) * d + j] = -1.0;
-            continue;
-        }
-        col[kMarMean * d + j] = m;
-        col[kMarVar * d + j] = V / W;
-        col[kMarSd * d + j] = sd;
-        col[kMarH * d + j] = h;
-        col[kMarC * d + j] = c;
-        col[kMarLo * d + j] = lo;
-        col[kMarStep * d + j] = step;
-        double* rho = dens + (int64_t)j * G;
-        const double norm = mar_norm(W, h);
-        for (int k = 0; k < G; ++k) {
-            const double g = mar_grid_point(lo, step, k);
-            double acc = 0.0;
-            for (int64_t i : used) acc = mar_add(acc, w[i], mar_arg(c, g, x[i * ld + j]));
-            rho[k] = acc / norm;
-        }
-        double mode[2];
-        mar_decide(rho, G, lo, step, probs, np, mode, dec.data());
-        col[kMarMode * d + j] = mode[0];
-        col[kMarModeDensity * d + j] = mode[1];
-        for (int t = 0; t < np; ++t)
-            for (int q = 0; q < kMarPerP; ++q) per_p[(t * kMarPerP + q) * d + j] = dec[(size_t)(t * kMarPerP + q)];
-    }
+    mar_serial_bounds(x, ld, n, d, w, nullptr, probs, np, G, scale, out);
 }
 
 }  // namespace mce_mar
 #endif
+
+#include "param_marginals_bounds.hpp"                           // (last: it opens with this file, whichever of the two is named first)

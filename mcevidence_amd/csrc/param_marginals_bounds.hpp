@@ -1,7 +1,7 @@
 // param_marginals_bounds.hpp -- marginals= with bounds=: the 1-D marginal densities of param_marginals.hpp where a parameter has hard
 // prior bounds (L, U): the grid ends on a bound it would cross, the density is Jones' linear boundary kernel in Jones & Foster's positive
 // form, and the HPD sums give a grid that ends on a bound half a cell there.  Shared by the host check
-// (tests/native/param_marginals_bounds_check.cpp, plain C++17 under g++) and the device kernels (param_marginals_bounds_kernels.hpp),
+// (tests/native/param_marginals_bounds_check.cpp, plain C++17 under g++) and the device kernels (param_marginals_kernels.hpp),
 // as param_marginals.hpp is.  docs/design/marginals_bounds.md states the rule; mcevidence_amd/marginals.py (measure_bounded) restates
 // it in NumPy.
 //
@@ -25,7 +25,8 @@
 //   * marb_consts, marb_density                                  steps 5' and 6';
 //   * marb_weighted                                              the end weights of step 8';
 //   * the result block's layout (kMarb.., marb_out_doubles);
-//   * marb_decide, marb_serial                                   the serial drivers.
+//   * mar_decide_ends, mar_serial_bounds                         the serial drivers of BOTH rules (mar_decide, mar_serial, marb_decide and
+//                                                                marb_serial forward to them).
 #pragma once
 
 #include "param_marginals.hpp"
@@ -142,12 +143,13 @@ MCE_HD inline double marb_weighted(double rho, int k, int G, bool at_lo, bool at
 
 }  // namespace mce_marb
 
-// ---- the serial drivers (host) --------------------------------------------------------------------------------------------------
+// ---- the serial drivers (host): ONE text for param_marginals.hpp's rule and this one ----------------------------------------------
 #if !defined(__HIP_DEVICE_COMPILE__)
-namespace mce_marb {
+namespace mce_mar {
 
-// steps 7' and 8' on the G densities of one column: as mar_decide, with the end weights
-inline void marb_decide(const double* rho, int G, double lo, double step, bool at_lo, bool at_hi, const double* probs, int np, double* mode, double* dec)
+// steps 5 and 6 (7' and 8') on the G densities of one column: mode[2] = the mode and its density; dec[p * kMarPerP ..]: lower, upper,
+// pieces, edge.  at_lo / at_hi: the end weights of step 8' (neither: every weight is 1, and marb_weighted hands rho back as it is)
+inline void mar_decide_ends(const double* rho, int G, double lo, double step, bool at_lo, bool at_hi, const double* probs, int np, double* mode, double* dec)
 {
     std::vector<int> order((size_t)G);
     for (int k = 0; k < G; ++k) order[(size_t)k] = k;
@@ -155,7 +157,7 @@ inline void marb_decide(const double* rho, int G, double lo, double step, bool a
     std::vector<double> cum((size_t)G);
     double run = 0.0;
     for (int p = 0; p < G; ++p) {
-        run += marb_weighted(rho[order[(size_t)p]], order[(size_t)p], G, at_lo, at_hi);
+        run += mce_marb::marb_weighted(rho[order[(size_t)p]], order[(size_t)p], G, at_lo, at_hi);
         cum[(size_t)p] = run;
     }
     const double Z = run;
@@ -183,12 +185,15 @@ inline void marb_decide(const double* rho, int G, double lo, double step, bool a
     }
 }
 
-// bounds: lo[d], then hi[d].  out: marb_out_doubles(d, np, G) doubles
-inline void marb_serial(const double* x, int64_t ld, int64_t n, int d, const double* w, const double* bounds, const double* probs, int np, int G, double scale,
-                        double* out)
+// the whole rule on one CPU thread.  bounds: null (param_marginals.hpp's rule, out: mar_out_doubles(d, np, G) doubles), or lo[d], then
+// hi[d] (this file's, out: marb_out_doubles(d, np, G) doubles)
+inline void mar_serial_bounds(const double* x, int64_t ld, int64_t n, int d, const double* w, const double* bounds, const double* probs, int np, int G, double scale,
+                              double* out)
 {
     using namespace mce_sum;
+    using namespace mce_marb;
     const double nan = __builtin_nan("");
+    const int per_col = bounds ? (int)kMarbPerCol : (int)kMarPerCol;
     double W = 0.0, A2 = 0.0, rows = 0.0;
     bool badw = false;
     int badcol = -1;
@@ -207,16 +212,16 @@ inline void marb_serial(const double* x, int64_t ld, int64_t n, int d, const dou
     int column;
     const int status = mar_status(badw, badcol, W, rows, &column);
     mar_pack_head(status, column, W, A2, rows, G, np, out);
-    out[kMarReserved] = 1.0;
+    if (bounds) out[kMarReserved] = 1.0;
     double* col = out + kMarHead;
-    const int64_t total = (int64_t)d * (kMarbPerCol + kMarPerP * np + G);
+    const int64_t total = (int64_t)d * (per_col + kMarPerP * np + G);
     for (int64_t k = 0; k < total; ++k) col[k] = nan;
     if (status != kMarOk) return;
-    double* per_p = col + (int64_t)kMarbPerCol * d;
+    double* per_p = col + (int64_t)per_col * d;
     double* dens = per_p + (int64_t)kMarPerP * np * d;
     std::vector<double> dec((size_t)(kMarPerP * (np > 0 ? np : 1)));
     for (int j = 0; j < d; ++j) {
-        const double L = bounds[j], U = bounds[d + j];
+        const double L = bounds ? bounds[j] : nan, U = bounds ? bounds[d + j] : nan;
         double S = 0.0, mn = HUGE_VAL, mx = -HUGE_VAL;
         for (int64_t i : used) {
             const double v = x[i * ld + j];
@@ -227,11 +232,14 @@ inline void marb_serial(const double* x, int64_t ld, int64_t n, int d, const dou
         const double m = S / W;
         double V = 0.0;
         for (int64_t i : used) V += sum_term(w[i], x[i * ld + j], m);
-        double sd, h, c, lo, step, at_lo, at_hi;
-        const int cs = marb_params(W, A2, V / W, mn, mx, L, U, scale, G, &sd, &h, &c, &lo, &step, &at_lo, &at_hi);
+        double sd, h, c, lo, step, at_lo = 0.0, at_hi = 0.0;
+        const int cs = bounds ? marb_params(W, A2, V / W, mn, mx, L, U, scale, G, &sd, &h, &c, &lo, &step, &at_lo, &at_hi)
+                              : mar_params(W, A2, V / W, mn, mx, scale, G, &sd, &h, &c, &lo, &step);
         col[kMarColStatus * d + j] = (double)cs;
-        col[kMarbBoundLo * d + j] = L;
-        col[kMarbBoundHi * d + j] = U;
+        if (bounds) {
+            col[kMarbBoundLo * d + j] = L;
+            col[kMarbBoundHi * d + j] = U;
+        }
         if (cs != kMarOk) {
             for (int t = 0; t < np; ++t) per_p[(t * kMarPerP + kMarPieces) * d + j] = -1.0;
             continue;
@@ -243,12 +251,20 @@ inline void marb_serial(const double* x, int64_t ld, int64_t n, int d, const dou
         col[kMarC * d + j] = c;
         col[kMarLo * d + j] = lo;
         col[kMarStep * d + j] = step;
-        col[kMarbAtLo * d + j] = at_lo;
-        col[kMarbAtHi * d + j] = at_hi;
+        if (bounds) {
+            col[kMarbAtLo * d + j] = at_lo;
+            col[kMarbAtHi * d + j] = at_hi;
+        }
         double* rho = dens + (int64_t)j * G;
         const double norm = mar_norm(W, h);
         for (int k = 0; k < G; ++k) {
             const double g = mar_grid_point(lo, step, k);
+            if (!bounds) {
+                double acc = 0.0;
+                for (int64_t i : used) acc = mar_add(acc, w[i], mar_arg(c, g, x[i * ld + j]));
+                rho[k] = acc / norm;
+                continue;
+            }
             double s0 = 0.0, s1 = 0.0;
             for (int64_t i : used) marb_term(c, g, x[i * ld + j], w[i], &s0, &s1);
             double a0, a1, a2, den;
@@ -256,12 +272,29 @@ inline void marb_serial(const double* x, int64_t ld, int64_t n, int d, const dou
             rho[k] = marb_density(marb_t0(s0, norm), marb_t1(s1, h, norm), a0, a1, a2, den);
         }
         double mode[2];
-        marb_decide(rho, G, lo, step, at_lo != 0.0, at_hi != 0.0, probs, np, mode, dec.data());
+        mar_decide_ends(rho, G, lo, step, at_lo != 0.0, at_hi != 0.0, probs, np, mode, dec.data());
         col[kMarMode * d + j] = mode[0];
         col[kMarModeDensity * d + j] = mode[1];
         for (int t = 0; t < np; ++t)
             for (int q = 0; q < kMarPerP; ++q) per_p[(t * kMarPerP + q) * d + j] = dec[(size_t)(t * kMarPerP + q)];
     }
+}
+
+}  // namespace mce_mar
+
+namespace mce_marb {
+
+// steps 7' and 8' on the G densities of one column
+inline void marb_decide(const double* rho, int G, double lo, double step, bool at_lo, bool at_hi, const double* probs, int np, double* mode, double* dec)
+{
+    mar_decide_ends(rho, G, lo, step, at_lo, at_hi, probs, np, mode, dec);
+}
+
+// bounds: lo[d], then hi[d].  out: marb_out_doubles(d, np, G) doubles
+inline void marb_serial(const double* x, int64_t ld, int64_t n, int d, const double* w, const double* bounds, const double* probs, int np, int G, double scale,
+                        double* out)
+{
+    mar_serial_bounds(x, ld, n, d, w, bounds, probs, np, G, scale, out);
 }
 
 }  // namespace mce_marb

@@ -56,7 +56,8 @@ DEFAULT_GRID = 512
 UNDERFLOW = 746.0                                      # kKdeUnderflow of csrc/kde_shift.hpp: a kernel value at or above it is +0.0
 SQRT_2PI = 2.5066282746310002
 HEAD = 8                                               # MCE_MARGINALS_HEAD: W, A2, rows used, status, column, grid, np, reserved
-PER_COL = 10                                           # mean, var, sd, h, c, lo, step, mode, mode_density, col_status
+COL_KEYS = ("mean", "var", "sd", "h", "c", "lo", "step", "mode", "mode_density", "col_status")
+PER_COL = len(COL_KEYS)                                # the per-column rows of a result block
 PER_P = 4                                              # lower, upper, pieces, edge
 _EXPECTED = "None, True, up to %d probabilities 0 < p < 1, or a dict of probs, grid (one of %s) and scale (finite, > 0) expected" % (
     MAX_PROBS, ", ".join(str(g) for g in GRIDS))
@@ -111,7 +112,7 @@ def _nan_block(d, npr, G, rows, status, column):
     nan = float("nan")
     col = np.full(d, nan)
     blk = dict(W=nan, A2=nan, rows=int(rows), status=int(status), column=int(column), grid=int(G))
-    for k in ("mean", "var", "sd", "h", "c", "lo", "step", "mode", "mode_density", "col_status"):
+    for k in COL_KEYS:
         blk[k] = col.copy()
     for k in ("lower", "upper", "pieces", "edge"):
         blk[k] = np.full((npr, d), nan)
@@ -124,12 +125,22 @@ def grid_points(lo, step, G):
     return lo + np.arange(G, dtype=np.float64) * step
 
 
-def hpd_selection(rho, probs):
-    """step 6 on one column's densities -> (order, [the mask of the selected grid points of every p])"""
+def end_weights(G, at_lo, at_hi):
+    """the weights of step 8': half a cell where the grid ends on a bound"""
+    w = np.ones(G)
+    if at_lo:
+        w[0] = 0.5
+    if at_hi:
+        w[G - 1] = 0.5
+    return w
+
+
+def _hpd_selection(rho, probs, ends=None):
+    """step 6 (``ends`` = (at_lo, at_hi): step 8', with ``end_weights``) on one column's densities"""
     rho = np.asarray(rho, dtype=np.float64)
     G = rho.size
     order = np.lexsort((np.arange(G), -rho))           # rho descending, then k ascending
-    cum = np.cumsum(rho[order])                        # (serial, in that order)
+    cum = np.cumsum(rho[order] if ends is None else (end_weights(G, *ends) * rho)[order])      # (serial, in that order)
     masks = []
     for p in probs:
         cut = min(int(np.searchsorted(cum, p * cum[-1], side="left")), G - 1)
@@ -139,11 +150,15 @@ def hpd_selection(rho, probs):
     return order, masks
 
 
-def decide(rho, lo, step, probs):
-    """steps 5 and 6 on one column's densities -> (mode, mode_density, lower[np], upper[np], pieces[np], edge[np])"""
+def hpd_selection(rho, probs):
+    """step 6 on one column's densities -> (order, [the mask of the selected grid points of every p])"""
+    return _hpd_selection(rho, probs)
+
+
+def _decide(rho, lo, step, probs, ends=None):
     rho = np.asarray(rho, dtype=np.float64)
     G = rho.size
-    order, masks = hpd_selection(rho, probs)
+    order, masks = _hpd_selection(rho, probs, ends)
     g = grid_points(lo, step, G)
     lower, upper, pieces, edge = [], [], [], []
     for sel in masks:
@@ -155,11 +170,25 @@ def decide(rho, lo, step, probs):
     return g[order[0]], rho[order[0]], np.array(lower), np.array(upper), np.array(pieces), np.array(edge)
 
 
+def decide(rho, lo, step, probs):
+    """steps 5 and 6 on one column's densities -> (mode, mode_density, lower[np], upper[np], pieces[np], edge[np])"""
+    return _decide(rho, lo, step, probs)
+
+
+def _col_ok(sd, h, c, step):
+    return (sd > 0.0) & np.isfinite(h) & (h > 0.0) & np.isfinite(c) & (c > 0.0) & np.isfinite(step) & (step > 0.0)
+
+
 def measure(a, x, probs, grid=DEFAULT_GRID, scale=1.0, at=None):
     """The rule on host arrays: weights ``a`` [n], values ``x`` [n, d] -> dict(W, A2, rows, status, column, grid, mean, var, sd, h, c,
     lo, step, mode, mode_density, col_status [d], lower, upper, pieces, edge [np][d], density [d][G]); the kernel matrix is formed in
     chunks of rows.  ``at``: another route's block -- its reported h, c, lo and step are taken instead of this form's own (the densities
     are defined at the reported values, and two routes' pow may differ in the last place): what a comparison of two routes needs"""
+    return _measure(a, x, probs, grid, scale, at)
+
+
+def _measure(a, x, probs, grid, scale, at, bounds=None):
+    """``measure`` (``bounds`` None: no R, no boundary step, no bound keys) and ``measure_bounded`` (``bounds`` = (lo[d], hi[d]))"""
     a = np.asarray(a, dtype=np.float64).reshape(-1)
     x = np.asarray(x, dtype=np.float64)
     x = x.reshape(a.size, -1) if x.ndim != 2 else x
@@ -168,6 +197,10 @@ def measure(a, x, probs, grid=DEFAULT_GRID, scale=1.0, at=None):
     if x.shape[0] != a.size:
         raise ValueError("marginals: %d weights, %d rows" % (a.size, x.shape[0]))
     d, npr = x.shape[1], len(probs)
+    if bounds is not None:
+        L, U = (np.asarray(v, dtype=np.float64).reshape(-1) for v in bounds)
+        if L.size != d or U.size != d or not np.all(L < U):
+            raise ValueError("bounds=%r: one lo < hi per column expected" % (bounds,))
     use = a != 0.0                                     # (a NaN weight is used: it is what status 3 reports)
     a, x = a[use], x[use]
     with np.errstate(all="ignore"):
@@ -183,8 +216,13 @@ def measure(a, x, probs, grid=DEFAULT_GRID, scale=1.0, at=None):
         elif a.size < 2:
             status = FEW_ROWS
         out = _nan_block(d, npr, G, a.size, status, column)
+        if bounds is not None:
+            for k in BOUND_KEYS:
+                out[k] = np.full(d, np.nan)
         if status != OK:
             return out
+        if bounds is not None:
+            out["bound_lo"], out["bound_hi"] = L.copy(), U.copy()
         A2 = float(np.sum(a * a))
         out["W"], out["A2"] = W, A2
         ess = W * W / A2
@@ -194,13 +232,28 @@ def measure(a, x, probs, grid=DEFAULT_GRID, scale=1.0, at=None):
         sd = np.sqrt(var)
         h = (scale * sd) * np.float64(4.0 / (3.0 * ess)) ** 0.2
         c = 1.0 / ((2.0 * h) * h)
-        lo = x.min(axis=0) - 3.0 * h
-        step = ((x.max(axis=0) + 3.0 * h) - lo) / float(G - 1)
+        mn, mx = x.min(axis=0), x.max(axis=0)
+        lo = mn - 3.0 * h
+        if bounds is None:
+            step = ((mx + 3.0 * h) - lo) / float(G - 1)
+        else:                                          # step 3': the column's own grid has to be one; then the ends move onto the bounds
+            hi = mx + 3.0 * h
+            base = _col_ok(sd, h, c, (hi - lo) / float(G - 1))
+            outside = (mn < L) | (mx > U)
+            at_lo, at_hi = L >= lo, U <= hi
+            lo, hi = np.where(at_lo, L, lo), np.where(at_hi, U, hi)
+            step = (hi - lo) / float(G - 1)
         if at is not None:
             keep = np.asarray(at["col_status"]) == OK
             h, c, lo, step = (np.where(keep, np.asarray(at[k], dtype=np.float64), v) for k, v in (("h", h), ("c", c), ("lo", lo), ("step", step)))
-        good = (sd > 0.0) & np.isfinite(h) & (h > 0.0) & np.isfinite(c) & (c > 0.0) & np.isfinite(step) & (step > 0.0)
-        out["col_status"] = np.where(good, float(OK), float(COLUMN_BAD))
+            if bounds is not None:
+                at_lo, at_hi = (np.where(keep, np.asarray(at[k]) == 1.0, v) for k, v in (("at_lo", at_lo), ("at_hi", at_hi)))
+        if bounds is None:
+            good = _col_ok(sd, h, c, step)
+            out["col_status"] = np.where(good, float(OK), float(COLUMN_BAD))
+        else:
+            good = base & ~outside & np.isfinite(step) & (step > 0.0)
+            out["col_status"] = np.where(base, np.where(outside, float(COLUMN_OUTSIDE), np.where(good, float(OK), float(COLUMN_BAD))), float(COLUMN_BAD))
         rows_at_a_time = max(1, CHUNK_BYTES // (8 * G))
         for j in range(d):
             if not good[j]:
@@ -209,38 +262,57 @@ def measure(a, x, probs, grid=DEFAULT_GRID, scale=1.0, at=None):
             for k, v in (("mean", mean), ("var", var), ("sd", sd), ("h", h), ("c", c), ("lo", lo), ("step", step)):
                 out[k][j] = v[j]
             g = grid_points(lo[j], step[j], G)
-            S = np.zeros(G)
+            S, R = np.zeros(G), None if bounds is None else np.zeros(G)
             for r0 in range(0, a.size, rows_at_a_time):
                 e = g[None, :] - x[r0:r0 + rows_at_a_time, j][:, None]
                 arg = c[j] * (e * e)
-                S += np.sum(a[r0:r0 + rows_at_a_time, None] * np.where(arg >= UNDERFLOW, 0.0, np.exp(-arg)), axis=0)
-            rho = S / ((W * h[j]) * SQRT_2PI)
+                t = a[r0:r0 + rows_at_a_time, None] * np.where(arg >= UNDERFLOW, 0.0, np.exp(-arg))
+                S += np.sum(t, axis=0)
+                if R is not None:
+                    R += np.sum(t * -e, axis=0)
+            norm = (W * h[j]) * SQRT_2PI
+            if bounds is None:
+                rho, ends = S / norm, None
+            else:
+                out["at_lo"][j], out["at_hi"][j] = float(at_lo[j]), float(at_hi[j])
+                rho = boundary_density(S / norm, (R / h[j]) / norm, *boundary_constants(g, L[j], U[j], h[j]))
+                ends = (bool(at_lo[j]), bool(at_hi[j]))
             out["density"][j] = rho
-            out["mode"][j], out["mode_density"][j], out["lower"][:, j], out["upper"][:, j], out["pieces"][:, j], out["edge"][:, j] = decide(
-                rho, lo[j], step[j], probs)
+            out["mode"][j], out["mode_density"][j], out["lower"][:, j], out["upper"][:, j], out["pieces"][:, j], out["edge"][:, j] = _decide(
+                rho, lo[j], step[j], probs, ends)
         return out
+
+
+def _from_block(block, d, npr, G, keys):
+    """one system's result block with the per-column rows ``keys`` -> what ``_measure`` returns"""
+    block = np.asarray(block, dtype=np.float64)
+    P = len(keys)
+    col = block[HEAD:HEAD + P * d].reshape(P, d)
+    per = block[HEAD + P * d:HEAD + (P + PER_P * npr) * d].reshape(npr, PER_P, d)
+    out = dict(W=float(block[0]), A2=float(block[1]), rows=int(block[2]), status=int(block[3]), column=int(block[4]), grid=int(G))
+    for i, k in enumerate(keys):
+        out[k] = col[i].copy()
+    for i, k in enumerate(("lower", "upper", "pieces", "edge")):
+        out[k] = per[:, i, :].copy()
+    out["density"] = block[HEAD + (P + PER_P * npr) * d:].reshape(d, G).copy()
+    return out
 
 
 def from_block(block, d, npr, G):
     """one system's result block of ``mce_param_marginals_dev`` -> what ``measure`` returns"""
-    block = np.asarray(block, dtype=np.float64)
-    col = block[HEAD:HEAD + PER_COL * d].reshape(PER_COL, d)
-    per = block[HEAD + PER_COL * d:HEAD + (PER_COL + PER_P * npr) * d].reshape(npr, PER_P, d)
-    out = dict(W=float(block[0]), A2=float(block[1]), rows=int(block[2]), status=int(block[3]), column=int(block[4]), grid=int(G))
-    for i, k in enumerate(("mean", "var", "sd", "h", "c", "lo", "step", "mode", "mode_density", "col_status")):
-        out[k] = col[i].copy()
-    for i, k in enumerate(("lower", "upper", "pieces", "edge")):
-        out[k] = per[:, i, :].copy()
-    out["density"] = block[HEAD + (PER_COL + PER_P * npr) * d:].reshape(d, G).copy()
-    return out
+    return _from_block(block, d, npr, G, COL_KEYS)
+
+
+def _host_system(a, x):
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    return a, (x.reshape(a.size, -1) if x.ndim != 2 else x)
 
 
 def measure_native(a, x, probs, grid=DEFAULT_GRID, scale=1.0, device=None):
     """``measure`` by the library from HOST arrays (``mce_param_marginals_f64``, uploaded to ``device``)"""
     from . import _capi
-    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    x = x.reshape(a.size, -1) if x.ndim != 2 else x
+    a, x = _host_system(a, x)
     blk, = _capi.param_marginals([(x, x.shape[1], a)], probs, grid, scale, device=int(device or 0))
     return from_block(blk, x.shape[1], len(probs), grid)
 
@@ -401,149 +473,33 @@ def boundary_density(T0, T1, a0, a1, a2, den):
         return np.where(pos & ~(np.isfinite(den) & (den > 0.0)), f0, rho)
 
 
-def end_weights(G, at_lo, at_hi):
-    w = np.ones(G)
-    if at_lo:
-        w[0] = 0.5
-    if at_hi:
-        w[G - 1] = 0.5
-    return w
-
-
 def hpd_selection_bounded(rho, probs, at_lo, at_hi):
     """step 8' on one column's densities -> (order, [the mask of the selected grid points of every p]): ``hpd_selection`` with half a
     cell where the grid ends on a bound"""
-    rho = np.asarray(rho, dtype=np.float64)
-    G = rho.size
-    order = np.lexsort((np.arange(G), -rho))
-    cum = np.cumsum((end_weights(G, at_lo, at_hi) * rho)[order])
-    masks = []
-    for p in probs:
-        cut = min(int(np.searchsorted(cum, p * cum[-1], side="left")), G - 1)
-        sel = np.zeros(G, dtype=bool)
-        sel[order[:cut + 1]] = True
-        masks.append(sel)
-    return order, masks
+    return _hpd_selection(rho, probs, (at_lo, at_hi))
 
 
 def decide_bounded(rho, lo, step, probs, at_lo, at_hi):
     """steps 7' and 8' on one column's densities -> what ``decide`` returns"""
-    rho = np.asarray(rho, dtype=np.float64)
-    G = rho.size
-    order, masks = hpd_selection_bounded(rho, probs, at_lo, at_hi)
-    g = grid_points(lo, step, G)
-    lower, upper, pieces, edge = [], [], [], []
-    for sel in masks:
-        at = np.flatnonzero(sel)
-        lower.append(g[at[0]])
-        upper.append(g[at[-1]])
-        pieces.append(float(np.count_nonzero(sel & ~np.concatenate(([False], sel[:-1])))))
-        edge.append(1.0 if sel[0] or sel[-1] else 0.0)
-    return g[order[0]], rho[order[0]], np.array(lower), np.array(upper), np.array(pieces), np.array(edge)
+    return _decide(rho, lo, step, probs, (at_lo, at_hi))
 
 
 def measure_bounded(a, x, bounds, probs, grid=DEFAULT_GRID, scale=1.0, at=None):
     """The rule with bounds on host arrays: ``measure``'s arguments and ``bounds`` = (lo[d], hi[d]) (``bounds_spec``) -> ``measure``'s
     dict with bound_lo, bound_hi, at_lo, at_hi [d] (at_lo / at_hi: 1 where the grid ends on the bound).  col_status 8: a used value
     outside its bounds.  ``at``: another route's block, whose reported h, c, lo and step are taken, as in ``measure``"""
-    a = np.asarray(a, dtype=np.float64).reshape(-1)
-    x = np.asarray(x, dtype=np.float64)
-    x = x.reshape(a.size, -1) if x.ndim != 2 else x
-    probs = tuple(float(p) for p in probs)
-    G = int(grid)
-    if x.shape[0] != a.size:
-        raise ValueError("marginals: %d weights, %d rows" % (a.size, x.shape[0]))
-    d, npr = x.shape[1], len(probs)
-    L, U = (np.asarray(v, dtype=np.float64).reshape(-1) for v in bounds)
-    if L.size != d or U.size != d or not np.all(L < U):
-        raise ValueError("bounds=%r: one lo < hi per column expected" % (bounds,))
-    use = a != 0.0
-    a, x = a[use], x[use]
-    with np.errstate(all="ignore"):
-        W = float(np.sum(a))
-        status, column = OK, _summary.COLUMN_NONE
-        badcols = np.flatnonzero(~np.isfinite(x).all(axis=0)) if a.size else np.zeros(0, dtype=int)
-        if not (np.isfinite(a).all() and (a >= 0.0).all()):
-            status = NOT_FINITE
-        elif badcols.size:
-            status, column = NOT_FINITE, int(badcols[0])
-        elif not W > 0.0:
-            status = NO_WEIGHT
-        elif a.size < 2:
-            status = FEW_ROWS
-        out = _nan_block(d, npr, G, a.size, status, column)
-        for k in BOUND_KEYS:
-            out[k] = np.full(d, np.nan)
-        if status != OK:
-            return out
-        out["bound_lo"], out["bound_hi"] = L.copy(), U.copy()
-        A2 = float(np.sum(a * a))
-        out["W"], out["A2"] = W, A2
-        ess = W * W / A2
-        mean = np.sum(a[:, None] * x, axis=0) / W
-        dev = x - mean[None, :]
-        var = np.sum(a[:, None] * (dev * dev), axis=0) / W
-        sd = np.sqrt(var)
-        h = (scale * sd) * np.float64(4.0 / (3.0 * ess)) ** 0.2
-        c = 1.0 / ((2.0 * h) * h)
-        mn, mx = x.min(axis=0), x.max(axis=0)
-        lo, hi = mn - 3.0 * h, mx + 3.0 * h
-        base = (sd > 0.0) & np.isfinite(h) & (h > 0.0) & np.isfinite(c) & (c > 0.0) & np.isfinite((hi - lo) / float(G - 1)) & ((hi - lo) / float(G - 1) > 0.0)
-        outside = (mn < L) | (mx > U)
-        at_lo, at_hi = L >= lo, U <= hi
-        lo, hi = np.where(at_lo, L, lo), np.where(at_hi, U, hi)
-        step = (hi - lo) / float(G - 1)
-        if at is not None:
-            keep = np.asarray(at["col_status"]) == OK
-            h, c, lo, step = (np.where(keep, np.asarray(at[k], dtype=np.float64), v) for k, v in (("h", h), ("c", c), ("lo", lo), ("step", step)))
-            at_lo, at_hi = (np.where(keep, np.asarray(at[k]) == 1.0, v) for k, v in (("at_lo", at_lo), ("at_hi", at_hi)))
-        good = base & ~outside & np.isfinite(step) & (step > 0.0)
-        out["col_status"] = np.where(base, np.where(outside, float(COLUMN_OUTSIDE), np.where(good, float(OK), float(COLUMN_BAD))), float(COLUMN_BAD))
-        rows_at_a_time = max(1, CHUNK_BYTES // (8 * G))
-        for j in range(d):
-            if not good[j]:
-                out["pieces"][:, j] = -1.0
-                continue
-            for k, v in (("mean", mean), ("var", var), ("sd", sd), ("h", h), ("c", c), ("lo", lo), ("step", step)):
-                out[k][j] = v[j]
-            out["at_lo"][j], out["at_hi"][j] = float(at_lo[j]), float(at_hi[j])
-            g = grid_points(lo[j], step[j], G)
-            S, R = np.zeros(G), np.zeros(G)
-            for r0 in range(0, a.size, rows_at_a_time):
-                e = g[None, :] - x[r0:r0 + rows_at_a_time, j][:, None]
-                arg = c[j] * (e * e)
-                t = a[r0:r0 + rows_at_a_time, None] * np.where(arg >= UNDERFLOW, 0.0, np.exp(-arg))
-                S += np.sum(t, axis=0)
-                R += np.sum(t * -e, axis=0)
-            norm = (W * h[j]) * SQRT_2PI
-            rho = boundary_density(S / norm, (R / h[j]) / norm, *boundary_constants(g, L[j], U[j], h[j]))
-            out["density"][j] = rho
-            out["mode"][j], out["mode_density"][j], out["lower"][:, j], out["upper"][:, j], out["pieces"][:, j], out["edge"][:, j] = decide_bounded(
-                rho, lo[j], step[j], probs, bool(at_lo[j]), bool(at_hi[j]))
-        return out
+    return _measure(a, x, probs, grid, scale, at, bounds=bounds)
 
 
 def from_block_bounded(block, d, npr, G):
     """one system's result block of ``mce_param_marginals_bounded_dev`` -> what ``measure_bounded`` returns"""
-    block = np.asarray(block, dtype=np.float64)
-    P = PER_COL_BOUNDED
-    col = block[HEAD:HEAD + P * d].reshape(P, d)
-    per = block[HEAD + P * d:HEAD + (P + PER_P * npr) * d].reshape(npr, PER_P, d)
-    out = dict(W=float(block[0]), A2=float(block[1]), rows=int(block[2]), status=int(block[3]), column=int(block[4]), grid=int(G))
-    for i, k in enumerate(("mean", "var", "sd", "h", "c", "lo", "step", "mode", "mode_density", "col_status") + BOUND_KEYS):
-        out[k] = col[i].copy()
-    for i, k in enumerate(("lower", "upper", "pieces", "edge")):
-        out[k] = per[:, i, :].copy()
-    out["density"] = block[HEAD + (P + PER_P * npr) * d:].reshape(d, G).copy()
-    return out
+    return _from_block(block, d, npr, G, COL_KEYS + BOUND_KEYS)
 
 
 def measure_bounded_native(a, x, bounds, probs, grid=DEFAULT_GRID, scale=1.0, device=None):
     """``measure_bounded`` by the library from HOST arrays (``mce_param_marginals_bounded_f64``, uploaded to ``device``)"""
     from . import _capi
-    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    x = x.reshape(a.size, -1) if x.ndim != 2 else x
+    a, x = _host_system(a, x)
     blk, = _capi.param_marginals_bounded([(x, x.shape[1], a)], [bounds], probs, grid, scale, device=int(device or 0))
     return from_block_bounded(blk, x.shape[1], len(probs), grid)
 

@@ -257,25 +257,27 @@ def contours_measure_dev(systems, spec, device, stream):
 def marginals_measure_dev(systems, spec, device, stream):
     """ONE ``mce_param_marginals_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
     columns, device address of w)] and ``spec`` = (probs, grid, scale) -> one ``marginals.measure`` dict per system"""
-    import torch
     from . import _capi
-    probs, grid, scale = spec
-    wsb = _capi.param_marginals_workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(probs), grid)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
-    blocks = _capi.param_marginals_dev(systems, probs, grid, scale, ws.data_ptr(), wsb, stream)
-    return [_marginals.from_block(b, s[3], len(probs), grid) for b, s in zip(blocks, systems)]
+    return _marginals_dev(_capi.param_marginals_workspace_bytes, lambda *a: _capi.param_marginals_dev(systems, *a), _marginals.from_block, systems, spec,
+                          device, stream)
 
 
 def marginals_bounded_measure_dev(systems, bounds, spec, device, stream):
     """ONE ``mce_param_marginals_bounded_dev`` call for ``systems`` (as ``marginals_measure_dev`` takes them), ``bounds`` = one
     (lo[d], hi[d]) per system (``marginals.bounds_spec``) and ``spec`` -> one ``marginals.measure_bounded`` dict per system"""
-    import torch
     from . import _capi
+    return _marginals_dev(_capi.param_marginals_bounded_workspace_bytes, lambda *a: _capi.param_marginals_bounded_dev(systems, bounds, *a),
+                          _marginals.from_block_bounded, systems, spec, device, stream)
+
+
+def _marginals_dev(workspace_bytes, call, from_block, systems, spec, device, stream):
+    """the workspace, the one library call (``call``: what follows the systems and the bounds) and the blocks of either family"""
+    import torch
     probs, grid, scale = spec
-    wsb = _capi.param_marginals_bounded_workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(probs), grid)
+    wsb = workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(probs), grid)
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
-    blocks = _capi.param_marginals_bounded_dev(systems, bounds, probs, grid, scale, ws.data_ptr(), wsb, stream)
-    return [_marginals.from_block_bounded(b, s[3], len(probs), grid) for b, s in zip(blocks, systems)]
+    blocks = call(probs, grid, scale, ws.data_ptr(), wsb, stream)
+    return [from_block(b, s[3], len(probs), grid) for b, s in zip(blocks, systems)]
 
 
 def covariance_measure_dev(systems, device, stream):

@@ -1,4 +1,4 @@
-"""marginals with bounds on the device: ``mce_param_marginals_bounded_dev`` (csrc/param_marginals_bounds_kernels.hpp) on the cases of
+"""marginals with bounds on the device: ``mce_param_marginals_bounded_dev`` (csrc/param_marginals_kernels.hpp, <true>) on the cases of
 tests/marginals_bounds_cases.py: the moments and h within their bounds, every density within its bound of the exact boundary-kernel
 estimate at the reported h, c, lo and step (mpmath on the query points, the extended format on all), every density within two bounds of
 ``marginals.measure_bounded``'s, every decision bit for bit the serial rule's with the end weights on the device's own densities (NumPy and

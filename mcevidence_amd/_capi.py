@@ -728,6 +728,39 @@ def like_moments(systems, device=0):
     return _like_moments(load().mce_like_moments_f64, [(f.ctypes.data if f.size else 0, w.ctypes.data if w.size else 0, f.size) for f, w in keep], (int(device),))
 
 
+def _host_systems(systems, who, with_fs=False):
+    """``systems`` = [(x[n, ld], d, w)] host arrays (``with_fs``: [(x[n, ld], d, w, fs or None)]) -> (what keeps them alive, [(address of x,
+    ld, n, d, address of w)] (``with_fs``: and the address of fs, or 0))"""
+    keep = []
+    for system in systems:
+        x, d, w, f = system if with_fs else (*system, None)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        f = None if f is None else np.ascontiguousarray(f, dtype=np.float64).reshape(-1)
+        if x.shape[0] != w.size or (f is not None and f.size != w.size):
+            raise ValueError("%s: rows%s of one length expected" % (who, ", w and fs" if with_fs else " and w"))
+        keep.append((x, int(d), w, f))
+    fs = (lambda f: (f.ctypes.data if f is not None and f.size else 0,)) if with_fs else (lambda f: ())
+    return keep, [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) + fs(f) for x, d, w, f in keep]
+
+
+def _seg_array(seg_type, segs):
+    """``segs`` = [(x, ld, n, d, w)] or [(x, ld, n, d, w, fs)], addresses -> the ``SummarySeg`` or ``CovSeg`` array of a call"""
+    arr = (seg_type * max(len(segs), 1))()
+    for i, (x, ld, n, d, w, *fs) in enumerate(segs):
+        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w = x or None, int(ld), int(n), int(d), w or None
+        if fs:
+            arr[i].fs = fs[0] or None
+    return arr
+
+
+def _split(out, sizes):
+    """``out`` cut into the blocks of ``sizes`` doubles, one behind the other"""
+    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
+    return [out[at[i]:at[i + 1]] for i in range(len(sizes))]
+
+
 def param_summary_out_doubles(d, nq):
     return int(load().mce_param_summary_out_doubles(int(d), int(nq)))
 
@@ -737,16 +770,13 @@ def param_summary_workspace_bytes(nrows_total, nrows_max, nseg, dmax, nq, pass_e
 
 
 def _param_summary(call, segs, q, pass_elems, tail):
-    arr = (SummarySeg * max(len(segs), 1))()
-    for i, (x, ld, n, d, w, fs) in enumerate(segs):
-        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, fs or None
+    arr = _seg_array(SummarySeg, segs)
     q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
     nq = q.size
     sizes = [summary_block_doubles(d, nq) if 1 <= int(d) <= 127 else 0 for _, _, _, d, _, _ in segs]
     out = np.full(max(sum(sizes), 1), np.nan)
     check(call(_c.cast(arr, _P), len(segs), q.ctypes.data, nq, int(pass_elems), out.ctypes.data, *tail))
-    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
-    return [out[at[i]:at[i + 1]] for i in range(len(segs))]
+    return _split(out, sizes)
 
 
 def summary_block_doubles(d, nq):
@@ -763,17 +793,7 @@ def param_summary_dev(segs, q, ws, ws_bytes, stream=0, pass_elems=0):
 
 def param_summary(systems, q, device=0, pass_elems=0):
     """mce_param_summary_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w, fs or None)], uploaded by the library"""
-    keep = []
-    for x, d, w, f in systems:
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
-        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-        f = None if f is None else np.ascontiguousarray(f, dtype=np.float64).reshape(-1)
-        if x.shape[0] != w.size or (f is not None and f.size != w.size):
-            raise ValueError("param summary: rows, w and fs of one length expected")
-        keep.append((x, int(d), w, f))
-    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0, f.ctypes.data if f is not None and f.size else 0)
-            for x, d, w, f in keep]
+    keep, segs = _host_systems(systems, "param summary", with_fs=True)
     return _param_summary(load().mce_param_summary_f64, segs, q, pass_elems, (int(device),))
 
 
@@ -791,14 +811,11 @@ def cov_block_doubles(d):
 
 
 def _param_cov(call, segs, tail):
-    arr = (CovSeg * max(len(segs), 1))()
-    for i, (x, ld, n, d, w) in enumerate(segs):
-        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w = x or None, int(ld), int(n), int(d), w or None
+    arr = _seg_array(CovSeg, segs)
     sizes = [cov_block_doubles(d) if 1 <= int(d) <= 127 else 0 for _, _, _, d, _ in segs]
     out = np.full(max(sum(sizes), 1), np.nan)
     check(call(_c.cast(arr, _P), len(segs), out.ctypes.data, *tail))
-    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
-    return [out[at[i]:at[i + 1]] for i in range(len(segs))]
+    return _split(out, sizes)
 
 
 def param_cov_dev(segs, ws, ws_bytes, stream=0):
@@ -810,15 +827,7 @@ def param_cov_dev(segs, ws, ws_bytes, stream=0):
 
 def param_cov(systems, device=0):
     """mce_param_cov_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
-    keep = []
-    for x, d, w in systems:
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
-        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-        if x.shape[0] != w.size:
-            raise ValueError("param cov: rows and w of one length expected")
-        keep.append((x, int(d), w))
-    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
+    keep, segs = _host_systems(systems, "param cov")
     return _param_cov(load().mce_param_cov_f64, segs, (int(device),))
 
 
@@ -887,25 +896,10 @@ def marginals_block_doubles(d, np_, grid):
     return MCE_MARGINALS_HEAD + int(d) * (10 + 4 * int(np_) + int(grid))
 
 
-def _host_systems(systems, who):
-    """``systems`` = [(x[n, ld], d, w)] host arrays -> (what keeps them alive, [(address of x, ld, n, d, address of w)])"""
-    keep = []
-    for x, d, w in systems:
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
-        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-        if x.shape[0] != w.size:
-            raise ValueError("%s: rows and w of one length expected" % who)
-        keep.append((x, int(d), w))
-    return keep, [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
-
-
 def _param_marginals(call, segs, bounds, probs, grid, scale, tail):
     """``bounds``: None (the plain entry points), or per system (lo[d], hi[d]) -> the HOST array of a bounded call, 2 d doubles per
     segment, which goes in front of ``probs``"""
-    arr = (SummarySeg * max(len(segs), 1))()
-    for i, (x, ld, n, d, w) in enumerate(segs):
-        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, None
+    arr = _seg_array(SummarySeg, segs)
     extra = ()
     if bounds is not None:
         if len(bounds) != len(segs):
@@ -925,8 +919,7 @@ def _param_marginals(call, segs, bounds, probs, grid, scale, tail):
     sizes = [block_doubles(d, npr, grid) if shape_ok and 1 <= int(d) <= 127 else 0 for _, _, _, d, _ in segs]
     out = np.full(max(sum(sizes), 1), np.nan)
     check(call(_c.cast(arr, _P), len(segs), *extra, probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
-    at = np.concatenate(([0], np.cumsum(sizes))).astype(int)
-    return [out[at[i]:at[i + 1]] for i in range(len(segs))]
+    return _split(out, sizes)
 
 
 def param_marginals_dev(segs, probs, grid, scale, ws, ws_bytes, stream=0):
@@ -982,9 +975,7 @@ def contours_block_doubles(nc, np_, grid):
 
 
 def _param_contours(call, segs, cols, probs, grid, scale, tail):
-    arr = (SummarySeg * max(len(segs), 1))()
-    for i, (x, ld, n, d, w) in enumerate(segs):
-        arr[i].x, arr[i].ld, arr[i].n, arr[i].d, arr[i].w, arr[i].fs = x or None, int(ld), int(n), int(d), w or None, None
+    arr = _seg_array(SummarySeg, segs)
     cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
     probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
     npr, grid = probs.size, int(grid)
@@ -992,7 +983,7 @@ def _param_contours(call, segs, cols, probs, grid, scale, tail):
     size = contours_block_doubles(cols.size, npr, grid) if shape_ok else 0
     out = np.full(max(size * len(segs), 1), np.nan)
     check(call(_c.cast(arr, _P), len(segs), cols.ctypes.data, cols.size, probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
-    return [out[i * size:(i + 1) * size] for i in range(len(segs))]
+    return _split(out, [size] * len(segs))
 
 
 def param_contours_dev(segs, cols, probs, grid, scale, ws, ws_bytes, stream=0):
@@ -1004,15 +995,7 @@ def param_contours_dev(segs, cols, probs, grid, scale, ws, ws_bytes, stream=0):
 
 def param_contours(systems, cols, probs, grid, scale, device=0):
     """mce_param_contours_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
-    keep = []
-    for x, d, w in systems:
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        x = x.reshape(-1, max(int(d), 1)) if x.ndim != 2 else x
-        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-        if x.shape[0] != w.size:
-            raise ValueError("param contours: rows and w of one length expected")
-        keep.append((x, int(d), w))
-    segs = [(x.ctypes.data if x.size else 0, x.shape[1], w.size, d, w.ctypes.data if w.size else 0) for x, d, w in keep]
+    keep, segs = _host_systems(systems, "param contours")
     return _param_contours(load().mce_param_contours_f64, segs, cols, probs, grid, scale, (int(device),))
 
 

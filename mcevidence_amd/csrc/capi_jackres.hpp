@@ -144,10 +144,8 @@ int mce_jack_leave_out_dev(const mce_jack_leave_out_seg* segs, int32_t nseg, dou
     hipLaunchKernelGGL(jg_centre_kernel, per_slot, tb, 0, st, W.segs, W.tile0, nslots, W.sums, W.sys);
     if (tiles.ntiles > 0 && moments) hipLaunchKernelGGL(jg_var_tile_kernel, per_tile, tb, 0, st, W.segs, W.tile0, (int)nseg, nslots, W.sys, W.part);
     hipLaunchKernelGGL(jg_result_kernel, per_slot, tb, 0, st, W.segs, W.tile0, nslots, W.sys, W.part, W.res);
-    MCE_HIP(hipGetLastError());
     std::vector<double> host(nres + 1);
-    MCE_HIP(hipMemcpyAsync(host.data(), W.res, (nres + 1) * 8, hipMemcpyDeviceToHost, st));
-    MCE_HIP(hipStreamSynchronize(st));                            // the one wait
+    if ((rc = seg_dev_end(host.data(), W.res, nres + 1, st)) != MCE_OK) return rc;
     if (host[nres] != 0.0) return fail(MCE_ERR_INVALID, "jackknife: a group id outside 0 .. G - 1");
     std::copy(host.begin(), host.begin() + (ptrdiff_t)nres, out);
     return MCE_OK;

@@ -116,10 +116,7 @@ int mce_kde_shift_dev(const mce_kde_seg* segs, int32_t nseg, double* out, void* 
         hipLaunchKernelGGL(kde_mass_tile_kernel, dim3((unsigned)ntiles), tb, 0, st, W.segs, W.tile0, (int)nseg, W.sys, W.partial, W.mass);
     }
     hipLaunchKernelGGL(kde_result_kernel, dim3((unsigned)nseg), tb, 0, st, W.segs, W.tile0, W.sys, W.mass, W.res);
-    MCE_HIP(hipGetLastError());
-    MCE_HIP(hipMemcpyAsync(out, W.res, (size_t)nseg * mce_kde::kKdeOut * 8, hipMemcpyDeviceToHost, st));
-    MCE_HIP(hipStreamSynchronize(st));                            // the one wait
-    return MCE_OK;
+    return seg_dev_end(out, W.res, (size_t)nseg * mce_kde::kKdeOut, st);
 }
 
 int mce_kde_shift_f64(const mce_kde_seg* segs, int32_t nseg, double* out, int32_t device)

@@ -4,18 +4,17 @@
 // call, without and with hard prior bounds (param_marginals_kernels.hpp has the launches, param_marginals.hpp and
 // param_marginals_bounds.hpp the rules).  The two families share every line here but their kernels' instance: kBounds.  The bounds are
 // a HOST array that travels with the segment table.  Everything is enqueued on the caller's stream; the host waits once, for one block
-// of results.  Argument checks come before any device call.  Ten launches, whatever the number of systems.
+// of results.  Argument checks come before any device call.  Ten launches, whatever the number of systems: the five of summary's
+// moments (capi_sum_front.hpp: the head of the workspace, the per-segment checks and tables and these launches), then mar_prep /
+// mar_density / mar_fold / mar_hpd / mar_result.
 #pragma once
 
-#include "capi_seg.hpp"
+#include "capi_sum_front.hpp"
 #include "param_marginals.hpp"
 #include "param_marginals_bounds.hpp"
 #include "param_marginals_kernels.hpp"
 
 namespace {
-
-constexpr int32_t kMarMaxSegs = 1 << 16;
-constexpr int64_t kMarMaxRows = 0x7fffffffLL;
 
 // no table of nseg segments with nrows rows has more (system, part) pairs than this
 size_t mar_max_parts(int64_t nrows_total, int32_t nseg)
@@ -27,27 +26,17 @@ int64_t mar_block_doubles(bool bounded, int d, int np, int G) { return bounded ?
 
 // the workspace of a call: nrows_total rows in nseg segments, at most dmax columns, np probabilities, G grid points.  bounded: the wider
 // prm rows, the bounds, two sums per part and the wider blocks
-struct MarWs {
-    mce::SumSeg* segs;
-    int64_t* tile0;
-    double *head, *cols, *part, *sys, *col, *prm, *bnd, *probs, *S, *res;
-    mce::SumRun* runs;
+struct MarWs : SumFrontWs {
+    double *prm, *bnd, *probs, *S, *res;
     mce::MarSeg* msegs;
     size_t total;
     MarWs(bool bounded, int64_t nrows_total, int32_t nseg, int32_t dmax, int32_t np, int32_t G, void* ws = nullptr)
     {
-        const size_t Sg = (size_t)nseg, T = (size_t)mce_seg::seg_max_tiles(nrows_total, nseg), R = Sg * (size_t)dmax, D = (size_t)dmax;
+        const size_t Sg = (size_t)nseg, R = Sg * (size_t)dmax, D = (size_t)dmax;
         const size_t prm_w = bounded ? mce::MarForm<true>::kPrm : mce::MarForm<false>::kPrm;
         const size_t sums = bounded ? mce::MarForm<true>::kSums : mce::MarForm<false>::kSums;
         WsPlan P(ws);
-        segs = P.take<mce::SumSeg>(Sg);
-        tile0 = P.take<int64_t>(Sg);
-        head = P.take<double>(T * mce::kSumTileHead);
-        cols = P.take<double>(T * mce::kSumTileCol * D);
-        part = P.take<double>(T * D);
-        sys = P.take<double>(Sg * mce::kSumSys);
-        col = P.take<double>(R * mce::kSumCol);
-        runs = P.take<mce::SumRun>(R);
+        take(P, nrows_total, nseg, dmax, true);
         msegs = P.take<mce::MarSeg>(Sg);
         prm = P.take<double>(R * prm_w);
         bnd = P.take<double>(bounded ? R * 2 : 0);
@@ -58,54 +47,37 @@ struct MarWs {
     }
 };
 
-struct MarTables {
-    std::vector<mce::SumSeg> segs;
+struct MarTables : SumFrontTables {
     std::vector<mce::MarSeg> msegs;
-    mce_seg::SegTable tiles;
-    std::vector<mce::SumRun> runs;
     std::vector<double> bnd;                                    // with bounds: per run L, U
-    int64_t out_doubles = 0, parts = 0;
-    int32_t dmax = 1, max_parts = 0;
+    int64_t parts = 0;
+    int32_t max_parts = 0;
 };
 
 bool mar_shape_ok(int32_t nseg, int32_t dmax, int32_t np, int32_t G)
 {
-    return nseg >= 1 && nseg <= kMarMaxSegs && dmax >= 1 && dmax <= mce_mar::kMarMaxDim && np >= 1 && np <= mce_mar::kMarMaxP && mce_mar::mar_grid_ok(G);
+    return nseg >= 1 && nseg <= kSumMaxSegs && dmax >= 1 && dmax <= mce_mar::kMarMaxDim && np >= 1 && np <= mce_mar::kMarMaxP && mce_mar::mar_grid_ok(G);
 }
 
 // the argument checks of all forms, and the tables.  bounds (null: the call has none): per segment lo[d], then hi[d]; they are checked
 // last, and then the blocks are the wider ones
 int mar_tables(const mce_summary_seg* segs, int32_t nseg, const double* bounds, const double* probs, int32_t np, int32_t G, double scale, MarTables& T)
 {
-    if (!segs || !probs) return fail(MCE_ERR_INVALID, "null pointer argument");
-    if (nseg < 1 || nseg > kMarMaxSegs) return fail(MCE_ERR_INVALID, "param marginals: %d segments (1 .. %d expected)", nseg, kMarMaxSegs);
+    int rc = sum_front_args("param marginals", segs && probs, nseg);
+    if (rc != MCE_OK) return rc;
     if (np < 1 || np > mce_mar::kMarMaxP) return fail(MCE_ERR_INVALID, "param marginals: %d probabilities (1 .. %d expected)", np, mce_mar::kMarMaxP);
     for (int32_t t = 0; t < np; ++t)
         if (!(probs[t] > 0.0 && probs[t] < 1.0)) return fail(MCE_ERR_INVALID, "param marginals: probability %d is %g (0 < p < 1 expected)", t, probs[t]);
     if (!mce_mar::mar_grid_ok(G)) return fail(MCE_ERR_INVALID, "param marginals: grid=%d (64, 128, 256, 512 or 1024 expected)", G);
     if (!mce_mar::mar_pos_finite(scale)) return fail(MCE_ERR_INVALID, "param marginals: scale=%g (finite and > 0 expected)", scale);
-    T.segs.assign((size_t)nseg, mce::SumSeg{});
-    T.msegs.assign((size_t)nseg, mce::MarSeg{});
-    for (int32_t s = 0; s < nseg; ++s) {
-        const mce_summary_seg& g = segs[s];
-        if (g.d < 1 || g.d > mce_mar::kMarMaxDim) return fail(MCE_ERR_INVALID, "param marginals: segment %d has d=%d (1 .. %d expected)", s, g.d, mce_mar::kMarMaxDim);
-        if (g.n < 0 || g.n > kMarMaxRows || g.ld < g.d || (g.n > 0 && (!g.x || !g.w)))
-            return fail(MCE_ERR_INVALID, "param marginals: segment %d has %lld rows, ld=%lld, d=%d at x %s, w %s", s, (long long)g.n, (long long)g.ld, g.d,
-                        g.x ? "valid" : "null", g.w ? "valid" : "null");
-        mce::SumSeg& o = T.segs[(size_t)s];
-        o.x = g.x; o.w = g.w; o.fs = nullptr; o.ld = g.ld; o.n = g.n; o.d = g.d; o.pad = 0;
-        o.out_off = T.out_doubles;
-        o.col0 = (int64_t)T.runs.size();
-        T.msegs[(size_t)s] = mce::MarSeg{T.parts, T.out_doubles};
+    rc = sum_front_tables("param marginals", segs, nseg, T, SumFrontNoCheck{}, [&](int32_t, const mce_summary_seg& g) {
+        T.msegs.push_back(mce::MarSeg{T.parts, T.out_doubles});
         const int nparts = mce_mar::mar_nparts(g.n);
         T.parts += (int64_t)nparts * g.d;
         T.max_parts = std::max(T.max_parts, (int32_t)nparts);
-        T.out_doubles += mar_block_doubles(bounds != nullptr, g.d, np, G);
-        T.tiles.add(g.n);
-        T.dmax = std::max(T.dmax, g.d);
-        for (int32_t j = 0; j < g.d; ++j) T.runs.push_back(mce::SumRun{0, 0, s, j});
-    }
-    if (!T.tiles.fits()) return fail(MCE_ERR_INVALID, "param marginals: %lld rows in one call", (long long)T.tiles.nrows);
+        return mar_block_doubles(bounds != nullptr, g.d, np, G);
+    });
+    if (rc != MCE_OK) return rc;
     if (!bounds) return MCE_OK;
     for (int32_t s = 0; s < nseg; ++s) {
         const int32_t d = segs[s].d;
@@ -137,21 +109,14 @@ int mar_dev(const mce_summary_seg* segs, int32_t nseg, const double* bounds, con
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = seg_dev_begin("param marginals", ws_bytes, W.total, T.segs, T.tiles.tile0, W.segs, W.tile0, st)) != MCE_OK) return rc;
     if ((size_t)T.parts > mar_max_parts(T.tiles.nrows, nseg) * (size_t)T.dmax) return fail(MCE_ERR_WORKSPACE, "param marginals: %lld parts, fewer planned", (long long)T.parts);
-    const int dmax = T.dmax, G = grid, nblk = mce_mar::mar_nblocks(G);
+    const int G = grid, nblk = mce_mar::mar_nblocks(G);
     const int64_t R = (int64_t)T.runs.size();
     if (R * nblk > mce_seg::kSegMaxTiles) return fail(MCE_ERR_INVALID, "param marginals: %lld columns in one call", (long long)R);
-    MCE_HIP(hipMemcpyAsync(W.runs, T.runs.data(), T.runs.size() * sizeof(SumRun), hipMemcpyHostToDevice, st));
     MCE_HIP(hipMemcpyAsync(W.msegs, T.msegs.data(), T.msegs.size() * sizeof(MarSeg), hipMemcpyHostToDevice, st));
     if (kBounds) MCE_HIP(hipMemcpyAsync(W.bnd, T.bnd.data(), T.bnd.size() * 8, hipMemcpyHostToDevice, st));
     MCE_HIP(hipMemcpyAsync(W.probs, probs, (size_t)np * 8, hipMemcpyHostToDevice, st));
-    const dim3 tb(kPsumThreads);
-    const unsigned ntiles = (unsigned)T.tiles.ntiles;
     // the moments, by summary's kernels as they stand
-    if (ntiles > 0) hipLaunchKernelGGL(sum_tile_kernel, dim3(ntiles), tb, 0, st, W.segs, W.tile0, (int)nseg, dmax, W.head, W.cols);
-    hipLaunchKernelGGL(sum_sys_kernel, dim3((unsigned)nseg), tb, 0, st, W.segs, W.tile0, W.head, W.sys);
-    hipLaunchKernelGGL(sum_col_kernel, dim3((unsigned)R), tb, 0, st, W.segs, W.tile0, W.runs, dmax, W.cols, W.sys, W.col);
-    if (ntiles > 0) hipLaunchKernelGGL(sum_var_tile_kernel, dim3(ntiles), tb, 0, st, W.segs, W.tile0, (int)nseg, dmax, W.col, W.part);
-    hipLaunchKernelGGL(sum_var_col_kernel, dim3((unsigned)R), tb, 0, st, W.segs, W.tile0, W.runs, dmax, W.part, W.sys, W.col);
+    if ((rc = sum_front_launch(W, T, nseg, true, st)) != MCE_OK) return rc;
     // the bandwidths and grids (and end flags); the kernel sums per part; the fold (and the boundary kernel); the decisions; the blocks
     const dim3 mt(kMarThreads);
     hipLaunchKernelGGL(mar_prep_kernel<kBounds>, dim3((unsigned)((R + kMarThreads - 1) / kMarThreads)), mt, 0, st, W.segs, W.runs, R, W.sys, W.col, W.bnd, G, scale, W.prm);
@@ -160,10 +125,7 @@ int mar_dev(const mce_summary_seg* segs, int32_t nseg, const double* bounds, con
     hipLaunchKernelGGL(mar_fold_kernel<kBounds>, dim3((unsigned)(R * nblk)), mt, 0, st, W.segs, W.msegs, W.runs, W.prm, W.sys, G, nblk, (int)np, W.S, W.res);
     hipLaunchKernelGGL(mar_hpd_kernel<kBounds>, dim3((unsigned)R), mt, 0, st, W.segs, W.msegs, W.runs, W.prm, W.probs, (int)np, G, W.res);
     hipLaunchKernelGGL(mar_result_kernel<kBounds>, dim3((unsigned)nseg), mt, 0, st, W.segs, W.msegs, W.sys, W.col, W.prm, G, (int)np, W.res);
-    MCE_HIP(hipGetLastError());
-    MCE_HIP(hipMemcpyAsync(out, W.res, (size_t)T.out_doubles * 8, hipMemcpyDeviceToHost, st));
-    MCE_HIP(hipStreamSynchronize(st));                            // the one wait
-    return MCE_OK;
+    return seg_dev_end(out, W.res, (size_t)T.out_doubles, st);
 }
 
 // the _f64 form of both families

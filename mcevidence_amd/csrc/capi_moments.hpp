@@ -77,10 +77,7 @@ int mce_like_moments_dev(const mce_moments_seg* segs, int32_t nseg, double* out,
     hipLaunchKernelGGL(mom_centre_kernel, per_sys, tb, 0, st, W.segs, W.tile0, W.sums, W.sys);
     if (tiles.ntiles > 0) hipLaunchKernelGGL(mom_var_tile_kernel, per_tile, tb, 0, st, W.segs, W.tile0, (int)nseg, W.sys, W.part);
     hipLaunchKernelGGL(mom_result_kernel, per_sys, tb, 0, st, W.segs, W.tile0, W.sys, W.part, W.res);
-    MCE_HIP(hipGetLastError());
-    MCE_HIP(hipMemcpyAsync(out, W.res, (size_t)nseg * mce_mom::kMomOut * 8, hipMemcpyDeviceToHost, st));
-    MCE_HIP(hipStreamSynchronize(st));                            // the one wait
-    return MCE_OK;
+    return seg_dev_end(out, W.res, (size_t)nseg * mce_mom::kMomOut, st);
 }
 
 int mce_like_moments_f64(const mce_moments_seg* segs, int32_t nseg, double* out, int32_t device)

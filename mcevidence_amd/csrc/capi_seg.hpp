@@ -1,6 +1,7 @@
 // capi_seg.hpp -- part of capi.hip (one translation unit): what the host sides of the segment-tile families (capi_moments.hpp,
-// capi_jackres.hpp, capi_summary.hpp, capi_cov.hpp, capi_marginals.hpp, capi_contours.hpp; the scheme: seg_tiles.hpp) share: the opening of their _dev forms and the staging of their
-// host-pointer forms.  Each family keeps its own argument checks and error texts.
+// capi_jackres.hpp, capi_summary.hpp, capi_cov.hpp, capi_kde.hpp, capi_marginals.hpp, capi_contours.hpp; the scheme: seg_tiles.hpp)
+// share: the opening and the end of their _dev forms and the staging of their host-pointer forms.  Each family keeps its own argument
+// checks and error texts.  (What the four families that begin with summary's moments share beyond this: capi_sum_front.hpp.)
 #pragma once
 
 #include "seg_tiles.hpp"
@@ -18,6 +19,32 @@ int seg_dev_begin(const char* who, size_t ws_bytes, size_t need, const std::vect
     if (rc != MCE_OK) return rc;
     MCE_HIP(hipMemcpyAsync(d_segs, table.data(), table.size() * sizeof(Seg), hipMemcpyHostToDevice, st));
     MCE_HIP(hipMemcpyAsync(d_tile0, tile0.data(), tile0.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    return MCE_OK;
+}
+
+// the end of a _dev form, after its last launch: the launches went through, and the block of results is with the caller
+int seg_dev_end(double* out, const double* res, size_t doubles, hipStream_t st)
+{
+    MCE_HIP(hipGetLastError());
+    MCE_HIP(hipMemcpyAsync(out, res, doubles * 8, hipMemcpyDeviceToHost, st));
+    MCE_HIP(hipStreamSynchronize(st));                            // the one wait
+    return MCE_OK;
+}
+
+// kernels that stage more LDS than the default limit: raise it once per device (attr_set: the family's flags; a failure is not
+// remembered: the next call asks again)
+struct SegLdsAttr {
+    const void* kernel;
+    size_t bytes;
+};
+int seg_attr_once(std::atomic<bool> (&attr_set)[kMaxDevices], std::initializer_list<SegLdsAttr> list)
+{
+    int dev = 0;
+    MCE_HIP(hipGetDevice(&dev));
+    if (dev >= kMaxDevices || !attr_set[dev].load()) {
+        for (const SegLdsAttr& a : list) MCE_HIP(hipFuncSetAttribute(a.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.bytes));
+        if (dev < kMaxDevices) attr_set[dev].store(true);
+    }
     return MCE_OK;
 }
 

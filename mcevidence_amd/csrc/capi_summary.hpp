@@ -1,21 +1,19 @@
 // capi_summary.hpp -- part of capi.hip (one translation unit): mce_param_summary_out_doubles / mce_param_summary_workspace_bytes /
 // mce_param_summary_dev / mce_param_summary_f64: the posterior summary (weighted means, variances, extremes, weighted quantiles, best
 // fit) of the parameter columns of MANY systems (the ready roots of a farm wave) that are on the device, in one call
-// (param_summary_kernels.hpp has the launches, param_summary.hpp the rule).  Everything is enqueued on the caller's stream; the host
-// waits once, for one block of results.  Argument checks come before any device call.  The runs (system, column) are sorted in PASSES
-// of at most pass_elems elements, so the number of launches depends on the number of passes, not on the number of systems.
+// (param_summary_kernels.hpp has the launches, param_summary.hpp the rule).  The weighted moments -- the head of the workspace, the
+// per-segment checks and tables, the first five launches -- are capi_sum_front.hpp's, which cov, marginals and contours begin with too;
+// here: fs, the passes and the quantiles.  Everything is enqueued on the caller's stream; the host waits once, for one block of results
+// (seg_dev_end).  Argument checks come before any device call.  The runs (system, column) are sorted in PASSES of at most pass_elems
+// elements, so the number of launches depends on the number of passes, not on the number of systems.
 #pragma once
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
-#include "capi_seg.hpp"
+#include "capi_sum_front.hpp"
 #include "param_summary.hpp"
-#include "param_summary_kernels.hpp"
 
 namespace {
-
-constexpr int32_t kSumMaxSegs = 1 << 16;
-constexpr int64_t kSumMaxRows = 0x7fffffffLL;                   // (rocPRIM's segmented sort counts a pass in 32 bits)
 
 int64_t sum_pass_elems(int64_t pass_elems) { return pass_elems > 0 ? pass_elems : (int64_t)MCE_SUMMARY_PASS_ELEMS; }
 
@@ -40,11 +38,8 @@ size_t sum_sort_tmp_bytes(int64_t size, int64_t segments)
 }
 
 // the workspace of a call: nrows_total rows in nseg segments, the longest of nrows_max rows, at most dmax columns, nq targets
-struct SumWs {
-    mce::SumSeg* segs;
-    int64_t* tile0;
-    double *head, *cols, *part, *sys, *col, *quant, *q;
-    mce::SumRun* runs;
+struct SumWs : SumFrontWs {
+    double *quant, *q;
     unsigned *ob, *oe;
     double *tot, *res;
     unsigned long long* keys[2];
@@ -58,18 +53,11 @@ struct SumWs {
         cap = std::max<int64_t>(std::max(std::min(sum_pass_elems(pass_elems), nrows_total * dmax), nrows_max), 1);
         max_runs = (int64_t)nseg * dmax;
         max_scan = cap / mce::kSumScanTile + max_runs + 1;
-        const size_t S = (size_t)nseg, T = (size_t)mce_seg::seg_max_tiles(nrows_total, nseg), R = (size_t)max_runs, D = (size_t)dmax;
+        const size_t S = (size_t)nseg, R = (size_t)max_runs;
         WsPlan P(ws);
-        segs = P.take<mce::SumSeg>(S);
-        tile0 = P.take<int64_t>(S);
-        head = P.take<double>(T * mce::kSumTileHead);
-        cols = P.take<double>(T * mce::kSumTileCol * D);
-        part = P.take<double>(T * D);
-        sys = P.take<double>(S * mce::kSumSys);
-        col = P.take<double>(R * mce::kSumCol);
+        take(P, nrows_total, nseg, dmax, true);
         quant = P.take<double>(R * (size_t)nq);
         q = P.take<double>((size_t)MCE_SUMMARY_MAX_Q);
-        runs = P.take<mce::SumRun>(R);
         ob = P.take<unsigned>(R);
         oe = P.take<unsigned>(R);
         tot = P.take<double>((size_t)max_scan);
@@ -92,58 +80,45 @@ struct SumPass {
     int64_t run0 = 0, nruns = 0, total = 0, ntiles = 0;
 };
 
-struct SumTables {
-    std::vector<mce::SumSeg> segs;
-    mce_seg::SegTable tiles;
-    std::vector<mce::SumRun> runs;
+struct SumTables : SumFrontTables {
     std::vector<unsigned> ob, oe;
     std::vector<SumPass> passes;
-    int64_t nmax = 0, out_doubles = 0;
-    int32_t dmax = 1;
+    int64_t nmax = 0;
 };
 
 // the argument checks of both forms, and the tables
 int sum_tables(const mce_summary_seg* segs, int32_t nseg, const double* q, int32_t nq, int64_t pass_elems, SumTables& T)
 {
-    if (!segs || !q) return fail(MCE_ERR_INVALID, "null pointer argument");
-    if (nseg < 1 || nseg > kSumMaxSegs) return fail(MCE_ERR_INVALID, "param summary: %d segments (1 .. %d expected)", nseg, kSumMaxSegs);
+    int rc = sum_front_args("param summary", segs && q, nseg);
+    if (rc != MCE_OK) return rc;
     if (nq < 1 || nq > MCE_SUMMARY_MAX_Q) return fail(MCE_ERR_INVALID, "param summary: %d targets (1 .. %d expected)", nq, MCE_SUMMARY_MAX_Q);
     for (int32_t t = 0; t < nq; ++t)
         if (!(q[t] > 0.0 && q[t] < 1.0)) return fail(MCE_ERR_INVALID, "param summary: target %d is %g (0 < q < 1 expected)", t, q[t]);
     if (pass_elems < 0 || pass_elems > kSumMaxRows) return fail(MCE_ERR_INVALID, "param summary: pass_elems=%lld", (long long)pass_elems);
-    const int64_t pe = sum_pass_elems(pass_elems);
-    T.segs.assign((size_t)nseg, mce::SumSeg{});
-    SumPass cur;
-    for (int32_t s = 0; s < nseg; ++s) {
-        const mce_summary_seg& g = segs[s];
-        if (g.d < 1 || g.d > mce_sum::kSumMaxDim) return fail(MCE_ERR_INVALID, "param summary: segment %d has d=%d (1 .. %d expected)", s, g.d, mce_sum::kSumMaxDim);
-        if (g.n < 0 || g.n > kSumMaxRows || g.ld < g.d || (g.n > 0 && (!g.x || !g.w)))
-            return fail(MCE_ERR_INVALID, "param summary: segment %d has %lld rows, ld=%lld, d=%d at x %s, w %s", s, (long long)g.n, (long long)g.ld, g.d,
-                        g.x ? "valid" : "null", g.w ? "valid" : "null");
-        mce::SumSeg& o = T.segs[(size_t)s];
-        o.x = g.x; o.w = g.w; o.fs = g.n > 0 ? g.fs : nullptr; o.ld = g.ld; o.n = g.n; o.d = g.d; o.pad = 0;
-        o.out_off = T.out_doubles;
-        o.col0 = (int64_t)T.runs.size();
-        T.out_doubles += mce_sum::sum_out_doubles(g.d, nq);
-        T.tiles.add(g.n);
+    rc = sum_front_tables("param summary", segs, nseg, T, SumFrontNoCheck{}, [&](int32_t s, const mce_summary_seg& g) {
+        if (g.n > 0) T.segs[(size_t)s].fs = g.fs;
         T.nmax = std::max(T.nmax, g.n);
-        T.dmax = std::max(T.dmax, g.d);
-        for (int32_t j = 0; j < g.d; ++j) {
-            // a pass: runs in (system, column) order while they fit; a run longer than pass_elems is a pass of its own
-            if (cur.nruns > 0 && cur.total + g.n > pe) {
-                T.passes.push_back(cur);
-                cur = SumPass{(int64_t)T.runs.size(), 0, 0, 0};
-            }
-            T.runs.push_back(mce::SumRun{cur.total, cur.ntiles, s, j});
-            T.ob.push_back((unsigned)cur.total);
-            T.oe.push_back((unsigned)(cur.total + g.n));
-            cur.nruns += 1;
-            cur.total += g.n;
-            cur.ntiles += (g.n + mce::kSumScanTile - 1) / mce::kSumScanTile;
+        return mce_sum::sum_out_doubles(g.d, nq);
+    });
+    if (rc != MCE_OK) return rc;
+    // the passes: runs in (system, column) order while they fit; a run longer than pass_elems is a pass of its own
+    const int64_t pe = sum_pass_elems(pass_elems);
+    SumPass cur;
+    for (size_t r = 0; r < T.runs.size(); ++r) {
+        const int64_t n = T.segs[(size_t)T.runs[r].seg].n;
+        if (cur.nruns > 0 && cur.total + n > pe) {
+            T.passes.push_back(cur);
+            cur = SumPass{(int64_t)r, 0, 0, 0};
         }
+        T.runs[r].begin = cur.total;
+        T.runs[r].tile0 = cur.ntiles;
+        T.ob.push_back((unsigned)cur.total);
+        T.oe.push_back((unsigned)(cur.total + n));
+        cur.nruns += 1;
+        cur.total += n;
+        cur.ntiles += (n + mce::kSumScanTile - 1) / mce::kSumScanTile;
     }
     if (cur.nruns > 0) T.passes.push_back(cur);
-    if (!T.tiles.fits()) return fail(MCE_ERR_INVALID, "param summary: %lld rows in one call", (long long)T.tiles.nrows);
     return MCE_OK;
 }
 
@@ -176,21 +151,12 @@ int mce_param_summary_dev(const mce_summary_seg* segs, int32_t nseg, const doubl
     const SumWs W(T.tiles.nrows, T.nmax, nseg, T.dmax, nq, pass_elems, ws);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = seg_dev_begin("param summary", ws_bytes, W.total, T.segs, T.tiles.tile0, W.segs, W.tile0, st)) != MCE_OK) return rc;
-    const int dmax = T.dmax;
-    const int64_t R = (int64_t)T.runs.size();
-
-    MCE_HIP(hipMemcpyAsync(W.runs, T.runs.data(), T.runs.size() * sizeof(SumRun), hipMemcpyHostToDevice, st));
     MCE_HIP(hipMemcpyAsync(W.ob, T.ob.data(), T.ob.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
     MCE_HIP(hipMemcpyAsync(W.oe, T.oe.data(), T.oe.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
     MCE_HIP(hipMemcpyAsync(W.q, q, (size_t)nq * 8, hipMemcpyHostToDevice, st));
-    const dim3 tb(kPsumThreads);
-    const unsigned ntiles = (unsigned)T.tiles.ntiles;
-    if (ntiles > 0) hipLaunchKernelGGL(sum_tile_kernel, dim3(ntiles), tb, 0, st, W.segs, W.tile0, (int)nseg, dmax, W.head, W.cols);
-    hipLaunchKernelGGL(sum_sys_kernel, dim3((unsigned)nseg), tb, 0, st, W.segs, W.tile0, W.head, W.sys);
-    hipLaunchKernelGGL(sum_col_kernel, dim3((unsigned)R), tb, 0, st, W.segs, W.tile0, W.runs, dmax, W.cols, W.sys, W.col);
-    if (ntiles > 0) hipLaunchKernelGGL(sum_var_tile_kernel, dim3(ntiles), tb, 0, st, W.segs, W.tile0, (int)nseg, dmax, W.col, W.part);
-    hipLaunchKernelGGL(sum_var_col_kernel, dim3((unsigned)R), tb, 0, st, W.segs, W.tile0, W.runs, dmax, W.part, W.sys, W.col);
+    if ((rc = sum_front_launch(W, T, nseg, true, st)) != MCE_OK) return rc;
     MCE_HIP(hipGetLastError());
+    const dim3 tb(kPsumThreads);
     for (const SumPass& P : T.passes) {
         if (P.total > W.cap || P.ntiles > W.max_scan) return fail(MCE_ERR_WORKSPACE, "param summary: a pass of %lld elements, %lld planned", (long long)P.total, (long long)W.cap);
         rocprim::double_buffer<unsigned long long> keys(W.keys[0], W.keys[1]);
@@ -212,10 +178,7 @@ int mce_param_summary_dev(const mce_summary_seg* segs, int32_t nseg, const doubl
         MCE_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(sum_result_kernel, dim3((unsigned)nseg), tb, 0, st, W.segs, W.sys, W.col, W.quant, (int)nq, W.res);
-    MCE_HIP(hipGetLastError());
-    MCE_HIP(hipMemcpyAsync(out, W.res, (size_t)T.out_doubles * 8, hipMemcpyDeviceToHost, st));
-    MCE_HIP(hipStreamSynchronize(st));                            // the one wait
-    return MCE_OK;
+    return seg_dev_end(out, W.res, (size_t)T.out_doubles, st);
 }
 
 int mce_param_summary_f64(const mce_summary_seg* segs, int32_t nseg, const double* q, int32_t nq, int64_t pass_elems, double* out, int32_t device)

@@ -4,7 +4,8 @@
 // Plain C++ stores only, no atomics, 64-bit row indices.  cols[nc] (the chosen columns) is one list per call.
 //
 //   (sum_tile / sum_sys / sum_col / sum_var_tile / sum_var_col of param_summary_kernels.hpp, as they stand: W, A2, rows, m, v, min, max)
-//   con_prep_kernel      one thread per (system, chosen column): the system's status, then h, c, lo, step and the column's status
+//   con_prep_kernel      one thread per (system, chosen column): the system's status (mar_sys_status of param_marginals_kernels.hpp),
+//                        then h, c, lo, step and the column's status
 //   con_density_kernel   the hot path.  A workgroup of four waves owns one x column, a GROUP of up to kConJB partner columns and one PART of
 //                        the system's tiles.  Per chunk of 16 rows it stages (x, a) of its columns, forms the (1 + kConJB) * 16 * G kernel
 //                        values into LDS (the x column's already times the weight; a row that is not used, or past the end, as zeros), and
@@ -24,6 +25,7 @@
 #include "block_reduce.hpp"
 #include "density_order.hpp"
 #include "param_contours.hpp"
+#include "param_marginals_kernels.hpp"
 #include "param_summary_kernels.hpp"
 #include "seg_tiles.hpp"
 
@@ -61,15 +63,6 @@ __device__ __forceinline__ double* con_dens_rows(double* block, int nc, int np)
     return con_p_rows(block, nc) + (int64_t)mce_con::kConPerP * np * mce_con::con_npairs(nc);
 }
 
-// the system's status from the moment kernels' outputs (all d columns of the segment count, as in mar_prep_kernel)
-__device__ __forceinline__ int con_sys_status(const SumSeg& g, const double* __restrict__ s, const double* __restrict__ col, int* column)
-{
-    int badcol = -1;
-    for (int j = g.d - 1; j >= 0; --j)
-        if (col[(g.col0 + j) * kSumCol + 4] > 0.0) badcol = j;
-    return mce_mar::mar_status(((int)s[3] & 1) != 0, badcol, s[0], s[2], column);
-}
-
 // grid: the (system, chosen column) pairs, one thread each.  prm[(system * nc + t)][kConPrm]
 __global__ __launch_bounds__(kConThreads) void con_prep_kernel(const SumSeg* __restrict__ segs, int nseg, const int32_t* __restrict__ cols, int nc,
                                                               const double* __restrict__ sys, const double* __restrict__ col, int G, double scale,
@@ -81,7 +74,7 @@ __global__ __launch_bounds__(kConThreads) void con_prep_kernel(const SumSeg* __r
     const SumSeg& g = segs[y];
     const double* s = sys + (int64_t)y * kSumSys;
     int column;
-    const int status = con_sys_status(g, s, col, &column);
+    const int status = mar_sys_status(g, s, col, &column);
     double* out = prm + r * kConPrm;
     const double nan = __builtin_nan("");
     double sd = nan, h = nan, c = nan, lo = nan, step = nan;
@@ -326,7 +319,7 @@ __global__ __launch_bounds__(kConThreads) void con_result_kernel(const SumSeg* _
     double* out = res + csegs[y].out_off;
     if (threadIdx.x == 0) {
         int column;
-        const int status = con_sys_status(g, s, col, &column);
+        const int status = mar_sys_status(g, s, col, &column);
         mce_con::con_pack_head(status, column, s[0], s[1], s[2], G, np, nc, out);
     }
     const double nan = __builtin_nan("");

@@ -8,7 +8,8 @@
 // two is MarForm<kBounds> or an `if constexpr`.  The <false> instances hold nothing of the bounded rule: one sum, no bounds reads.
 //
 //   (sum_tile / sum_sys / sum_col / sum_var_tile / sum_var_col of param_summary_kernels.hpp, as they stand: W, A2, rows, m, v, min, max)
-//   mar_prep_kernel      one thread per run: the system's status, then h, c, lo, step and the column's status (prm[run][MarForm::kPrm]);
+//   mar_prep_kernel      one thread per run: the system's status (mar_sys_status, which con_prep and con_result call too), then h, c, lo,
+//                        step and the column's status (prm[run][MarForm::kPrm]);
 //                        <true>: step 3' from bnd[run][2] = L, U, and L, U, at_lo, at_hi behind them
 //   mar_density_kernel   the hot path.  A workgroup owns one (run, block of 256 grid points) and one PART of the system's tiles, a thread
 //                        one grid point in a register.  The part's tiles are staged through LDS as (x, a) pairs, 512 rows at a time (a
@@ -66,6 +67,15 @@ template <bool kBounds> __device__ __forceinline__ double* mar_dens_rows(double*
     return block + mce_mar::kMarHead + (int64_t)(MarForm<kBounds>::kPerCol + mce_mar::kMarPerP * np) * d;
 }
 
+// the system's status from the moment kernels' outputs (s: its kSumSys sums; all d columns of the segment count: the lowest refused one)
+__device__ __forceinline__ int mar_sys_status(const SumSeg& g, const double* __restrict__ s, const double* __restrict__ col, int* column)
+{
+    int badcol = -1;
+    for (int j = g.d - 1; j >= 0; --j)
+        if (col[(g.col0 + j) * kSumCol + 4] > 0.0) badcol = j;
+    return mce_mar::mar_status(((int)s[3] & 1) != 0, badcol, s[0], s[2], column);
+}
+
 // grid: the runs, one thread each.  bnd[run][2]: L, U (<false>: not read)
 template <bool kBounds>
 __global__ __launch_bounds__(kMarThreads) void mar_prep_kernel(const SumSeg* __restrict__ segs, const SumRun* __restrict__ runs, int64_t nruns,
@@ -77,11 +87,8 @@ __global__ __launch_bounds__(kMarThreads) void mar_prep_kernel(const SumSeg* __r
     const int y = runs[r].seg;
     const SumSeg& g = segs[y];
     const double* s = sys + (int64_t)y * kSumSys;
-    int badcol = -1;
-    for (int j = g.d - 1; j >= 0; --j)
-        if (col[(g.col0 + j) * kSumCol + 4] > 0.0) badcol = j;
     int column;
-    const int status = mce_mar::mar_status(((int)s[3] & 1) != 0, badcol, s[0], s[2], &column);
+    const int status = mar_sys_status(g, s, col, &column);
     double* out = prm + r * MarForm<kBounds>::kPrm;
     const double nan = __builtin_nan("");
     double sd = nan, h = nan, c = nan, lo = nan, step = nan;
@@ -289,11 +296,8 @@ __global__ __launch_bounds__(kMarThreads) void mar_result_kernel(const SumSeg* _
     const double* s = sys + (int64_t)y * kSumSys;
     double* out = res + msegs[y].out_off;
     if (threadIdx.x == 0) {
-        int badcol = -1;
-        for (int j = g.d - 1; j >= 0; --j)
-            if (col[(g.col0 + j) * kSumCol + 4] > 0.0) badcol = j;
         int column;
-        const int status = mce_mar::mar_status(((int)s[3] & 1) != 0, badcol, s[0], s[2], &column);
+        const int status = mar_sys_status(g, s, col, &column);
         mce_mar::mar_pack_head(status, column, s[0], s[1], s[2], G, np, out);
         if constexpr (kBounds) out[mce_mar::kMarReserved] = 1.0;
     }

@@ -230,65 +230,59 @@ def moments_measure_dev(systems, device, stream):
     return [_information.from_block(b) for b in _capi.like_moments_dev(systems, ws.data_ptr(), wsb, stream)]
 
 
+def _blocks_dev(workspace_bytes, ws_args, call, from_block, systems, device, stream):
+    """what the per-parameter statistics below share: the workspace (``workspace_bytes`` of the rows of all systems, their number,
+    their widest and ``ws_args``), the one library call (``call``: what follows the systems and their spec) and ``from_block`` of every
+    system's block"""
+    import torch
+    wsb = workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), *ws_args)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
+    return [from_block(b, s) for b, s in zip(call(ws.data_ptr(), wsb, stream), systems)]
+
+
 def summary_measure_dev(systems, q, device, stream, pass_elems=0):
     """ONE ``mce_param_summary_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
     columns, device address of w, device address of fs)] and the targets ``q`` -> one ``summary.measure`` dict per system"""
-    import torch
     from . import _capi
-    wsb = _capi.param_summary_workspace_bytes(sum(s[2] for s in systems), max(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(q),
-                                              pass_elems)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
-    blocks = _capi.param_summary_dev(systems, q, ws.data_ptr(), wsb, stream, pass_elems)
-    return [_summary.from_block(b, s[3], len(q)) for b, s in zip(blocks, systems)]
+    nmax = max(s[2] for s in systems)
+    return _blocks_dev(lambda rows, nseg, dmax: _capi.param_summary_workspace_bytes(rows, nmax, nseg, dmax, len(q), pass_elems), (),
+                       lambda *a: _capi.param_summary_dev(systems, q, *a, pass_elems), lambda b, s: _summary.from_block(b, s[3], len(q)), systems, device, stream)
 
 
 def contours_measure_dev(systems, spec, device, stream):
     """ONE ``mce_param_contours_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
     columns, device address of w)] and ``spec`` = (probs, grid, scale, cols) -> one ``contours.measure`` dict per system"""
-    import torch
     from . import _capi
     probs, grid, scale, cols = spec
-    wsb = _capi.param_contours_workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(cols), len(probs), grid)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
-    blocks = _capi.param_contours_dev(systems, cols, probs, grid, scale, ws.data_ptr(), wsb, stream)
-    return [_contours.from_block(b, len(cols), len(probs), grid) for b in blocks]
+    return _blocks_dev(_capi.param_contours_workspace_bytes, (len(cols), len(probs), grid), lambda *a: _capi.param_contours_dev(systems, cols, probs, grid, scale, *a),
+                       lambda b, s: _contours.from_block(b, len(cols), len(probs), grid), systems, device, stream)
 
 
 def marginals_measure_dev(systems, spec, device, stream):
     """ONE ``mce_param_marginals_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
     columns, device address of w)] and ``spec`` = (probs, grid, scale) -> one ``marginals.measure`` dict per system"""
     from . import _capi
-    return _marginals_dev(_capi.param_marginals_workspace_bytes, lambda *a: _capi.param_marginals_dev(systems, *a), _marginals.from_block, systems, spec,
-                          device, stream)
+    probs, grid, scale = spec
+    return _blocks_dev(_capi.param_marginals_workspace_bytes, (len(probs), grid), lambda *a: _capi.param_marginals_dev(systems, probs, grid, scale, *a),
+                       lambda b, s: _marginals.from_block(b, s[3], len(probs), grid), systems, device, stream)
 
 
 def marginals_bounded_measure_dev(systems, bounds, spec, device, stream):
     """ONE ``mce_param_marginals_bounded_dev`` call for ``systems`` (as ``marginals_measure_dev`` takes them), ``bounds`` = one
     (lo[d], hi[d]) per system (``marginals.bounds_spec``) and ``spec`` -> one ``marginals.measure_bounded`` dict per system"""
     from . import _capi
-    return _marginals_dev(_capi.param_marginals_bounded_workspace_bytes, lambda *a: _capi.param_marginals_bounded_dev(systems, bounds, *a),
-                          _marginals.from_block_bounded, systems, spec, device, stream)
-
-
-def _marginals_dev(workspace_bytes, call, from_block, systems, spec, device, stream):
-    """the workspace, the one library call (``call``: what follows the systems and the bounds) and the blocks of either family"""
-    import torch
     probs, grid, scale = spec
-    wsb = workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), len(probs), grid)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
-    blocks = call(probs, grid, scale, ws.data_ptr(), wsb, stream)
-    return [from_block(b, s[3], len(probs), grid) for b, s in zip(blocks, systems)]
+    return _blocks_dev(_capi.param_marginals_bounded_workspace_bytes, (len(probs), grid),
+                       lambda *a: _capi.param_marginals_bounded_dev(systems, bounds, probs, grid, scale, *a),
+                       lambda b, s: _marginals.from_block_bounded(b, s[3], len(probs), grid), systems, device, stream)
 
 
 def covariance_measure_dev(systems, device, stream):
     """ONE ``mce_param_cov_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured columns,
     device address of w)] -> one ``covariance.measure`` dict per system"""
-    import torch
     from . import _capi
-    wsb = _capi.param_cov_workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems))
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
-    blocks = _capi.param_cov_dev(systems, ws.data_ptr(), wsb, stream)
-    return [_covariance.from_block(b, s[3]) for b, s in zip(blocks, systems)]
+    return _blocks_dev(_capi.param_cov_workspace_bytes, (), lambda *a: _capi.param_cov_dev(systems, *a), lambda b, s: _covariance.from_block(b, s[3]), systems,
+                       device, stream)
 
 
 # ---- the jackknife of a chain that stays on the device (docs/design/jackknife_resident.md; this module and farm.py) -----------------

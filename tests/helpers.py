@@ -741,9 +741,10 @@ def _ln_terms(od, w, fs, D):
     return ln, np.where(w < 0, _LD(-1), _LD(1))[:, None]
 
 
-def equalised_inputs(od, D, col, rng):
+def equalised_inputs(od, D, col, rng, nspecial=3):
     """(w, fs) for the oracle's distances od[nq, >= col + 1]: w from the integers 1 .. 5, fs_q = -D ln od[q, col] + u_q with
-    u_q in (-1, 0] (fs_q = u_q where od[q, col] == 0); three rows dealt by rng get fs = -inf, three others a negative weight."""
+    u_q in (-1, 0] (fs_q = u_q where od[q, col] == 0); three rows dealt by rng get fs = -inf, three others a negative weight
+    (``nspecial`` of each: a set of a handful of rows asks for fewer, so that some row still counts)."""
     od = np.asarray(od, dtype=_LD)
     nq = od.shape[0]
     w = rng.integers(1, 6, nq).astype(np.float64)
@@ -752,9 +753,9 @@ def equalised_inputs(od, D, col, rng):
     with np.errstate(divide="ignore"):
         fs = np.where(r > 0, -_LD(D) * np.log(np.where(r > 0, r, _LD(1))), _LD(0)) + u
     fs = np.asarray(fs, dtype=np.float64)
-    special = rng.permutation(nq)[:6]
-    fs[special[:3]] = -np.inf
-    w[special[3:]] *= -1.0
+    special = rng.permutation(nq)[:2 * nspecial]
+    fs[special[:nspecial]] = -np.inf
+    w[special[nspecial:]] *= -1.0
     return w, fs
 
 
@@ -806,17 +807,18 @@ def blind_rows(od, w, fs, D, c, T):
     return (eff > 0) & (eff <= 2 * _LD(T))
 
 
-def sum_oracle(od, D, k0, kmax, first, rng, n=None, W=1, unfused=False):
+def sum_oracle(od, D, k0, kmax, first, rng, n=None, W=1, unfused=False, nspecial=3):
     """The oracle's side of the sum certificate, before the library is called.  od: np.longdouble distances, kmax - k0 + 1 columns
     (fewer where the set ends).  first: equalise the FIRST list column (a wrong nearest neighbour seen with the power the last
     column gives a wrong K-th) -- unless a term of another column would then overflow, which falls back to the last.
+    nspecial: the rows of each special kind (equalised_inputs).
     -> dict(w, fs, S, A, T, amax, col (list column equalised), blind (rows), rows); raises ValueError above AMBIGUOUS_CAP."""
     od = np.asarray(od, dtype=_LD)
     nq, K = od.shape[0], kmax - k0
     state = rng.bit_generator.state
     for c in ((0, K - 1) if first else (K - 1,)):
         rng.bit_generator.state = state
-        w, fs = equalised_inputs(od, D, c, rng)
+        w, fs = equalised_inputs(od, D, c, rng, nspecial)
         ln, _ = _ln_terms(od[:, :K], w, fs, D)
         if c == K - 1 or float(ln.max()) < 700.0:
             break

@@ -216,7 +216,8 @@ def whole_sum(lib, c, Y, w, fs, sym, prune):
     return lib.knn_dotp(Y, None, w, fs, c["kmax"], 1)
 
 
-def run_fused(lib, c, X, Y, sm, off, so, knn_oracle, odl):
+def run_fused(lib, c, X, Y, sm, off, so, knn_oracle, odl, assert_kernel=assert_kernel):
+    """(assert_kernel: what the kernel string is held to -- tests/test_gpu_small_sums.py brings its own)"""
     w, fs, kmax, k0 = so["w"], so["fs"], c["kmax"], c["k0"]
     if c["W"] > 1:
         # devices=[0, 0, 0]: the library's threads each take a part (mce_knn_dotp_part_f64) and leave their kernel strings in their
@@ -246,12 +247,16 @@ def run_fused(lib, c, X, Y, sm, off, so, knn_oracle, odl):
     return total, kernel
 
 
-def run_parts(lib, c, Y, so):
-    """knn_dotp_part, one part after the other"""
+def run_parts(lib, c, Y, so, assert_kernel=assert_kernel, searches=lambda r: True):
+    """knn_dotp_part, one part after the other.  searches(r): part r runs a search at all (a rank without a block or a wave returns
+    zeros at once and leaves the kernel string of whatever ran before)"""
     parts = []
     for r in range(c["W"]):
         parts.append(lib.knn_dotp_part(Y, so["w"], so["fs"], c["kmax"], r, c["W"]))
-        assert_kernel(c, lib.last_kernel())
+        if searches(r):
+            assert_kernel(c, lib.last_kernel())
+        else:
+            assert not parts[-1].any(), (r, parts[-1])
         assert parts[-1][0] == 0.0 and np.all(np.isfinite(parts[-1]))
     if c["W"] == 100:                                           # 6000 rows are 94 waves of 64 queries (96 with the padding of 12 blocks)
         assert all(not p.any() for p in parts[96:]), "a part beyond the last wave is not zero"
@@ -259,7 +264,7 @@ def run_parts(lib, c, Y, so):
     return np.sum(parts, axis=0), lib.last_kernel()
 
 
-def run_kd(lib, c, Y, so):
+def run_kd(lib, c, Y, so, assert_kernel=assert_kernel):
     import torch
     n, d, kmax, W = len(Y), c["d"], c["kmax"], c["W"]
     assert lib.prune_part_applies(n, d, kmax, W)

@@ -373,11 +373,15 @@ int mce_eig_sym_batch_f64(const double* cov, int32_t d, int64_t nsys, int32_t mo
 int mce_last_eig_stats(double* out, int32_t n);
 
 /* Run-time certificate of a finished search (reference: the result of `nbrs.kneighbors(samples)`, MCEvidence.py:1104, whose
- * exactness everything downstream rests on).  For `nsample` query rows spread evenly over the set (the pattern shifted by
- * `seed`) every reference row's squared distance is recomputed by plain fp64 differences -- none of the search's machinery:
+ * exactness everything downstream rests on).  For `nsample` query rows spread evenly over the set (sample s of n = min(nsample,
+ * nq) is row (seed % nq + floor(s nq / n)) % nq: n distinct rows, no cyclic gap between them above ceil(nq / n)) every reference
+ * row's squared distance is recomputed by plain fp64 differences -- none of the search's machinery:
  * no matrix cores, no packed operands, no bounds, no lists -- and counted against the K distances the search reported for
  * that row (`dist`, [nq][ld] as mce_knn_f64 / dist_out write them): nobody outside the list may be closer than its k-th
  * entry, and at least k rows must lie within it (relative tolerance 1e-9 on the squared distance).  d <= 128, K <= 32.
+ * An entry that is no distance fails its row: NaN, a negative number, and +inf in column k (counted from 1) unless fewer than k
+ * usable reference rows exist (the own row is not usable under MCE_SELF_EXCLUDE) -- the one case in which a search has nothing to
+ * report there; an entry point of this library refuses K > usable rows, so its lists never hold one.
  * _dev: device pointers, the caller's stream, never synchronises; `d_result` (device, 2 ints) receives {rows checked, rows
  * that failed}; workspace from mce_verify_workspace_bytes.  The host-pointer form uploads, checks, and returns
  * MCE_ERR_VERIFY (message: how many rows failed) or MCE_OK; `failed` (optional) receives the count. */

@@ -1079,6 +1079,7 @@ def last_verify_rows():
 def verify_knn(X, Y, dist, self_mode=SELF_NONE, self_offset=0, nsample=1024, seed=0, device=0):
     """Run-time certificate of a finished search (mce_verify_knn_f64): ``nsample`` query rows spread over X are re-checked
     against ``dist`` (what ``knn`` returned for them) by an exact fp64 scan of all of Y -- none of the search's machinery.
+    NaN and negative entries fail their row, and so does +inf in a column that the usable reference rows could have filled.
     Returns the number of rows that failed (0 = the sample agrees)."""
     lib = load()
     X = _f64(X, "X")
@@ -1421,6 +1422,18 @@ def dotp_workspace_bytes(nq, kmax):
 
 def knn_dev(dX, nq, dY, nr, d, K, self_mode, self_offset, d_dist, d_idx, ws, ws_bytes, stream=0):
     check(load().mce_knn_f64_dev(dX, nq, dY, nr, d, K, self_mode, self_offset, d_dist, d_idx or None, ws, ws_bytes, stream or None))
+
+
+def verify_workspace_bytes(nsample, K):
+    """scratch bytes of ``verify_knn_dev`` (0: invalid sizes)"""
+    return int(load().mce_verify_workspace_bytes(int(nsample), int(K)))
+
+
+def verify_knn_dev(dX, nq, dY, nr, d, K, self_mode, self_offset, d_dist, ld, nsample, seed, d_result, ws, ws_bytes, stream=0):
+    """mce_verify_knn_f64_dev: the run-time certificate on device buffers, on the caller's stream, never synchronises;
+    ``d_result`` (2 int32 on the device) receives {rows checked, rows that failed}.  Returns the error code (MCE_OK: launched)."""
+    return int(load().mce_verify_knn_f64_dev(dX, int(nq), dY, int(nr), int(d), int(K), int(self_mode), int(self_offset), d_dist, int(ld), int(nsample),
+                                             int(seed) & (2 ** 64 - 1), d_result, ws, int(ws_bytes), stream or None))
 
 
 def dotp_dev(d_dist, nq, ld, k0, kmax, d, d_w, d_fs, d_dotp, ws, ws_bytes, stream=0):

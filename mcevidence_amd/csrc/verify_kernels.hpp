@@ -9,7 +9,10 @@
 //     #{j : d2(q, j) <  r_k^2 (1 - tol)} <= k - 1      (nobody outside the list is closer than its k-th entry)
 //     #{j : d2(q, j) <= r_k^2 (1 + tol)} >= k          (the k-th entry is not closer than the data allow)
 // (the own row skipped under MCE_SELF_EXCLUDE; tol = 1e-9 relative, the parity tolerance of ln E).  A neighbour the filter
-// dropped shows up in the first count.  Cost: nsample x nr x d fused multiply-adds at the fp64 vector rate + the LDS
+// dropped shows up in the first count.  Entries that are no distance: NaN and negative entries fail the row.  +inf in column k
+// is what a search reports when fewer than k usable reference rows exist, and is accepted only then: with r_k = +inf the second
+// count is the number of usable rows, and the row fails unless that is <= k - 1.  (No legal search reports one -- the plan
+// refuses K > usable rows -- so a list slot left unfilled fails.)  Cost: nsample x nr x d fused multiply-adds at the fp64 vector rate + the LDS
 // broadcasts of the query rows: ~2 ms for 1024 rows of C3 (1 M x 27), 0.5 ms for 256.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,11 +26,13 @@ constexpr int kVerifyMaxDim = 128;
 constexpr int kVerifyMaxK = 32;
 constexpr double kVerifyTol = 1e-9;
 
-// sample s of n: rows spread evenly over [0, nq), the whole pattern shifted by `seed`
+// sample s of n <= nq: rows spread evenly over [0, nq), the whole pattern shifted by `seed`:  (seed % nq + floor(s nq / n)) % nq.
+// floor(s nq / n) rises by floor(nq / n) or one more per step and stays below nq, so the n rows are distinct and no cyclic gap
+// between them exceeds ceil(nq / n).  Evaluated as s (nq / n) + s (nq % n) / n: both s and nq % n are below n < 2^31.
 __host__ __device__ inline int64_t verify_row(int64_t s, int64_t n, int64_t nq, unsigned long long seed)
 {
-    const int64_t stride = nq / n > 0 ? nq / n : 1;
-    return (int64_t)((seed % (unsigned long long)nq + (unsigned long long)(s * stride)) % (unsigned long long)nq);
+    const unsigned long long at = (unsigned long long)(s * (nq / n) + s * (nq % n) / n);
+    return (int64_t)((seed % (unsigned long long)nq + at) % (unsigned long long)nq);
 }
 
 __host__ __device__ constexpr size_t verify_lds_bytes(int D, int K) { return (size_t)kVerifyQB * D * 8 + (size_t)kVerifyQB * K * (8 + 8 + 4 + 4) + kVerifyQB * 8; }
@@ -105,8 +110,9 @@ __global__ __launch_bounds__(kVerifyThreads) void verify_scan_kernel(const doubl
     }
 }
 
-// result[0] = rows checked, result[1] = rows that fail either count for some column (columns whose reported distance is
-// infinite -- fewer than k usable reference rows -- are not judged)
+// result[0] = rows checked, result[1] = rows that fail either count for some column, or hold an entry that is no distance: NaN,
+// a negative number, or +inf in a column that the usable reference rows could have filled (the upper count of such a column is
+// the number of usable rows, since every d2 <= +inf: the entry is right only if that count is <= k, k counted from 0)
 __global__ __launch_bounds__(kVerifyThreads) void verify_check_kernel(const double* __restrict__ dist, int ld, int64_t nq, int K, int nsample, unsigned long long seed,
                                                                       const int* __restrict__ cnt, int* __restrict__ result)
 {
@@ -116,7 +122,8 @@ __global__ __launch_bounds__(kVerifyThreads) void verify_check_kernel(const doub
     bool bad = false;
     for (int k = 0; k < K; ++k) {
         const double r = dist[row * (int64_t)ld + k];
-        if (!(r < __builtin_huge_val())) { bad |= (r != r); continue; }
+        bad |= (r != r) | (r < 0.0);
+        if (r == __builtin_huge_val()) { bad |= cnt[((int64_t)s * 2 + 1) * K + k] > k; continue; }
         bad |= cnt[((int64_t)s * 2 + 0) * K + k] > k;
         bad |= cnt[((int64_t)s * 2 + 1) * K + k] < k + 1;
     }

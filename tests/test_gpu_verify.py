@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import LNE_TOL, orc
+from verify_cases import sample_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -65,10 +66,11 @@ def test_recheck_catches_wrong_lists(capi):
     # (d) the own row taken for a neighbour: lists of a search WITHOUT self-exclusion judged under it
     incl, _ = capi.knn(Y, Y, K, self_mode=capi.SELF_INCLUDE)
     assert capi.verify_knn(Y, Y, incl, self_mode=capi.SELF_EXCLUDE, nsample=n) == n
-    # a sample only sees its own rows: 1 corrupted row in 30 000, 300 sampled -> found or not, never more than one
+    # a sample only sees its own rows: 1 corrupted row in 30 000, 300 sampled -> found exactly when the row is one of them
     bad = good.copy()
     bad[rows[0], K - 1] *= 1.5
-    assert capi.verify_knn(Y, Y, bad, self_mode=capi.SELF_EXCLUDE, nsample=300) in (0, 1)
+    for seed in (0, int(rows[0]), int(rows[0]) + 7):
+        assert capi.verify_knn(Y, Y, bad, self_mode=capi.SELF_EXCLUDE, nsample=300, seed=seed) == int(rows[0] in sample_rows(300, n, seed))
     assert capi.verify_knn(Y, Y, bad, self_mode=capi.SELF_EXCLUDE, nsample=n) == 1
 
 

@@ -1167,22 +1167,29 @@ def _rows_f64(a, name, d, check=True):
     return a
 
 
+def _feed_host_args(S1, S2, d, w, f, sentence, shifted=True):
+    """The host inputs of a feed entry point: ((S1, S2, w, f) as the checked fp64 arrays the library reads -- keep them alive over the
+    call --, (S1, n1, ld1, S2, n2, ld2) as its leading ctypes arguments).  ``f``: the likelihood terms fs (``_f64_fs``), or with
+    ``shifted=False`` the log-likelihoods as they are; ``sentence``: the caller's words for w / f without one entry per row of S1."""
+    S1 = _rows_f64(S1, "samples", d, check=False)
+    S2 = None if S2 is None else _rows_f64(S2, "samples2", d, check=False)
+    w = _f64(w, "weight")
+    f = _f64_fs(f) if shifted else np.ascontiguousarray(f, dtype=np.float64)
+    if w.shape != (S1.shape[0],) or f.shape != w.shape:
+        raise ValueError(sentence)
+    rows2 = (None, 0, 0) if S2 is None else (S2.ctypes.data, S2.shape[0], S2.strides[0] // 8)
+    return (S1, S2, w, f), (S1.ctypes.data, S1.shape[0], S1.strides[0] // 8) + rows2
+
+
 def evidence_feed(S1, S2, d, cov_mode, kmax, w, fs, device=0):
     """Covariance + whitening + kNN + reduction on the device from ONE upload of the raw parameter
     rows.  Returns (dotp[kmax], jacobian, eigenvalues[d])."""
     lib = load()
-    S1 = _rows_f64(S1, "samples", d, check=False)
-    S2 = None if S2 is None else _rows_f64(S2, "samples2", d, check=False)
-    w = _f64(w, "weight")
-    fs = _f64_fs(fs)
-    if w.shape != (S1.shape[0],) or fs.shape != w.shape:
-        raise ValueError("weight and fs must have one entry per s1 row")
+    (S1, S2, w, fs), rows = _feed_host_args(S1, S2, d, w, fs, "weight and fs must have one entry per s1 row")
     out = np.zeros(int(kmax))
     jac = ctypes.c_double(0.0)
     ev = np.zeros(int(d))
-    check(lib.mce_evidence_feed_f64(S1.ctypes.data, S1.shape[0], S1.strides[0] // 8,
-                                    S2.ctypes.data if S2 is not None else None, 0 if S2 is None else S2.shape[0],
-                                    0 if S2 is None else S2.strides[0] // 8, int(d), int(cov_mode), int(kmax),
+    check(lib.mce_evidence_feed_f64(*rows, int(d), int(cov_mode), int(kmax),
                                     w.ctypes.data, fs.ctypes.data, out.ctypes.data, ctypes.byref(jac), ev.ctypes.data, int(device)))
     return out, float(jac.value), ev
 
@@ -1193,19 +1200,12 @@ def evidence_feed_part(S1, S2, d, cov_mode, kmax, w, fs, part, nparts, device=0,
     the partial sums still to be all-reduced over the ranks, and the device-side fingerprint of the uploaded inputs
     (None if not asked for)."""
     lib = load()
-    S1 = _rows_f64(S1, "samples", d, check=False)
-    S2 = None if S2 is None else _rows_f64(S2, "samples2", d, check=False)
-    w = _f64(w, "weight")
-    fs = _f64_fs(fs)
-    if w.shape != (S1.shape[0],) or fs.shape != w.shape:
-        raise ValueError("weight and fs must have one entry per s1 row")
+    (S1, S2, w, fs), rows = _feed_host_args(S1, S2, d, w, fs, "weight and fs must have one entry per s1 row")
     out = np.zeros(int(kmax))
     jac = ctypes.c_double(0.0)
     ev = np.zeros(int(d))
     csum = ctypes.c_uint64(0)
-    check(lib.mce_evidence_feed_part_f64(S1.ctypes.data, S1.shape[0], S1.strides[0] // 8,
-                                         S2.ctypes.data if S2 is not None else None, 0 if S2 is None else S2.shape[0],
-                                         0 if S2 is None else S2.strides[0] // 8, int(d), int(cov_mode), int(kmax),
+    check(lib.mce_evidence_feed_part_f64(*rows, int(d), int(cov_mode), int(kmax),
                                          w.ctypes.data, fs.ctypes.data, int(part), int(nparts), out.ctypes.data, ctypes.byref(jac),
                                          ev.ctypes.data, ctypes.byref(csum) if want_checksum else None, int(device)))
     return out, float(jac.value), ev, (int(csum.value) if want_checksum else None)
@@ -1241,15 +1241,11 @@ def evidence_feed_whiten(S1, d, kmax, w, fs, d_X_out, d_w_out, d_fs_out, device=
     whitened rows, weights and likelihood terms are left in the caller's DEVICE buffers (pointers; [n, d], [n], [n] doubles).
     Returns (jacobian, eigenvalues[d], checksum)."""
     lib = load()
-    S1 = _rows_f64(S1, "samples", d, check=False)
-    w = _f64(w, "weight")
-    fs = _f64_fs(fs)
-    if w.shape != (S1.shape[0],) or fs.shape != w.shape:
-        raise ValueError("weight and fs must have one entry per row")
+    (S1, _, w, fs), rows = _feed_host_args(S1, None, d, w, fs, "weight and fs must have one entry per row")
     jac = ctypes.c_double(0.0)
     ev = np.zeros(int(d))
     csum = ctypes.c_uint64(0)
-    check(lib.mce_evidence_feed_whiten_f64(S1.ctypes.data, S1.shape[0], S1.strides[0] // 8, int(d), int(kmax), w.ctypes.data, fs.ctypes.data,
+    check(lib.mce_evidence_feed_whiten_f64(*rows[:3], int(d), int(kmax), w.ctypes.data, fs.ctypes.data,
                                            d_X_out, d_w_out, d_fs_out, ctypes.byref(jac), ev.ctypes.data,
                                            ctypes.byref(csum) if want_checksum else None, int(device)))
     return float(jac.value), ev, (int(csum.value) if want_checksum else None)
@@ -1268,20 +1264,13 @@ def evidence_feed_prefix(S1, S2, d, cov_mode, kmax, w, logl, prefix, device=0):
     ``logl``: the log-likelihoods, not shifted (a NaN makes every prefix that holds it NaN, like ``np.amax``).
     Returns (dotp[B, kmax], loglmax[B], jacobian[B])."""
     lib = load()
-    S1 = _rows_f64(S1, "samples", d, check=False)
-    S2 = None if S2 is None else _rows_f64(S2, "samples2", d, check=False)
-    w = _f64(w, "weight")
-    logl = np.ascontiguousarray(logl, dtype=np.float64)
-    if w.shape != (S1.shape[0],) or logl.shape != w.shape:
-        raise ValueError("weight and logl must have one entry per s1 row")
+    (S1, S2, w, logl), rows = _feed_host_args(S1, S2, d, w, logl, "weight and logl must have one entry per s1 row", shifted=False)
     prefix = _prefix_arg(prefix)
     B = len(prefix)
     out = np.zeros((max(B, 1), max(int(kmax), 0)))
     lmax = np.zeros(max(B, 1))
     jac = np.zeros(max(B, 1))
-    check(lib.mce_evidence_feed_prefix_f64(S1.ctypes.data, S1.shape[0], S1.strides[0] // 8,
-                                           S2.ctypes.data if S2 is not None else None, 0 if S2 is None else S2.shape[0],
-                                           0 if S2 is None else S2.strides[0] // 8, int(d), int(cov_mode), int(kmax),
+    check(lib.mce_evidence_feed_prefix_f64(*rows, int(d), int(cov_mode), int(kmax),
                                            w.ctypes.data, logl.ctypes.data, prefix.ctypes.data if B else None, B,
                                            out.ctypes.data, lmax.ctypes.data, jac.ctypes.data, int(device)))
     return out[:B], lmax[:B], jac[:B]
@@ -1330,20 +1319,13 @@ def evidence_feed_batch(problems, devices=None, return_exceptions=False):
     outs = []
     for i, (S1, S2, d, cov_mode, kmax, w, fs) in enumerate(problems):
         d, kmax = int(d), int(kmax)
-        S1 = _rows_f64(S1, "samples", d, check=False)
-        S2 = None if S2 is None else _rows_f64(S2, "samples2", d, check=False)
-        w = _f64(w, "weight")
-        fs = _f64_fs(fs)
-        if w.shape != (S1.shape[0],) or fs.shape != w.shape:
-            raise ValueError("problem %d: weight and fs must have one entry per s1 row" % i)
+        (S1, S2, w, fs), rows = _feed_host_args(S1, S2, d, w, fs, "problem %d: weight and fs must have one entry per s1 row" % i)
         out = np.zeros(max(kmax, 0))
         ev = np.zeros(max(d, 0))
         keep.append((S1, S2, w, fs))
         outs.append((out, ev))
         q = arr[i]
-        q.S1, q.n1, q.ld1 = S1.ctypes.data, S1.shape[0], S1.strides[0] // 8
-        if S2 is not None:
-            q.S2, q.n2, q.ld2 = S2.ctypes.data, S2.shape[0], S2.strides[0] // 8
+        q.S1, q.n1, q.ld1, q.S2, q.n2, q.ld2 = rows
         q.d, q.cov_mode, q.kmax = d, int(cov_mode), kmax
         q.w, q.fs, q.dotp, q.eigenvalues = w.ctypes.data, fs.ctypes.data, out.ctypes.data, ev.ctypes.data
     devs, ndev = _devices_arg(devices)

@@ -1,6 +1,8 @@
 // capi_common.hpp -- part of capi.hip (one translation unit): error reporting, per-thread search statistics, the tuning / test
-// knobs (the ONE place the library reads the environment), per-call options, planner hints and the device / pinned memory pools.
+// knobs (the ONE place the library reads the environment), per-call options, planner hints, the device / pinned memory pools and,
+// through ws_plan.hpp, WsPlan: the planner every workspace and arena of the library is declared with.
 #pragma once
+#include "ws_plan.hpp"
 namespace {
 
 thread_local char g_err[512] = "";

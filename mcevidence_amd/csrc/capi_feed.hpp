@@ -1,6 +1,9 @@
 // capi_feed.hpp -- part of capi.hip: the host-pointer fused call on one device, the evidence feed (covariance -> eigen-system ->
-// whitening -> search -> reduction, MCEvidence.py:842-947 + :1093-1117) as a pipelined batch, and their entry points.
+// whitening -> search -> reduction, MCEvidence.py:842-947 + :1093-1117) as a pipelined batch, and their entry points.  Where a job's
+// arrays lie on the device and in the pinned block is feed_layout.hpp's; the stages that the convergence batches (capi_prefix.hpp)
+// share with the feed -- the checks, the copy in, the host's solves, the device solver's results, the certificate -- are defined here.
 #pragma once
+#include "feed_layout.hpp"
 namespace {
 
 // (the host eigen-solver, jacobi_eig, lives in eig_jacobi.hpp with the rules it shares with the device solver)
@@ -28,6 +31,12 @@ int launch_covariance(const double* dS, int64_t n, int d, double* scratch_partia
     MCE_HIP(hipGetLastError());
     return MCE_OK;
 }
+// the doubles of scratch_partial: the covariance kernels' partials or the mean kernels', whichever are more
+size_t feed_part_doubles(int d)
+{
+    return (size_t)std::max<int64_t>((int64_t)mce::kCovBlocks * (d * (d + 1) / 2), (int64_t)mce::kMeanBlocks * mce::kStatStride);
+}
+static_assert(mce_feed::kMean3 == 3 * mce::kMaxDimPad, "the mean block of the covariance kernels");
 
 // one device's share of the fused path: queries [q_lo, q_hi)
 int fused_on_device(int device, const double* X, int64_t q_lo, int64_t q_hi, const double* Y, int64_t nr, int32_t d,
@@ -69,6 +78,30 @@ int fused_on_device(int device, const double* X, int64_t q_lo, int64_t q_hi, con
     return MCE_OK;
 }
 
+// `work(i)` (-> its code, its text in g_err) for each of the first n devices: on the caller's thread for one device, else one thread
+// per device, the caller's options inherited (g_err is thread-local: each text is collected).  The first failing device is reported.
+template <class Work> int for_each_device(const std::vector<int>& devs, int n, Work work)
+{
+    std::vector<int> rcs(n, MCE_OK);
+    std::vector<std::string> errs(n);
+    auto run = [&](int i) {
+        rcs[i] = work(i);
+        if (rcs[i] != MCE_OK) errs[i] = g_err;
+    };
+    if (n == 1) {
+        run(0);
+    } else {
+        std::vector<std::thread> th;
+        const CallOptions inherited = t_opt;
+        for (int i = 0; i < n; ++i) th.emplace_back([&, i]() { t_opt = inherited; run(i); });
+        for (auto& t : th) t.join();
+    }
+    for (int i = 0; i < n; ++i)
+        if (rcs[i] != MCE_OK) return fail(rcs[i], "device %d: %s", devs[i], errs[i].c_str());
+    return MCE_OK;
+}
+std::vector<int> device_list(const int32_t* devices, int32_t ndev) { return (!devices || ndev <= 0) ? std::vector<int>{0} : std::vector<int>(devices, devices + ndev); }
+
 constexpr int kFeedMaxDim = 127;      // device feeders: d <= 63 on the narrow kernels, 64..127 on the wide ones (round 5; the search: knn_mfma.hpp's wide form)
 static_assert(kFeedMaxDim <= mce::kWideMaxDim && mce::whiten_wide_lds_bytes(kFeedMaxDim) <= 160 * 1024, "wide feeders");
 // ---- evidence feed: covariance -> eigen-system -> whitening -> search -> reduction ---------------
@@ -91,17 +124,18 @@ constexpr int kWaveMaxJobs = 1024;
 constexpr int kFeedStreams = 4;   // per set (upload+covariance | whiten+search)
 constexpr int kFeedGroup = 8;     // problems per pipeline step
 
+// what a job is handed: the rows, the weights and the likelihood terms (the convergence batches: the log-likelihoods)
+struct FeedIn { const double *S1, *S2, *w, *f; int64_t n1, ld1, n2, ld2; int d; };
+
 struct FeedJob {
     mce_feed_problem* q = nullptr;
     int64_t index = 0;
     Plan plan;
     int k0 = 1, K = 0, rc = MCE_OK;
     int64_t nr = 0, ntot = 0;
-    size_t wsb = 0, dev_bytes = 0, host_bytes = 0;
-    size_t o_S = 0, o_W = 0, o_F = 0, o_O = 0, o_small = 0, o_part = 0, o_ws = 0, o_vd = 0, o_vw = 0, o_vr = 0;
-    int nverify = 0;          // mce_options.verify: rows re-checked after the search (a whole problem only, not a rank's share)
-    char* dbase = nullptr;    // this job's slice of the wave's device arena
-    double* hbase = nullptr;  // this job's slice of the pinned host arena: cov[2] | evec[2] | scale[2] | dotp
+    mce_feed::FeedSizes z;    // (nverify: a whole problem only, not a rank's share; dev_eig: mce_options.eig_mode 2, stage B is skipped)
+    mce_feed::FeedArena a;    // this job's slice of the wave's device arena ...
+    mce_feed::FeedPinned h;   // ... and of the pinned host arena
     double jac = 0.0;
     int part = 0, nparts = 1;         // one rank's share of the problem (mce_evidence_feed_part_f64); 1: all of it
     double* out_X = nullptr;          // mce_evidence_feed_whiten_f64: no search -- the whitened rows, the weights and the likelihood terms are left in
@@ -113,8 +147,6 @@ struct FeedJob {
     unsigned long long checksum = 0;
     int64_t q_lo = 0, q_hi = 0;       // cross evidence of a part: its rows of s1
     std::vector<double> lam;  // eigenvalues of the system that defines J (s1's in 'single' mode)
-    bool dev_eig = false;     // the eigen-systems on the device (mce_options.eig_mode 2): stage B is skipped
-    size_t o_eig = 0;         // its block: cov[nsys] | evec[nsys] | scale[nsys] | lam[nsys] | status[nsys] (nsys slots: both systems in one launch)
     EigStats eig;             // what this job solved where
     std::string err;
     hipEvent_t upload_ev = nullptr;   // orders the job's stream behind its blocking uploads
@@ -124,37 +156,55 @@ struct FeedJob {
     FeedJob& operator=(const FeedJob&) = delete;
 
     int d() const { return q->d; }
-    double* dS1() const { return reinterpret_cast<double*>(dbase + o_S); }
-    double* dS2() const { return dS1() + (size_t)q->n1 * q->d; }
-    double* dW() const { return reinterpret_cast<double*>(dbase + o_W); }
-    double* dF() const { return reinterpret_cast<double*>(dbase + o_F); }
-    double* dO() const { return reinterpret_cast<double*>(dbase + o_O); }
-    double* d_mean3() const { return reinterpret_cast<double*>(dbase + o_small); }
-    double* d_cov() const { return d_mean3() + 3 * 64; }
-    double* d_evec() const { return d_cov() + (size_t)q->d * q->d; }
-    double* d_scale() const { return d_evec() + (size_t)q->d * q->d; }
-    unsigned long long* d_sum() const { return reinterpret_cast<unsigned long long*>(d_scale() + q->d); }
-    double* d_part() const { return reinterpret_cast<double*>(dbase + o_part); }
-    char* ws() const { return dbase + o_ws; }
-    double* h_cov(int i) const { return hbase + (size_t)i * q->d * q->d; }
-    double* h_evec(int i) const { return hbase + (size_t)(2 + i) * q->d * q->d; }
-    double* h_scale(int i) const { return hbase + (size_t)4 * q->d * q->d + (size_t)i * q->d; }
-    double* h_dotp() const { return hbase + (size_t)4 * q->d * q->d + (size_t)2 * q->d; }
-    unsigned long long* h_sum() const { return reinterpret_cast<unsigned long long*>(h_dotp() + q->kmax); }
-    int* h_verify() const { return reinterpret_cast<int*>(h_sum() + 1); }        // {rows checked, rows failed}
-    double* d_vdist() const { return reinterpret_cast<double*>(dbase + o_vd); }
-    int32_t* d_vres() const { return reinterpret_cast<int32_t*>(dbase + o_vr); }
+    FeedIn in() const { return FeedIn{q->S1, q->S2, q->w, q->fs, q->n1, q->ld1, q->n2, q->ld2, q->d}; }
     bool two_systems() const { return q->cov_mode == 1 && q->S2 != nullptr; }
-    int nsys() const { return two_systems() ? 2 : 1; }
-    double* e_cov(int i) const { return reinterpret_cast<double*>(dbase + o_eig) + (size_t)i * q->d * q->d; }
-    double* e_evec(int i) const { return e_cov(nsys()) + (size_t)i * q->d * q->d; }
-    double* e_scale(int i) const { return e_evec(nsys()) + (size_t)i * q->d; }
-    double* e_lam(int i) const { return e_scale(nsys()) + (size_t)i * q->d; }
-    int32_t* e_status(int i) const { return reinterpret_cast<int32_t*>(e_lam(nsys())) + i * mce_eig::kStatInts; }
-    size_t e_back_bytes() const { return (size_t)nsys() * (q->d * sizeof(double) + mce_eig::kStatInts * sizeof(int32_t)); }      // lam | status: one copy
-    double* h_lam(int i) const { return reinterpret_cast<double*>(h_verify() + 2) + (size_t)i * q->d; }
-    int32_t* h_status(int i) const { return reinterpret_cast<int32_t*>(h_lam(nsys())) + i * mce_eig::kStatInts; }
+    void place(void* dbase, void* hbase) { a = mce_feed::FeedArena(z, dbase), h = mce_feed::FeedPinned(z, hbase); }          // (null, null): the sizes only
     void set_error(int code) { rc = code; err = g_err; }
+};
+
+// the checks behind an entry point's own null-pointer check, in this order: the sizes, d, (the convergence batches: no two systems),
+// kmax -- cross evidence counts from the nearest row (k0 = 0), auto evidence past the row itself (k0 = 1)
+int feed_check(const FeedIn& in, int cov_mode, int kmax, bool one_system_only, int& k0, int& K)
+{
+    if (in.n1 < 2 || in.d < 1 || in.ld1 < in.d || (in.S2 && (in.n2 < 1 || in.ld2 < in.d)) || (cov_mode != 0 && cov_mode != 1))
+        return fail(MCE_ERR_INVALID, "invalid sizes n1=%lld ld1=%lld n2=%lld ld2=%lld d=%d cov_mode=%d", (long long)in.n1, (long long)in.ld1,
+                    (long long)in.n2, (long long)in.ld2, in.d, cov_mode);
+    if (in.d > kFeedMaxDim) return fail(MCE_ERR_DIM_RANGE, "device feeders support d <= %d (got %d)", kFeedMaxDim, in.d);
+    if (one_system_only && cov_mode == 1 && in.S2)
+        return fail(MCE_ERR_INVALID, "cov_mode 1 with S2: the two sets' own eigen-systems depend on the solver's conventions; not offered for prefixes");
+    k0 = in.S2 ? 0 : 1;
+    K = kmax - k0;
+    if (kmax <= k0) return fail(MCE_ERR_INVALID, "kmax=%d must exceed k0=%d", kmax, k0);
+    return MCE_OK;
+}
+
+// the rows (packed to d columns), weights and likelihoods into the arena.  ev null: the copies on st.  Otherwise blocking copies, and
+// *ev (created on first use), recorded behind them, orders st after them: see feed_stage_a.
+int feed_copy_in(const FeedIn& in, double* dS1, double* dS2, double* dW, double* dF, hipMemcpyKind kind, hipStream_t st, hipEvent_t* ev)
+{
+    const size_t D = sizeof(double), row = (size_t)in.d * D, vec = (size_t)in.n1 * D;
+    if (!ev) {
+        MCE_HIP(hipMemcpy2DAsync(dS1, row, in.S1, (size_t)in.ld1 * D, row, (size_t)in.n1, kind, st));
+        if (in.S2) MCE_HIP(hipMemcpy2DAsync(dS2, row, in.S2, (size_t)in.ld2 * D, row, (size_t)in.n2, kind, st));
+        MCE_HIP(hipMemcpyAsync(dW, in.w, vec, kind, st));
+        MCE_HIP(hipMemcpyAsync(dF, in.f, vec, kind, st));
+        return MCE_OK;
+    }
+    MCE_HIP(hipMemcpy2D(dS1, row, in.S1, (size_t)in.ld1 * D, row, (size_t)in.n1, kind));
+    if (in.S2) MCE_HIP(hipMemcpy2D(dS2, row, in.S2, (size_t)in.ld2 * D, row, (size_t)in.n2, kind));
+    MCE_HIP(hipMemcpy(dW, in.w, vec, kind));
+    MCE_HIP(hipMemcpy(dF, in.f, vec, kind));
+    if (!*ev) MCE_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    MCE_HIP(hipEventRecord(*ev, nullptr));
+    MCE_HIP(hipStreamWaitEvent(st, *ev, 0));
+    return MCE_OK;
+}
+
+// destroyed BEFORE the arena it guards: an early return (a failing HIP call) must not hand the arena back to the pool while
+// kernels -- of other jobs, on other streams -- are still running on it
+struct Quiesce {
+    bool armed = true;
+    ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); }
 };
 
 // argument checks + sizes; no device work
@@ -162,19 +212,15 @@ int feed_plan(FeedJob& j)
 {
     const mce_feed_problem& q = *j.q;
     if (!q.S1 || !q.w || !q.fs || !q.dotp) return fail(MCE_ERR_INVALID, "null pointer argument");
-    if (q.n1 < 2 || q.d < 1 || q.ld1 < q.d || (q.S2 && (q.n2 < 1 || q.ld2 < q.d)) || (q.cov_mode != 0 && q.cov_mode != 1))
-        return fail(MCE_ERR_INVALID, "invalid sizes n1=%lld ld1=%lld n2=%lld ld2=%lld d=%d cov_mode=%d", (long long)q.n1, (long long)q.ld1,
-                    (long long)q.n2, (long long)q.ld2, q.d, q.cov_mode);
-    if (q.d > kFeedMaxDim) return fail(MCE_ERR_DIM_RANGE, "device feeders support d <= %d (got %d)", kFeedMaxDim, q.d);
-    j.k0 = q.S2 ? 0 : 1;
-    j.K = q.kmax - j.k0;
-    if (q.kmax <= j.k0) return fail(MCE_ERR_INVALID, "kmax=%d must exceed k0=%d", q.kmax, j.k0);
+    int rc = feed_check(j.in(), q.cov_mode, q.kmax, false, j.k0, j.K);
+    if (rc != MCE_OK) return rc;
     j.nr = q.S2 ? q.n2 : q.n1;
     j.ntot = q.n1 + (q.S2 ? q.n2 : 0);
     SameSetHint hint(q.S2 == nullptr);          // auto evidence: one set; cross evidence: never the symmetric sweep
-    int rc = make_plan(q.n1, j.nr, q.d, j.K, j.k0 == 1 ? MCE_SELF_EXCLUDE : MCE_SELF_NONE, j.plan);
+    rc = make_plan(q.n1, j.nr, q.d, j.K, j.k0 == 1 ? MCE_SELF_EXCLUDE : MCE_SELF_NONE, j.plan);
     if (rc != MCE_OK) return rc;
-    j.wsb = j.out_X ? 0 : j.plan.total + dotp_ws_bytes(q.n1, q.kmax);
+    mce_feed::FeedSizes& z = j.z;
+    z.search_ws_bytes = j.out_X ? 0 : j.plan.total + dotp_ws_bytes(q.n1, q.kmax);
     j.q_lo = 0;
     j.q_hi = q.n1;
     if (j.nparts > 1 && q.S2) {
@@ -185,95 +231,65 @@ int feed_plan(FeedJob& j)
             Plan shard;
             rc = make_plan(j.q_hi - j.q_lo, j.nr, q.d, j.K, MCE_SELF_NONE, shard);
             if (rc != MCE_OK) return rc;
-            j.wsb = std::max(j.wsb, shard.total + dotp_ws_bytes(j.q_hi - j.q_lo, q.kmax));
+            z.search_ws_bytes = std::max(z.search_ws_bytes, shard.total + dotp_ws_bytes(j.q_hi - j.q_lo, q.kmax));
         }
     }
-    const int d = q.d, npair = d * (d + 1) / 2;
-    size_t off = 0;
-    j.o_S = off;     off = align_up(off + (size_t)j.ntot * d * sizeof(double), 256);
-    j.o_W = off;     off = align_up(off + (size_t)q.n1 * sizeof(double), 256);
-    j.o_F = off;     off = align_up(off + (size_t)q.n1 * sizeof(double), 256);
-    j.o_O = off;     off = align_up(off + (size_t)q.kmax * sizeof(double), 256);
-    j.o_small = off; off = align_up(off + (size_t)(3 * 64 + 2 * d * d + d + 1) * sizeof(double), 256);     // mean3 | cov | evec | scale | checksum
-    j.o_part = off;  off = align_up(off + (size_t)std::max<int64_t>((int64_t)mce::kCovBlocks * npair, (int64_t)mce::kMeanBlocks * mce::kStatStride) * sizeof(double), 256);
-    j.o_ws = off;    off = align_up(off + j.wsb, 256);
-    j.nverify = (j.nparts == 1 && !j.out_X && d <= mce::kVerifyMaxDim && j.K <= mce::kVerifyMaxK) ? (int)std::min<int64_t>(eff_verify(j.plan.filter(), q.n1), q.n1) : 0;
-    if (j.nverify > 0) {
-        j.o_vd = off; off = align_up(off + (size_t)q.n1 * j.K * sizeof(double), 256);
-        j.o_vw = off; off = align_up(off + mce_verify_workspace_bytes(j.nverify, j.K), 256);
-        j.o_vr = off; off = align_up(off + 2 * sizeof(int), 256);
-    }
-    j.dev_eig = eff_eig_mode() == 2;
-    if (j.dev_eig) {
-        j.o_eig = off;
-        off = align_up(off + (size_t)j.nsys() * (2 * d * d + 2 * d) * sizeof(double) + (size_t)j.nsys() * mce_eig::kStatInts * sizeof(int32_t), 256);
-    }
-    j.dev_bytes = off;
-    j.host_bytes = align_up((size_t)(4 * d * d + 2 * d + q.kmax + 2) * sizeof(double) + (j.dev_eig ? j.e_back_bytes() : 0), 64);
+    z.n1 = q.n1; z.ntot = j.ntot; z.d = q.d; z.kmax = q.kmax; z.K = j.K;
+    z.nsys = j.two_systems() ? 2 : 1;
+    z.part_doubles = feed_part_doubles(q.d);
+    z.nverify = (j.nparts == 1 && !j.out_X && q.d <= mce::kVerifyMaxDim && j.K <= mce::kVerifyMaxK) ? (int)std::min<int64_t>(eff_verify(j.plan.filter(), q.n1), q.n1) : 0;
+    z.verify_ws_bytes = mce_verify_workspace_bytes(z.nverify, j.K);
+    z.dev_eig = eff_eig_mode() == 2;
+    z.stat_ints = mce_eig::kStatInts;
+    j.place(nullptr, nullptr);
     return MCE_OK;
 }
 
 int feed_stage_a(FeedJob& j, hipStream_t st)
 {
     const mce_feed_problem& q = *j.q;
+    const mce_feed::FeedArena& a = j.a;
     const int d = q.d;
-    const size_t row = (size_t)d * sizeof(double);
     // Uploads: blocking copies from the caller's pageable arrays (measured faster than hipMemcpyAsync on the job's
     // non-blocking stream: 300 Planck-sized chains 0.131 vs 0.153 s), followed by an EXPLICIT dependency -- an event
     // recorded on the stream the copies ran on, waited for by the job's stream -- so the covariance kernels behind them
     // are ordered after the uploads by the API's rules, not by how this runtime happens to implement a pageable copy
     // (a blocking hipMemcpy from pageable memory only promises that the SOURCE has been consumed on return, and
     // hipStreamNonBlocking streams do not synchronise with the legacy default stream).  MCE_FEED_UPLOAD=async: the
-    // copies themselves on the job's stream.
-    const bool async_upload = env_feed_upload_async();
-    if (j.src_device) {
-        // the rows are on this device already (the caller has synchronised the stream that produced them)
-        MCE_HIP(hipMemcpy2DAsync(j.dS1(), row, q.S1, (size_t)q.ld1 * sizeof(double), row, (size_t)q.n1, hipMemcpyDeviceToDevice, st));
-        if (q.S2) MCE_HIP(hipMemcpy2DAsync(j.dS2(), row, q.S2, (size_t)q.ld2 * sizeof(double), row, (size_t)q.n2, hipMemcpyDeviceToDevice, st));
-        MCE_HIP(hipMemcpyAsync(j.dW(), q.w, (size_t)q.n1 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        MCE_HIP(hipMemcpyAsync(j.dF(), q.fs, (size_t)q.n1 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    } else if (async_upload || st == nullptr) {
-        MCE_HIP(hipMemcpy2DAsync(j.dS1(), row, q.S1, (size_t)q.ld1 * sizeof(double), row, (size_t)q.n1, hipMemcpyHostToDevice, st));
-        if (q.S2) MCE_HIP(hipMemcpy2DAsync(j.dS2(), row, q.S2, (size_t)q.ld2 * sizeof(double), row, (size_t)q.n2, hipMemcpyHostToDevice, st));
-        MCE_HIP(hipMemcpyAsync(j.dW(), q.w, (size_t)q.n1 * sizeof(double), hipMemcpyHostToDevice, st));
-        MCE_HIP(hipMemcpyAsync(j.dF(), q.fs, (size_t)q.n1 * sizeof(double), hipMemcpyHostToDevice, st));
-    } else {
-        MCE_HIP(hipMemcpy2D(j.dS1(), row, q.S1, (size_t)q.ld1 * sizeof(double), row, (size_t)q.n1, hipMemcpyHostToDevice));
-        if (q.S2) MCE_HIP(hipMemcpy2D(j.dS2(), row, q.S2, (size_t)q.ld2 * sizeof(double), row, (size_t)q.n2, hipMemcpyHostToDevice));
-        MCE_HIP(hipMemcpy(j.dW(), q.w, (size_t)q.n1 * sizeof(double), hipMemcpyHostToDevice));
-        MCE_HIP(hipMemcpy(j.dF(), q.fs, (size_t)q.n1 * sizeof(double), hipMemcpyHostToDevice));
-        if (!j.upload_ev) MCE_HIP(hipEventCreateWithFlags(&j.upload_ev, hipEventDisableTiming));
-        MCE_HIP(hipEventRecord(j.upload_ev, nullptr));
-        MCE_HIP(hipStreamWaitEvent(st, j.upload_ev, 0));
-    }
+    // copies themselves on the job's stream.  Rows that are on this device already (the caller has synchronised the
+    // stream that produced them) are copied on the job's stream.
+    const bool on_stream = j.src_device || env_feed_upload_async() || st == nullptr;
+    int rc = feed_copy_in(j.in(), a.S1, a.S2, a.W, a.F, j.src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st, on_stream ? nullptr : &j.upload_ev);
+    if (rc != MCE_OK) return rc;
     if (j.want_sum) {
         // fingerprint of what this rank was handed (RAW rows, weights, fs), before anything is whitened in place
-        MCE_HIP(mce::zero_async(j.d_sum(), sizeof(unsigned long long), st));
+        MCE_HIP(mce::zero_async(a.sum, sizeof(unsigned long long), st));
         const int64_t nw[3] = {j.ntot * (int64_t)d, q.n1, q.n1};
-        const double* src[3] = {j.dS1(), j.dW(), j.dF()};
+        const double* src[3] = {a.S1, a.W, a.F};
         for (int b = 0; b < 3; ++b) {
             const unsigned blocks = (unsigned)std::min<int64_t>((nw[b] + mce::kSumThreads - 1) / mce::kSumThreads, 2048);
             hipLaunchKernelGGL(mce::checksum_kernel, dim3(blocks), dim3(mce::kSumThreads), 0, st, reinterpret_cast<const unsigned long long*>(src[b]), nw[b],
-                               (unsigned long long)(b + 1) << 56 ^ (unsigned long long)q.n1 << 8 ^ (unsigned long long)d, j.d_sum());
+                               (unsigned long long)(b + 1) << 56 ^ (unsigned long long)q.n1 << 8 ^ (unsigned long long)d, a.sum);
             MCE_HIP(hipGetLastError());
         }
-        MCE_HIP(hipMemcpyAsync(j.h_sum(), j.d_sum(), sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    }
-    if (j.dev_eig) {
-        // the covariances into the solver's slots, both systems of a 'single' cross evidence in ONE launch; nothing comes down
-        int rc = launch_covariance(j.dS1(), q.cov_mode == 0 ? j.ntot : q.n1, d, j.d_part(), j.d_mean3(), j.e_cov(0), st);
-        if (rc == MCE_OK && j.two_systems()) rc = launch_covariance(j.dS2(), q.n2, d, j.d_part(), j.d_mean3(), j.e_cov(1), st);
-        if (rc != MCE_OK) return rc;
-        return launch_eig(j.e_cov(0), d, j.nsys(), j.e_evec(0), j.e_scale(0), j.e_lam(0), j.e_status(0), st);
+        MCE_HIP(hipMemcpyAsync(j.h.sum, a.sum, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     }
     // "all": one eigen-system from s1 U s2; "single": s1's own, and s2's own for s2 (J stays s1's)
-    int rc = launch_covariance(j.dS1(), q.cov_mode == 0 ? j.ntot : q.n1, d, j.d_part(), j.d_mean3(), j.d_cov(), st);
-    if (rc != MCE_OK) return rc;
-    MCE_HIP(hipMemcpyAsync(j.h_cov(0), j.d_cov(), (size_t)d * d * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (j.two_systems()) {
-        rc = launch_covariance(j.dS2(), q.n2, d, j.d_part(), j.d_mean3(), j.d_cov(), st);
+    const int64_t n_first = q.cov_mode == 0 ? j.ntot : q.n1;
+    if (j.z.dev_eig) {
+        // the covariances into the solver's slots, both systems of a 'single' cross evidence in ONE launch; nothing comes down
+        rc = launch_covariance(a.S1, n_first, d, a.part, a.mean3, a.eig.cov_at(0), st);
+        if (rc == MCE_OK && j.two_systems()) rc = launch_covariance(a.S2, q.n2, d, a.part, a.mean3, a.eig.cov_at(1), st);
         if (rc != MCE_OK) return rc;
-        MCE_HIP(hipMemcpyAsync(j.h_cov(1), j.d_cov(), (size_t)d * d * sizeof(double), hipMemcpyDeviceToHost, st));
+        return launch_eig(a.eig.cov, d, j.z.nsys, a.eig.evec, a.eig.scale, a.eig.back.lam, a.eig.back.status, st);
+    }
+    rc = launch_covariance(a.S1, n_first, d, a.part, a.mean3, a.cov, st);
+    if (rc != MCE_OK) return rc;
+    MCE_HIP(hipMemcpyAsync(j.h.cov_at(0), a.cov, (size_t)d * d * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (j.two_systems()) {
+        rc = launch_covariance(a.S2, q.n2, d, a.part, a.mean3, a.cov, st);
+        if (rc != MCE_OK) return rc;
+        MCE_HIP(hipMemcpyAsync(j.h.cov_at(1), a.cov, (size_t)d * d * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     return MCE_OK;
 }
@@ -301,20 +317,37 @@ double feed_jacobian(const std::vector<double>& lam)
     return std::exp(0.5 * logdet);
 }
 
+// the host's solves (stage B): system i from cov[i] into evec[i] (the same block will do) and scale[i], its eigenvalues into lam[i];
+// counted into `stats`.  The first system that fails ends the loop: `at` is its index.
+int feed_solve_host(int nsys, int d, const double* cov, double* evec, double* scale, std::vector<std::vector<double>>& lam, EigStats& stats, int& at)
+{
+    lam.assign(nsys, std::vector<double>());
+    for (at = 0; at < nsys; ++at) {
+        const int rc = feed_eig_system(cov + (size_t)at * d * d, d, evec + (size_t)at * d * d, scale + (size_t)at * d, lam[at]);
+        if (rc != MCE_OK) return rc;
+        stats.host += 1;
+    }
+    return MCE_OK;
+}
+
+// the same from the device solver, once its status words and eigenvalues are on the host: every system is counted into `stats`; the
+// first that failed names the error (`at`: its index) -- its searches ran on placeholder rows, whatever their certificate says
+int feed_eig_results(const mce_feed::EigBack& h, int nsys, EigStats& stats, int& at)
+{
+    for (int i = 0; i < nsys; ++i) eig_stats_add(stats, h.status_at(i));
+    for (at = 0; at < nsys; ++at)
+        if (h.status_at(at)[mce_eig::kStatCode] != mce_eig::kStatusOk) return eig_status_fail(h.status_at(at), h.lam_at(at));
+    return MCE_OK;
+}
+
 int feed_stage_b(FeedJob& j)
 {
-    const int d = j.d();
-    const int nsys = j.two_systems() ? 2 : 1;
-    for (int sidx = 0; sidx < nsys; ++sidx) {
-        std::vector<double> lam;
-        const int rc = feed_eig_system(j.h_cov(sidx), d, j.h_evec(sidx), j.h_scale(sidx), lam);
-        if (rc != MCE_OK) return rc;
-        j.eig.host += 1;
-        if (sidx == 0) {
-            j.jac = feed_jacobian(lam);
-            j.lam = lam;
-        }
-    }
+    std::vector<std::vector<double>> lam;
+    int at = 0;
+    const int rc = feed_solve_host(j.z.nsys, j.d(), j.h.cov, j.h.evec, j.h.scale, lam, j.eig, at);
+    if (rc != MCE_OK) return rc;
+    j.lam = lam[0];
+    j.jac = feed_jacobian(j.lam);
     return MCE_OK;
 }
 
@@ -335,10 +368,10 @@ int launch_whiten(const double* S, int64_t n, int d, const double* d_evec, const
 int feed_whiten(FeedJob& j, int sidx, double* rows, int64_t n, hipStream_t st)
 {
     const int d = j.d();
-    if (j.dev_eig) return launch_whiten(rows, n, d, j.e_evec(sidx), j.e_scale(sidx), rows, st, j.e_status(sidx));
-    MCE_HIP(hipMemcpyAsync(j.d_evec(), j.h_evec(sidx), (size_t)d * d * sizeof(double), hipMemcpyHostToDevice, st));
-    MCE_HIP(hipMemcpyAsync(j.d_scale(), j.h_scale(sidx), (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
-    return launch_whiten(rows, n, d, j.d_evec(), j.d_scale(), rows, st);
+    if (j.z.dev_eig) return launch_whiten(rows, n, d, j.a.eig.evec_at(sidx), j.a.eig.scale_at(sidx), rows, st, j.a.eig.back.status_at(sidx));
+    MCE_HIP(hipMemcpyAsync(j.a.evec, j.h.evec_at(sidx), (size_t)d * d * sizeof(double), hipMemcpyHostToDevice, st));
+    MCE_HIP(hipMemcpyAsync(j.a.scale, j.h.scale_at(sidx), (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+    return launch_whiten(rows, n, d, j.a.evec, j.a.scale, rows, st);
 }
 
 // the whitening kernels stage more LDS than the default limit: raise it once per device
@@ -356,72 +389,78 @@ int whiten_attr_once()
     return MCE_OK;
 }
 
+// mce_options.verify: the rows a search ran on and its distances are still on the device; re-check a sample of nverify of them
+// (stream-ordered; the call's search `index` seeds the sample) and send {rows checked, rows failed} to h_res
+int feed_verify_enqueue(const double* X, int64_t nq, const double* Y, int64_t nref, int d, int K, int k0, const double* d_dist, int nverify, int64_t index,
+                        int32_t* d_res, void* vws, int* h_res, hipStream_t st)
+{
+    const int rc = mce_verify_knn_f64_dev(X, nq, Y, nref, d, K, k0 == 1 ? MCE_SELF_EXCLUDE : MCE_SELF_NONE, 0, d_dist, K, nverify,
+                                          0x9E3779B97F4A7C15ull * (unsigned long long)(index + 1), d_res, vws, mce_verify_workspace_bytes(nverify, K), st);
+    if (rc != MCE_OK) return rc;
+    MCE_HIP(hipMemcpyAsync(h_res, d_res, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    return MCE_OK;
+}
+
 int feed_stage_c(FeedJob& j, hipStream_t st)
 {
     const mce_feed_problem& q = *j.q;
+    const mce_feed::FeedArena& a = j.a;
+    const size_t wsb = j.z.search_ws_bytes;
     int rc = whiten_attr_once();
     if (rc != MCE_OK) return rc;
     if (j.two_systems()) {
-        rc = feed_whiten(j, 0, j.dS1(), q.n1, st);
+        rc = feed_whiten(j, 0, a.S1, q.n1, st);
         if (rc != MCE_OK) return rc;
-        rc = feed_whiten(j, 1, j.dS2(), q.n2, st);
+        rc = feed_whiten(j, 1, a.S2, q.n2, st);
     } else {
-        rc = feed_whiten(j, 0, j.dS1(), q.cov_mode == 0 ? j.ntot : q.n1, st);
+        rc = feed_whiten(j, 0, a.S1, q.cov_mode == 0 ? j.ntot : q.n1, st);
     }
     if (rc != MCE_OK) return rc;
     SameSetHint hint(q.S2 == nullptr);          // as in feed_plan: the workspace was sized with it
     if (j.out_X) {                              // whitening only: hand the rows over, no search (the sums stay zero)
-        MCE_HIP(hipMemcpyAsync(j.out_X, j.dS1(), (size_t)q.n1 * q.d * sizeof(double), hipMemcpyDeviceToDevice, st));
-        MCE_HIP(hipMemcpyAsync(j.out_w, j.dW(), (size_t)q.n1 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        MCE_HIP(hipMemcpyAsync(j.out_f, j.dF(), (size_t)q.n1 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        rc = (mce::zero_async(j.dO(), (size_t)q.kmax * sizeof(double), st) == hipSuccess) ? MCE_OK : fail(MCE_ERR_HIP, "clearing the sums failed");
+        MCE_HIP(hipMemcpyAsync(j.out_X, a.S1, (size_t)q.n1 * q.d * sizeof(double), hipMemcpyDeviceToDevice, st));
+        MCE_HIP(hipMemcpyAsync(j.out_w, a.W, (size_t)q.n1 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        MCE_HIP(hipMemcpyAsync(j.out_f, a.F, (size_t)q.n1 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        rc = (mce::zero_async(a.O, (size_t)q.kmax * sizeof(double), st) == hipSuccess) ? MCE_OK : fail(MCE_ERR_HIP, "clearing the sums failed");
     } else if (j.nparts > 1 && !q.S2)           // one rank's share of an auto-evidence search: the library's partition
-        rc = mce_knn_dotp_part_f64_dev(j.dS1(), q.n1, q.d, q.kmax, j.part, j.nparts, j.dW(), j.dF(), j.dO(), j.ws(), j.wsb, st);
+        rc = mce_knn_dotp_part_f64_dev(a.S1, q.n1, q.d, q.kmax, j.part, j.nparts, a.W, a.F, a.O, a.ws, wsb, st);
     else if (j.nparts > 1 && j.q_hi <= j.q_lo)
-        rc = (mce::zero_async(j.dO(), (size_t)q.kmax * sizeof(double), st) == hipSuccess) ? MCE_OK : fail(MCE_ERR_HIP, "clearing the sums failed");
+        rc = (mce::zero_async(a.O, (size_t)q.kmax * sizeof(double), st) == hipSuccess) ? MCE_OK : fail(MCE_ERR_HIP, "clearing the sums failed");
     else if (j.nparts > 1)                      // ... of a cross-evidence search: its rows of s1 against all of s2
-        rc = mce_knn_dotp_f64_dev(j.dS1() + j.q_lo * (int64_t)q.d, j.q_hi - j.q_lo, j.dS2(), j.nr, q.d, q.kmax, 0, 0, j.dW() + j.q_lo, j.dF() + j.q_lo,
-                                  j.dO(), nullptr, j.ws(), j.wsb, st);
+        rc = mce_knn_dotp_f64_dev(a.S1 + j.q_lo * (int64_t)q.d, j.q_hi - j.q_lo, a.S2, j.nr, q.d, q.kmax, 0, 0, a.W + j.q_lo, a.F + j.q_lo,
+                                  a.O, nullptr, a.ws, wsb, st);
     else
-        rc = mce_knn_dotp_f64_dev(j.dS1(), q.n1, q.S2 ? j.dS2() : j.dS1(), j.nr, q.d, q.kmax, j.k0, 0, j.dW(), j.dF(), j.dO(),
-                                  j.nverify > 0 ? j.d_vdist() : nullptr, j.ws(), j.wsb, st);
+        rc = mce_knn_dotp_f64_dev(a.S1, q.n1, q.S2 ? a.S2 : a.S1, j.nr, q.d, q.kmax, j.k0, 0, a.W, a.F, a.O, a.vdist, a.ws, wsb, st);
     if (rc != MCE_OK) return rc;
-    MCE_HIP(hipMemcpyAsync(j.h_dotp(), j.dO(), (size_t)q.kmax * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (j.dev_eig) MCE_HIP(hipMemcpyAsync(j.h_lam(0), j.e_lam(0), j.e_back_bytes(), hipMemcpyDeviceToHost, st));
-    if (j.nverify > 0) {
-        // mce_options.verify: the whitened rows the search ran on are still here; re-check a sample of them (stream-ordered)
-        rc = mce_verify_knn_f64_dev(j.dS1(), q.n1, q.S2 ? j.dS2() : j.dS1(), j.nr, q.d, j.K, j.k0 == 1 ? MCE_SELF_EXCLUDE : MCE_SELF_NONE, 0, j.d_vdist(),
-                                    j.K, j.nverify, 0x9E3779B97F4A7C15ull * (unsigned long long)(j.index + 1), j.d_vres(), j.dbase + j.o_vw,
-                                    mce_verify_workspace_bytes(j.nverify, j.K), st);
-        if (rc != MCE_OK) return rc;
-        MCE_HIP(hipMemcpyAsync(j.h_verify(), j.d_vres(), 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
+    MCE_HIP(hipMemcpyAsync(j.h.dotp, a.O, (size_t)q.kmax * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (j.z.dev_eig) MCE_HIP(hipMemcpyAsync(j.h.eig.lam, a.eig.back.lam, a.eig.back.bytes, hipMemcpyDeviceToHost, st));
+    if (j.z.nverify > 0)          // (a.vdist is there exactly then)
+        return feed_verify_enqueue(a.S1, q.n1, q.S2 ? a.S2 : a.S1, j.nr, q.d, j.K, j.k0, a.vdist, j.z.nverify, j.index, a.vres, a.vws, j.h.verify, st);
     return MCE_OK;
 }
 
 void feed_stage_d(FeedJob& j)
 {
     mce_feed_problem& q = *j.q;
-    if (j.dev_eig) {
-        // the solve's status first: the search of a failed system ran on placeholder rows, whatever its certificate says
-        for (int i = 0; i < j.nsys(); ++i) eig_stats_add(j.eig, j.h_status(i));
-        for (int i = 0; i < j.nsys(); ++i)
-            if (j.h_status(i)[mce_eig::kStatCode] != mce_eig::kStatusOk) {
-                j.set_error(eig_status_fail(j.h_status(i), j.h_lam(i)));
-                g_last_verify_rows.store(0);
-                return;
-            }
-        j.lam.assign(j.h_lam(0), j.h_lam(0) + q.d);
+    if (j.z.dev_eig) {
+        int at = 0;
+        const int rc = feed_eig_results(j.h.eig, j.z.nsys, j.eig, at);
+        if (rc != MCE_OK) {
+            j.set_error(rc);
+            g_last_verify_rows.store(0);
+            return;
+        }
+        j.lam.assign(j.h.eig.lam, j.h.eig.lam + q.d);
         j.jac = feed_jacobian(j.lam);
     }
-    std::copy(j.h_dotp(), j.h_dotp() + q.kmax, q.dotp);
+    std::copy(j.h.dotp, j.h.dotp + q.kmax, q.dotp);
     q.jacobian = j.jac;
     if (q.eigenvalues) std::copy(j.lam.begin(), j.lam.end(), q.eigenvalues);
-    if (j.want_sum) j.checksum = *j.h_sum();
-    g_last_verify_rows.store(j.nverify > 0 ? j.h_verify()[0] : 0);
-    if (j.nverify > 0 && j.h_verify()[1] != 0)
+    if (j.want_sum) j.checksum = *j.h.sum;
+    g_last_verify_rows.store(j.z.nverify > 0 ? j.h.verify[0] : 0);
+    if (j.z.nverify > 0 && j.h.verify[1] != 0)
         j.set_error(fail(MCE_ERR_VERIFY, "k-NN re-check failed: %d of %d sampled query rows have a neighbour list that an exact fp64 scan of all %lld reference rows "
-                         "contradicts", j.h_verify()[1], j.h_verify()[0], (long long)j.nr));
+                         "contradicts", j.h.verify[1], j.h.verify[0], (long long)j.nr));
 }
 
 // all jobs of one device, in waves; per-job failures are recorded in the job, a failure of the
@@ -465,33 +504,27 @@ int feed_run_on_device(int device, std::vector<FeedJob*>& jobs)
     size_t lo = 0;
     while (lo < jobs.size()) {
         size_t hi = lo, dev_bytes = 0, host_bytes = 0;
-        while (hi < jobs.size() && (hi == lo || (dev_bytes + jobs[hi]->dev_bytes <= wave_bytes && hi - lo < (size_t)kWaveMaxJobs))) {
-            dev_bytes += jobs[hi]->dev_bytes;
-            host_bytes += jobs[hi]->host_bytes;
+        while (hi < jobs.size() && (hi == lo || (dev_bytes + jobs[hi]->a.total <= wave_bytes && hi - lo < (size_t)kWaveMaxJobs))) {
+            dev_bytes += jobs[hi]->a.total;
+            host_bytes += jobs[hi]->h.total;
             ++hi;
         }
         DevBuf arena;
-        // destroyed BEFORE the arena: an early return (a failing HIP call in the loops below) must not hand the
-        // arena back to the pool while kernels of other jobs are still running on the other streams
-        struct Quiesce {
-            bool armed = true;
-            ~Quiesce() { if (armed) (void)hipDeviceSynchronize(); }
-        } quiesce;
+        Quiesce quiesce;
         PinnedArena& pinned = g_pinned;
         MCE_HIP(arena.alloc(dev_bytes));
         MCE_HIP(pinned.reserve(host_bytes));
         size_t doff = 0, hoff = 0;
         for (size_t i = lo; i < hi; ++i) {
-            jobs[i]->dbase = static_cast<char*>(arena.p) + doff;
-            jobs[i]->hbase = reinterpret_cast<double*>(static_cast<char*>(pinned.p) + hoff);
-            doff += jobs[i]->dev_bytes;
-            hoff += jobs[i]->host_bytes;
+            jobs[i]->place(static_cast<char*>(arena.p) + doff, static_cast<char*>(pinned.p) + hoff);
+            doff += jobs[i]->a.total;
+            hoff += jobs[i]->h.total;
         }
         if (!piped) {
             FeedJob& j = *jobs[lo];
             if (j.rc == MCE_OK) {
                 int r = feed_stage_a(j, nullptr);
-                if (r == MCE_OK && !j.dev_eig) { MCE_HIP(hipStreamSynchronize(nullptr)); r = feed_stage_b(j); }
+                if (r == MCE_OK && !j.z.dev_eig) { MCE_HIP(hipStreamSynchronize(nullptr)); r = feed_stage_b(j); }
                 if (r == MCE_OK) r = feed_stage_c(j, nullptr);
                 if (r == MCE_OK) { MCE_HIP(hipStreamSynchronize(nullptr)); feed_stage_d(j); }
                 else { j.set_error(r); (void)hipStreamSynchronize(nullptr); }
@@ -521,7 +554,7 @@ int feed_run_on_device(int device, std::vector<FeedJob*>& jobs)
                 FeedJob& j = *jobs[i];
                 if (j.rc != MCE_OK) continue;
                 int r = MCE_OK;
-                if (j.dev_eig) MCE_HIP(hipStreamWaitEvent(sc[i % sc.size()], events[i - g0], 0));      // the device waits for stage A, the host does not
+                if (j.z.dev_eig) MCE_HIP(hipStreamWaitEvent(sc[i % sc.size()], events[i - g0], 0));      // the device waits for stage A, the host does not
                 else { MCE_HIP(hipEventSynchronize(events[i - g0])); r = feed_stage_b(j); }
                 if (r == MCE_OK) r = feed_stage_c(j, sc[i % sc.size()]);
                 if (r != MCE_OK) j.set_error(r);
@@ -538,6 +571,37 @@ int feed_run_on_device(int device, std::vector<FeedJob*>& jobs)
             if (jobs[i]->rc == MCE_OK) feed_stage_d(*jobs[i]);
         lo = hi;
     }
+    return MCE_OK;
+}
+
+mce_feed_problem feed_problem(const double* S1, int64_t n1, int64_t ld1, const double* S2, int64_t n2, int64_t ld2, int32_t d, int32_t cov_mode, int32_t kmax,
+                              const double* w, const double* fs, double* dotp, double* eigenvalues)
+{
+    mce_feed_problem q;
+    std::memset(&q, 0, sizeof(q));
+    q.S1 = S1; q.n1 = n1; q.ld1 = ld1;
+    q.S2 = S2; q.n2 = S2 ? n2 : 0; q.ld2 = S2 ? ld2 : 0;
+    q.d = d; q.cov_mode = cov_mode; q.kmax = kmax;
+    q.w = w; q.fs = fs; q.dotp = dotp; q.eigenvalues = eigenvalues;
+    return q;
+}
+
+// one job that is not a batch's (a rank's part, the whitening alone): `job` carries what makes it so; q.dotp takes the sums
+int feed_run_one(FeedJob& job, mce_feed_problem& q, bool src_device, double* jacobian, uint64_t* checksum, int32_t device)
+{
+    job.q = &q;
+    job.src_device = src_device;
+    job.want_sum = checksum != nullptr;
+    g_eig_stats = EigStats();
+    int rc = feed_plan(job);
+    if (rc != MCE_OK) return rc;
+    std::vector<FeedJob*> jobs{&job};
+    rc = feed_run_on_device(device, jobs);
+    g_eig_stats = job.eig;
+    if (rc != MCE_OK) return rc;
+    if (job.rc != MCE_OK) return fail(job.rc, "%s", job.err.c_str());
+    *jacobian = q.jacobian;
+    if (checksum) *checksum = job.checksum;
     return MCE_OK;
 }
 
@@ -562,9 +626,7 @@ static int feed_batch_impl(bool src_device, mce_feed_problem* problems, int64_t 
         const int r = feed_plan(jobs[i]);
         if (r != MCE_OK) jobs[i].set_error(r);
     }
-    std::vector<int> devs;
-    if (!devices || ndev <= 0) devs.push_back(0);
-    else devs.assign(devices, devices + ndev);
+    const std::vector<int> devs = device_list(devices, ndev);
     const int n = (int)std::min<int64_t>((int64_t)devs.size(), nprob);
     // greedy balance by pair count (largest first), then restore the caller's order per device
     std::vector<std::vector<FeedJob*>> per_dev(n);
@@ -584,24 +646,9 @@ static int feed_batch_impl(bool src_device, mce_feed_problem* problems, int64_t 
         }
         for (auto& v : per_dev) std::sort(v.begin(), v.end(), [](const FeedJob* a, const FeedJob* b) { return a->index < b->index; });
     }
-    std::vector<int> rcs(n, MCE_OK);
-    std::vector<std::string> errs(n);
-    auto work = [&](int i) {
-        if (per_dev[i].empty()) return;
-        rcs[i] = feed_run_on_device(devs[i], per_dev[i]);
-        if (rcs[i] != MCE_OK) errs[i] = g_err;
-    };
-    if (n == 1) {
-        work(0);
-    } else {
-        std::vector<std::thread> th;
-        const CallOptions inherited = t_opt;
-        for (int i = 0; i < n; ++i) th.emplace_back([&, i]() { t_opt = inherited; work(i); });
-        for (auto& t : th) t.join();
-    }
+    const int rc = for_each_device(devs, n, [&](int i) { return per_dev[i].empty() ? MCE_OK : feed_run_on_device(devs[i], per_dev[i]); });
     for (const FeedJob& j : jobs) eig_stats_merge(g_eig_stats, j.eig);
-    for (int i = 0; i < n; ++i)
-        if (rcs[i] != MCE_OK) return fail(rcs[i], "device %d: %s", devs[i], errs[i].c_str());
+    if (rc != MCE_OK) return rc;
     int first = MCE_OK;
     for (int64_t i = 0; i < nprob; ++i) {
         problems[i].status = jobs[i].rc;
@@ -630,17 +677,11 @@ int mce_evidence_feed_f64(const double* S1, int64_t n1, int64_t ld1, const doubl
                           double* dotp, double* jacobian, double* eigenvalues, int32_t device)
 {
     if (!jacobian) return fail(MCE_ERR_INVALID, "null pointer argument");
-    mce_feed_problem q;
-    std::memset(&q, 0, sizeof(q));
-    q.S1 = S1; q.n1 = n1; q.ld1 = ld1;
-    q.S2 = S2; q.n2 = S2 ? n2 : 0; q.ld2 = S2 ? ld2 : 0;
-    q.d = d; q.cov_mode = cov_mode; q.kmax = kmax;
-    q.w = w; q.fs = fs; q.dotp = dotp; q.eigenvalues = eigenvalues;
+    mce_feed_problem q = feed_problem(S1, n1, ld1, S2, n2, ld2, d, cov_mode, kmax, w, fs, dotp, eigenvalues);
     const int rc = mce_evidence_feed_batch_f64(&q, 1, &device, 1);
     if (rc == MCE_OK) *jacobian = q.jacobian;
     return rc;
 }
-
 
 static int feed_part_impl(bool src_device, const double* S1, int64_t n1, int64_t ld1, const double* S2, int64_t n2, int64_t ld2,
                           int32_t d, int32_t cov_mode, int32_t kmax, const double* w, const double* fs,
@@ -649,29 +690,11 @@ static int feed_part_impl(bool src_device, const double* S1, int64_t n1, int64_t
 {
     if (!jacobian) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (nparts < 1 || part < 0 || part >= nparts) return fail(MCE_ERR_INVALID, "part %d of %d", part, nparts);
-    mce_feed_problem q;
-    std::memset(&q, 0, sizeof(q));
-    q.S1 = S1; q.n1 = n1; q.ld1 = ld1;
-    q.S2 = S2; q.n2 = S2 ? n2 : 0; q.ld2 = S2 ? ld2 : 0;
-    q.d = d; q.cov_mode = cov_mode; q.kmax = kmax;
-    q.w = w; q.fs = fs; q.dotp = dotp_part; q.eigenvalues = eigenvalues;
+    mce_feed_problem q = feed_problem(S1, n1, ld1, S2, n2, ld2, d, cov_mode, kmax, w, fs, dotp_part, eigenvalues);
     FeedJob job;
-    job.q = &q;
     job.part = part;
     job.nparts = nparts;
-    job.src_device = src_device;
-    job.want_sum = checksum != nullptr;
-    g_eig_stats = EigStats();
-    int rc = feed_plan(job);
-    if (rc != MCE_OK) return rc;
-    std::vector<FeedJob*> jobs{&job};
-    rc = feed_run_on_device(device, jobs);
-    g_eig_stats = job.eig;
-    if (rc != MCE_OK) return rc;
-    if (job.rc != MCE_OK) return fail(job.rc, "%s", job.err.c_str());
-    *jacobian = q.jacobian;
-    if (checksum) *checksum = job.checksum;
-    return MCE_OK;
+    return feed_run_one(job, q, src_device, jacobian, checksum, device);
 }
 
 int mce_evidence_feed_part_f64(const double* S1, int64_t n1, int64_t ld1, const double* S2, int64_t n2, int64_t ld2,
@@ -695,29 +718,12 @@ static int feed_whiten_impl(bool src_device, const double* S1, int64_t n1, int64
                             uint64_t* checksum, int32_t device)
 {
     if (!jacobian || !d_X_out || !d_w_out || !d_fs_out) return fail(MCE_ERR_INVALID, "null pointer argument");
-    mce_feed_problem q;
-    std::memset(&q, 0, sizeof(q));
     double sums[MCE_MAX_K + 2];
-    q.S1 = S1; q.n1 = n1; q.ld1 = ld1;
-    q.d = d; q.cov_mode = 0; q.kmax = kmax;
-    q.w = w; q.fs = fs; q.dotp = sums; q.eigenvalues = eigenvalues;
+    mce_feed_problem q = feed_problem(S1, n1, ld1, nullptr, 0, 0, d, 0, kmax, w, fs, sums, eigenvalues);
     if (kmax < 2 || kmax > MCE_MAX_K + 1) return fail(MCE_ERR_K_RANGE, "kmax=%d", kmax);
     FeedJob job;
-    job.q = &q;
     job.out_X = d_X_out; job.out_w = d_w_out; job.out_f = d_fs_out;
-    job.src_device = src_device;
-    job.want_sum = checksum != nullptr;
-    g_eig_stats = EigStats();
-    int rc = feed_plan(job);
-    if (rc != MCE_OK) return rc;
-    std::vector<FeedJob*> jobs{&job};
-    rc = feed_run_on_device(device, jobs);
-    g_eig_stats = job.eig;
-    if (rc != MCE_OK) return rc;
-    if (job.rc != MCE_OK) return fail(job.rc, "%s", job.err.c_str());
-    *jacobian = q.jacobian;
-    if (checksum) *checksum = job.checksum;
-    return MCE_OK;
+    return feed_run_one(job, q, src_device, jacobian, checksum, device);
 }
 
 int mce_evidence_feed_whiten_f64(const double* S1, int64_t n1, int64_t ld1, int32_t d, int32_t kmax, const double* w, const double* fs,
@@ -746,32 +752,18 @@ int mce_knn_dotp_f64(const double* X, int64_t nq, const double* Y, int64_t nr, i
         int rc = make_plan(nq, nr, d, kmax - k0, k0 == 1 ? MCE_SELF_EXCLUDE : MCE_SELF_NONE, p);
         if (rc != MCE_OK) return rc;
     }
-    std::vector<int> devs;
-    if (!devices || ndev <= 0) devs.push_back(0);
-    else devs.assign(devices, devices + ndev);
+    const std::vector<int> devs = device_list(devices, ndev);
     const int n = (int)std::min<int64_t>((int64_t)devs.size(), nq);
     std::vector<std::vector<double>> parts(n, std::vector<double>(kmax, 0.0));
-    std::vector<int> rcs(n, MCE_OK);
-    std::vector<std::string> errs(n);
     // auto evidence over one set: let each device take a library-chosen part (rows for the sweep, blocks of the
     // shared k-d order for the pruned walk) instead of a row range
     const bool whole_set = n > 1 && X == Y && nq == nr && k0 == 1 && self_offset == 0 && !dist_out;
-    auto work = [&](int i) {
+    const int rc = for_each_device(devs, n, [&](int i) {
         const int64_t lo = nq * i / n, hi = nq * (i + 1) / n;
-        if (whole_set) rcs[i] = mce_knn_dotp_part_f64(Y, nr, d, kmax, i, n, w, fs, parts[i].data(), devs[i]);
-        else rcs[i] = fused_on_device(devs[i], X, lo, hi, Y, nr, d, kmax, k0, self_offset, w, fs, parts[i].data(), dist_out);
-        if (rcs[i] != MCE_OK) errs[i] = g_err;   // g_err is thread-local
-    };
-    if (n == 1) {
-        work(0);
-    } else {
-        std::vector<std::thread> th;
-        const CallOptions inherited = t_opt;
-        for (int i = 0; i < n; ++i) th.emplace_back([&, i]() { t_opt = inherited; work(i); });
-        for (auto& t : th) t.join();
-    }
-    for (int i = 0; i < n; ++i)
-        if (rcs[i] != MCE_OK) return fail(rcs[i], "device %d: %s", devs[i], errs[i].c_str());
+        if (whole_set) return mce_knn_dotp_part_f64(Y, nr, d, kmax, i, n, w, fs, parts[i].data(), devs[i]);
+        return fused_on_device(devs[i], X, lo, hi, Y, nr, d, kmax, k0, self_offset, w, fs, parts[i].data(), dist_out);
+    });
+    if (rc != MCE_OK) return rc;
     for (int k = 0; k < kmax; ++k) {   // fixed device order -> reproducible
         double s = 0.0;
         for (int i = 0; i < n; ++i) s += parts[i][k];

@@ -13,26 +13,9 @@ namespace {
 
 constexpr int32_t kPrepMaxParts = 65536;
 
-size_t prep_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 template <class T> T* prep_at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
 
-// a workspace, declared ONCE as a row of take()s: every array starts on a multiple of 256 bytes.  Over no workspace (ws = null) the
-// row only counts -- `total` is what a *_workspace_bytes function returns --, over a workspace it also hands out the typed pointers,
-// so the size and the pointers cannot disagree.
-struct WsPlan {
-    char* base;
-    size_t total = 0;
-    explicit WsPlan(void* ws) : base(static_cast<char*>(ws)) {}
-    template <class T> T* take(size_t count) { return take_bytes<T>(count * sizeof(T)); }
-    template <class T> T* take_bytes(size_t bytes)
-    {
-        T* const p = base ? reinterpret_cast<T*>(base + total) : nullptr;
-        total += prep_align(bytes);
-        return p;
-    }
-};
-
+// (WsPlan, the planner of every workspace, and prep_align: ws_plan.hpp)
 // the select workspace of a chain of n rows in nparts parts: the parts, the totals, the weights, their prefix sums, the candidates
 // (the bin rule: up to n + 1 bins) and seven per-tile arrays
 struct PrepWs {

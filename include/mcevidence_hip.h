@@ -781,6 +781,22 @@ int mce_param_contours_dev(const mce_summary_seg* segs, int32_t nseg, const int3
 int mce_param_contours_f64(const mce_summary_seg* segs, int32_t nseg, const int32_t* cols, int32_t nc, const double* probs, int32_t np, int32_t grid, double scale,
                            double* out, int32_t device);
 
+/* The same for chains sampled under hard prior bounds (csrc/param_contours.hpp's steps 3" .. 8"; docs/design/contours_bounds.md).
+ * bounds: a HOST array of 2 nc doubles per segment, lo[nc] then hi[nc] of the chosen columns, -inf / +inf where a side is open; a pair
+ * that is not lo < hi, or a null pointer: MCE_ERR_INVALID before any device call.  A grid ends on a bound it would cross (at_lo /
+ * at_hi), the density is the three-term linear boundary kernel of the product kernel on the rectangle in its positive form -- next to S
+ * the first-moment sums R_x and R_y are formed for every column that is not open, and f0 exp(min(f1 / f0, 4) - 1) is reported -- and
+ * the running sum of a region gives a cell on a grid end that lies on a bound half its weight per such axis.  A used value outside its
+ * bounds: col_status 8 (7 comes first); a pair takes the status of its failing column, the x axis' first.  A pair whose two columns are
+ * open has mce_param_contours_dev's bits.  out: mce_param_contours_bounded_out_doubles(nc, np, grid) doubles per system: as above with
+ * the column rows bound_lo[nc], bound_hi, at_lo, at_hi after col_status.  The same ten launches and one wait. */
+size_t mce_param_contours_bounded_out_doubles(int32_t nc, int32_t np, int32_t grid);
+size_t mce_param_contours_bounded_workspace_bytes(int64_t nrows_total, int32_t nseg, int32_t dmax, int32_t nc, int32_t np, int32_t grid);
+int mce_param_contours_bounded_dev(const mce_summary_seg* segs, int32_t nseg, const int32_t* cols, int32_t nc, const double* bounds, const double* probs, int32_t np,
+                                   int32_t grid, double scale, double* out, void* ws, size_t ws_bytes, void* stream);
+int mce_param_contours_bounded_f64(const mce_summary_seg* segs, int32_t nseg, const int32_t* cols, int32_t nc, const double* bounds, const double* probs, int32_t np,
+                                   int32_t grid, double scale, double* out, int32_t device);
+
 /* The farm: MANY chain files -> fp64 on the device in one pass per wave (the reference's Planck grid, planck_mcevidence.py:306-348:
  * thousands of small roots).  A farm reader handle is created once per device and reused for every wave: it owns one stream, device
  * scratch and ONE pinned staging buffer of `capacity_bytes` (a multiple of 4096); no allocation and no stream per file or per wave (an

@@ -242,6 +242,10 @@ SIGNATURES["mce_param_contours_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_i
 SIGNATURES["mce_param_contours_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32])
 SIGNATURES["mce_param_contours_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _P, _c.c_size_t, _P])
 SIGNATURES["mce_param_contours_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _c.c_int32])
+SIGNATURES["mce_param_contours_bounded_out_doubles"] = (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_contours_bounded_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32])
+SIGNATURES["mce_param_contours_bounded_dev"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _P, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_param_contours_bounded_f64"] = (_c.c_int, [_P, _c.c_int32, _P, _c.c_int32, _P, _P, _c.c_int32, _c.c_int32, _c.c_double, _P, _c.c_int32])
 
 
 class JackGroupsSeg(ctypes.Structure):
@@ -974,15 +978,34 @@ def contours_block_doubles(nc, np_, grid):
     return MCE_CONTOURS_HEAD + 9 * nc + (nc * (nc - 1) // 2) * (4 + 7 * int(np_) + grid * grid)
 
 
-def _param_contours(call, segs, cols, probs, grid, scale, tail):
+def contours_bounded_block_doubles(nc, np_, grid):
+    """doubles of one system's result block: MCE_CONTOURS_HEAD + 13 nc + P (4 + 7 np + grid^2), P = nc (nc - 1) / 2"""
+    return contours_block_doubles(nc, np_, grid) + 4 * int(nc)
+
+
+def _param_contours(call, segs, cols, probs, grid, scale, tail, bounds=None):
+    """``bounds``: None (the plain entry points), or per system (lo[nc], hi[nc]) of the chosen columns -> the HOST array of a bounded
+    call, 2 nc doubles per segment, which goes in front of ``probs``"""
     arr = _seg_array(SummarySeg, segs)
     cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    extra = ()
+    if bounds is not None:
+        if len(bounds) != len(segs):
+            raise ValueError("param contours: one pair of bounds arrays per system expected")
+        flat = []
+        for lo, hi in bounds:
+            lo, hi = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (lo, hi))
+            if lo.size != cols.size or hi.size != cols.size:
+                raise ValueError("param contours: %d lower and %d upper bounds for %d columns" % (lo.size, hi.size, cols.size))
+            flat += [lo, hi]
+        flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0))
+        extra = (flat.ctypes.data if flat.size else None,)
     probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
     npr, grid = probs.size, int(grid)
     shape_ok = 1 <= npr <= MCE_MARGINALS_MAX_P and grid in (32, 64) and 2 <= cols.size <= MCE_CONTOURS_MAX_COLS
-    size = contours_block_doubles(cols.size, npr, grid) if shape_ok else 0
+    size = (contours_block_doubles if bounds is None else contours_bounded_block_doubles)(cols.size, npr, grid) if shape_ok else 0
     out = np.full(max(size * len(segs), 1), np.nan)
-    check(call(_c.cast(arr, _P), len(segs), cols.ctypes.data, cols.size, probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
+    check(call(_c.cast(arr, _P), len(segs), cols.ctypes.data, cols.size, *extra, probs.ctypes.data, npr, grid, float(scale), out.ctypes.data, *tail))
     return _split(out, [size] * len(segs))
 
 
@@ -997,6 +1020,26 @@ def param_contours(systems, cols, probs, grid, scale, device=0):
     """mce_param_contours_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
     keep, segs = _host_systems(systems, "param contours")
     return _param_contours(load().mce_param_contours_f64, segs, cols, probs, grid, scale, (int(device),))
+
+
+def param_contours_bounded_out_doubles(nc, np_, grid):
+    return int(load().mce_param_contours_bounded_out_doubles(int(nc), int(np_), int(grid)))
+
+
+def param_contours_bounded_workspace_bytes(nrows_total, nseg, dmax, nc, np_, grid):
+    return int(load().mce_param_contours_bounded_workspace_bytes(int(nrows_total), int(nseg), int(dmax), int(nc), int(np_), int(grid)))
+
+
+def param_contours_bounded_dev(segs, cols, bounds, probs, grid, scale, ws, ws_bytes, stream=0):
+    """mce_param_contours_bounded_dev: ``param_contours_dev`` with hard prior bounds, ``bounds`` = [(lo[nc], hi[nc])] per system (HOST
+    arrays of the chosen columns, -inf / +inf: open) -> one float64 block per system (``contours.from_block_bounded`` reads it)"""
+    return _param_contours(load().mce_param_contours_bounded_dev, segs, cols, probs, grid, scale, (ws or None, int(ws_bytes), stream or None), bounds=bounds)
+
+
+def param_contours_bounded(systems, cols, bounds, probs, grid, scale, device=0):
+    """mce_param_contours_bounded_f64: the same from HOST arrays, ``systems`` = [(x[n, ld], d, w)], uploaded by the library"""
+    keep, segs = _host_systems(systems, "param contours")
+    return _param_contours(load().mce_param_contours_bounded_f64, segs, cols, probs, grid, scale, (int(device),), bounds=bounds)
 
 
 def jack_groups_dev(segs, stream=0):

@@ -87,6 +87,9 @@ def build_parser(prog=None):
                    help="with --contours: the grid points per axis (default 64)")
     p.add_argument("--contours-scale", dest="contours_scale", default=None, type=float, metavar="S",
                    help="with --contours: the bandwidth as a multiple of the normal-reference rule (default 1)")
+    p.add_argument("--contours-bounds", dest="contours_bounds", nargs="*", default=None, metavar="NAME=LO:HI",
+                   help="with --contours: honour hard prior bounds in the 2-D densities (the linear boundary kernel of the product kernel; the grids end on "
+                        "the bounds). Without a value: the bounds of the root's .ranges or log.param file; or NAME=LO:HI ..., an empty side or N: open")
     p.add_argument("--contours-out", dest="contours_out", default=None, metavar="FILE.npz",
                    help="with --contours: write the names, the pairs, the two grid axes, the densities and the levels of every pair to FILE.npz, one set per root")
     p.add_argument("--tension", dest="tension", nargs=2, default=None, metavar=("ROOT_A", "ROOT_B"),
@@ -112,14 +115,15 @@ def _summary_kw(args):
     return {"summary": tuple(args.summary) if args.summary else True}
 
 
-def _bounds_kw(args):
-    """--bounds, where it was given: "ranges", or the mapping of its NAME=LO:HI values"""
-    if getattr(args, "bounds", None) is None:
+def _bounds_kw(args, dest="bounds"):
+    """--bounds (``dest="contours_bounds"``: --contours-bounds), where it was given: "ranges", or the mapping of its NAME=LO:HI values"""
+    given = getattr(args, dest, None)
+    if given is None:
         return {}
-    if not args.bounds:
+    if not given:
         return {"bounds": "ranges"}
     out = {}
-    for item in args.bounds:
+    for item in given:
         name, eq, pair = item.partition("=")
         lo, colon, hi = pair.partition(":")
         if not name or not eq or not colon:
@@ -143,12 +147,13 @@ def _marginals_kw(args):
 
 
 def _contours_kw(args):
-    """--contours / --contours-params / --contours-grid / --contours-scale, where the first was given"""
+    """--contours / --contours-params / --contours-grid / --contours-scale / --contours-bounds, where the first was given"""
     if args.contours is None:
         return {}
-    if args.contours_params is None and args.contours_grid is None and args.contours_scale is None:
+    bounds = _bounds_kw(args, "contours_bounds")
+    if args.contours_params is None and args.contours_grid is None and args.contours_scale is None and not bounds:
         return {"contours": tuple(args.contours) if args.contours else True}
-    kw = {"probs": tuple(args.contours) if args.contours else True}
+    kw = dict({"probs": tuple(args.contours) if args.contours else True}, **bounds)
     if args.contours_params is not None:
         kw["params"] = [int(v) if v.isdigit() else v for v in args.contours_params]
     if args.contours_grid is not None:
@@ -370,8 +375,9 @@ def main(argv=None):
         build_parser(prog="MCEvidence.py").error("--marginals-grid, --marginals-scale and --marginals-out belong to --marginals")
     if args.bounds is not None and args.marginals is None:
         build_parser(prog="MCEvidence.py").error("--bounds belongs to --marginals")
-    if (args.contours_params is not None or args.contours_grid is not None or args.contours_scale is not None or args.contours_out is not None) and args.contours is None:
-        build_parser(prog="MCEvidence.py").error("--contours-params, --contours-grid, --contours-scale and --contours-out belong to --contours")
+    if (args.contours_params is not None or args.contours_grid is not None or args.contours_scale is not None or args.contours_out is not None or
+            args.contours_bounds is not None) and args.contours is None:
+        build_parser(prog="MCEvidence.py").error("--contours-params, --contours-grid, --contours-scale, --contours-bounds and --contours-out belong to --contours")
     if args.tension is not None:
         if args.farm or args.resident:
             build_parser(prog="MCEvidence.py").error("--tension runs its three roots in one batched pass: it does not combine with --farm or --resident")

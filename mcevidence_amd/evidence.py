@@ -257,7 +257,7 @@ class MCEvidence(object):
         # the hard prior bounds of the marginals (docs/design/marginals_bounds.md): None (off: nothing changes), "ranges", a mapping
         # name -> (lo, hi) or one (lo, hi) pair per parameter; resolved against the parameter names when the marginals are formed
         self.bounds = gdkwargs.pop("bounds", None)
-        _marginals.refuse_bounds(self.bounds, self.marginals_spec, root=method if isinstance(method, str) else None)
+        _marginals.refuse_bounds(self.bounds, self.marginals_spec, root=method if isinstance(method, str) else None, contours=gdkwargs.get("contours"))
         # the 2-D joint densities, modes and credible levels of the parameter pairs with every evidence() call
         # (docs/design/contours.md): None (off: nothing changes), True, the probabilities, or a dict of probs, grid, scale and params
         self.contours_spec = gdkwargs.pop("contours", None)
@@ -548,7 +548,8 @@ class MCEvidence(object):
     def _fill_contours(self):
         """``info["contours"]`` of this call (the constructor's ``contours`` keyword; unset: nothing happens): the rule of contours.py on
         s1's weights and its raw first ``ndim`` columns -- by ``mce_param_contours_f64`` where the HIP backend is in use, otherwise in
-        NumPy; under a process group every rank computes its own, no collective"""
+        NumPy; with the key ``"bounds"`` the rule with hard prior bounds, by ``mce_param_contours_bounded_f64`` or ``measure_bounded``;
+        under a process group every rank computes its own, no collective"""
         if not _contours.wanted(self.contours_spec):
             return
         _contours.refuse(self.contours_spec, brange=self.brange, nbatch=self.nbatch)
@@ -557,12 +558,15 @@ class MCEvidence(object):
         probs, grid, scale, cols = sp
         samples, _, _ = self.gd.arrays("s1")
         a, x = self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim]
+        bnd = _contours.bounds_spec(self.contours_spec, names=names, ndim=self.ndim, root=self.fname if isinstance(self.fname, str) else None, bounds=self.bounds)
         if getattr(self.backend, "name", None) == "hip":
             import torch
             devs = getattr(self.backend, "devices", None)
-            blk = _contours.measure_native(a, x, cols, probs, grid, scale, device=devs[0] if devs else (torch.cuda.current_device() if torch.cuda.is_available() else 0))
+            device = devs[0] if devs else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+            blk = (_contours.measure_native(a, x, cols, probs, grid, scale, device=device) if bnd is None else
+                   _contours.measure_bounded_native(a, x, cols, bnd, probs, grid, scale, device=device))
         else:
-            blk = _contours.measure(a, x, cols, probs, grid, scale)
+            blk = _contours.measure(a, x, cols, probs, grid, scale) if bnd is None else _contours.measure_bounded(a, x, cols, bnd, probs, grid, scale)
         self.param_contours = self.info["contours"] = _contours.build(blk, sp, names)
 
     def _fill_covariance(self):

@@ -306,13 +306,15 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     for v in mars:
         _marginals.spec(v)
     bnds = _per_root_bounds(bounds, n)
-    for v, b, r in zip(mars, bnds, roots):
-        _marginals.refuse_bounds(b, v, root=r if isinstance(r, str) else None)
-    mar_kw = [dict({"marginals": v}, **({} if b is None else {"bounds": b})) if _marginals.wanted(v) else {} for v, b in zip(mars, bnds)]
     cons = _per_root_marginals(contours, n)
+    for v, b, r, c in zip(mars, bnds, roots, cons):
+        _marginals.refuse_bounds(b, v, root=r if isinstance(r, str) else None, contours=c)
+    mar_kw = [dict({"marginals": v}, **({} if b is None else {"bounds": b})) if _marginals.wanted(v) else {} for v, b in zip(mars, bnds)]
     for v in cons:
         _contours.spec(v)
-    con_kw = [{"contours": v} if _contours.wanted(v) else {} for v in cons]
+    # (a root that leaves for another route takes bounds= with it where its contours ask for the call's)
+    con_kw = [dict({"contours": v}, **({"bounds": b} if b is not None and _contours.bounds_wanted(v) and v["bounds"] is True and not _marginals.wanted(m) else {}))
+              if _contours.wanted(v) else {} for v, b, m in zip(cons, bnds, mars)]
     covs = _per_root(covariance, n, "covariance")
     for v in covs:
         _covariance.spec(v)
@@ -532,20 +534,32 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                                          _res.marginals_bounded_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in masked],
                                                                             [mbnds[r.index] for r in masked], msp, device, stream.cuda_stream)))
                 # contours: likewise, one call per distinct (probs, grid, scale, columns); a root whose ``params`` do not fit its own
-                # parameters fails alone, with the ValueError of ``contours.spec``
-                conblks, cspecs = {}, {}
+                # parameters fails alone, with the ValueError of ``contours.spec``.  The roots whose contours ask for bounds go through the
+                # bounded call, each with its own; bounds that do not fit a root fail it alone
+                conblks, cspecs, cbnds = {}, {}, {}
                 for r in [r for r in ready if _contours.wanted(cons[r.index])]:
+                    rname = roots[r.index] if isinstance(roots[r.index], str) else None
                     try:
-                        cspecs[r.index] = _contours.spec(cons[r.index], ndim=r.problem[6],
-                                                         names=_summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
+                        cnames = _summary.param_names(rname, r.problem[6])
+                        cspecs[r.index] = _contours.spec(cons[r.index], ndim=r.problem[6], names=cnames)
+                        cb = _contours.bounds_spec(cons[r.index], names=cnames, ndim=r.problem[6], root=rname, bounds=bnds[r.index])
+                        if cb is not None:
+                            cbnds[r.index] = cb
                     except ValueError as e:
+                        cspecs.pop(r.index, None)
                         fail(r.index, e)
                 ready = [r for r in ready if not (_contours.wanted(cons[r.index]) and r.index not in cspecs)]
                 for csp in sorted(set(cspecs.values())):
-                    cwho = [r for r in ready if cspecs.get(r.index) == csp]
-                    conblks.update(zip((r.index for r in cwho),
-                                       _res.contours_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in cwho],
-                                                                 csp, device, stream.cuda_stream)))
+                    cwho = [r for r in ready if cspecs.get(r.index) == csp and r.index not in cbnds]
+                    if cwho:
+                        conblks.update(zip((r.index for r in cwho),
+                                           _res.contours_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in cwho],
+                                                                     csp, device, stream.cuda_stream)))
+                    cwho = [r for r in ready if cspecs.get(r.index) == csp and r.index in cbnds]
+                    if cwho:
+                        conblks.update(zip((r.index for r in cwho),
+                                           _res.contours_bounded_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in cwho],
+                                                                             [cbnds[r.index] for r in cwho], csp, device, stream.cuda_stream)))
                 # covariance: the ready roots that ask for it in one call, while the gathered rows are raw
                 casked = [r for r in ready if _covariance.wanted(covs[r.index])]
                 cblks = dict(zip((r.index for r in casked),

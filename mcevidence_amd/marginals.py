@@ -422,12 +422,17 @@ def bounds_spec(bounds, names=None, ndim=None, root=None, marginals=True):
     return lo, hi
 
 
-def refuse_bounds(bounds, marginals, root=True):
-    """what every route refuses before any work: ``bounds`` without ``marginals``, a string other than "ranges", "ranges" on a route
-    without a root name (``root=None``)"""
+def _contours_take_bounds(contours):
+    """does ``contours=`` ask for boundary-corrected 2-D densities (its key ``"bounds"``)?  ``True`` there takes the call's ``bounds=``"""
+    return isinstance(contours, dict) and contours.get("bounds") is not None and contours.get("bounds") is not False
+
+
+def refuse_bounds(bounds, marginals, root=True, contours=None):
+    """what every route refuses before any work: ``bounds`` without ``marginals`` (unless ``contours`` takes them: its ``"bounds"`` is
+    True), a string other than "ranges", "ranges" on a route without a root name (``root=None``)"""
     if bounds is None:
         return
-    if not wanted(marginals):
+    if not wanted(marginals) and not (_contours_take_bounds(contours) and contours["bounds"] is True):
         raise ValueError("bounds=%r without marginals: the bounds are those of the 1-D marginal densities" % (bounds,))
     if isinstance(bounds, str):
         if bounds != "ranges":
@@ -437,8 +442,8 @@ def refuse_bounds(bounds, marginals, root=True):
 
 
 def note_contours(contours):
-    """marginals with bounds next to contours: ONE INFO line"""
-    if contours is not None and contours is not False:
+    """marginals with bounds next to contours that do not ask for the bounds themselves: ONE INFO line"""
+    if contours is not None and contours is not False and not _contours_take_bounds(contours):
         logger.info("contours: the 2-D densities are not boundary-corrected; bounds= applies to the 1-D marginals alone")
 
 

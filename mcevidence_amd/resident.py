@@ -87,7 +87,7 @@ def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all"
     ``marginals`` it is the ValueError every route raises."""
     _summary.spec(summary)
     _marginals.spec(marginals)
-    _marginals.refuse_bounds(bounds, marginals)
+    _marginals.refuse_bounds(bounds, marginals, contours=contours)
     _contours.spec(contours)
     _covariance.spec(covariance)
     if not ischain:
@@ -265,6 +265,17 @@ def marginals_measure_dev(systems, spec, device, stream):
     probs, grid, scale = spec
     return _blocks_dev(_capi.param_marginals_workspace_bytes, (len(probs), grid), lambda *a: _capi.param_marginals_dev(systems, probs, grid, scale, *a),
                        lambda b, s: _marginals.from_block(b, s[3], len(probs), grid), systems, device, stream)
+
+
+def contours_bounded_measure_dev(systems, bounds, spec, device, stream):
+    """ONE ``mce_param_contours_bounded_dev`` call for ``systems`` (as ``contours_measure_dev`` takes them), ``bounds`` = one
+    (lo[nc], hi[nc]) of the chosen columns per system (``contours.bounds_spec``) and ``spec`` -> one ``contours.measure_bounded`` dict per
+    system"""
+    from . import _capi
+    probs, grid, scale, cols = spec
+    return _blocks_dev(_capi.param_contours_bounded_workspace_bytes, (len(cols), len(probs), grid),
+                       lambda *a: _capi.param_contours_bounded_dev(systems, cols, bounds, probs, grid, scale, *a),
+                       lambda b, s: _contours.from_block_bounded(b, len(cols), len(probs), grid), systems, device, stream)
 
 
 def marginals_bounded_measure_dev(systems, bounds, spec, device, stream):
@@ -655,12 +666,15 @@ class ResidentChains(object):
         probs = _summary.spec(summary)
         want_cov = _covariance.spec(covariance) is not None
         mspec = _marginals.spec(marginals)
-        _marginals.refuse_bounds(bounds, marginals, root=self.names_root)
-        bnd = _marginals.bounds_spec(bounds, names=_summary.param_names(self.names_root, nd), root=self.names_root, marginals=marginals)
+        _marginals.refuse_bounds(bounds, marginals, root=self.names_root, contours=contours)
+        bnd = None     # (bounds= without marginals= is here only where contours take it: refuse_bounds)
+        if mspec is not None:
+            bnd = _marginals.bounds_spec(bounds, names=_summary.param_names(self.names_root, nd), root=self.names_root, marginals=marginals)
         if bnd is not None:
             _marginals.note_contours(contours)
         cnames = _summary.param_names(self.names_root, nd) if _contours.wanted(contours) else None
         cspec = _contours.spec(contours, ndim=nd, names=cnames)
+        cbnd = _contours.bounds_spec(contours, names=cnames, ndim=nd, root=self.names_root, bounds=bounds)
         torch = self._torch
         ms = self.stats["ms"]
         with torch.cuda.device(self.device):
@@ -703,7 +717,11 @@ class ResidentChains(object):
             conblk = None
             if cspec is not None:
                 t0 = time.perf_counter()
-                conblk, = contours_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())], cspec, self.device, self._stream())
+                csys = [(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())]
+                if cbnd is None:
+                    conblk, = contours_measure_dev(csys, cspec, self.device, self._stream())
+                else:
+                    conblk, = contours_bounded_measure_dev(csys, [cbnd], cspec, self.device, self._stream())
                 ms["contours"] = _ms(t0)
             cblk = None
             if want_cov:
@@ -797,7 +815,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     _information.refuse(ctor.get("information"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _summary.refuse(ctor.get("summary"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _marginals.refuse(ctor.get("marginals"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
-    _marginals.refuse_bounds(ctor.get("bounds"), ctor.get("marginals"), root=root if isinstance(root, str) else None)
+    _marginals.refuse_bounds(ctor.get("bounds"), ctor.get("marginals"), root=root if isinstance(root, str) else None, contours=ctor.get("contours"))
     _contours.refuse(ctor.get("contours"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     _covariance.refuse(ctor.get("covariance"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     reason = RESIDENT if _is_file_root(root) else REASONS["not_files"]

@@ -265,7 +265,7 @@ def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", shift="
     covariance=True, info=True, **kw)`` (a root the farm does not cover takes its per-root route); ``route="host"``: three
     ``MCEvidence(root, information=True, covariance=True, **kw).evidence(info=True)``.  ``kw``: the farm's keywords (``kmax``, ``ndim``,
     ``priorvolume``, ``burnlen``, ``thinlen``, ``thin_corr``, ``jackknife``, ..; the four of them that may be sequences have one entry per
-    root, in the order A, B, AB; ``marginals`` with ``bounds`` go to all three roots, ``bounds="ranges"`` reading every root's own file).  Returns (lnE_a, lnE_b, lnE_ab, info): ``info["tension"]`` is ``combine``'s dict, ``info["roots"]`` the
+    root, in the order A, B, AB; ``marginals`` with ``bounds`` go to all three roots, ``bounds="ranges"`` reading every root's own file; so does the key ``"bounds"`` of ``contours``).  Returns (lnE_a, lnE_b, lnE_ab, info): ``info["tension"]`` is ``combine``'s dict, ``info["roots"]`` the
     three runs' info dicts, ``info["route"]`` the route asked for.  The assumptions are ``combine``'s.  ``shift``: "gaussian" (the dict and
     the lines as they are without the keyword), "kde" or "both": ``parameter_shift_kde`` with ``boost`` and ``bandwidth_scale`` on the rows
     and weights ``covariance=`` measured in A and B, in ``info["tension"]["shift_kde"]`` -- the Gaussian shift stays in either case.  The

@@ -163,55 +163,27 @@ def _contours_kw(args):
     return {"contours": kw}
 
 
-def _print_contours(info, logged=False):
-    """the contours lines, after the marginals lines and before the ln(B) lines; ``logged``: the route has logged them already"""
-    from .contours import lines
-    if (info or {}).get("contours") and not logged:
-        for line in lines(info["contours"]):
-            print(line)
+def _print_stats(info, logged=False, information=True):
+    """the lines of the statistics (posterior.STATS' order: information, summary, marginals, contours), before the ln(B) lines; ``logged``: the
+    route has logged those after the information lines already; ``information=False``: without the information lines"""
+    from .posterior import STATS
+    for st in STATS:
+        if (info or {}).get(st.key) and (information if st.key == "information" else not logged):
+            for line in st.lines(info[st.key]):
+                print(line)
 
 
-def _save_contours(args, roots, infos):
-    """--contours-out, where it was given"""
-    if args.contours_out is not None:
-        from .contours import save
-        save(args.contours_out, roots, infos)
-
-
-def _print_marginals(info, logged=False):
-    """the marginals lines, after the summary lines and before the ln(B) lines; ``logged``: the route has logged them already"""
-    from .marginals import lines
-    if (info or {}).get("marginals") and not logged:
-        for line in lines(info["marginals"]):
-            print(line)
-
-
-def _save_marginals(args, roots, infos):
-    """--marginals-out, where it was given"""
-    if args.marginals_out is not None:
-        from .marginals import save
-        save(args.marginals_out, roots, infos)
-
-
-def _print_summary(info, logged=False):
-    """the summary lines, after the information lines and before the ln(B) lines; ``logged``: the route has logged them already"""
-    from .summary import lines
-    if (info or {}).get("summary") and not logged:
-        for line in lines(info["summary"]):
-            print(line)
+def _save_stats(args, roots, infos):
+    """--marginals-out and --contours-out, where they were given"""
+    from . import contours, marginals
+    for path, module in ((args.marginals_out, marginals), (args.contours_out, contours)):
+        if path is not None:
+            module.save(path, roots, infos)
 
 
 def _information_kw(args):
     """--information, where it was given"""
     return {"information": True} if args.information else {}
-
-
-def _print_information(info):
-    """the information lines, before the ln(B) lines"""
-    from .information import lines
-    if (info or {}).get("information"):
-        for line in lines(info["information"]):
-            print(line)
 
 
 def _jackknife_kw(args):
@@ -288,13 +260,9 @@ def farm_main(args):
         print()
         print("Using file: ", r)
         _print_converge(inf)
-        _print_information(inf)
-        _print_summary(inf)
-        _print_marginals(inf)
-        _print_contours(inf)
+        _print_stats(inf)
         note = _print_lnb(mle, inf) or note
-    _save_marginals(args, roots, infos)
-    _save_contours(args, roots, infos)
+    _save_stats(args, roots, infos)
     if note:
         _print_jackknife_note(note)
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
@@ -333,13 +301,9 @@ def tension_main(args):
         print()
         print("Using file: ", r)
         _print_converge(inf)
-        _print_information(inf)
-        _print_summary(inf)
-        _print_marginals(inf)
-        _print_contours(inf)
+        _print_stats(inf)
         note = _print_lnb(mle, inf) or note
-    _save_marginals(args, roots, info["roots"])
-    _save_contours(args, roots, info["roots"])
+    _save_stats(args, roots, info["roots"])
     print()
     print("Tension of {} and {} (joint run: {})".format(*roots))
     for line in tension.lines(info["tension"]):
@@ -398,12 +362,9 @@ def main(argv=None):
                                   **_jackknife_kw(args), **_backend_kw(args))
         if want_info:
             out, inf = out
-            _save_marginals(args, [args.root_name], [inf])
-            _save_contours(args, [args.root_name], [inf])
+            _save_stats(args, [args.root_name], [inf])
         if args.jackknife is not None:
-            _print_summary(inf, logged=args.verbose >= 1)
-            _print_marginals(inf, logged=args.verbose >= 1)
-            _print_contours(inf, logged=args.verbose >= 1)
+            _print_stats(inf, logged=args.verbose >= 1, information=False)
             jk = _print_lnb(out, inf)
             if jk:
                 _print_jackknife_note(jk)
@@ -419,17 +380,13 @@ def main(argv=None):
         mce.jackknife = {"groups": args.jackknife, "by": args.jackknife_by}
         out = mce.evidence()
         jk = mce.info["jackknife"]
-        _print_information(mce.info)
-        _print_summary(mce.info, logged=args.verbose >= 1)
-        _print_marginals(mce.info, logged=args.verbose >= 1)
-        _print_contours(mce.info, logged=args.verbose >= 1)
+        _print_stats(mce.info, logged=args.verbose >= 1)
         for k in range(1, len(jk["lnE"]) + 1):
             print("   ln(B)[k={}] = {} \u00b1 {}".format(k, jk["lnE"][k - 1], jk["sigma"][k - 1]))
         print("* \u00b1: delete-a-group jackknife over {} {} (conservative, not a calibrated 1 sigma).".format(jk["groups"], jk["by"]))
     else:
         out = mce.evidence()
-    _save_marginals(args, [args.root_name], [getattr(mce, "info", None)])
-    _save_contours(args, [args.root_name], [getattr(mce, "info", None)])
+    _save_stats(args, [args.root_name], [getattr(mce, "info", None)])
     print("* ln(B)[k] is the natural logarithm of the Baysian evidence estimated using the kth Nearest Neighbour.")
     print("")
     return out

@@ -28,10 +28,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import information as _information
-from . import summary as _summary
-from . import contours as _contours
-from . import marginals as _marginals
-from . import covariance as _covariance
+from . import posterior as _post
 from .chains import MCSamples, rank0_draw
 from .resident import mle_from_sums
 
@@ -206,21 +203,15 @@ class MCEvidence(object):
         (they are not forwarded to the chain reader): ``backend`` -- an object with a
         ``knn_dotp`` method; default ``HipBackend()`` -- and ``jackknife`` -- None, True, a number of
         groups or a dict of ``evidence_jackknife``'s keywords: ``evidence()`` then also stores the jackknife
-        error bars in ``info["jackknife"]`` -- and ``information`` -- None or True: ``evidence()`` then also stores <ln L>_P, D_KL and the
-        Bayesian model dimensionality in ``info["information"]`` (information.py; docs/design/information.md) -- and ``summary`` -- None,
-        True (68 % and 95 %) or up to 7 probabilities: ``evidence()`` then also stores the weighted means, standard deviations,
-        equal-tailed limits and the best-fit sample of the first ``ndim`` parameters in ``info["summary"]`` and in
-        ``self.param_summary`` (summary.py; docs/design/summary.md; ``self.summary()`` stays the reference's printing method) -- and
-        ``covariance`` -- None or True: ``evidence()`` then also stores the weighted mean and covariance matrix of the first ``ndim``
-        parameters in ``info["covariance"]`` and in ``self.param_cov`` (covariance.py; docs/design/tension.md) -- and ``marginals`` -- None,
-        True, up to 7 probabilities or dict(probs, grid, scale): ``evidence()`` then also stores the 1-D marginal density of each of the
-        first ``ndim`` parameters on a grid, its mode and its highest-posterior-density regions in ``info["marginals"]`` and in
-        ``self.param_marginals`` (marginals.py; docs/design/marginals.md), with ``bounds`` -- None, "ranges", a mapping name -> (lo, hi) or one
-        (lo, hi) per parameter -- the hard prior bounds those densities honour (docs/design/marginals_bounds.md) -- and ``contours`` --
-        None, True, up to 7 probabilities or
-        dict(probs, grid, scale, params): ``evidence()`` then also stores the 2-D joint density of every pair of the chosen parameters
-        (default: all of the first ``ndim``, at most 32) on a grid, its mode and the levels and regions of the probabilities in
-        ``info["contours"]`` and in ``self.param_contours`` (contours.py; docs/design/contours.md).
+        error bars in ``info["jackknife"]`` -- and the statistics of posterior.py (docs/design/posterior_stats.md), each None (off: nothing
+        changes) or its value: ``evidence()`` then also stores the result in ``info[<keyword>]``:
+        ``information`` (True): <ln L>_P, D_KL and the Bayesian model dimensionality (docs/design/information.md);
+        ``summary`` (True or up to 7 probabilities): means, standard deviations, equal-tailed limits, the best fit; also in ``self.param_summary``
+        (docs/design/summary.md; ``self.summary()`` stays the reference's printing method);
+        ``marginals`` (True, probabilities or dict(probs, grid, scale)): 1-D densities, modes, HPD regions; also in ``self.param_marginals``;
+        ``bounds`` (None, "ranges", a mapping name -> (lo, hi) or one (lo, hi) per parameter): the hard prior bounds the marginals honour;
+        ``contours`` (True, probabilities or dict(probs, grid, scale, params, bounds)): 2-D densities of the parameter pairs; also in ``self.param_contours``;
+        ``covariance`` (True): the weighted mean and covariance matrix of the parameters; also in ``self.param_cov`` (docs/design/tension.md).
 
         method      chain root name / file name(s), or list/tuple/dict of chain arrays
                     (columns: weight, -lnL, parameters...)
@@ -239,35 +230,15 @@ class MCEvidence(object):
         # jackknife error bars with every evidence() call (docs/design/jackknife.md): None (off), True (16 blocks), a number of blocks,
         # or a dict of evidence_jackknife's keywords; evidence() keeps the reference's signature, so the switch lives here
         self.jackknife = gdkwargs.pop("jackknife", None)
-        # <ln L>_P, D_KL and the model dimensionality with every evidence() call (docs/design/information.md): None (off: nothing
-        # changes) or True; consumed here for the same reason
-        self.information = gdkwargs.pop("information", None)
-        _information.refuse(self.information, brange=brange, nbatch=nbatch, isfunc=isfunc)
-        # posterior means, credible limits and the best fit with every evidence() call (docs/design/summary.md): None (off: nothing
-        # changes), True or the probabilities of the limits; consumed here for the same reason
-        self.summary_spec = gdkwargs.pop("summary", None)
-        # (what the last evidence() found is kept as ``param_summary``: ``summary`` is the reference's method of this class)
-        self.param_summary = None
-        _summary.refuse(self.summary_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
-        # the 1-D marginal densities, modes and HPD regions with every evidence() call (docs/design/marginals.md): None (off: nothing
-        # changes), True, the probabilities, or a dict of probs, grid and scale; consumed here for the same reason
-        self.marginals_spec = gdkwargs.pop("marginals", None)
-        self.param_marginals = None
-        _marginals.refuse(self.marginals_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
-        # the hard prior bounds of the marginals (docs/design/marginals_bounds.md): None (off: nothing changes), "ranges", a mapping
-        # name -> (lo, hi) or one (lo, hi) pair per parameter; resolved against the parameter names when the marginals are formed
+        # the statistics next to ln E with every evidence() call (posterior.py): the keywords' values are kept here (``summary`` is the
+        # reference's method of this class, so that value is ``summary_spec`` and what evidence() found ``param_summary``; likewise the others),
+        # ``bounds`` is resolved against the parameter names when the densities are formed; consumed here for the same reason
+        for st in _post.STATS:
+            setattr(self, st.spec_attr, gdkwargs.pop(st.key, None))
+            if st.attr is not None:
+                setattr(self, st.attr, None)
         self.bounds = gdkwargs.pop("bounds", None)
-        _marginals.refuse_bounds(self.bounds, self.marginals_spec, root=method if isinstance(method, str) else None, contours=gdkwargs.get("contours"))
-        # the 2-D joint densities, modes and credible levels of the parameter pairs with every evidence() call
-        # (docs/design/contours.md): None (off: nothing changes), True, the probabilities, or a dict of probs, grid, scale and params
-        self.contours_spec = gdkwargs.pop("contours", None)
-        self.param_contours = None
-        _contours.refuse(self.contours_spec, brange=brange, nbatch=nbatch, isfunc=isfunc)
-        # the weighted mean and covariance matrix of the parameters with every evidence() call (docs/design/tension.md): None (off:
-        # nothing changes) or True; consumed here for the same reason
-        self.covariance = gdkwargs.pop("covariance", None)
-        self.param_cov = None
-        _covariance.refuse(self.covariance, brange=brange, nbatch=nbatch, isfunc=isfunc)
+        _post.check(self._stat_values(), root=method if isinstance(method, str) else None, brange=brange, nbatch=nbatch, isfunc=isfunc)
         self.logger = logger
         self.verbose = verbose
         self.debug = bool(debug or verbose > 1)
@@ -490,114 +461,53 @@ class MCEvidence(object):
         dotp, logLmax, jac = got
         return np.stack([self._feed_finish((S, logLmax[b]), dotp[b], jac[b], logPriorVolume) for b, S in enumerate(sizes)])
 
-    def _fill_information(self, MLE, pos_lnp):
-        """``info["information"]`` of this call (the constructor's ``information`` keyword; unset: nothing happens): the rule of
-        information.py on s1's weights and fs, on the host -- under a process group every rank computes its own, no collective"""
-        if not _information.wanted(self.information):
-            return
-        _information.refuse(self.information, brange=self.brange, nbatch=self.nbatch)
-        _, lnp, _ = self.gd.arrays("s1")
-        logL = np.asarray(-lnp if pos_lnp else lnp, dtype=np.float64)
-        logLmax = np.amax(logL)
-        a, fs = self.gd.data["s1"].adjusted_weights, logL - logLmax
-        inf = _information.build(_information.moments(a, fs), logLmax, MLE)
-        jk = self.info.get("jackknife") if _information.wanted(self.jackknife) else None
-        if jk is not None:
-            from .jackknife import group_ids
-            _information.with_jackknife(inf, a, fs, group_ids(self.gd, "s1", jk["groups"], jk["by"]), logLmax, jk)
-        self.info["information"] = inf
+    def _stat_values(self):
+        """the statistics' keywords and ``bounds`` as this object holds them"""
+        return dict({st.key: getattr(self, st.spec_attr) for st in _post.STATS}, bounds=self.bounds)
 
-    def _fill_summary(self, pos_lnp):
-        """``info["summary"]`` of this call (the constructor's ``summary`` keyword; unset: nothing happens): the rule of summary.py on
-        s1's weights, its raw first ``ndim`` columns and fs, on the host -- under a process group every rank computes its own, no
-        collective"""
-        probs = _summary.spec(self.summary_spec)
-        if probs is None:
+    def _fill(self, st, MLE=None, pos_lnp=False):
+        """``info[st.key]`` of this call (the constructor's keyword of that name; unset: nothing happens): the statistic's rule on s1's
+        weights, its raw first ``ndim`` columns and fs -- by the library where the statistic has a native form and the HIP backend is in
+        use, otherwise in NumPy; under a process group every rank computes its own, no collective"""
+        values = self._stat_values()
+        if not _post.wanted(values[st.key]):
             return
-        _summary.refuse(self.summary_spec, brange=self.brange, nbatch=self.nbatch)
+        st.check(values, brange=self.brange, nbatch=self.nbatch)
         samples, lnp, _ = self.gd.arrays("s1")
         logL = np.asarray(-lnp if pos_lnp else lnp, dtype=np.float64)
         logLmax = np.amax(logL)
-        blk = _summary.measure(self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim], logL - logLmax,
-                               _summary.targets(probs))
-        self.param_summary = self.info["summary"] = _summary.build(blk, probs, logLmax, _summary.param_names(self.fname, self.ndim))
+        a, x, fs = self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim], logL - logLmax
+        names = _post.param_names(self.fname, self.ndim)
+        req = st.resolve(values, names, self.ndim, self.fname)
+        found = st.build(st.measure_host(a, x, fs, req, self.backend), req, names, logLmax, MLE)
+        jk = self.info.get("jackknife") if st is _post.INFORMATION and _post.wanted(self.jackknife) else None
+        if jk is not None:
+            from .jackknife import group_ids
+            _information.with_jackknife(found, a, fs, group_ids(self.gd, "s1", jk["groups"], jk["by"]), logLmax, jk)
+        self.info[st.key] = found
+        if st.attr is not None:
+            setattr(self, st.attr, found)
+
+    # (``_fill`` of one statistic by the names the statistics' own tests know it by)
+    def _fill_summary(self, pos_lnp=False):
+        self._fill(_post.SUMMARY, None, pos_lnp)
 
     def _fill_marginals(self):
-        """``info["marginals"]`` of this call (the constructor's ``marginals`` keyword; unset: nothing happens): the rule of marginals.py
-        on s1's weights and its raw first ``ndim`` columns -- by ``mce_param_marginals_f64`` where the HIP backend is in use, otherwise
-        in NumPy; under a process group every rank computes its own, no collective"""
-        sp = _marginals.spec(self.marginals_spec)
-        if sp is None:
-            return
-        _marginals.refuse(self.marginals_spec, brange=self.brange, nbatch=self.nbatch)
-        samples, _, _ = self.gd.arrays("s1")
-        a, x = self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim]
-        names = _summary.param_names(self.fname, self.ndim)
-        bnd = _marginals.bounds_spec(self.bounds, names=names, root=self.fname if isinstance(self.fname, str) else None, marginals=self.marginals_spec)
-        if bnd is not None:
-            _marginals.note_contours(self.contours_spec)
-        if getattr(self.backend, "name", None) == "hip":
-            import torch
-            devs = getattr(self.backend, "devices", None)
-            device = devs[0] if devs else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
-            blk = _marginals.measure_native(a, x, *sp, device=device) if bnd is None else _marginals.measure_bounded_native(a, x, bnd, *sp, device=device)
-        else:
-            blk = _marginals.measure(a, x, *sp) if bnd is None else _marginals.measure_bounded(a, x, bnd, *sp)
-        self.param_marginals = self.info["marginals"] = _marginals.build(blk, sp, names)
+        self._fill(_post.MARGINALS)
 
     def _fill_contours(self):
-        """``info["contours"]`` of this call (the constructor's ``contours`` keyword; unset: nothing happens): the rule of contours.py on
-        s1's weights and its raw first ``ndim`` columns -- by ``mce_param_contours_f64`` where the HIP backend is in use, otherwise in
-        NumPy; with the key ``"bounds"`` the rule with hard prior bounds, by ``mce_param_contours_bounded_f64`` or ``measure_bounded``;
-        under a process group every rank computes its own, no collective"""
-        if not _contours.wanted(self.contours_spec):
-            return
-        _contours.refuse(self.contours_spec, brange=self.brange, nbatch=self.nbatch)
-        names = _summary.param_names(self.fname, self.ndim)
-        sp = _contours.spec(self.contours_spec, ndim=self.ndim, names=names)
-        probs, grid, scale, cols = sp
-        samples, _, _ = self.gd.arrays("s1")
-        a, x = self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim]
-        bnd = _contours.bounds_spec(self.contours_spec, names=names, ndim=self.ndim, root=self.fname if isinstance(self.fname, str) else None, bounds=self.bounds)
-        if getattr(self.backend, "name", None) == "hip":
-            import torch
-            devs = getattr(self.backend, "devices", None)
-            device = devs[0] if devs else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
-            blk = (_contours.measure_native(a, x, cols, probs, grid, scale, device=device) if bnd is None else
-                   _contours.measure_bounded_native(a, x, cols, bnd, probs, grid, scale, device=device))
-        else:
-            blk = _contours.measure(a, x, cols, probs, grid, scale) if bnd is None else _contours.measure_bounded(a, x, cols, bnd, probs, grid, scale)
-        self.param_contours = self.info["contours"] = _contours.build(blk, sp, names)
+        self._fill(_post.CONTOURS)
 
     def _fill_covariance(self):
-        """``info["covariance"]`` of this call (the constructor's ``covariance`` keyword; unset: nothing happens): the rule of
-        covariance.py on s1's weights and its raw first ``ndim`` columns, on the host -- under a process group every rank computes its
-        own, no collective"""
-        if _covariance.spec(self.covariance) is None:
-            return
-        _covariance.refuse(self.covariance, brange=self.brange, nbatch=self.nbatch)
-        samples, _, _ = self.gd.arrays("s1")
-        blk = _covariance.measure(self.gd.data["s1"].adjusted_weights, np.asarray(samples, dtype=np.float64)[:, :self.ndim])
-        self.param_cov = self.info["covariance"] = _covariance.build(blk, _covariance.param_names(self.fname, self.ndim))
+        self._fill(_post.COVARIANCE)
 
     def _report(self, MLE, verbose, info, pos_lnp=False):
-        self._fill_information(MLE, pos_lnp)
-        self._fill_summary(pos_lnp)
-        self._fill_marginals()
-        self._fill_contours()
-        self._fill_covariance()
-        if verbose > 0 and "information" in self.info and _information.wanted(self.information):
-            for line in _information.lines(self.info["information"]):
-                self.logger.info(line)
-        if verbose > 0 and "summary" in self.info and _summary.wanted(self.summary_spec):
-            for line in _summary.lines(self.info["summary"]):
-                self.logger.info(line)
-        if verbose > 0 and "marginals" in self.info and _marginals.wanted(self.marginals_spec):
-            for line in _marginals.lines(self.info["marginals"]):
-                self.logger.info(line)
-        if verbose > 0 and "contours" in self.info and _contours.wanted(self.contours_spec):
-            for line in _contours.lines(self.info["contours"]):
-                self.logger.info(line)
+        for st in _post.STATS:
+            self._fill(st, MLE, pos_lnp)
+        for st in _post.STATS:
+            if verbose > 0 and st.key in self.info and _post.wanted(getattr(self, st.spec_attr)):
+                for line in st.lines(self.info[st.key]):
+                    self.logger.info(line)
         if verbose > 0:
             for k in range(1, self.kmax):
                 self.logger.info("   ln(B)[k={}] = {}".format(k, MLE[k - 1] if self.brange is None else MLE[:, k - 1]))

@@ -19,12 +19,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import information as _information
+from . import posterior as _post
 from . import resident as _res
-from . import summary as _summary
-from . import contours as _contours
-from . import marginals as _marginals
-from . import covariance as _covariance
 
 logger = logging.getLogger("mcevidence_amd")
 
@@ -130,47 +126,8 @@ def _per_root(value, n, name):
     return [value] * n
 
 
-def _per_root_summary(value, n):
-    """``summary`` of the farm -> one value per root.  The value itself may be a sequence (of probabilities), so the rule is by the
-    ENTRIES: a list / tuple whose entries are all None, a bool or a sequence is one entry per root and must have ``n`` of them; a
-    sequence of bare numbers is ONE value, the probabilities of every root; a mixture of the two is refused"""
-    if isinstance(value, (list, tuple, np.ndarray)) and len(value) > 0:
-        slot = [v is None or isinstance(v, (bool, np.bool_, list, tuple, np.ndarray)) for v in value]
-        if all(slot):
-            return _per_root(list(value), n, "summary")
-        if any(slot):
-            raise ValueError("summary=%r: either probabilities (one value for every root) or one entry per root (None, True or a sequence of "
-                             "probabilities each), not a mixture" % (value,))
-    return [value] * n
-
-
-def _per_root_marginals(value, n):
-    """``marginals`` of the farm -> one value per root, by ``_per_root_summary``'s rule with a dict as one more kind of entry: a dict, or a
-    sequence of bare numbers, is ONE value for every root; a list / tuple whose entries are all None, a bool, a sequence or a dict is one
-    entry per root"""
-    if isinstance(value, (list, tuple, np.ndarray)) and len(value) > 0:
-        slot = [v is None or isinstance(v, (bool, np.bool_, list, tuple, np.ndarray, dict)) for v in value]
-        if all(slot):
-            return _per_root(list(value), n, "marginals")
-        if any(slot):
-            raise ValueError("marginals=%r: either one value for every root or one entry per root (None, True, a sequence of probabilities or a "
-                             "dict each), not a mixture" % (value,))
-    return [value] * n
-
-
-def _per_root_bounds(value, n):
-    """``bounds`` of the farm -> one value per root, by ``_per_root_marginals``' rule: None, "ranges", a mapping, or a sequence of
-    (lo, hi) pairs is ONE value for every root; a list / tuple whose entries are all None, "ranges", a mapping or a sequence of pairs
-    is one entry per root"""
-    def is_pair(v):
-        return isinstance(v, (list, tuple, np.ndarray)) and len(v) == 2 and not any(isinstance(e, (list, tuple, np.ndarray, dict)) for e in v)
-    if isinstance(value, (list, tuple, np.ndarray)) and len(value) > 0 and not all(is_pair(v) for v in value):
-        slot = [v is None or isinstance(v, (str, dict)) or (isinstance(v, (list, tuple, np.ndarray)) and all(is_pair(e) for e in v)) for v in value]
-        if all(slot):
-            return _per_root(list(value), n, "bounds")
-        raise ValueError("bounds=%r: either one value for every root or one entry per root (None, 'ranges', a mapping or a sequence of (lo, hi) "
-                         "pairs each), not a mixture" % (value,))
-    return [value] * n
+# (the rules of posterior.py by the names the statistics' own tests know them by)
+_per_root_summary, _per_root_marginals, _per_root_bounds = _post.SUMMARY.per_root, _post.MARGINALS.per_root, _post.per_root_bounds
 
 
 def _parse_wave(pool, device, wave_bytes, paths, lens, ms):
@@ -241,7 +198,7 @@ def read_files(paths, device=0, wave_bytes=None):
 
 
 class _Root(object):
-    __slots__ = ("index", "files", "lens", "size", "ndim", "pvol", "burn", "thin", "parts", "ncols", "nrows", "nparam", "nd", "rc", "keep", "problem", "scal", "conv", "jack")
+    __slots__ = ("index", "files", "lens", "size", "ndim", "pvol", "burn", "thin", "parts", "ncols", "nrows", "nparam", "nd", "rc", "keep", "system", "scal", "conv", "jack")
 
 
 def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen=0, thinlen=0, covtype="all", pos_lnp=False, idchain=0,
@@ -262,27 +219,19 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     by its measured autocorrelation length on the per-root resident route.  ``converge`` (one value or one per root; with
     ``converge_by``): the Gelman-Rubin R-1 of every such root's burned, unthinned chains, in ``info["converge"]`` -- ONE
     ``mce_chain_conv_dev`` call per wave and per (columns, ndim) group covers the unthinned roots of the wave; a thinned or a
-    ``thin_corr`` root is measured on its per-root route.  ``information`` (one value or one per root): <ln L>_P, D_KL and the model
-    dimensionality of every such root in ``info["information"]`` -- ONE ``mce_like_moments_dev`` call per wave over all its ready roots,
-    thinned and unthinned alike.  ``jackknife`` (one value or one per root: None, True, a number of groups or dict(groups, by)): the
+    ``thin_corr`` root is measured on its per-root route.  ``jackknife`` (one value or one per root: None, True, a number of groups or dict(groups, by)): the
     delete-a-group error bars of every such root in ``info["jackknife"]``, as ``evidence_from_files(root, jackknife=...)`` returns them --
     the group ids of all asking roots of a wave come from ONE ``mce_jack_groups_dev`` call and their leave-one-group-out blocks from ONE
     ``mce_jack_leave_out_dev`` call; the ladders (whitening, searches, ``mce_jack_dotp_dev``) run root by root after the wave's batched
-    feed, and a root whose ladder raises fails alone.  ``summary`` (None, True or up to 7 probabilities for every root -- a sequence of bare numbers is ONE value; or one entry per
-    root, a list whose entries are each None, True or a sequence of probabilities, so ``[(0.9,), (0.5,)]`` and not ``[0.9, 0.5]`` gives two
-    roots one probability each; a list of such entries of another length, or a mixture, is a ``ValueError`` before any work): the
-    weighted means, standard deviations, equal-tailed limits and the best-fit sample of every such root's first ``ndim`` parameters in
-    ``info["summary"]`` -- ONE ``mce_param_summary_dev`` call per wave (and per set of probabilities) over all its ready roots, thinned
-    and unthinned alike, before the feed.  ``covariance`` (one value or one per root: None or True): the weighted mean and covariance matrix
-    of every such root's first ``ndim`` parameters in ``info["covariance"]`` -- ONE ``mce_param_cov_dev`` call per wave over all its ready
-    roots that ask, thinned and unthinned alike, before the feed.  ``marginals`` (one value or one per root, by ``summary``'s rule; a dict is
-    one value): the 1-D marginal densities, modes and HPD regions of every such root's first ``ndim`` parameters in ``info["marginals"]`` --
-    ONE ``mce_param_marginals_dev`` call per wave and per distinct (probs, grid, scale) over all its ready roots that ask, before the feed.
-    ``bounds`` (one value or one per root, by the same rule: None, "ranges", a mapping name -> (lo, hi) or one (lo, hi) per parameter): the
-    hard prior bounds of such a root's marginals (docs/design/marginals_bounds.md) -- the roots with bounds go through ONE
-    ``mce_param_marginals_bounded_dev`` call per wave and distinct (probs, grid, scale), each with its own bounds; the others as before.
-    ``contours`` (by the same rule): the 2-D joint densities, modes and credible levels of the pairs of every such root's chosen parameters
-    in ``info["contours"]`` -- ONE ``mce_param_contours_dev`` call per wave and per distinct (probs, grid, scale, columns), at the same place.
+    feed, and a root whose ladder raises fails alone.  The statistics of posterior.py (docs/design/posterior_stats.md has their values, the
+    rule for one value or one entry per root, and who shares a call), each in ``info[<keyword>]`` as ``evidence_from_files`` returns it:
+    ``information`` (one value or one per root: None or True).
+    ``summary`` (a sequence of bare numbers is ONE value, so ``[(0.9,), (0.5,)]`` and not ``[0.9, 0.5]`` gives two roots one probability each).
+    ``marginals`` and ``contours`` (by ``summary``'s rule; a dict is one value).
+    ``bounds`` (by the same rule: None, "ranges", a mapping or one (lo, hi) per parameter): the hard prior bounds of the marginals.
+    ``covariance`` (one value or one per root: None or True).
+    Each is ONE library call per wave, per distinct spec and per form (plain or bounded) over the ready roots that ask, thinned and unthinned
+    alike, before the feed; a root whose request does not fit its own parameters fails alone.
     Without a GPU: ``RuntimeError``."""
     from . import _capi
     _capi.require_device()
@@ -296,34 +245,26 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
     corr_kw = {k: v for k, v in (("corr_min", corr_min), ("corr_max_lag", corr_max_lag)) if v is not None}
     convs = _per_root(converge, n, "converge")
     conv_kw = [{} if c in (None, False) else {"converge": c, "converge_by": converge_by} for c in convs]
-    infos = _per_root(information, n, "information")
-    info_kw = [{"information": v} if _information.wanted(v) else {} for v in infos]      # (what a root takes with it to another route)
-    jacks = _per_root(jackknife, n, "jackknife")
-    jack_kw = [{} if v is None or v is False else {"jackknife": v} for v in jacks]
-    sums = _per_root_summary(summary, n)
-    sum_kw = [{"summary": v} if _summary.wanted(v) else {} for v in sums]
-    mars = _per_root_marginals(marginals, n)
-    for v in mars:
-        _marginals.spec(v)
-    bnds = _per_root_bounds(bounds, n)
-    cons = _per_root_marginals(contours, n)
-    for v, b, r, c in zip(mars, bnds, roots, cons):
-        _marginals.refuse_bounds(b, v, root=r if isinstance(r, str) else None, contours=c)
-    mar_kw = [dict({"marginals": v}, **({} if b is None else {"bounds": b})) if _marginals.wanted(v) else {} for v, b in zip(mars, bnds)]
-    for v in cons:
-        _contours.spec(v)
-    # (a root that leaves for another route takes bounds= with it where its contours ask for the call's)
-    con_kw = [dict({"contours": v}, **({"bounds": b} if b is not None and _contours.bounds_wanted(v) and v["bounds"] is True and not _marginals.wanted(m) else {}))
-              if _contours.wanted(v) else {} for v, b, m in zip(cons, bnds, mars)]
-    covs = _per_root(covariance, n, "covariance")
-    for v in covs:
-        _covariance.spec(v)
-    cov_kw = [{"covariance": v} if _covariance.wanted(v) else {} for v in covs]
+    # one dict of values per root: the statistics' keywords (posterior.py), bounds and jackknife, each spread by its own rule and
+    # validated where it always was (a summary value no route takes fails its root alone, in ``plan``)
+    given = dict(information=information, jackknife=jackknife, summary=summary, marginals=marginals, bounds=bounds, contours=contours, covariance=covariance)
+    rules = dict({st.key: st.per_root for st in _post.STATS}, bounds=_post.per_root_bounds, jackknife=lambda v, m: _per_root(v, m, "jackknife"))
+    rnames = [r if isinstance(r, str) else None for r in roots]
+    vals = [{} for _ in roots]
+    for key, validated in (("information", ()), ("jackknife", ()), ("summary", ()), ("marginals", ("marginals",)), ("bounds", ()),
+                           ("contours", ("bounds", "contours")), ("covariance", ("covariance",))):
+        for v, x in zip(vals, rules[key](given[key], n)):
+            v[key] = x
+        for k in validated:
+            for v, rname in zip(vals, rnames):
+                _post.check(v, root=rname, keys=(k,))
+    jack_kw = [{} if v["jackknife"] is None or v["jackknife"] is False else {"jackknife": v["jackknife"]} for v in vals]
+    carry = [dict(_post.carry(v), **conv_kw[i], **jack_kw[i]) for i, v in enumerate(vals)]      # (what a root takes with it to another route)
     common = dict(kmax=kmax, idchain=idchain, idpattern=idpattern, iw=iw, ilike=ilike, itheta=itheta)
     if _res._distributed():
         from .evidence import MCEvidence, evidence_many
         extra = dict(common, split=split, verbose=0, **({"backend": backend} if backend else {}))
-        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **conv_kw[i], **info_kw[i], **jack_kw[i], **sum_kw[i], **mar_kw[i], **con_kw[i], **cov_kw[i], **extra)
+        objs = [MCEvidence(r, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], thin_corr=tcorr[i], **corr_kw, **carry[i], **extra)
                 for i, r in enumerate(roots)]
         return evidence_many(objs, info=info, covtype=covtype, pos_lnp=pos_lnp)
     import torch
@@ -349,8 +290,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
         if reason == _res.RESIDENT:
             try:
                 reason = _res.plan(thinlen=thins[i], covtype="single" if covtype is None else covtype, ndim=ndims[i], thin_corr=tcorr[i],
-                                   converge=convs[i], converge_by=converge_by, jackknife=jacks[i], summary=sums[i], covariance=covs[i], marginals=mars[i],
-                                   contours=cons[i], bounds=bnds[i])
+                                   converge=convs[i], converge_by=converge_by, **{k: v for k, v in vals[i].items() if k != "information"})
             except ValueError as e:                # (thin_corr together with thinlen; a converge or jackknife value no route takes)
                 fail(i, e)
                 continue
@@ -364,9 +304,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             r.index, r.files = i, _res._resolve_files(root, idchain, idpattern)
             r.lens = [os.stat(p).st_size for p in r.files]
             r.size = farm_layout(r.lens)[1]
-            r.ndim, r.pvol, r.burn, r.thin, r.rc, r.keep, r.problem, r.scal = ndims[i], pvols[i], burns[i], thins[i], None, None, None, None
+            r.ndim, r.pvol, r.burn, r.thin, r.rc, r.keep, r.system, r.scal = ndims[i], pvols[i], burns[i], thins[i], None, None, None, None
             r.conv = _res._chains.converge_spec(convs[i], converge_by)          # None, or (threshold, by); afterwards: info["converge"]
-            r.jack = _res.jack_spec(jacks[i], len(r.files))                     # None, or dict(groups, by, G)
+            r.jack = _res.jack_spec(vals[i]["jackknife"], len(r.files))                     # None, or dict(groups, by, G)
             todo.append(r)
         except Exception as e:                     # (no files, an unreadable path, by="chains" of one file: what the host route raises too)
             fail(i, e)
@@ -476,8 +416,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                 for k, r in enumerate(seg):
                     r.scal = tuple(scal[k])
                     r.keep = (params, w, fs)
-                    r.problem = (params.data_ptr() + par0 * 8, r.nrows, r.nparam, 0, 0, 0, r.nd, 0 if cov == "all" else 1, kmax_eff,
-                                 w.data_ptr() + row0 * 8, fs.data_ptr() + row0 * 8)
+                    r.system = _post.System(params.data_ptr() + par0 * 8, r.nparam, r.nrows, r.nd, w.data_ptr() + row0 * 8, fs.data_ptr() + row0 * 8)
                     row0 += r.nrows
                     par0 += r.nrows * r.nparam
             for r in plain:
@@ -487,8 +426,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                         n1 = int(s1["w"].shape[0])
                         fs1, r.scal = r.rc._reduce(s1, pos_lnp)
                         r.keep = (s1, fs1)
-                        r.problem = (s1["params"].data_ptr(), n1, r.nparam, 0, 0, 0, r.nd, 0 if cov == "all" else 1, kmax_eff, s1["w"].data_ptr(),
-                                     fs1.data_ptr())
+                        r.system = _post.System(s1["params"].data_ptr(), r.nparam, n1, r.nd, s1["w"].data_ptr(), fs1.data_ptr())
                     _res.check_reduced(*r.scal)
                     ready.append(r)
                 except Exception as e:
@@ -499,72 +437,14 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             # ---- feed: every root of the wave in one library call -----------------------------------------------------------------
             t0 = time.perf_counter()
             if ready:
-                # information: the ready roots that ask for it, thinned and unthinned alike, in one call (problem: .., n1 at 1, w at 9, fs at 10)
-                asked = [r for r in ready if _information.wanted(infos[r.index])]
-                moms = dict(zip((r.index for r in asked),
-                                _res.moments_measure_dev([(r.problem[10], r.problem[9], r.problem[1]) for r in asked], device, stream.cuda_stream))) if asked else {}
-                # summary: the ready roots that ask for it in one call per set of probabilities, while the gathered rows are raw (the
-                # ladders below whiten them) (problem: params at 0, n1 at 1, nparam at 2, nd at 6, w at 9, fs at 10)
-                sblks = {}
-                for probs in sorted(set(_summary.spec(sums[r.index]) for r in ready if _summary.wanted(sums[r.index]))):
-                    sasked = [r for r in ready if _summary.wanted(sums[r.index]) and _summary.spec(sums[r.index]) == probs]
-                    sblks.update(zip((r.index for r in sasked),
-                                     _res.summary_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9], r.problem[10]) for r in sasked],
-                                                              _summary.targets(probs), device, stream.cuda_stream)))
-                # marginals: the ready roots that ask for them in one call per distinct (probs, grid, scale), while the gathered rows are raw
-                # (a root with bounds: the bounded call, each root with its own; bounds that do not fit a root's parameters fail it alone)
-                mblks, mbnds = {}, {}
-                for r in [r for r in ready if _marginals.wanted(mars[r.index]) and bnds[r.index] is not None]:
-                    rname = roots[r.index] if isinstance(roots[r.index], str) else None
-                    try:
-                        mbnds[r.index] = _marginals.bounds_spec(bnds[r.index], names=_summary.param_names(rname, r.problem[6]), root=rname, marginals=mars[r.index])
-                        _marginals.note_contours(cons[r.index])
-                    except ValueError as e:
-                        fail(r.index, e)
-                ready = [r for r in ready if not (_marginals.wanted(mars[r.index]) and bnds[r.index] is not None and r.index not in mbnds)]
-                for msp in sorted(set(_marginals.spec(mars[r.index]) for r in ready if _marginals.wanted(mars[r.index]))):
-                    masked = [r for r in ready if _marginals.wanted(mars[r.index]) and _marginals.spec(mars[r.index]) == msp and r.index not in mbnds]
-                    if masked:
-                        mblks.update(zip((r.index for r in masked),
-                                         _res.marginals_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in masked],
-                                                                    msp, device, stream.cuda_stream)))
-                    masked = [r for r in ready if _marginals.wanted(mars[r.index]) and _marginals.spec(mars[r.index]) == msp and r.index in mbnds]
-                    if masked:
-                        mblks.update(zip((r.index for r in masked),
-                                         _res.marginals_bounded_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in masked],
-                                                                            [mbnds[r.index] for r in masked], msp, device, stream.cuda_stream)))
-                # contours: likewise, one call per distinct (probs, grid, scale, columns); a root whose ``params`` do not fit its own
-                # parameters fails alone, with the ValueError of ``contours.spec``.  The roots whose contours ask for bounds go through the
-                # bounded call, each with its own; bounds that do not fit a root fail it alone
-                conblks, cspecs, cbnds = {}, {}, {}
-                for r in [r for r in ready if _contours.wanted(cons[r.index])]:
-                    rname = roots[r.index] if isinstance(roots[r.index], str) else None
-                    try:
-                        cnames = _summary.param_names(rname, r.problem[6])
-                        cspecs[r.index] = _contours.spec(cons[r.index], ndim=r.problem[6], names=cnames)
-                        cb = _contours.bounds_spec(cons[r.index], names=cnames, ndim=r.problem[6], root=rname, bounds=bnds[r.index])
-                        if cb is not None:
-                            cbnds[r.index] = cb
-                    except ValueError as e:
-                        cspecs.pop(r.index, None)
-                        fail(r.index, e)
-                ready = [r for r in ready if not (_contours.wanted(cons[r.index]) and r.index not in cspecs)]
-                for csp in sorted(set(cspecs.values())):
-                    cwho = [r for r in ready if cspecs.get(r.index) == csp and r.index not in cbnds]
-                    if cwho:
-                        conblks.update(zip((r.index for r in cwho),
-                                           _res.contours_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in cwho],
-                                                                     csp, device, stream.cuda_stream)))
-                    cwho = [r for r in ready if cspecs.get(r.index) == csp and r.index in cbnds]
-                    if cwho:
-                        conblks.update(zip((r.index for r in cwho),
-                                           _res.contours_bounded_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in cwho],
-                                                                             [cbnds[r.index] for r in cwho], csp, device, stream.cuda_stream)))
-                # covariance: the ready roots that ask for it in one call, while the gathered rows are raw
-                casked = [r for r in ready if _covariance.wanted(covs[r.index])]
-                cblks = dict(zip((r.index for r in casked),
-                                 _res.covariance_measure_dev([(r.problem[0], r.problem[2], r.problem[1], r.problem[6], r.problem[9]) for r in casked],
-                                                             device, stream.cuda_stream))) if casked else {}
+                # the statistics of the ready roots that ask, thinned and unthinned alike, while the gathered rows are raw (the ladders
+                # below whiten them): posterior.measure_wave has the rule for who shares a call and who fails alone
+                names = {r.index: _post.param_names(rnames[r.index], r.nd) if _post.carry(vals[r.index]) else None for r in ready}
+                found, unfit, _ = _post.measure_wave([_post.Asking(r.index, r.system, vals[r.index], names[r.index], rnames[r.index]) for r in ready],
+                                                     device, stream.cuda_stream)
+                for i, e in unfit.items():
+                    fail(i, e)
+                ready = [r for r in ready if r.index not in unfit]
                 # jackknife: the group ids of the ready roots that ask for it in one call, their leave-one-group-out blocks in another
                 # (src: the kept rows of a thinned root; fs only where the deleted sets' moments are wanted)
                 jasked = [r for r in ready if r.jack is not None]
@@ -572,24 +452,25 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                 if jasked:
                     jgroups = dict(zip((r.index for r in jasked),
                                        _res.jack_groups_dev([(r.rc._src if r.rc is not None else None, r.rc._parts if r.rc is not None else r.parts,
-                                                              r.problem[1], r.jack["G"], r.jack["by"]) for r in jasked], device, stream.cuda_stream)))
+                                                              r.system.rows, r.jack["G"], r.jack["by"]) for r in jasked], device, stream.cuda_stream)))
                     jblocks = dict(zip((r.index for r in jasked),
-                                       _res.jack_leave_out_dev([(r.problem[9], r.problem[10] if r.index in moms else 0, jgroups[r.index], r.problem[1], r.jack["G"])
-                                                                for r in jasked], device, stream.cuda_stream)))
+                                       _res.jack_leave_out_dev([(r.system.w, r.system.fs if "information" in found[r.index] else 0, jgroups[r.index], r.system.rows,
+                                                                 r.jack["G"]) for r in jasked], device, stream.cuda_stream)))
+                cov_mode = 0 if cov == "all" else 1
                 with backend._scoped():
-                    got = _capi.evidence_feed_batch_dev([r.problem for r in ready], device=device, return_exceptions=True)
+                    got = _capi.evidence_feed_batch_dev([_post.feed_problem(r.system, cov_mode, kmax_eff) for r in ready], device=device, return_exceptions=True)
                     for r, g in zip(ready, got):
                         if isinstance(g, Exception):
                             # (the library words only the first failure of a batch: this problem alone, for its own message)
                             try:
-                                p = r.problem
-                                _capi.evidence_feed_part_dev(p[0], p[1], p[2], 0, 0, 0, p[6], p[7], p[8], p[9], p[10], 0, 1, device=device, want_checksum=False)
+                                y = r.system
+                                _capi.evidence_feed_part_dev(y.params, y.rows, y.ld, 0, 0, 0, y.nd, cov_mode, kmax_eff, y.w, y.fs, 0, 1, device=device, want_checksum=False)
                                 fail(r.index, g)
                             except Exception as e:
                                 fail(r.index, e)
                             continue
                         dotp, jac, _ = g
-                        n1 = r.problem[1]
+                        n1 = r.system.rows
                         try:
                             out = _res.mle_from_sums(dotp, jac, r.scal[1], r.scal[0], n1, kmax_eff, math.log(r.pvol), False)[1:]
                         except Exception as e:
@@ -599,20 +480,10 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                         inf = _res.route_info(FARM, r.nparam, r.nd, n1, [n1])
                         if r.conv is not None:
                             inf["converge"] = r.conv
-                        if r.index in moms:
-                            inf["information"] = _information.build(moms[r.index], r.scal[0], out)
-                        if r.index in sblks:
-                            inf["summary"] = _summary.build(sblks[r.index], _summary.spec(sums[r.index]), r.scal[0],
-                                                            _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
-                        if r.index in mblks:
-                            inf["marginals"] = _marginals.build(mblks[r.index], _marginals.spec(mars[r.index]),
-                                                                _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
-                        if r.index in conblks:
-                            inf["contours"] = _contours.build(conblks[r.index], cspecs[r.index],
-                                                              _summary.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
-                        if r.index in cblks:
-                            inf["covariance"] = _covariance.build(cblks[r.index],
-                                                                  _covariance.param_names(roots[r.index] if isinstance(roots[r.index], str) else None, r.problem[6]))
+                        for st in _post.STATS:
+                            if st.key in found[r.index]:
+                                blk, req = found[r.index][st.key]
+                                inf[st.key] = st.build(blk, req, names[r.index], r.scal[0], out)
                         if r.jack is not None:
                             pending.append((r, out, inf))
                             continue
@@ -620,9 +491,9 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
                 # the ladders, root by root (a root whose ladder raises -- rows still short after the last rung -- fails alone)
                 for r, out, inf in pending:
                     try:
-                        p = r.problem
-                        run = _res.jack_run(p[0], p[1], p[2], p[6], p[8], p[9], p[10], jgroups[r.index], r.jack, device, backend)
-                        inf["jackknife"] = _res.jack_result(run, jblocks[r.index], r.jack, r.scal[1], r.scal[0], p[1], kmax_eff, math.log(r.pvol))
+                        y = r.system
+                        run = _res.jack_run(y.params, y.rows, y.ld, y.nd, kmax_eff, y.w, y.fs, jgroups[r.index], r.jack, device, backend)
+                        inf["jackknife"] = _res.jack_result(run, jblocks[r.index], r.jack, r.scal[1], r.scal[0], y.rows, kmax_eff, math.log(r.pvol))
                         if "information" in inf:
                             _res.jack_information(inf["information"], jblocks[r.index], r.scal[0], inf["jackknife"])
                         results[r.index] = out if not info else (out, inf)
@@ -641,13 +512,7 @@ def evidence_many_from_files(roots, *, kmax=5, ndim=None, priorvolume=1, burnlen
             kw = dict(common, ndim=ndims[i], priorvolume=pvols[i], burnlen=burns[i], thinlen=thins[i], pos_lnp=pos_lnp, split=split, info=True, verbose=0)
             if tcorr[i] not in (None, False):
                 kw.update(corr_kw, thin_corr=tcorr[i])
-            kw.update(conv_kw[i])
-            kw.update(info_kw[i])
-            kw.update(jack_kw[i])
-            kw.update(sum_kw[i])
-            kw.update(mar_kw[i])
-            kw.update(con_kw[i])
-            kw.update(cov_kw[i])
+            kw.update(carry[i])
             if covtype != "all":
                 kw["covtype"] = covtype
             if backend is not None:

@@ -24,10 +24,7 @@ import numpy as np
 
 from . import chains as _chains
 from . import information as _information
-from . import summary as _summary
-from . import contours as _contours
-from . import marginals as _marginals
-from . import covariance as _covariance
+from . import posterior as _post
 
 logger = logging.getLogger("mcevidence_amd")
 
@@ -80,16 +77,10 @@ def plan(thinlen=0, isfunc=None, brange=None, nbatch=1, verbose=1, covtype="all"
     ``converge_by`` (the Gelman-Rubin R-1 of the burned chains) are resident work too and decline nothing; a value they cannot take
     is the ValueError every route raises.  ``jackknife`` (the delete-a-group error bars; ``nchains``: the chains, where known) is resident
     work for an auto evidence; with a split it declines to the host route, which whitens s1 and s2 there; a number of groups or a
-    ``by`` it cannot take is the ValueError every route raises.  ``summary`` (the posterior summary of the parameters) is resident work
-    and declines nothing; a value it cannot take is the ValueError every route raises.  ``covariance`` (the weighted mean and covariance
-    matrix of the parameters) is resident work too: it is validated and declines nothing; so is ``marginals`` (the 1-D marginal densities), and so is
-    ``contours`` (the 2-D joint densities of the parameter pairs).  ``bounds`` (the hard prior bounds of the marginals) declines nothing either; without
-    ``marginals`` it is the ValueError every route raises."""
-    _summary.spec(summary)
-    _marginals.spec(marginals)
-    _marginals.refuse_bounds(bounds, marginals, contours=contours)
-    _contours.spec(contours)
-    _covariance.spec(covariance)
+    ``by`` it cannot take is the ValueError every route raises.  ``summary``, ``marginals``, ``contours``, ``covariance`` and ``bounds``
+    (the statistics of posterior.py) are resident work too: they are validated -- a value they cannot take is the ValueError every route
+    raises -- and decline nothing."""
+    _post.check(dict(summary=summary, marginals=marginals, contours=contours, covariance=covariance, bounds=bounds))
     if not ischain:
         return REASONS["ischain"]
     _chains.thin_corr_scale(thin_corr, thinlen)
@@ -220,82 +211,6 @@ def conv_measure_dev(systems, ncols, iw, itheta, nd, device, stream):
             for y in range(len(systems))]
 
 
-def moments_measure_dev(systems, device, stream):
-    """ONE ``mce_like_moments_dev`` call for ``systems`` = [(device address of fs, device address of w, rows)] -> one
-    ``information.moments`` dict per system"""
-    import torch
-    from . import _capi
-    wsb = _capi.like_moments_workspace_bytes(sum(n for _, _, n in systems), len(systems))
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
-    return [_information.from_block(b) for b in _capi.like_moments_dev(systems, ws.data_ptr(), wsb, stream)]
-
-
-def _blocks_dev(workspace_bytes, ws_args, call, from_block, systems, device, stream):
-    """what the per-parameter statistics below share: the workspace (``workspace_bytes`` of the rows of all systems, their number,
-    their widest and ``ws_args``), the one library call (``call``: what follows the systems and their spec) and ``from_block`` of every
-    system's block"""
-    import torch
-    wsb = workspace_bytes(sum(s[2] for s in systems), len(systems), max(s[3] for s in systems), *ws_args)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device="cuda:%d" % int(device))
-    return [from_block(b, s) for b, s in zip(call(ws.data_ptr(), wsb, stream), systems)]
-
-
-def summary_measure_dev(systems, q, device, stream, pass_elems=0):
-    """ONE ``mce_param_summary_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
-    columns, device address of w, device address of fs)] and the targets ``q`` -> one ``summary.measure`` dict per system"""
-    from . import _capi
-    nmax = max(s[2] for s in systems)
-    return _blocks_dev(lambda rows, nseg, dmax: _capi.param_summary_workspace_bytes(rows, nmax, nseg, dmax, len(q), pass_elems), (),
-                       lambda *a: _capi.param_summary_dev(systems, q, *a, pass_elems), lambda b, s: _summary.from_block(b, s[3], len(q)), systems, device, stream)
-
-
-def contours_measure_dev(systems, spec, device, stream):
-    """ONE ``mce_param_contours_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
-    columns, device address of w)] and ``spec`` = (probs, grid, scale, cols) -> one ``contours.measure`` dict per system"""
-    from . import _capi
-    probs, grid, scale, cols = spec
-    return _blocks_dev(_capi.param_contours_workspace_bytes, (len(cols), len(probs), grid), lambda *a: _capi.param_contours_dev(systems, cols, probs, grid, scale, *a),
-                       lambda b, s: _contours.from_block(b, len(cols), len(probs), grid), systems, device, stream)
-
-
-def marginals_measure_dev(systems, spec, device, stream):
-    """ONE ``mce_param_marginals_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured
-    columns, device address of w)] and ``spec`` = (probs, grid, scale) -> one ``marginals.measure`` dict per system"""
-    from . import _capi
-    probs, grid, scale = spec
-    return _blocks_dev(_capi.param_marginals_workspace_bytes, (len(probs), grid), lambda *a: _capi.param_marginals_dev(systems, probs, grid, scale, *a),
-                       lambda b, s: _marginals.from_block(b, s[3], len(probs), grid), systems, device, stream)
-
-
-def contours_bounded_measure_dev(systems, bounds, spec, device, stream):
-    """ONE ``mce_param_contours_bounded_dev`` call for ``systems`` (as ``contours_measure_dev`` takes them), ``bounds`` = one
-    (lo[nc], hi[nc]) of the chosen columns per system (``contours.bounds_spec``) and ``spec`` -> one ``contours.measure_bounded`` dict per
-    system"""
-    from . import _capi
-    probs, grid, scale, cols = spec
-    return _blocks_dev(_capi.param_contours_bounded_workspace_bytes, (len(cols), len(probs), grid),
-                       lambda *a: _capi.param_contours_bounded_dev(systems, cols, bounds, probs, grid, scale, *a),
-                       lambda b, s: _contours.from_block_bounded(b, len(cols), len(probs), grid), systems, device, stream)
-
-
-def marginals_bounded_measure_dev(systems, bounds, spec, device, stream):
-    """ONE ``mce_param_marginals_bounded_dev`` call for ``systems`` (as ``marginals_measure_dev`` takes them), ``bounds`` = one
-    (lo[d], hi[d]) per system (``marginals.bounds_spec``) and ``spec`` -> one ``marginals.measure_bounded`` dict per system"""
-    from . import _capi
-    probs, grid, scale = spec
-    return _blocks_dev(_capi.param_marginals_bounded_workspace_bytes, (len(probs), grid),
-                       lambda *a: _capi.param_marginals_bounded_dev(systems, bounds, probs, grid, scale, *a),
-                       lambda b, s: _marginals.from_block_bounded(b, s[3], len(probs), grid), systems, device, stream)
-
-
-def covariance_measure_dev(systems, device, stream):
-    """ONE ``mce_param_cov_dev`` call for ``systems`` = [(device address of the raw rows, row stride in doubles, rows, measured columns,
-    device address of w)] -> one ``covariance.measure`` dict per system"""
-    from . import _capi
-    return _blocks_dev(_capi.param_cov_workspace_bytes, (), lambda *a: _capi.param_cov_dev(systems, *a), lambda b, s: _covariance.from_block(b, s[3]), systems,
-                       device, stream)
-
-
 # ---- the jackknife of a chain that stays on the device (docs/design/jackknife_resident.md; this module and farm.py) -----------------
 def jack_spec(jackknife, nchains=None):
     """None, or dict(groups, by, G) of the ``jackknife`` keyword: G is the number of groups (None while ``by="chains"`` does not
@@ -373,6 +288,10 @@ def route_info(route, nparam, nd, nread, nsample):
             "Nsamples": ", ".join(str(x) for x in nsample), "route": route}
 
 
+#: the order ``ResidentChains.evidence`` resolves (and so validates) its statistics in; it measures them in ``posterior.STATS``' order
+_RESOLVED = ("information", "summary", "covariance", "marginals", "contours")
+
+
 class ResidentChains(object):
     """One or more chains on GPU ``device``, burned, concatenated and thinned there.
 
@@ -399,11 +318,8 @@ class ResidentChains(object):
         self.thin_corr = None
         spec = _chains.converge_spec(converge, converge_by)
         self.converge = None
-        self.information = None                            # (what the last evidence(information=True) found)
-        self.summary = None                                # (what the last evidence(summary=..) found)
-        self.marginals = None                              # (what the last evidence(marginals=..) found)
-        self.contours = None                               # (what the last evidence(contours=..) found)
-        self.covariance = None                             # (what the last evidence(covariance=..) found)
+        for st in _post.STATS:                             # (information, summary, marginals, contours, covariance:
+            setattr(self, st.key, None)                    #  what the last evidence(<key>=..) found)
         self.names_root = None                             # (the root whose .paramnames file names the parameters, where there is one)
         self.jackknife = None                              # (what the last evidence(jackknife=...) found,
         self.jackknife_block = None                        #  and its leave-one-group-out block: _capi.JACK_LEAVE_OUT_FIELDS per slot)
@@ -641,17 +557,9 @@ class ResidentChains(object):
         ``evidence_jackknife`` in ``info["jackknife"]`` (and ``self.jackknife``) -- after the usual feed, whose result is returned
         unchanged, the gathered rows are whitened on the device, ``mce_jack_groups_dev`` forms the group ids, the ladder runs on device
         tensors and ONE ``mce_jack_leave_out_dev`` call gives S_b, SumW_b and, with ``information``, the deleted sets' moments.
-        ``summary`` (None, True or up to 7 probabilities): the weighted means, standard deviations, equal-tailed limits and the best-fit
-        sample of the first ``ndim`` parameters in ``info["summary"]``, from one ``mce_param_summary_dev`` call on the gathered rows,
-        weights and fs -- BEFORE the feed and the jackknife ladder, while the rows are certainly raw (the ladder whitens them).
-        ``covariance`` (None or True): the weighted mean and covariance matrix of the first ``ndim`` parameters in ``info["covariance"]``,
-        from one ``mce_param_cov_dev`` call on the gathered rows and weights, made at the same place for the same reason.
-        ``marginals`` (None, True, probabilities or dict(probs, grid, scale)): the 1-D marginal densities, modes and HPD regions of the
-        first ``ndim`` parameters in ``info["marginals"]`` (and ``self.marginals``), from one ``mce_param_marginals_dev`` call there too.
-        ``contours`` (None, True, probabilities or dict(probs, grid, scale, params)): the 2-D joint densities, modes and credible levels
-        of the pairs of the chosen parameters in ``info["contours"]`` (and ``self.contours``), from one ``mce_param_contours_dev`` call
-        at the same place.  ``bounds`` (None, "ranges", a mapping name -> (lo, hi) or one (lo, hi) per parameter): the hard prior bounds
-        of the marginals (docs/design/marginals_bounds.md); then the one call is ``mce_param_marginals_bounded_dev``'s."""
+        ``summary``, ``marginals``, ``contours``, ``covariance`` and ``bounds``: the statistics of posterior.py
+        (docs/design/posterior_stats.md), each from ONE library call on the gathered rows and weights BEFORE the feed and the jackknife
+        ladder, while the rows are certainly raw (the ladder whitens them); in ``info[<key>]`` and ``self.<key>``."""
         from . import _capi
         from .evidence import HipBackend
         backend = backend or HipBackend()
@@ -663,18 +571,9 @@ class ResidentChains(object):
         if reason != RESIDENT:
             raise ResidentDecline(reason)
         jspec = jack_spec(jackknife, self.nchains)
-        probs = _summary.spec(summary)
-        want_cov = _covariance.spec(covariance) is not None
-        mspec = _marginals.spec(marginals)
-        _marginals.refuse_bounds(bounds, marginals, root=self.names_root, contours=contours)
-        bnd = None     # (bounds= without marginals= is here only where contours take it: refuse_bounds)
-        if mspec is not None:
-            bnd = _marginals.bounds_spec(bounds, names=_summary.param_names(self.names_root, nd), root=self.names_root, marginals=marginals)
-        if bnd is not None:
-            _marginals.note_contours(contours)
-        cnames = _summary.param_names(self.names_root, nd) if _contours.wanted(contours) else None
-        cspec = _contours.spec(contours, ndim=nd, names=cnames)
-        cbnd = _contours.bounds_spec(contours, names=cnames, ndim=nd, root=self.names_root, bounds=bounds)
+        values = dict(information=information, summary=summary, marginals=marginals, contours=contours, covariance=covariance, bounds=bounds)
+        names = _post.param_names(self.names_root, nd) if _post.carry(values) else None
+        reqs = {k: _post.BY_KEY[k].resolve(values, names, nd, self.names_root) for k in _RESOLVED}
         torch = self._torch
         ms = self.stats["ms"]
         with torch.cuda.device(self.device):
@@ -699,46 +598,24 @@ class ResidentChains(object):
             fs, (logLmax, SumW, nan_like, bad_w) = self._reduce(s1, pos_lnp)
             ms["reduce"] = _ms(t0)
             check_reduced(logLmax, SumW, nan_like, bad_w)
-            sblk = None
-            if probs is not None:
-                t0 = time.perf_counter()
-                sblk, = summary_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr(), fs.data_ptr())], _summary.targets(probs),
-                                            self.device, self._stream())
-                ms["summary"] = _ms(t0)
-            mblk = None
-            if mspec is not None:
-                t0 = time.perf_counter()
-                msys = [(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())]
-                if bnd is None:
-                    mblk, = marginals_measure_dev(msys, mspec, self.device, self._stream())
-                else:
-                    mblk, = marginals_bounded_measure_dev(msys, [bnd], mspec, self.device, self._stream())
-                ms["marginals"] = _ms(t0)
-            conblk = None
-            if cspec is not None:
-                t0 = time.perf_counter()
-                csys = [(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())]
-                if cbnd is None:
-                    conblk, = contours_measure_dev(csys, cspec, self.device, self._stream())
-                else:
-                    conblk, = contours_bounded_measure_dev(csys, [cbnd], cspec, self.device, self._stream())
-                ms["contours"] = _ms(t0)
-            cblk = None
-            if want_cov:
-                t0 = time.perf_counter()
-                cblk, = covariance_measure_dev([(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr())], self.device, self._stream())
-                ms["covariance"] = _ms(t0)
+            system = _post.System(s1["params"].data_ptr(), self.nparam, n1, nd, s1["w"].data_ptr(), fs.data_ptr())
+            blocks = {}
+
+            def measure(st):
+                if reqs[st.key] is not None:
+                    t0 = time.perf_counter()
+                    blocks[st.key], = st.measure_dev([system], [reqs[st.key]], self.device, self._stream())
+                    ms[st.key] = _ms(t0)
+            for st in _post.STATS[1:]:                 # (summary, marginals, contours, covariance: before the feed)
+                measure(st)
             t0 = time.perf_counter()
             with backend._scoped():
                 dotp, jac, _, _ = _capi.evidence_feed_part_dev(s1["params"].data_ptr(), n1, self.nparam, s2["params"].data_ptr() if cross else 0, n2,
                                                                self.nparam, nd, 0 if covtype == "all" else 1, kmax, s1["w"].data_ptr(), fs.data_ptr(),
                                                                0, 1, device=self.device, want_checksum=False)
             ms["feed"] = _ms(t0)
-            mom = None
-            if _information.wanted(information):
-                t0 = time.perf_counter()
-                mom, = moments_measure_dev([(fs.data_ptr(), s1["w"].data_ptr(), n1)], self.device, self._stream())
-                ms["information"] = _ms(t0)
+            measure(_post.INFORMATION)
+            mom = blocks.get("information")
             jrun = jblock = None
             if jspec is not None:
                 t0 = time.perf_counter()
@@ -747,11 +624,8 @@ class ResidentChains(object):
                 jblock, = jack_leave_out_dev([(s1["w"].data_ptr(), fs.data_ptr() if mom is not None else 0, gq, n1, jspec["G"])], self.device, self._stream())
                 ms["jackknife"] = _ms(t0)
         out = mle_from_sums(dotp, jac, SumW, logLmax, n1, kmax, math.log(priorvolume), cross)[1:]
-        self.information = None if mom is None else _information.build(mom, logLmax, out)
-        self.summary = None if sblk is None else _summary.build(sblk, probs, logLmax, _summary.param_names(self.names_root, nd))
-        self.marginals = None if mblk is None else _marginals.build(mblk, mspec, _summary.param_names(self.names_root, nd))
-        self.contours = None if conblk is None else _contours.build(conblk, cspec, cnames)
-        self.covariance = None if cblk is None else _covariance.build(cblk, _covariance.param_names(self.names_root, nd))
+        for st in _post.STATS:
+            setattr(self, st.key, st.build(blocks[st.key], reqs[st.key], names, logLmax, out) if st.key in blocks else None)
         self.jackknife_block = jblock
         self.jackknife = None if jrun is None else jack_result(jrun, jblock, jspec, SumW, logLmax, n1, kmax, math.log(priorvolume))
         if self.jackknife is not None and self.information is not None:
@@ -763,35 +637,16 @@ class ResidentChains(object):
             inf["thin_corr"] = self.thin_corr
         if self.converge is not None:
             inf["converge"] = self.converge
-        if self.information is not None:
-            inf["information"] = self.information
-        if self.jackknife is not None:
-            inf["jackknife"] = self.jackknife
-        if self.summary is not None:
-            inf["summary"] = self.summary
-        if self.marginals is not None:
-            inf["marginals"] = self.marginals
-        if self.contours is not None:
-            inf["contours"] = self.contours
-        if self.covariance is not None:
-            inf["covariance"] = self.covariance
+        for key, found in [("information", self.information), ("jackknife", self.jackknife)] + [(st.key, getattr(self, st.key)) for st in _post.STATS[1:]]:
+            if found is not None:
+                inf[key] = found
         return out, inf
 
 
 def log_information(inf):
-    """the information lines, then the summary lines, then the marginals lines, then the contours lines, before the ln(B) lines"""
-    if (inf or {}).get("information"):
-        for line in _information.lines(inf["information"]):
-            logger.info(line)
-    if (inf or {}).get("summary"):
-        for line in _summary.lines(inf["summary"]):
-            logger.info(line)
-    if (inf or {}).get("marginals"):
-        for line in _marginals.lines(inf["marginals"]):
-            logger.info(line)
-    if (inf or {}).get("contours"):
-        for line in _contours.lines(inf["contours"]):
-            logger.info(line)
+    """the lines of the statistics (information, summary, marginals, contours), before the ln(B) lines"""
+    for line in _post.log_lines(inf):
+        logger.info(line)
 
 
 _EVIDENCE_KEYS = ("rand", "info", "profile", "pvolume", "pos_lnp", "nproc", "prewhiten")
@@ -812,20 +667,15 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
     covtype = ctor.get("covtype", "all")               # (given: the call's covtype too; not given: evidence()'s default)
     covtype = "single" if covtype is None else covtype
     split = bool(ctor.get("split", False))
-    _information.refuse(ctor.get("information"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
-    _summary.refuse(ctor.get("summary"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
-    _marginals.refuse(ctor.get("marginals"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
-    _marginals.refuse_bounds(ctor.get("bounds"), ctor.get("marginals"), root=root if isinstance(root, str) else None, contours=ctor.get("contours"))
-    _contours.refuse(ctor.get("contours"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
-    _covariance.refuse(ctor.get("covariance"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
+    values = _post.values_of(ctor.get)                 # (the statistics' keywords and bounds)
+    _post.check(values, root=root if isinstance(root, str) else None, brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1), isfunc=ctor.get("isfunc"))
     reason = RESIDENT if _is_file_root(root) else REASONS["not_files"]
     if reason == RESIDENT:
         reason = plan(thinlen=ctor.get("thinlen", 0.0), isfunc=ctor.get("isfunc"), brange=ctor.get("brange"), nbatch=ctor.get("nbatch", 1),
                       verbose=max(ctor.get("verbose", 1), 2 if ctor.get("debug") else 0), covtype=covtype, split=split, ndim=None,
                       distributed=_distributed(), ischain=ctor.get("ischain", True), thin_corr=ctor.get("thin_corr"),
                       converge=ctor.get("converge"), converge_by=ctor.get("converge_by", "auto"), jackknife=ctor.get("jackknife"),
-                      summary=ctor.get("summary"), covariance=ctor.get("covariance"), marginals=ctor.get("marginals"),
-                      contours=ctor.get("contours"), bounds=ctor.get("bounds"))
+                      **{k: v for k, v in values.items() if k != "information"})
     if reason == RESIDENT:
         level = logging.INFO if ctor.get("verbose", 1) == 1 else logging.WARNING
         if not logging.getLogger().handlers:
@@ -842,9 +692,7 @@ def evidence_from_files(root, *, require_resident=False, **kwargs):
             pv = call.get("pvolume")
             got = rc.evidence(kmax=ctor.get("kmax", 5), ndim=ctor.get("ndim"), priorvolume=ctor.get("priorvolume", 1) if pv is None else pv,
                               covtype=covtype, pos_lnp=call.get("pos_lnp", False), split=split, s1frac=ctor.get("s1frac", 0.5), info=True,
-                              backend=ctor.get("backend"), information=ctor.get("information"), jackknife=ctor.get("jackknife"),
-                              summary=ctor.get("summary"), covariance=ctor.get("covariance"), marginals=ctor.get("marginals"),
-                              contours=ctor.get("contours"), bounds=ctor.get("bounds"))
+                              backend=ctor.get("backend"), jackknife=ctor.get("jackknife"), **values)
             mle, inf = got
             if ctor.get("verbose", 1) > 0:
                 log_information(inf)

@@ -275,10 +275,11 @@ def estimate(xa, a, xb, b, boost=1, bandwidth_scale=1.0, max_rows=MAX_ROWS, devi
         cov = _cov.measure(w, x)
     elif tensor:
         import torch
-        from .resident import covariance_measure_dev
+        from .posterior import COVARIANCE, Request, System
         x, w = x.contiguous(), w.contiguous()
         with torch.cuda.device(x.device):
-            cov = covariance_measure_dev([(x.data_ptr() if n else 0, d, n, d, w.data_ptr() if n else 0)], x.device.index, torch.cuda.current_stream().cuda_stream)[0]
+            cov = COVARIANCE.measure_dev([System(x.data_ptr() if n else 0, d, n, d, w.data_ptr() if n else 0, 0)], [Request(True, None)], x.device.index,
+                                         torch.cuda.current_stream().cuda_stream)[0]
     else:
         from . import _capi
         x, w = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)

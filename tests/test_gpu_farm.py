@@ -385,3 +385,50 @@ def test_one_handle_serves_every_call(small_roots):
     assert st2["waves"] == st1["waves"] + 1 and st3["waves"] == st1["waves"] + 2 and st3["files"] == st1["files"] + 2 * nfiles
     # no allocation per file or per wave: nothing since the first wave of this size
     assert st2["allocs"] == st1["allocs"] == st3["allocs"] and st2["allocs_wave"] == 0 and st3["allocs_wave"] == 0 and st3["grows"] == st1["grows"]
+
+
+# ------------------------------------------------------------------------------------------- 9. every statistic at once, mixed per root
+def mixed_roots(td):
+    """four roots of two files each, three parameters, 400 rows per file (integer weights); the second root has a .ranges file.  Returns
+    (roots, the farm's keywords: one entry per root for every statistic of posterior.py, the jackknife and the thinning)"""
+    from mcevidence_amd.synth import gaussian_chain
+    roots = []
+    for r in range(4):
+        chains = [gaussian_chain(seed=900 + 2 * r + c, n=400, d=3, weights="int", cov="corr") for c in range(2)]
+        lo = min(float(ch[:, 2].min()) for ch in chains) - 0.5
+        roots.append(os.path.join(str(td), "mixed%d" % r))
+        write_cosmomc_chains(roots[-1], chains, [("p0", lo, None), ("p1", -50.0, 50.0), ("p2", -50.0, None)] if r == 1 else None, fmt="%.17g")
+    m1 = {"probs": (0.9,), "grid": 64}
+    kw = dict(information=[True, True, None, True], summary=[(0.9,), True, None, None], marginals=[m1, {"grid": 128}, None, m1],
+              bounds=[None, "ranges", None, None], contours=[{"grid": 32}, None, None, {"grid": 32, "probs": (0.5,), "bounds": {"p1": (-40.0, None)}}],
+              covariance=[True, None, None, True], jackknife=[4, None, None, 4], thinlen=[0, 0, 0, 2])
+    return roots, kw
+
+
+def same_info(a, b):
+    """two info entries, bit for bit in every float (the route's name and the ladder's timings left out)"""
+    if isinstance(a, dict):
+        keys = set(a) - {"route", "kernel_ms"}
+        return isinstance(b, dict) and keys == set(b) - {"route", "kernel_ms"} and all(same_info(a[k], b[k]) for k in keys)
+    if isinstance(a, (str, bool, int, type(None))) or (isinstance(a, (list, tuple)) and any(isinstance(x, (str, tuple, list)) for x in a)):
+        return type(a) is type(b) and a == b
+    return same(a, b)
+
+
+def test_every_statistic_at_once_mixed_per_root_equals_the_per_root_resident_route(tmp_path):
+    roots, kw = mixed_roots(tmp_path)
+    got = farm.evidence_many_from_files(roots, kmax=3, info=True, **kw)
+    assert farm.LAST_STATS["counts"]["farm"] == len(roots) and farm.LAST_STATS["counts"]["fallback"] == 0
+    for i, (root, (lnE, info)) in enumerate(zip(roots, got)):
+        assert info["route"] == "farm"
+        one = {k: v[i] for k, v in kw.items() if v[i] is not None}
+        want_lnE, want = pkg.evidence_from_files(root, kmax=3, info=True, verbose=0, require_resident=True, **one)
+        assert want["route"] == "resident" and same(lnE, want_lnE)
+        assert set(info) & set(kw) == set(one) - {"bounds", "thinlen"} == set(want) & set(kw), (i, sorted(info))
+        assert same_info(info, want), (i, [k for k in info if k in want and not same_info(info[k], want[k])])
+        for key in ("marginals", "contours"):
+            if key in info:                              # (every column and pair measured: the comparison is of numbers, not of NaN)
+                assert info[key]["status"] == 0 and not np.any(info[key]["col_status"]) and not np.any(info[key].get("pair_status", 0))
+    assert got[1][1]["marginals"]["at_lo"][0] == 1.0 and got[1][1]["marginals"]["grid"] == 128 and "bound_lo" not in got[0][1]["marginals"]
+    assert got[3][1]["contours"]["bound_lo"][1] == -40.0 and "bound_lo" not in got[0][1]["contours"] and got[3][1]["Nsamples_read"] != 800
+    assert set(got[2][1]) & set(kw) == set() and "sigma" in got[0][1]["information"] and "sigma" not in got[1][1]["information"]

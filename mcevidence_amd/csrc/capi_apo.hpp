@@ -38,14 +38,9 @@ int pairs_once_plan(int64_t nr, int32_t d, int32_t kmax, Plan& p, bool quiet)
 // ranks against 17.4 / 8.7 / 4.4 for perfect shares).  So a block's panels are dealt to S independent chains, each with its own
 // list set (merged at the end; the chains share the row's published bound): S such that the rank has ~3 chains per slot, the
 // panels short enough that the longest block has two units per chain.  MCE_PAIRS_ONCE_SPLIT / MCE_PAIRS_ONCE_PANEL override.
-struct PairsOnceShape {
-    int nsplit = 1, panel = 0;
-    size_t off_d = 0, off_i = 0;      // list sets [nsplit][KCAP][nq_pad] (nsplit > 1: behind the plan's workspace and the reduction's scratch)
-    size_t total = 0;
-};
-PairsOnceShape pairs_once_shape(const Plan& p, int64_t nr, int32_t kmax, int32_t nparts)
+// -> S, the list sets [S][KCAP][nq_pad] (the rank's workspace is PairsOnceArena(p.sizes, dotp_ws_bytes(nr, kmax), S, ws)), and the panel length
+int pairs_once_shape(const Plan& p, int32_t nparts, int& panel)
 {
-    PairsOnceShape sh;
     const int nown = (p.nqblk + nparts - 1) / std::max(nparts, 1);
     // (the two overrides are read ONCE per process: the five entry points below derive the workspace layout from them again and again)
     const int env_split = env_pairs_once_split();
@@ -53,23 +48,9 @@ PairsOnceShape pairs_once_shape(const Plan& p, int64_t nr, int32_t kmax, int32_t
     int S = std::min(8, std::max(1, (1536 + nown - 1) / std::max(nown, 1)));
     if (env_split) S = env_split;
     const int def_panel = kSymPanelChunks[p.KST];
-    int panel = S > 1 ? (int)std::max<int64_t>(8, std::min<int64_t>(def_panel, p.nchunk / (2 * S))) : 0;
+    panel = S > 1 ? (int)std::max<int64_t>(8, std::min<int64_t>(def_panel, p.nchunk / (2 * S))) : 0;
     if (env_panel) panel = env_panel;
-    sh.nsplit = S;
-    sh.panel = panel;
-    size_t off = p.total + dotp_ws_bytes(nr, kmax);
-    if (S > 1) {
-        off = align_up(off, 256);
-        sh.off_d = off;
-        off = align_up(off + (size_t)S * p.KCAP * (size_t)p.nq_pad * sizeof(double), 256);
-        sh.off_i = off;
-        off = align_up(off + (size_t)S * p.KCAP * (size_t)p.nq_pad * sizeof(int), 256);
-    } else {
-        sh.off_d = p.off_pd;
-        sh.off_i = p.off_pi;
-    }
-    sh.total = off;
-    return sh;
+    return S;
 }
 // The four calls of one rank's share work on ONE workspace in a fixed order (prepare, sweep, export, finish) with the same
 // arguments; this table -- keyed by the workspace pointer, host memory, no device round trip -- records where a workspace
@@ -79,7 +60,7 @@ struct ApoCall { int64_t nr; int d, kmax, part, nparts, nsplit, panel, phase; };
 std::mutex g_apo_mutex;
 std::unordered_map<const void*, ApoCall> g_apo_calls;
 // phase_from <= recorded phase <= phase_to required (0: no record needed -- prepare); afterwards the record's phase is phase_set (-1: erased)
-int apo_step(const void* ws, int64_t nr, int d, int kmax, int part, int nparts, const PairsOnceShape& sh, int phase_from, int phase_to, int phase_set,
+int apo_step(const void* ws, int64_t nr, int d, int kmax, int part, int nparts, int nsplit, int panel, int phase_from, int phase_to, int phase_set,
              const char* what)
 {
     std::lock_guard<std::mutex> lk(g_apo_mutex);
@@ -88,7 +69,7 @@ int apo_step(const void* ws, int64_t nr, int d, int kmax, int part, int nparts, 
         if (it == g_apo_calls.end())
             return fail(MCE_ERR_INVALID, "pairs-once partition: %s on a workspace that mce_pairs_once_prepare_dev has not prepared", what);
         const ApoCall& c = it->second;
-        if (c.nr != nr || c.d != d || c.kmax != kmax || c.part != part || c.nparts != nparts || c.nsplit != sh.nsplit || c.panel != sh.panel)
+        if (c.nr != nr || c.d != d || c.kmax != kmax || c.part != part || c.nparts != nparts || c.nsplit != nsplit || c.panel != panel)
             return fail(MCE_ERR_INVALID, "pairs-once partition: %s with other arguments than the workspace was prepared with (prepared: nr=%lld d=%d kmax=%d part %d "
                         "of %d, %d chains, panel %d)", what, (long long)c.nr, c.d, c.kmax, c.part, c.nparts, c.nsplit, c.panel);
         if (c.phase < phase_from || c.phase > phase_to)
@@ -96,15 +77,15 @@ int apo_step(const void* ws, int64_t nr, int d, int kmax, int part, int nparts, 
                         what, c.phase);
     }
     if (phase_set < 0) { if (it != g_apo_calls.end()) g_apo_calls.erase(it); }
-    else g_apo_calls[ws] = ApoCall{nr, d, kmax, part, nparts, sh.nsplit, sh.panel, phase_set};
+    else g_apo_calls[ws] = ApoCall{nr, d, kmax, part, nparts, nsplit, panel, phase_set};
     return MCE_OK;
 }
 // The preamble of the four calls: the plan, the rank count against the blocks, the shape of the rank's share, the workspace, the
-// step's place in the sequence (apo_step); then the plan as the rank's share, whose list offsets point at the shape's list sets.
+// step's place in the sequence (apo_step); then the plan as the rank's share and its arena W, whose lists() are the share's list sets.
 // (export reports a bad rank count as "part r of W"; export and finish report a small workspace without the sizes)
 enum PairsOnceStep { kApoPrepare, kApoSweep, kApoExport, kApoFinish };
-int pairs_once_begin(PairsOnceStep step, const void* ws, size_t ws_bytes, int64_t nr, int32_t d, int32_t kmax, int32_t part, int32_t nparts, Plan& p,
-                     PairsOnceShape& sh)
+int pairs_once_begin(PairsOnceStep step, void* ws, size_t ws_bytes, int64_t nr, int32_t d, int32_t kmax, int32_t part, int32_t nparts, Plan& p,
+                     std::optional<mce::PairsOnceArena>& W)
 {
     static const struct { int from, to, set; const char* what; } kSteps[4] = {{0, 0, 1, "prepare"}, {1, 1, 2, "sweep"}, {2, 3, 3, "export"},
                                                                                {2, 3, -1, "finish"}};      // (export may be skipped by a rank with nothing to ship)
@@ -113,12 +94,14 @@ int pairs_once_begin(PairsOnceStep step, const void* ws, size_t ws_bytes, int64_
     if (nparts > p.nqblk || (step == kApoExport && nparts < 2))        // (the other three calls have refused nparts < 2 already)
         return step == kApoExport ? fail(MCE_ERR_INVALID, "part %d of %d", part, nparts)
                                   : fail(MCE_ERR_INVALID, "pairs-once partition: %d ranks for %d blocks", nparts, p.nqblk);
-    sh = pairs_once_shape(p, nr, kmax, nparts);
-    if (ws_bytes < sh.total)
-        return step >= kApoExport ? fail(MCE_ERR_WORKSPACE, "workspace too small") : fail(MCE_ERR_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, sh.total);
-    rc = apo_step(ws, nr, d, kmax, part, nparts, sh, kSteps[step].from, kSteps[step].to, kSteps[step].set, kSteps[step].what);
+    int panel = 0;
+    const int S = pairs_once_shape(p, nparts, panel);
+    W.emplace(p.sizes, dotp_ws_bytes(nr, kmax), S, ws);
+    if (ws_bytes < W->total)
+        return step >= kApoExport ? fail(MCE_ERR_WORKSPACE, "workspace too small") : fail(MCE_ERR_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, W->total);
+    rc = apo_step(ws, nr, d, kmax, part, nparts, S, panel, kSteps[step].from, kSteps[step].to, kSteps[step].set, kSteps[step].what);
     if (rc != MCE_OK) return rc;
-    p.apo = true; p.apo_nsplit = sh.nsplit; p.apo_panel = sh.panel; p.off_pd = sh.off_d; p.off_pi = sh.off_i;
+    p.apo = true; p.apo_nsplit = S; p.apo_panel = panel;
     p.part = part; p.nparts = nparts;
     return MCE_OK;
 }
@@ -176,7 +159,8 @@ size_t mce_pairs_once_workspace_bytes(int64_t nr, int32_t d, int32_t kmax, int32
 {
     Plan p;
     if (nparts < 2 || pairs_once_plan(nr, d, kmax, p, true) != MCE_OK) return 0;
-    return pairs_once_shape(p, nr, kmax, nparts).total;
+    int panel = 0;
+    return mce::PairsOnceArena(p.sizes, dotp_ws_bytes(nr, kmax), pairs_once_shape(p, nparts, panel)).total;
 }
 
 int mce_pairs_once_prepare_dev(const double* dY, int64_t nr, int32_t d, int32_t kmax, int32_t part, int32_t nparts, size_t* bounds_offset,
@@ -185,29 +169,28 @@ int mce_pairs_once_prepare_dev(const double* dY, int64_t nr, int32_t d, int32_t 
     if (!dY || !ws || !bounds_offset || !bounds_count) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (nparts < 2 || part < 0 || part >= nparts) return fail(MCE_ERR_INVALID, "part %d of %d (the pairs-once partition needs two ranks or more)", part, nparts);
     Plan p;
-    PairsOnceShape sh;
-    int rc = pairs_once_begin(kApoPrepare, ws, ws_bytes, nr, d, kmax, part, nparts, p, sh);
+    std::optional<mce::PairsOnceArena> W;
+    int rc = pairs_once_begin(kApoPrepare, ws, ws_bytes, nr, d, kmax, part, nparts, p, W);
     if (rc != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* wsc = static_cast<char*>(ws);
+    const mce::SearchArena& A = W->A;
     p.apo_phase = 1;
     // every row's bound starts at +inf, every slot empty; the prepass below fills in the rows of this rank's blocks
     const unsigned long long inf_bits = 0x7FF0000000000000ull;
-    hipLaunchKernelGGL(pairs_once_fill_kernel, dim3(1024), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(wsc + p.off_sym + p.sl.thr), p.nq_pad, inf_bits);
+    hipLaunchKernelGGL(pairs_once_fill_kernel, dim3(1024), dim3(256), 0, st, A.sym.thr, p.nq_pad, inf_bits);
     MCE_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pairs_once_fill_kernel, dim3(2048), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(wsc + p.off_sym + p.sl.slots),
-                       p.nq_pad * (int64_t)p.KCAP, inf_bits);
+    hipLaunchKernelGGL(pairs_once_fill_kernel, dim3(2048), dim3(256), 0, st, A.sym.slots, p.nq_pad * (int64_t)p.KCAP, inf_bits);
     MCE_HIP(hipGetLastError());
-    if (sh.nsplit > 1) {
+    if (W->S > 1) {
         static_assert(mce::f16_qpb(4) == 512, "one workgroup per block of list columns");
         hipLaunchKernelGGL(mce::sym_chain_init_kernel, dim3((unsigned)mce::apo_rank_count(p.nqblk, part, nparts)), dim3(512), 0, st,
-                           reinterpret_cast<double*>(wsc + sh.off_d), reinterpret_cast<int*>(wsc + sh.off_i), p.nq_pad, p.KCAP, sh.nsplit, (int)part, (int)nparts);
+                           W->lists().d, W->lists().i, p.nq_pad, p.KCAP, W->S, (int)part, (int)nparts);
         MCE_HIP(hipGetLastError());
     }
     SameSetHint hint(true);
-    rc = run_search(p, dY, nr, dY, nr, d, kmax - 1, MCE_SELF_EXCLUDE, 0, wsc, st);
+    rc = run_search(p, dY, nr, dY, nr, d, kmax - 1, MCE_SELF_EXCLUDE, 0, A, W->lists(), st);
     if (rc != MCE_OK) return rc;
-    *bounds_offset = p.off_sym + p.sl.thr;
+    *bounds_offset = (size_t)((char*)A.sym.thr - (char*)ws);
     *bounds_count = p.nq_pad;
     return MCE_OK;
 }
@@ -218,21 +201,21 @@ int mce_pairs_once_sweep_dev(const double* dY, int64_t nr, int32_t d, int32_t km
     if (!dY || !d_counts || !d_flags || !ws) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (nparts < 2 || part < 0 || part >= nparts) return fail(MCE_ERR_INVALID, "part %d of %d (the pairs-once partition needs two ranks or more)", part, nparts);
     Plan p;
-    PairsOnceShape sh;
-    int rc = pairs_once_begin(kApoSweep, ws, ws_bytes, nr, d, kmax, part, nparts, p, sh);
+    std::optional<mce::PairsOnceArena> W;
+    int rc = pairs_once_begin(kApoSweep, ws, ws_bytes, nr, d, kmax, part, nparts, p, W);
     if (rc != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* wsc = static_cast<char*>(ws);
+    const mce::SearchArena& A = W->A;
     p.apo_phase = 2;
-    const mce::KnnF16Args a = sym_args(p, wsc, nr, d, kmax - 1, 1);
+    const mce::KnnF16Args a = sym_args(p, A, W->lists(), nr, d, kmax - 1, 1);
     // the bounds are everybody's now (MIN over the ranks): the row-side gate constants follow from them
     hipLaunchKernelGGL(pairs_once_row_gates_kernel, dim3((unsigned)(p.nq_pad / 256)), dim3(256), 0, st, a.sym.thr, a.sym.rrow, a.sym.rtile, a.qinfo, a.params, nr, p.KST);
     MCE_HIP(hipGetLastError());
     SameSetHint hint(true);
-    rc = run_search(p, dY, nr, dY, nr, d, kmax - 1, MCE_SELF_EXCLUDE, 0, wsc, st);
+    rc = run_search(p, dY, nr, dY, nr, d, kmax - 1, MCE_SELF_EXCLUDE, 0, A, W->lists(), st);
     if (rc != MCE_OK) return rc;
     if (!p.sym_active) return fail(MCE_ERR_INVALID, "pairs-once partition: the sweep did not run");
-    int* offs = reinterpret_cast<int*>(wsc + p.off_sym + p.sl.keys_a);     // [nqblk + 1] offsets + 1 error word (the sort's keys: n_pad words, free by now)
+    int* offs = reinterpret_cast<int*>(A.sym.keys_a);     // [nqblk + 1] offsets + 1 error word (the sort's keys: n_pad words, free by now)
     static_assert(sizeof(long long) == sizeof(int64_t), "counts");
     hipLaunchKernelGGL(mce::apo_offsets_kernel, dim3(1), dim3(mce::kApoScanThreads), 0, st, a.sym.bucket_cnt, a.sym.bucket_flag, a.sym.cap, p.nqblk, (int)part,
                        (int)nparts, offs, reinterpret_cast<long long*>(d_counts), d_flags);
@@ -244,14 +227,13 @@ int mce_pairs_once_export_dev(int64_t nr, int32_t d, int32_t kmax, int32_t part,
 {
     if (!ws) return fail(MCE_ERR_INVALID, "null pointer argument");
     Plan p;
-    PairsOnceShape sh;
-    const int rc = pairs_once_begin(kApoExport, ws, ws_bytes, nr, d, kmax, part, nparts, p, sh);
+    std::optional<mce::PairsOnceArena> W;
+    const int rc = pairs_once_begin(kApoExport, ws, ws_bytes, nr, d, kmax, part, nparts, p, W);
     if (rc != MCE_OK) return rc;
     if (!d_send) return MCE_OK;           // (nothing to ship)
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* wsc = static_cast<char*>(ws);
-    const mce::KnnF16Args a = sym_args(p, wsc, nr, d, kmax - 1, 1);
-    const int* offs = reinterpret_cast<const int*>(wsc + p.off_sym + p.sl.keys_a);
+    const mce::KnnF16Args a = sym_args(p, W->A, W->lists(), nr, d, kmax - 1, 1);
+    const int* offs = reinterpret_cast<const int*>(W->A.sym.keys_a);
     hipLaunchKernelGGL(mce::apo_export_kernel, dim3((unsigned)p.nqblk), dim3(256), 0, st, a.sym.bucket, offs, a.sym.cap, p.nqblk, (int)nparts,
                        static_cast<mce::SymEntry*>(d_send));
     MCE_HIP(hipGetLastError());
@@ -265,15 +247,15 @@ int mce_pairs_once_finish_dev(const double* dY, int64_t nr, int32_t d, int32_t k
     if (!dY || !d_w || !d_fs || !d_dotp || !d_flags || !ws || (nrecv > 0 && !d_recv)) return fail(MCE_ERR_INVALID, "null pointer argument");
     if (nparts < 2 || part < 0 || part >= nparts || nrecv < 0) return fail(MCE_ERR_INVALID, "part %d of %d, %lld entries", part, nparts, (long long)nrecv);
     Plan p;
-    PairsOnceShape sh;
-    int rc = pairs_once_begin(kApoFinish, ws, ws_bytes, nr, d, kmax, part, nparts, p, sh);
+    std::optional<mce::PairsOnceArena> W;
+    int rc = pairs_once_begin(kApoFinish, ws, ws_bytes, nr, d, kmax, part, nparts, p, W);
     if (rc != MCE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* wsc = static_cast<char*>(ws);
+    const mce::SearchArena& A = W->A;
     const int K = kmax - 1;
-    mce::KnnF16Args a = sym_args(p, wsc, nr, d, K, 1);
+    mce::KnnF16Args a = sym_args(p, A, W->lists(), nr, d, K, 1);
     const int nown = mce::apo_rank_count(p.nqblk, part, nparts);          // this rank's blocks: part, part + nparts, ...
-    int* err = reinterpret_cast<int*>(wsc + p.off_sym + p.sl.keys_a) + p.nqblk + 1;
+    int* err = reinterpret_cast<int*>(A.sym.keys_a) + p.nqblk + 1;
     MCE_HIP(mce::zero_async(err, sizeof(int), st));
     const int qpb = mce::f16_qpb(p.KCAP);
     if (nrecv > 0) {
@@ -288,17 +270,17 @@ int mce_pairs_once_finish_dev(const double* dY, int64_t nr, int32_t d, int32_t k
     MCE_HIP(hipGetLastError());
     a.seed_cfg = 0;
     MCE_HIP(p.vh->launch_sym_repair(a, st));         // own blocks whose bucket overflowed here or elsewhere, or whose units gave up waiting
-    if (sh.nsplit > 1 && nown > 0) {
-        hipLaunchKernelGGL(mce::sym_chain_clear_kernel, dim3((unsigned)nown), dim3(512), 0, st, a.sym.bucket_flag, a.part_d, a.part_i, p.nq_pad, p.KCAP, sh.nsplit, (int)part, (int)nparts);
+    if (W->S > 1 && nown > 0) {
+        hipLaunchKernelGGL(mce::sym_chain_clear_kernel, dim3((unsigned)nown), dim3(512), 0, st, a.sym.bucket_flag, a.part_d, a.part_i, p.nq_pad, p.KCAP, W->S, (int)part, (int)nparts);
         MCE_HIP(hipGetLastError());
     }
     MCE_HIP(launch_sym_merge(p.KCAP, a.part_d, a.part_i, p.nq_pad, a.sym, part, p.nqblk, st, nparts));      // (into list set 0)
     // the reduction enumerates every nparts-th block of list columns through a block table (reduce_kernels.hpp: border): the identity
     hipLaunchKernelGGL(mce::apo_iota_kernel, dim3((unsigned)((p.nqblk + 255) / 256)), dim3(256), 0, st, a.sym.done, p.nqblk);
     MCE_HIP(hipGetLastError());
-    p.sym_qb_lo = 0; p.sym_qb_hi = p.nqblk; p.sym_active = true; p.L = sh.nsplit;
-    double* partial = reinterpret_cast<double*>(wsc + p.total);
-    rc = launch_merge(p, false, true, dY, dY, nr, d, K, MCE_SELF_EXCLUDE, 0, nullptr, nullptr, 1, (int)kmax, d_w, d_fs, partial, wsc, st);
+    p.sym_qb_lo = 0; p.sym_qb_hi = p.nqblk; p.sym_active = true; p.L = W->S;
+    double* const partial = W->partial;
+    rc = launch_merge(p, false, true, dY, dY, nr, d, K, MCE_SELF_EXCLUDE, 0, nullptr, nullptr, 1, (int)kmax, d_w, d_fs, partial, A, W->lists(), st);
     if (rc != MCE_OK) return rc;
     rc = finish_dotp(partial, (int64_t)nown * qpb, 1, kmax, d_dotp, st);
     if (rc != MCE_OK) return rc;

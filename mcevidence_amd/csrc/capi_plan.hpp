@@ -50,10 +50,8 @@ struct Plan {
     const mce::KnnDeepVariant* vd = nullptr;  // non-null: the DEEP fp16 filter (knn_deep.hpp: 64 <= d <= 127, K <= 32); vh and v are null then
     bool filter() const { return vh != nullptr || vd != nullptr; }      // exact lists behind an fp16 filter (no refine in the merge; certified by default)
     const mce::KnnLongVariant* vl = nullptr;  // non-null: the long-row fp64 sweep (knn_long.hpp: 128 <= d <= 1024, K <= 32); KS = its padded k-steps
-    size_t off_xf = 0, off_xn = 0;            // ... its packed queries and their squared norms
     bool generic = false;                     // plain exact kernel (K > 32, or d > 127 with the long-row sweep turned off)
     int KST = 0;
-    size_t off_yh = 0, off_xh = 0, off_qinfo = 0, off_params = 0;
     int KS = 0, KCAP = 0, QT = 0, CT = 0;
     int64_t nchunk = 0;      // reference chunks (CT tiles of 16 rows)
     int64_t nrow_pad = 0;    // padded reference rows
@@ -61,7 +59,8 @@ struct Plan {
     int64_t nq_pad = 0;
     int rsplit = 1;
     int L = 4;
-    size_t off_yf = 0, off_pd = 0, off_pi = 0, off_center = 0, off_msum = 0, total = 0;
+    mce::SearchSizes sizes;                   // what the workspace holds, as numbers (plan_sizes): the workspace is SearchArena(sizes, ws)
+    size_t total = 0;                         // ... and its bytes, SearchArena(sizes).total
     double cost = 0.0;                        // the split model's estimate for this plan (cycles per SIMD; exhaustive kernels)
     int ksel = 0;                             // fp64 sweep: entries kept per list -- K + kRefineMargin (capped at MCE_MAX_K): the lists are chosen on
                                               // GEMM-form keys, the final K among them on EXACT distances (reduce_kernels.hpp, REFINE); 0: K
@@ -79,14 +78,8 @@ struct Plan {
     int apo_nsplit = 1;                       // ... with this many independent chains (list sets) per block, and
     int apo_panel = 0;                        // ... panels of this many chunks (0: the default length)
     int64_t pl_nr = 0;                        // reference rows the plan was made for
-    mce::PruneLayout pl;
-    size_t off_prune = 0;
-    size_t off_heavy = 0;                     // pruned walk over one set: side lists of the heavy waves' extra sub-waves (knn_f16.hpp)
-    int heavy_max = 0;                        // ... room for this many waves at kPruneHeavyMaxSplit sub-waves
     bool sym = false;                         // workspace holds the symmetric sweep's scratch (run_search decides: X and Y must be one buffer)
     bool sym_active = false;                  // set by run_search: the lists are in sorted-row order, one split
-    mce::SymLayout sl;
-    size_t off_sym = 0;
     int sym_nsplit = 1;                       // symmetric sweep on one GPU: chains (list sets) per block, and
     int sym_panel = 0;                        // ... chunks per panel when that shortens them (0: the default length)
 };
@@ -103,8 +96,6 @@ const mce::KnnVariant* variant_for(int KS, int kcap_idx)
     }
 }
 
-// Validates (nq, nr, d, K, self_mode) and lays out the workspace.  Pure function of its
-// arguments so mce_knn_workspace_bytes() and the launcher always agree.
 // Seed phase of the exhaustive fp16 sweep for splits of (at least) `cps` chunks: chunks | group tiles << 16, 0 = none
 // (knn_f16.hpp: f16_seed_cfg).  MCE_F16_SEED_ROWS / MCE_F16_SEED_SHARE / MCE_F16_SEED_TG override (tests, tuning).
 // Small splits: a quarter of the chunks (then half) in smaller groups, as long as they hold twice the K groups a bound
@@ -143,7 +134,19 @@ double split_cost(const Plan& p, bool filt, int64_t nr, int32_t K, int r)
     return rounds * block;
 }
 
-int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, Plan& p)
+// ---- make_plan, step by step.  Pure functions of the sizes, the modes in force on this thread and the planner hints, so that
+// mce_knn_workspace_bytes() and the launcher always agree. ----
+// what the steps of one make_plan hand on to each other
+struct PlanShape {
+    int64_t nq, nr;
+    int32_t d, K;
+    bool wide_f64 = false;                    // 64 <= d <= 127, K <= 32: the fp64 sweep's wide form, or the deep filter
+    bool f16 = false, deep = false, filt = false;     // fp16 filter, deep fp16 filter, either: fp16 operands in the workspace, 32-row tiles, 512-query blocks
+    int64_t rows_per_chunk = 0;               // of the exhaustive sweep (the pruned walk's chunks are its own)
+    int rmin = 1;                             // fewest reference splits the kernel family allows
+};
+
+int plan_check_args(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode)
 {
     if (nq < 0 || nr < 1 || d < 1 || K < 1) return fail(MCE_ERR_INVALID, "invalid sizes nq=%lld nr=%lld d=%d K=%d", (long long)nq, (long long)nr, d, K);
     if (self_mode < 0 || self_mode > 2) return fail(MCE_ERR_INVALID, "invalid self_mode %d", self_mode);
@@ -153,96 +156,119 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
     if (K > usable)   // sklearn raises ValueError("Expected n_neighbors <= n_samples_fit")
         return fail(MCE_ERR_K_RANGE, "Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %lld", K, (long long)usable);
     if (nr >= (int64_t)1 << 31) return fail(MCE_ERR_INVALID, "nr=%lld exceeds 2^31-1 reference rows", (long long)nr);
+    return MCE_OK;
+}
 
-    // 64 <= d <= 127 (round 5): the fp64 MFMA sweep at KS = 20..32, one query tile per wave -- the vector-FMA kernel below was
-    // 66x the time of d = 63 at 100 k rows (knn_generic.hpp); it keeps d > 127 and K > 32
-    const bool wide_f64 = d > MCE_MAX_DIM && d <= mce::kWideMaxDim && K <= MCE_MAX_K;
-    // 128 <= d <= 1024 (round 6): the fp64 MFMA sweep with the k dimension in blocks (knn_long.hpp) -- the vector-FMA kernel below ran
-    // these at 0.12 of the fp64 vector peak; it keeps K > 32.  (MCE_LONG=0: comparisons.)
-    if (env_long_on() && d >= mce::kLongMinDim && d <= mce::kLongMaxDim && K <= MCE_MAX_K) {
-        p.ksel = std::min<int>(K + kRefineMargin, MCE_MAX_K);          // (GEMM-form keys: the merge picks the K on exact distances)
-        p.vl = &mce::g_knn_long[p.ksel <= 8 ? 0 : (p.ksel <= 16 ? 1 : 2)];
-        p.v = nullptr;
-        p.vh = nullptr;
-        p.KCAP = p.vl->kcap;
-        p.CT = p.vl->ct;
-        p.QT = mce::kLongQT;
-        p.KS = mce::long_ksp(d);
-        p.nqblk = (int)std::max<int64_t>(1, (nq + mce::kLongQPB - 1) / mce::kLongQPB);
-        p.nq_pad = (int64_t)p.nqblk * mce::kLongQPB;
-        const int64_t rows_per_chunk = (int64_t)p.CT * 16;
-        p.nchunk = (nr + rows_per_chunk - 1) / rows_per_chunk;
-        p.nrow_pad = p.nchunk * rows_per_chunk;
-        // reference splits: fill the chip (one 512-thread workgroup per CU) and trim the last partial round; every split re-pays a
-        // list warm-up of a few chunks' worth of insertions
-        int best_r = 1;
-        double best_c = 1e300;
-        const int rmax = (int)std::min<int64_t>(mce::kMaxLists, p.nchunk);
-        for (int r = 1; r <= rmax; ++r) {
-            const double c = std::ceil((double)p.nqblk * r / kAssumedCUs) * (std::ceil((double)p.nchunk / r) + 16.0);
-            if (c < best_c * 0.98) { best_c = c; best_r = r; }
+// The plan's workspace as numbers (search_layout.hpp: SearchArena places them) and its bytes.  Called again for every split count
+// the t_plan_cap loop tries.
+void plan_sizes(Plan& p, const PlanShape& s)
+{
+    mce::SearchSizes& z = p.sizes;
+    z = mce::SearchSizes();
+    z.family = p.vl ? mce::SearchFamily::long_rows : p.generic ? mce::SearchFamily::generic : p.filter() ? mce::SearchFamily::filter : mce::SearchFamily::sweep64;
+    z.nq = s.nq; z.nr = s.nr; z.nq_pad = p.nq_pad; z.nrow_pad = p.nrow_pad; z.nchunk = p.nchunk; z.nqblk = p.nqblk;
+    z.d = s.d; z.K = s.K; z.KS = p.KS; z.KST = p.KST; z.KCAP = p.KCAP;
+    if (p.vl) {
+        z.list_sets = p.L;
+        z.center_doubles = (size_t)(s.d + 4);
+        z.msum_doubles = (size_t)mce::kLongMeanBlocks * (size_t)s.d;
+    } else if (p.generic) {
+        z.list_sets = 1;                      // lists [1][K][nq_pad]
+    } else {
+        p.L = p.twopass ? 2 * p.rsplit : p.rsplit;
+        z.list_sets = std::max(p.L, p.sym_nsplit);
+        z.center_doubles = (size_t)3 * mce::kMaxDimPad;         // centre | box(Y) | box(X)
+        z.msum_doubles = (size_t)mce::kMeanBlocks * mce::kStatStride;
+        z.params_doubles = mce::HP_COUNT;
+    }
+    if (p.prune) {
+        p.pl_nr = s.nr;
+        z.prune = true;
+        z.prune_tmp_bytes = mce::prune_tmp_bytes(std::max(p.nq_pad, p.nrow_pad), (size_t)p.nqblk * mce::kPruneWavesPerBlock);
+        if (s.nq == s.nr && p.nqblk >= kPruneHeavyMinBlocks && prune_heavy_enabled()) {
+            z.heavy_max = std::max(p.nqblk * mce::kHWaves / kPruneHeavyMaxShare, kPruneHeavyMinCount);       // waves, at kPruneHeavyMaxSplit sub-waves (knn_f16.hpp)
+            z.heavy_cols = kPruneWaveQueries * (kPruneHeavyMaxSplit - 1);
         }
-        p.rsplit = best_r;
-        p.L = p.rsplit;
-        p.cost = best_c;
-        p.pl_nr = nr;
-        size_t off = 0;
-        p.off_pd = off;
-        off = align_up(off + (size_t)p.L * p.KCAP * (size_t)p.nq_pad * sizeof(double), 256);
-        p.off_pi = off;
-        off = align_up(off + (size_t)p.L * p.KCAP * (size_t)p.nq_pad * sizeof(int), 256);
-        p.off_center = off;
-        off = align_up(off + (size_t)(d + 4) * sizeof(double), 256);
-        p.off_msum = off;
-        off = align_up(off + (size_t)mce::kLongMeanBlocks * (size_t)d * sizeof(double), 256);
-        p.off_yf = off;
-        off = align_up(off + (size_t)p.nrow_pad * (size_t)p.KS * 4 * sizeof(double), 256);
-        p.off_xf = off;
-        off = align_up(off + (size_t)p.nq_pad * (size_t)p.KS * 4 * sizeof(double), 256);
-        p.off_xn = off;
-        off = align_up(off + (size_t)p.nq_pad * sizeof(double), 256);
-        p.total = off + 256;
-        return MCE_OK;
     }
-    if ((d > MCE_MAX_DIM && !wide_f64) || K > MCE_MAX_K) {
-        // outside the MFMA kernels' register budgets: plain exact kernel, lists [1][K][nq_pad]
-        p.generic = true;
-        p.v = nullptr;
-        p.vh = nullptr;
-        p.KCAP = K;
-        p.rsplit = 1;
-        p.L = 1;
-        p.nqblk = (int)std::max<int64_t>(1, (nq + mce::kGenThreads - 1) / mce::kGenThreads);
-        p.nq_pad = (int64_t)p.nqblk * mce::kGenThreads;
-        size_t off = 0;
-        p.off_pd = off;
-        off = align_up(off + (size_t)K * (size_t)p.nq_pad * sizeof(double), 256);
-        p.off_pi = off;
-        off = align_up(off + (size_t)K * (size_t)p.nq_pad * sizeof(int), 256);
-        p.off_center = off;      // (generic plans: scratch for the distance matrix of the fused path)
-        off = align_up(off + (size_t)nq * K * sizeof(double), 256);
-        p.off_msum = off;
-        p.total = off + 256;
-        return MCE_OK;
+    if (p.sym) {
+        z.sym = true;
+        z.sym_cap = sym_bucket_per_row(std::min<int>(s.K, p.KCAP)) * mce::f16_qpb(p.KCAP);      // (two passes: each fills lists of KCAP)
+        z.sym_tmp_bytes = mce::sym_tmp_bytes(p.nq_pad);
     }
+    p.total = mce::SearchArena(z).total;
+}
+
+// 128 <= d <= 1024 (round 6): the fp64 MFMA sweep with the k dimension in blocks (knn_long.hpp) -- the vector-FMA kernel ran
+// these at 0.12 of the fp64 vector peak; it keeps K > 32.  (MCE_LONG=0: comparisons.)
+void plan_long(Plan& p, const PlanShape& s)
+{
+    p.ksel = std::min<int>(s.K + kRefineMargin, MCE_MAX_K);          // (GEMM-form keys: the merge picks the K on exact distances)
+    p.vl = &mce::g_knn_long[p.ksel <= 8 ? 0 : (p.ksel <= 16 ? 1 : 2)];
+    p.v = nullptr;
+    p.vh = nullptr;
+    p.KCAP = p.vl->kcap;
+    p.CT = p.vl->ct;
+    p.QT = mce::kLongQT;
+    p.KS = mce::long_ksp(s.d);
+    p.nqblk = (int)std::max<int64_t>(1, (s.nq + mce::kLongQPB - 1) / mce::kLongQPB);
+    p.nq_pad = (int64_t)p.nqblk * mce::kLongQPB;
+    const int64_t rows_per_chunk = (int64_t)p.CT * 16;
+    p.nchunk = (s.nr + rows_per_chunk - 1) / rows_per_chunk;
+    p.nrow_pad = p.nchunk * rows_per_chunk;
+    // reference splits: fill the chip (one 512-thread workgroup per CU) and trim the last partial round; every split re-pays a
+    // list warm-up of a few chunks' worth of insertions
+    int best_r = 1;
+    double best_c = 1e300;
+    const int rmax = (int)std::min<int64_t>(mce::kMaxLists, p.nchunk);
+    for (int r = 1; r <= rmax; ++r) {
+        const double c = std::ceil((double)p.nqblk * r / kAssumedCUs) * (std::ceil((double)p.nchunk / r) + 16.0);
+        if (c < best_c * 0.98) { best_c = c; best_r = r; }
+    }
+    p.rsplit = best_r;
+    p.L = p.rsplit;
+    p.cost = best_c;
+    p.pl_nr = s.nr;
+    plan_sizes(p, s);
+}
+
+// outside the MFMA kernels' register budgets: plain exact kernel, lists [1][K][nq_pad]
+void plan_generic(Plan& p, const PlanShape& s)
+{
+    p.generic = true;
+    p.v = nullptr;
+    p.vh = nullptr;
+    p.KCAP = s.K;
+    p.rsplit = 1;
+    p.L = 1;
+    p.nqblk = (int)std::max<int64_t>(1, (s.nq + mce::kGenThreads - 1) / mce::kGenThreads);
+    p.nq_pad = (int64_t)p.nqblk * mce::kGenThreads;
+    plan_sizes(p, s);
+}
+
+// d <= 127, K <= 32: the fp64 sweep, the fp16 filter or the deep fp16 filter -- the kernel variant, the list capacity (one pass or
+// two), the tile geometry and the padded counts
+void plan_sweep_family(Plan& p, PlanShape& s)
+{
+    const int64_t nq = s.nq, nr = s.nr;
+    const int32_t d = s.d, K = s.K;
     p.KS = mce::mfma_ks_for(d);
     int ki = 0;
     while (ki < mce::kNumKcap - 1 && mce::kKcapList[ki] < K) ++ki;
     p.KCAP = mce::kKcapList[ki];
-    const bool f16 = !wide_f64 && (eff_search_mode() != 1) && mce::f16_supported(d, K);
+    s.f16 = !s.wide_f64 && (eff_search_mode() != 1) && mce::f16_supported(d, K);
     // 64 <= d <= 127 (round 6): the fp16 filter with 5, 6 or 8 k-steps (knn_deep.hpp), K <= 32 (beyond 16 in two passes); search mode 1
     // keeps the fp64 sweep's wide form.  (MCE_DEEP=0: comparisons.)
-    const bool deep = wide_f64 && (eff_search_mode() != 1) && mce::deep_supported(d, K) && env_deep_on();
-    const bool filt = f16 || deep;          // fp16 operands in the workspace, 32-row tiles, 512-query blocks
+    s.deep = s.wide_f64 && (eff_search_mode() != 1) && mce::deep_supported(d, K) && env_deep_on();
+    s.filt = s.f16 || s.deep;
     p.vd = nullptr;
     int qpb, rows_per_tile;
-    if (filt) {
+    if (s.filt) {
         if (K > 16) {                          // 16 nearest per reference split first, then the next K - 16 beyond them (LOWER)
             p.twopass = true;
             ki = 3;
             p.KCAP = 16;
         }
-        if (deep) {
+        if (s.deep) {
             p.KST = mce::deep_ksteps(d);
             p.vd = &by_kcap(ki, mce::g_knn_deep_kcap4, mce::g_knn_deep_kcap8, mce::g_knn_deep_kcap12, mce::g_knn_deep_kcap16)[p.KST == 5 ? 0 : (p.KST == 6 ? 1 : 2)];
             p.vh = nullptr;
@@ -280,48 +306,56 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
     // QTT = 4: C4 41.5 -> 37.7 ms).  From kWideMinBlocks blocks: the chip then still gets about a full round of the wider workgroups
     // (C2's 196 blocks would leave 60 % of the CUs idle).  Decided on the sizes alone, so that the workspace query and the call
     // agree; which sweep runs (pruned walk, symmetric, exhaustive) is settled later -- only the exhaustive one has a wide form.
-    p.wide_ok = f16 && !p.twopass && p.KST == 1 && p.vh->launch_wide && p.nqblk >= kWideMinBlocks && nr <= ((int64_t)1 << 25) && read_tuning().wide;
+    p.wide_ok = s.f16 && !p.twopass && p.KST == 1 && p.vh->launch_wide && p.nqblk >= kWideMinBlocks && nr <= ((int64_t)1 << 25) && read_tuning().wide;
     if (p.wide_ok && (p.nqblk & 1)) p.nqblk += 1;
     // The symmetric sweep's four-tile form (knn_panel.hpp, QT = 4) serves TWO query blocks per workgroup as well, but takes an odd
     // block count as it is (the last workgroup's second half idles): the layout is the same whatever MCE_PANEL_QT says.
-    const bool panel_wide_shape = f16 && !p.twopass && nq == nr && p.vh->launch_panel_wide && p.vh->launch_sym && p.nqblk >= 2;
+    const bool panel_wide_shape = s.f16 && !p.twopass && nq == nr && p.vh->launch_panel_wide && p.vh->launch_sym && p.nqblk >= 2;
     p.nq_pad = (int64_t)p.nqblk * qpb;
-    const int64_t rows_per_chunk = (int64_t)p.CT * rows_per_tile;
-    p.nchunk = (nr + rows_per_chunk - 1) / rows_per_chunk;
-    p.nrow_pad = p.nchunk * rows_per_chunk;
+    s.rows_per_chunk = (int64_t)p.CT * rows_per_tile;
+    p.nchunk = (nr + s.rows_per_chunk - 1) / s.rows_per_chunk;
+    p.nrow_pad = p.nchunk * s.rows_per_chunk;
     p.panel_wide_ok = panel_wide_shape && p.nrow_pad <= ((int64_t)1 << (mce::kHSymRowBits - 1));      // (queue words: 7 query-local bits, the row flag, 24 bits of row)
+}
 
-    if (f16 && !p.twopass && p.KST == 1 && d <= mce::kPruneMaxDim && p.vh->launch_prune && nq > 0 &&
+// the pruned walk where the shape has it and the mode asks for it: its chunks are list entries, not staged
+void plan_prune(Plan& p, const PlanShape& s)
+{
+    if (s.f16 && !p.twopass && p.KST == 1 && s.d <= mce::kPruneMaxDim && p.vh->launch_prune && s.nq > 0 &&
         p.nrow_pad <= ((int64_t)1 << mce::kHRelBits) && (int64_t)p.nqblk * p.nchunk <= mce::kPruneMaxPairs) {
         const int pm = eff_prune_mode();
         // (the k-d ordering costs ~4 ms per million reference rows whatever the number of queries, and sparse
         // query sets make large query tiles: measured at 2 M x 6, separate sets, the walk wins from nq ~ nr/10)
-        p.prune = pm == 2 || (pm == 0 && kPruneAutoMinRows[d] > 0 && nr >= kPruneAutoMinRows[d] && nq >= kPruneAutoMinQueries &&
-                                           nq >= nr / 8);
+        p.prune = pm == 2 || (pm == 0 && kPruneAutoMinRows[s.d] > 0 && s.nr >= kPruneAutoMinRows[s.d] && s.nq >= kPruneAutoMinQueries &&
+                                           s.nq >= s.nr / 8);
     }
     if (p.prune) {
         // no chunk staging in this mode: a "chunk" is just a list entry of 64 tiles (one per lane) = an aligned
         // k-d subtree of 2048 rows
         p.CT = mce::kHPruneChunkTiles;
-        p.nchunk = (nr + p.CT * 32 - 1) / (p.CT * 32);
+        p.nchunk = (s.nr + p.CT * 32 - 1) / (p.CT * 32);
         p.nrow_pad = p.nchunk * p.CT * 32;
         if (p.nrow_pad > ((int64_t)1 << mce::kHRelBits)) p.prune = false;
         if (!p.prune) {
             p.CT = p.vh->ct;
-            p.nchunk = (nr + rows_per_chunk - 1) / rows_per_chunk;
-            p.nrow_pad = p.nchunk * rows_per_chunk;
+            p.nchunk = (s.nr + s.rows_per_chunk - 1) / s.rows_per_chunk;
+            p.nrow_pad = p.nchunk * s.rows_per_chunk;
         }
     }
-    // reference splits: the model's cheapest count (split_cost)
+}
+
+// reference splits: the model's cheapest count (split_cost), the one-round overrides, tuning, the pruned walk's one
+int plan_splits(Plan& p, PlanShape& s)
+{
     int best_r = 1;
     double best_c = 1e300;
     const int rmax = (int)std::min<int64_t>(p.twopass ? mce::kMaxLists / 2 : mce::kMaxLists, p.nchunk);
-    const int rmin = f16 ? (int)((nr + ((int64_t)1 << mce::kHRelBits) - 1) >> mce::kHRelBits) : 1;   // queue entries hold 26-bit row offsets
-    if (deep && p.nrow_pad > ((int64_t)1 << mce::kHRelBits))      // (the deep kernel's queue entries hold ABSOLUTE 26-bit rows)
-        return fail(MCE_ERR_INVALID, "reference set too large for the fp16-filter path at d = %d (nr=%lld): use search mode 1", d, (long long)nr);
-    if (rmin > rmax) return fail(MCE_ERR_INVALID, "reference set too large for the fp16-filter path (nr=%lld)", (long long)nr);
+    const int rmin = s.rmin = s.f16 ? (int)((s.nr + ((int64_t)1 << mce::kHRelBits) - 1) >> mce::kHRelBits) : 1;   // queue entries hold 26-bit row offsets
+    if (s.deep && p.nrow_pad > ((int64_t)1 << mce::kHRelBits))      // (the deep kernel's queue entries hold ABSOLUTE 26-bit rows)
+        return fail(MCE_ERR_INVALID, "reference set too large for the fp16-filter path at d = %d (nr=%lld): use search mode 1", s.d, (long long)s.nr);
+    if (rmin > rmax) return fail(MCE_ERR_INVALID, "reference set too large for the fp16-filter path (nr=%lld)", (long long)s.nr);
     for (int r = std::max(1, rmin); r <= rmax; ++r) {
-        const double c = split_cost(p, filt, nr, K, r);
+        const double c = split_cost(p, s.filt, s.nr, s.K, r);
         if (c < best_c * 0.98) { best_c = c; best_r = r; }   // need >2% gain to take a bigger split
     }
     // Searches of at most one round of workgroups (up to ~130 k queries): the sweep of such a set is mostly candidate
@@ -329,46 +363,31 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
     // count that still fits one round AND leaves every split enough chunks for a seed phase (tools/_tmp scans, fused call,
     // model's choice -> this: 8 k x 6, K = 3: 0.41 -> 0.20 ms; 16 k x 6: 0.47 -> 0.23; 12 k x 27, K = 9: 0.75 -> 0.41; 16 k x 45:
     // 1.04 -> 0.47; from 24 k rows both agree).  Nothing seeded: the model's choice.
-    if (f16 && !p.twopass && p.nqblk <= kAssumedCUs) {
-        const int kneed = K + 1;      // (whatever the self mode: the workspace query does not know it, and the layout depends on r)
+    if (s.f16 && !p.twopass && p.nqblk <= kAssumedCUs) {
+        const int kneed = s.K + 1;      // (whatever the self mode: the workspace query does not know it, and the layout depends on r)
         for (int r = std::min(rmax, kAssumedCUs / p.nqblk); r >= std::max(1, rmin); --r)
             if (sweep_seed_cfg(p.nchunk / r, p.CT, kneed)) { best_r = r; break; }
     }
-    if (deep && p.nqblk <= kAssumedCUs) {
+    if (s.deep && p.nqblk <= kAssumedCUs) {
         // at most one round of workgroups: as above -- the largest split count that fits the round and leaves every split four
         // seed groups' worth of tiles per neighbour (knn_deep.hpp: its seed phase needs K + 1 groups)
         for (int r = std::min(rmax, kAssumedCUs / p.nqblk); r >= 1; --r)
-            if ((p.nchunk / r) * p.CT >= 4 * (K + 1)) { best_r = r; break; }
+            if ((p.nchunk / r) * p.CT >= 4 * (s.K + 1)) { best_r = r; break; }
     }
     if (const int r = read_tuning().rsplit) {          // tuning
         if (r >= std::max(1, rmin) && r <= rmax) best_r = r;
     }
     if (p.prune) best_r = 1;                  // every workgroup walks its own chunk list
     p.rsplit = best_r;
-    p.cost = split_cost(p, filt, nr, K, best_r);        // (the overrides above may have left the model's minimum)
-    // the workspace layout for the split count taken; a part of a search that was handed the WHOLE search's workspace
-    // (mce_knn_dotp_part_f64_dev: a row shard plans more reference splits than the whole set would, and every split has its
-    // own lists) takes fewer splits until it fits (t_plan_cap)
-    auto layout = [&]() {
-    p.L = p.twopass ? 2 * p.rsplit : p.rsplit;
+    p.cost = split_cost(p, s.filt, s.nr, s.K, best_r);        // (the overrides above may have left the model's minimum)
+    return MCE_OK;
+}
 
-    size_t off = 0;
-    p.off_yf = off;
-    if (filt) {
-        p.off_yh = off;
-        off = align_up(off + (size_t)p.nrow_pad * (size_t)(16 * p.KST) * 2, 256);
-        p.off_xh = off;
-        off = align_up(off + (size_t)p.nq_pad * (size_t)(16 * p.KST) * 2, 256);
-        p.off_qinfo = off;
-        off = align_up(off + (size_t)p.nq_pad * 2 * sizeof(double), 256);
-        p.off_params = off;
-        off = align_up(off + (size_t)mce::HP_COUNT * sizeof(double), 256);
-    } else {
-        off = align_up(off + (size_t)p.nrow_pad * (size_t)(4 * p.KS) * sizeof(double), 256);
-    }
-    // symmetric sweep: auto-evidence searches (the caller passes ONE buffer as X and Y; only the sizes are known here)
-    // (16 < K <= 32: two symmetric passes over 16-entry lists -- capi_search.hpp -- where the list capacity has the second-pass kernels)
-    if (f16 && (!p.twopass || p.vh->launch_panel_lower) && !p.prune && nq == nr && p.vh->launch_sym && p.nqblk >= 2 && p.nrow_pad <= ((int64_t)1 << mce::kHSymRowBits)) {
+// symmetric sweep: auto-evidence searches (the caller passes ONE buffer as X and Y; only the sizes are known here)
+// (16 < K <= 32: two symmetric passes over 16-entry lists -- capi_search.hpp -- where the list capacity has the second-pass kernels)
+void plan_sym(Plan& p, const PlanShape& s)
+{
+    if (s.f16 && (!p.twopass || p.vh->launch_panel_lower) && !p.prune && s.nq == s.nr && p.vh->launch_sym && p.nqblk >= 2 && p.nrow_pad <= ((int64_t)1 << mce::kHSymRowBits)) {
         const int sm = eff_sym_mode();
         p.sym = sm == 2 || (sm == 0 && p.nqblk >= kSymAutoMinBlocks[p.KST] * ((p.KST == 1 && p.KCAP == 16) ? 2 : 1));     // (1M x 15, K = 16: 62.3 vs 62.7 ms)
         // the symmetric sweep needs queries and references to be ONE buffer: known from the pointers (host entry points, and
@@ -388,37 +407,30 @@ int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, P
         p.sym_nsplit = S;
         if (S > 1) p.sym_panel = (int)std::max<int64_t>(8, std::min<int64_t>(kSymPanelChunks[p.KST], p.nchunk / (2 * S)));
     }
-    const int l_alloc = std::max(p.L, p.sym_nsplit);
-    p.off_pd = off;
-    off = align_up(off + (size_t)l_alloc * p.KCAP * (size_t)p.nq_pad * sizeof(double), 256);
-    p.off_pi = off;
-    off = align_up(off + (size_t)l_alloc * p.KCAP * (size_t)p.nq_pad * sizeof(int), 256);
-    p.off_center = off;
-    off = align_up(off + (size_t)3 * mce::kMaxDimPad * sizeof(double), 256);      // centre | box(Y) | box(X)
-    p.off_msum = off;
-    off = align_up(off + (size_t)mce::kMeanBlocks * mce::kStatStride * sizeof(double), 256);
-    if (p.prune) {
-        mce::prune_layout(nq, p.nq_pad, p.nqblk, nr, p.nrow_pad, p.nchunk, d, p.pl);
-        p.pl_nr = nr;
-        p.off_prune = off;
-        off = align_up(off + p.pl.total, 256);
-        if (nq == nr && p.nqblk >= kPruneHeavyMinBlocks && prune_heavy_enabled()) {
-            p.heavy_max = std::max(p.nqblk * mce::kHWaves / kPruneHeavyMaxShare, kPruneHeavyMinCount);       // waves
-            p.off_heavy = off;
-            off = align_up(off + (size_t)p.heavy_max * kPruneWaveQueries * (kPruneHeavyMaxSplit - 1) * p.KCAP * (sizeof(double) + sizeof(int)), 256);
-        }
-    }
-    if (p.sym) {
-        mce::sym_layout(nr, p.nq_pad, p.nqblk, d, p.KCAP, mce::f16_qpb(p.KCAP), sym_bucket_per_row(std::min<int>(K, p.KCAP)), p.sl);      // (two passes: each fills lists of KCAP)
-        p.off_sym = off;
-        off = align_up(off + p.sl.total, 256);
-    }
-    p.total = off;
-    };
-    layout();
-    while (t_plan_cap && p.total > t_plan_cap && p.rsplit > std::max(1, rmin)) {
+}
+
+// Validates (nq, nr, d, K, self_mode), picks the kernel family and its geometry and sizes the workspace.
+int make_plan(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t self_mode, Plan& p)
+{
+    int rc = plan_check_args(nq, nr, d, K, self_mode);
+    if (rc != MCE_OK) return rc;
+    PlanShape s{nq, nr, d, K};
+    // 64 <= d <= 127 (round 5): the fp64 MFMA sweep at KS = 20..32, one query tile per wave -- the vector-FMA kernel was
+    // 66x the time of d = 63 at 100 k rows (knn_generic.hpp); it keeps d > 127 and K > 32
+    s.wide_f64 = d > MCE_MAX_DIM && d <= mce::kWideMaxDim && K <= MCE_MAX_K;
+    if (env_long_on() && d >= mce::kLongMinDim && d <= mce::kLongMaxDim && K <= MCE_MAX_K) { plan_long(p, s); return MCE_OK; }
+    if ((d > MCE_MAX_DIM && !s.wide_f64) || K > MCE_MAX_K) { plan_generic(p, s); return MCE_OK; }
+    plan_sweep_family(p, s);
+    plan_prune(p, s);
+    if ((rc = plan_splits(p, s)) != MCE_OK) return rc;
+    plan_sym(p, s);
+    // the workspace for the split count taken; a part of a search that was handed the WHOLE search's workspace
+    // (mce_knn_dotp_part_f64_dev: a row shard plans more reference splits than the whole set would, and every split has its
+    // own lists) takes fewer splits until it fits (t_plan_cap)
+    plan_sizes(p, s);
+    while (t_plan_cap && p.total > t_plan_cap && p.rsplit > std::max(1, s.rmin)) {
         p.rsplit -= 1;
-        layout();
+        plan_sizes(p, s);
     }
     return MCE_OK;
 }
@@ -443,7 +455,7 @@ int plan_for_workspace(int64_t nq, int64_t nr, int32_t d, int32_t K, int32_t sel
         rc = make_plan(nq, nr, d, K, self_mode, p);
         if (rc != MCE_OK) return rc;
     }
-    if (ws_bytes < p.total + extra && p.heavy_max > 0) {        // the walk runs unsplit
+    if (ws_bytes < p.total + extra && p.sizes.heavy_max > 0) {        // the walk runs unsplit
         nh.emplace();
         rc = make_plan(nq, nr, d, K, self_mode, p);
         if (rc != MCE_OK) return rc;

@@ -65,35 +65,30 @@ struct SearchBracket {
 // offset of list set `set` (KCAP x nq_pad entries each): the second pass of a two-pass search writes behind the first's sets
 size_t list_set(const Plan& p, int set) { return (size_t)set * p.KCAP * (size_t)p.nq_pad; }
 
+static_assert(sizeof(mce::SymEntry) == mce::kSymEntryBytes && sizeof(_Float16) == sizeof(mce::half_t), "search_layout.hpp's element sizes");
+
 // the argument block of the fp16 filter from a plan and its workspace: packed operands, the rows searched (X, Y), the lists
-mce::KnnF16Args f16_args(const Plan& p, char* ws, const double* X, int64_t nq, const double* Y, int64_t nr, int32_t d, int32_t K, int self_exclude,
+mce::KnnF16Args f16_args(const Plan& p, const mce::SearchArena& A, const mce::ListSets& ls, const double* X, int64_t nq, const double* Y, int64_t nr, int32_t d, int32_t K, int self_exclude,
                          int64_t self_offset)
 {
     mce::KnnF16Args a;
-    a.Yh = ws + p.off_yh; a.nchunk_total = p.nchunk; a.rsplit = p.rsplit; a.Xh = ws + p.off_xh;
-    a.qinfo = reinterpret_cast<const double*>(ws + p.off_qinfo); a.params = reinterpret_cast<const double*>(ws + p.off_params);
+    a.Yh = A.yh; a.nchunk_total = p.nchunk; a.rsplit = p.rsplit; a.Xh = A.xh;
+    a.qinfo = A.qinfo; a.params = A.params;
     a.X = X; a.Y = Y; a.nq = nq; a.nr = nr; a.D = d; a.nq_pad = p.nq_pad; a.nqblk = p.nqblk;
     a.self_exclude = self_exclude; a.self_offset = self_offset; a.ksel = K;
-    a.part_d = reinterpret_cast<double*>(ws + p.off_pd); a.part_i = reinterpret_cast<int*>(ws + p.off_pi);
+    a.part_d = ls.d; a.part_i = ls.i;
     return a;
 }
 // ... of the symmetric sweep (also capi_apo.hpp): one set of n rows in the sweep's sorted order, its scratch (bounds, buckets), one split
-mce::KnnF16Args sym_args(const Plan& p, char* ws, int64_t n, int32_t d, int32_t K, int self_exclude)
+mce::KnnF16Args sym_args(const Plan& p, const mce::SearchArena& A, const mce::ListSets& ls, int64_t n, int32_t d, int32_t K, int self_exclude)
 {
-    char* const sw = ws + p.off_sym;
-    const double* rows = reinterpret_cast<const double*>(sw + p.sl.Ys);
-    mce::KnnF16Args a = f16_args(p, ws, rows, n, rows, n, d, K, self_exclude, 0);
+    const mce::SymArena& S = A.sym;
+    mce::KnnF16Args a = f16_args(p, A, ls, S.Ys, n, S.Ys, n, d, K, self_exclude, 0);
     a.rsplit = 1;
-    a.rperm = reinterpret_cast<const int*>(sw + p.sl.perm);
-    a.sym.thr = reinterpret_cast<unsigned long long*>(sw + p.sl.thr);
-    a.sym.rrow = reinterpret_cast<unsigned*>(sw + p.sl.rrow);
-    a.sym.rtile = reinterpret_cast<float*>(sw + p.sl.rtile);
-    a.sym.slots = reinterpret_cast<unsigned long long*>(sw + p.sl.slots);
-    a.sym.bucket_cnt = reinterpret_cast<int*>(sw + p.sl.bucket_cnt);
-    a.sym.bucket_flag = reinterpret_cast<int*>(sw + p.sl.bucket_flag);
-    a.sym.bucket = reinterpret_cast<mce::SymEntry*>(sw + p.sl.bucket);
-    a.sym.cap = p.sl.cap;
-    a.sym.done = reinterpret_cast<int*>(sw + p.sl.done);
+    a.rperm = S.perm;
+    a.sym.thr = S.thr; a.sym.rrow = S.rrow; a.sym.rtile = S.rtile; a.sym.slots = S.slots;
+    a.sym.bucket_cnt = S.bucket_cnt(); a.sym.bucket_flag = S.bucket_flag(); a.sym.done = S.done();
+    a.sym.bucket = S.bucket; a.sym.cap = S.cap;
     // panel = the packed rows one L2 (4 MB per XCD) serves to the units running at the same time; MCE_SYM_PANEL: chunks (tuning)
     const Tuning tun = read_tuning();
     a.sym.panel = tun.sym_panel > 0 ? tun.sym_panel : kSymPanelChunks[p.KST];
@@ -104,7 +99,7 @@ mce::KnnF16Args sym_args(const Plan& p, char* ws, int64_t n, int32_t d, int32_t 
 struct F16Search {
     const double* sX = nullptr;     // the rows the search reads: the caller's, or their sorted / k-d ordered copies
     const double* sY = nullptr;
-    mce::PruneOut po;               // pruned walk: k-d order, chunk lists, boxes
+    bool kd_same = false;           // pruned walk: one k-d order serves both sets
     bool use_sym = false;           // the symmetric sweep runs (queries and references one buffer)
 };
 
@@ -113,12 +108,13 @@ struct F16Search {
 struct Search {
     Plan& p;
     const double* dX; int64_t nq; const double* dY; int64_t nr; int32_t d, K;
-    int32_t self_mode; int64_t self_offset; char* ws; hipStream_t st;
+    int32_t self_mode; int64_t self_offset; const mce::SearchArena& A; hipStream_t st;
     int phase;                                // the all-pairs-once partition's call (capi_apo.hpp): 1 or 2; 0 otherwise
-    double* pd; int* pi;                      // lists
+    mce::ListSets ls;                         // lists: the arena's, or the pairs-once share's own sets
     double* center; double* msum;             // centre | box(Y) | box(X), and the partial sums of the column statistics
     int self_exclude;
     KernelBracket kb;
+    double* pd = ls.d; int* pi = ls.i;
     int generic(), long_rows(), deep(), fp64();
     int f16_prepare(F16Search& f), pruned(const F16Search& f), symmetric(), f16_sweep(const F16Search& f);     // fp16 filter: prologue + one sweep
 };
@@ -138,18 +134,15 @@ int Search::generic()
 int Search::long_rows()
 {
     const int threads = 256;
-    double* yf = reinterpret_cast<double*>(ws + p.off_yf);
-    double* xf = reinterpret_cast<double*>(ws + p.off_xf);
-    double* xn = reinterpret_cast<double*>(ws + p.off_xn);
-    hipLaunchKernelGGL(mce::pack_refs_kernel, dim3((unsigned)((p.nrow_pad + threads - 1) / threads)), dim3(threads), 0, st, dY, nr, (int)d, p.KS, p.nrow_pad, center, yf);
+    hipLaunchKernelGGL(mce::pack_refs_kernel, dim3((unsigned)((p.nrow_pad + threads - 1) / threads)), dim3(threads), 0, st, dY, nr, (int)d, p.KS, p.nrow_pad, center, A.yfl);
     MCE_HIP(hipGetLastError());
     const int64_t qe = p.nq_pad * (int64_t)p.KS;
-    hipLaunchKernelGGL(mce::long_pack_queries_kernel, dim3((unsigned)((qe + 255) / 256)), dim3(256), 0, st, dX, nq, (int)d, p.KS, p.nq_pad, center, xf);
+    hipLaunchKernelGGL(mce::long_pack_queries_kernel, dim3((unsigned)((qe + 255) / 256)), dim3(256), 0, st, dX, nq, (int)d, p.KS, p.nq_pad, center, A.xf);
     MCE_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mce::long_query_norms_kernel, dim3((unsigned)((p.nq_pad + 255) / 256)), dim3(256), 0, st, dX, nq, (int)d, p.nq_pad, center, xn);
+    hipLaunchKernelGGL(mce::long_query_norms_kernel, dim3((unsigned)((p.nq_pad + 255) / 256)), dim3(256), 0, st, dX, nq, (int)d, p.nq_pad, center, A.xn);
     MCE_HIP(hipGetLastError());
     mce::LongArgs a;
-    a.Yf = yf; a.Xf = xf; a.xn = xn;
+    a.Yf = A.yfl; a.Xf = A.xf; a.xn = A.xn;
     a.nchunk_total = p.nchunk; a.rsplit = p.rsplit; a.KSP = p.KS; a.KSB = mce::long_ksb(d);
     a.nq = nq; a.nq_pad = p.nq_pad; a.nqblk = p.nqblk;
     a.self_exclude = self_exclude; a.self_offset = self_offset; a.ksel = p.ksel > K ? p.ksel : K;
@@ -166,10 +159,8 @@ int Search::long_rows()
 // ---- the deep fp16 filter (64 <= d <= 127; knn_deep.hpp) + exact fp64 refine -------------------------------------------
 int Search::deep()
 {
-    _Float16* yh = reinterpret_cast<_Float16*>(ws + p.off_yh);
-    _Float16* xh = reinterpret_cast<_Float16*>(ws + p.off_xh);
-    double* qinfo = reinterpret_cast<double*>(ws + p.off_qinfo);
-    double* params = reinterpret_cast<double*>(ws + p.off_params);
+    _Float16 *const yh = reinterpret_cast<_Float16*>(A.yh), *const xh = reinterpret_cast<_Float16*>(A.xh);
+    double *const qinfo = A.qinfo, *const params = A.params;
     MCE_HIP(mce::zero_async(params, mce::HP_COUNT * sizeof(double), st));
     const bool separate_queries = !(dX >= dY && dX + (size_t)nq * d <= dY + (size_t)nr * d);
     // radius about the references' mean (the wide column means above), over both sets; power-of-two scale; packing
@@ -237,10 +228,8 @@ int Search::deep()
 // boxes, the power-of-two scale and the packing of both sets -- what its three sweeps share
 int Search::f16_prepare(F16Search& f)
 {
-    _Float16* yh = reinterpret_cast<_Float16*>(ws + p.off_yh);
-    _Float16* xh = reinterpret_cast<_Float16*>(ws + p.off_xh);
-    double* qinfo = reinterpret_cast<double*>(ws + p.off_qinfo);
-    double* params = reinterpret_cast<double*>(ws + p.off_params);
+    _Float16 *const yh = reinterpret_cast<_Float16*>(A.yh), *const xh = reinterpret_cast<_Float16*>(A.xh);
+    double *const qinfo = A.qinfo, *const params = A.params;
     double* box_y = center + mce::kMaxDimPad;
     double* box_x = center + 2 * mce::kMaxDimPad;
     if (phase != 2) MCE_HIP(mce::zero_async(params, mce::HP_COUNT * sizeof(double), st));
@@ -250,15 +239,16 @@ int Search::f16_prepare(F16Search& f)
     f.use_sym = p.sym && dX == dY && nq == nr && self_offset == 0 && g_split_depth == 0;
     if (f.use_sym) {
         // rows by distance from the mean: a 32-row tile then holds rows of nearly equal K-th neighbour distance
-        if (phase != 2) MCE_HIP(mce::sym_prepare(dY, nr, (int)d, center, p.nq_pad, ws + p.off_sym, p.sl, st));
-        f.sX = f.sY = reinterpret_cast<const double*>(ws + p.off_sym + p.sl.Ys);
+        if (phase != 2) MCE_HIP(mce::sym_prepare(dY, nr, (int)d, center, p.nq_pad, A.sym, st));
+        f.sX = f.sY = A.sym.Ys;
         separate_queries = false;
     }
     if (p.prune) {
         const bool same_set = (dX == dY && nq == nr);
         MCE_HIP(mce::prune_prepare(dX, nq, dY, nr, (int)d, same_set, mce::f16_qpb(p.KCAP), p.CT * 32, p.nq_pad, p.nqblk, p.nrow_pad,
-                                   p.nchunk, ws + p.off_prune, p.pl, st, f.po, p.kd_ready && same_set));
-        f.sX = f.po.Xs; f.sY = f.po.Ys;
+                                   p.nchunk, A.prune, st, p.kd_ready && same_set));
+        f.kd_same = same_set;
+        f.sX = same_set ? A.prune.Ys : A.prune.Xs; f.sY = A.prune.Ys;
         separate_queries = separate_queries && !same_set;
     }
     if (separate_queries) {
@@ -290,17 +280,17 @@ int Search::f16_prepare(F16Search& f)
 // ---- the pruned walk (prune.hpp): every wave of queries walks its own k-d ordered chunk list ---------------------------
 int Search::pruned(const F16Search& f)
 {
-    const mce::PruneOut& po = f.po;
-    mce::KnnF16Args a = f16_args(p, ws, f.sX, nq, f.sY, nr, d, K, self_exclude, self_offset);
-    a.clist = po.clist; a.cdist = po.cdist; a.list_len = (int)p.nchunk; a.rperm = po.rperm; a.qperm = po.qperm;
-    a.tbox_r = po.tbox_r; a.tbox_q = po.tbox_q; a.cbox_r = po.cbox_r; a.border = po.border;
+    const mce::PruneArena& po = A.prune;
+    mce::KnnF16Args a = f16_args(p, A, ls, f.sX, nq, f.sY, nr, d, K, self_exclude, self_offset);
+    a.clist = po.list_c; a.cdist = po.list_d; a.list_len = (int)p.nchunk; a.rperm = po.perm_r; a.qperm = f.kd_same ? po.perm_r : po.perm_q;
+    a.tbox_r = po.tboxT_r; a.tbox_q = f.kd_same ? po.tbox_r : po.tbox_q; a.cbox_r = po.box_r; a.border = po.border;
     // (a part of a multi-GPU run: every nparts-th WAVE of the dispatch order)
     const int nw_total = p.nqblk * mce::kHWaves;
     if (p.nparts > 1) { a.qblk0 = p.part; a.qblk_stride = p.nparts; a.nqblk_run = (nw_total - p.part + p.nparts - 1) / p.nparts; }
     // heavy waves (the first of this launch's dispatch order): several workgroups each, lists folded afterwards
     const int nblk_run = a.nqblk_run ? a.nqblk_run : nw_total;       // waves of this launch
     int hv_n = 0, hv_S = 1;
-    if (p.heavy_max > 0 && dX == dY && nq == nr) {
+    if (A.z.heavy_max > 0 && dX == dY && nq == nr) {
         // how many: the waves that would run longer than a fraction of the launch.  Measured at C5 (1 wave in 100 takes
         // 3.4x the mean, 1 in 1000 7.5x, 1 in 10 000 13x): ~700 of a 10-round launch, fewer of a longer one (it hides
         // longer waves) -- 1 / 2 / 4 / 8 GPUs: 0 / 184 / 367 / 700 waves per rank
@@ -308,17 +298,16 @@ int Search::pruned(const F16Search& f)
         const char* hv_env = env_prune_heavy();
         if ((kPruneHeavyDefault || (hv_env && !strcmp(hv_env, "auto"))) && rounds < kPruneHeavyMaxRounds) {
             const double fr = std::min(1.0, kPruneHeavyFullRounds / std::max(rounds, 1.0));
-            hv_n = std::min(std::max((int)(kPruneHeavyCount * fr), kPruneHeavyMinCount), std::min(p.heavy_max, nblk_run));
+            hv_n = std::min(std::max((int)(kPruneHeavyCount * fr), kPruneHeavyMinCount), std::min(A.z.heavy_max, nblk_run));
             hv_S = kPruneHeavySplit;
         }
         if (const char* e = hv_env) {
             int n_ = hv_n, s_ = kPruneHeavySplit;
-            if (sscanf(e, "%d,%d", &n_, &s_) >= 1) { hv_n = std::min(std::max(n_, 0), std::min(p.heavy_max, nblk_run)); hv_S = std::min(std::max(s_, 1), kPruneHeavyMaxSplit); }
+            if (sscanf(e, "%d,%d", &n_, &s_) >= 1) { hv_n = std::min(std::max(n_, 0), std::min(A.z.heavy_max, nblk_run)); hv_S = std::min(std::max(s_, 1), kPruneHeavyMaxSplit); }
         }
         if (hv_n == 0 || hv_S == 1) { hv_n = 0; hv_S = 1; }
     }
-    double* hv_d = reinterpret_cast<double*>(ws + p.off_heavy);
-    int* hv_i = reinterpret_cast<int*>(hv_d + (size_t)p.heavy_max * kPruneWaveQueries * (kPruneHeavyMaxSplit - 1) * p.KCAP);
+    double* const hv_d = A.heavy_d; int* const hv_i = A.heavy_i();
     a.seed_cfg = hv_n | (hv_S << 24);
     a.lo_d = hv_n ? hv_d : nullptr; a.lo_i = hv_n ? hv_i : nullptr;
     // MCE_PRUNE_TIMES=<file> (diagnostic): the duration of every workgroup of the walk, by position in the dispatch
@@ -394,8 +383,7 @@ int sym_units_and_flops(const Plan& p, const mce::PanelGeom& g, bool panel_kerne
 // ---- the symmetric sweep (one set: every pair of tiles multiplied once, for the lists of both) -------------------------
 int Search::symmetric()
 {
-    char* const sw = ws + p.off_sym;
-    mce::KnnF16Args a = sym_args(p, ws, nr, d, K, self_exclude);
+    mce::KnnF16Args a = sym_args(p, A, ls, nr, d, K, self_exclude);
     const Tuning tun = read_tuning();
     // prepass: every row's bound before any block runs (the seed phase as its own launch)
     // about 32 k rows (one k-step: 64 k), at most half of the chunks (tools/_tmp-style scans, fused call, share 8 -> 2:
@@ -439,7 +427,7 @@ int Search::symmetric()
         geom.nsplit = std::max(1, apo ? p.apo_nsplit : p.sym_nsplit);
         if (geom.nsplit > 1) {
             // one hand-over counter per chain: nqblk * nsplit words in the sort's second key array (n_pad words, free by now)
-            a.sym.done = reinterpret_cast<int*>(sw + p.sl.keys_b);
+            a.sym.done = reinterpret_cast<int*>(A.sym.keys_b);
             MCE_HIP(mce::zero_async(a.sym.done, (size_t)p.nqblk * geom.nsplit * sizeof(int), st));
             if (!apo) {
                 hipLaunchKernelGGL(mce::sym_chain_init_kernel, dim3((unsigned)p.nqblk), dim3(512), 0, st, pd, pi, p.nq_pad, p.KCAP, geom.nsplit, 0, 1);
@@ -497,7 +485,7 @@ int Search::symmetric()
                 // strided blocks, several chains per block: the units as a table (in the sort's value array: n_pad words, free by now)
                 const int nun = mce::panel_unit_count(geom);
                 if ((size_t)nun * sizeof(mce::PanelUnit) > (size_t)p.nq_pad * sizeof(int)) return fail(MCE_ERR_INVALID, "symmetric sweep: %d units do not fit the table", nun);
-                mce::PanelUnit* tab = reinterpret_cast<mce::PanelUnit*>(sw + p.sl.vals_a);
+                mce::PanelUnit* tab = reinterpret_cast<mce::PanelUnit*>(A.sym.vals_a);
                 if (nun > 0) {
                     hipLaunchKernelGGL(mce::panel_unit_table_kernel, dim3((unsigned)((nun + 255) / 256)), dim3(256), 0, st, geom, nun, tab);
                     MCE_HIP(hipGetLastError());
@@ -523,14 +511,14 @@ int Search::symmetric()
     g_last_flops_all = g_last_flops_main + (double)(seed_used & 0xffff) * p.CT * (double)(qb_hi - qb_lo) * 16.0 * 1024.0 * 32.0 * p.KST;
     snprintf(g_last_kernel, sizeof(g_last_kernel), "%s symmetric%s%s%s grid=%d block=%d lds=%zu qt=%d ct=%d panel=%d seed=%dx%d/%d bucket=%d", p.vh->name, panel_kernel ? " panel-kernel" : "",
              p.twopass ? " two passes" : "", geom.blk_stride > 1 ? " pairs-once" : (geom.nsplit > 1 ? " chains" : ""), sym_units,
-             mce::kHThreads, panel_wide ? p.vh->lds_bytes_panel_wide : (panel_kernel ? p.vh->lds_bytes_panel : p.vh->lds_bytes_sym), panel_wide ? 2 * p.QT : p.QT, p.CT, a.sym.panel, seed_used & 0xffff, (seed_used >> 16) & 0xfff, (seed_used >> 28) & 3, p.sl.cap);
+             mce::kHThreads, panel_wide ? p.vh->lds_bytes_panel_wide : (panel_kernel ? p.vh->lds_bytes_panel : p.vh->lds_bytes_sym), panel_wide ? 2 * p.QT : p.QT, p.CT, a.sym.panel, seed_used & 0xffff, (seed_used >> 16) & 0xfff, (seed_used >> 28) & 3, A.sym.cap);
     return MCE_OK;
 }
 
 // ---- the exhaustive sweep: every query block against every chunk of its reference split -------------------------------
 int Search::f16_sweep(const F16Search& f)
 {
-    mce::KnnF16Args a = f16_args(p, ws, f.sX, nq, f.sY, nr, d, K, self_exclude, self_offset);
+    mce::KnnF16Args a = f16_args(p, A, ls, f.sX, nq, f.sY, nr, d, K, self_exclude, self_offset);
     // seed phase: the host picks the group size; MCE_F16_SEED_ROWS / MCE_F16_SEED_SHARE override (tests, tuning)
     // (the kernel balances the splits to within one chunk: size the seed phase for the smallest)
     auto seed_cfg = [&](int ksel) { return sweep_seed_cfg(p.nchunk / p.rsplit, p.CT, ksel + a.self_exclude); };
@@ -569,12 +557,11 @@ int Search::f16_sweep(const F16Search& f)
 int Search::fp64()
 {
     const int threads = 256;
-    double* yf = reinterpret_cast<double*>(ws + p.off_yf);
     hipLaunchKernelGGL(mce::pack_refs_kernel, dim3((unsigned)((p.nrow_pad + threads - 1) / threads)), dim3(threads), 0, st, dY, nr,
-                       (int)d, p.KS, p.nrow_pad, center, yf);
+                       (int)d, p.KS, p.nrow_pad, center, A.yf);
     MCE_HIP(hipGetLastError());
     mce::KnnArgs a;
-    a.Yf = yf; a.nchunk_total = p.nchunk; a.rsplit = p.rsplit; a.X = dX; a.center = center; a.nq = nq; a.D = d;
+    a.Yf = A.yf; a.nchunk_total = p.nchunk; a.rsplit = p.rsplit; a.X = dX; a.center = center; a.nq = nq; a.D = d;
     a.nq_pad = p.nq_pad; a.nqblk = p.nqblk; a.self_exclude = self_exclude; a.self_offset = self_offset;
     a.ksel = p.ksel > K ? p.ksel : K;          // (K + kRefineMargin: the merge picks the K on exact distances)
     a.part_d = pd; a.part_i = pi;
@@ -589,16 +576,14 @@ int Search::fp64()
 
 // pack + search; leaves the lane/split lists in the workspace
 int run_search(Plan& p, const double* dX, int64_t nq, const double* dY, int64_t nr, int32_t d, int32_t K,
-               int32_t self_mode, int64_t self_offset, char* ws, hipStream_t st)
+               int32_t self_mode, int64_t self_offset, const mce::SearchArena& A, const mce::ListSets& ls, hipStream_t st)
 {
     p.sym_active = false;
     // the all-pairs-once partition runs in two calls with a collective between them (capi_apo.hpp): 1 = statistics, sort, packing and
     // the prepass of the rank's own blocks, then return (the bounds are all-reduced); 2 = the sweep on what phase 1 left in the workspace
     const int phase = p.apo ? p.apo_phase : 0;
-    double* center = reinterpret_cast<double*>(ws + p.off_center);
-    double* msum = reinterpret_cast<double*>(ws + p.off_msum);
-    Search s{p, dX, nq, dY, nr, d, K, self_mode, self_offset, ws, st, phase, reinterpret_cast<double*>(ws + p.off_pd), reinterpret_cast<int*>(ws + p.off_pi),
-             center, msum, (self_mode == MCE_SELF_EXCLUDE) ? 1 : 0, KernelBracket{}};
+    double *const center = A.center, *const msum = A.msum;
+    Search s{p, dX, nq, dY, nr, d, K, self_mode, self_offset, A, st, phase, ls, center, msum, (self_mode == MCE_SELF_EXCLUDE) ? 1 : 0, KernelBracket{}};
     if (p.generic) return s.generic();
     if (p.vl) {                 // (the long-row sweep: its own column means, any d)
         hipLaunchKernelGGL(mce::long_col_mean_partial_kernel, dim3(mce::kLongMeanBlocks), dim3(256), 0, st, dY, nr, (int)d, mce::kLongMeanBlocks, msum);
@@ -634,7 +619,7 @@ int run_search(Plan& p, const double* dX, int64_t nq, const double* dY, int64_t 
 // merge (+ optional distance output, + optional fused reduction) of the per-split lists
 int launch_merge(const Plan& p, bool write_dist, bool fuse, const double* dX, const double* dY, int64_t nq, int32_t d, int K,
                  int self_mode, int64_t self_offset, double* d_dist, int64_t* d_idx, int k0, int kmax,
-                 const double* d_w, const double* d_fs, double* partial, char* ws, hipStream_t st)
+                 const double* d_w, const double* d_fs, double* partial, const mce::SearchArena& A, const mce::ListSets& ls, hipStream_t st)
 {
     const bool same_set = (dX == dY && nq == p.pl_nr);
     // a part of a pruned search: only the list columns of its query blocks were filled; the merge threads
@@ -645,31 +630,29 @@ int launch_merge(const Plan& p, bool write_dist, bool fuse, const double* dX, co
     const int nunits = wave_parts ? p.nqblk * mce::kHWaves : p.nqblk;
     int64_t ncol = nq;
     int64_t col0 = 0, col1 = INT64_MAX;
-    const int* border = p.prune ? reinterpret_cast<const int*>(ws + p.off_prune + p.pl.border) : nullptr;
+    const int* border = p.prune ? A.prune.border : nullptr;
     if (p.sym_active && p.nparts > 1 && p.apo) {
         // the all-pairs-once partition: every nparts-th block of list columns, enumerated through the identity table the
         // finish call left in the `done` array (the kernel's border path)
         ncol = (int64_t)((nunits - p.part + p.nparts - 1) / p.nparts) * qpb;
-        border = reinterpret_cast<const int*>(ws + p.off_sym + p.sl.done);
+        border = A.sym.done();
     } else if (p.sym_active && p.nparts > 1) {         // one rank's blocks of a symmetric partition: a contiguous range of list columns
         col0 = (int64_t)p.sym_qb_lo * qpb;
         col1 = std::min<int64_t>((int64_t)p.sym_qb_hi * qpb, nq);
         ncol = std::max<int64_t>(col1 - col0, 0);
     } else if (p.nparts > 1) ncol = (int64_t)((nunits - p.part + p.nparts - 1) / p.nparts) * qpb;
     const unsigned blocks = (unsigned)std::max<int64_t>((ncol + mce::kRedThreads - 1) / mce::kRedThreads, 1);
-    const double* pd = reinterpret_cast<const double*>(ws + p.off_pd);
-    const int* pi = reinterpret_cast<const int*>(ws + p.off_pi);
     const bool refine = !p.filter() && !p.generic;   // fp64 sweep keys are GEMM-form: refine; the others are exact
     const double lnc = fuse ? ln_unit_ball(d) : 0.0;
     // pruned search: list column q is the q-th query in k-d order; its caller row is qperm[q]
     const int* qperm = nullptr;
-    if (p.prune) qperm = reinterpret_cast<const int*>(ws + p.off_prune + (same_set ? p.pl.perm_r : p.pl.perm_q));
-    if (p.sym_active) qperm = reinterpret_cast<const int*>(ws + p.off_sym + p.sl.perm);     // list column = sorted position
+    if (p.prune) qperm = same_set ? A.prune.perm_r : A.prune.perm_q;
+    if (p.sym_active) qperm = A.sym.perm;     // list column = sorted position
 #define MCE_MERGE(W, F, R)                                                                                          \
-    hipLaunchKernelGGL((mce::merge_lists_kernel<W, F, R>), dim3(blocks), dim3(mce::kRedThreads), 0, st, pd, pi, p.L,  \
+    hipLaunchKernelGGL((mce::merge_lists_kernel<W, F, R>), dim3(blocks), dim3(mce::kRedThreads), 0, st, (const double*)ls.d, (const int*)ls.i, p.L,  \
                        p.KCAP, nq, p.nq_pad, dX, dY, (int)d, K, (refine && p.ksel > K) ? p.ksel : K, self_mode, self_offset, d_dist, d_idx, K, k0, kmax, \
                        d_w, d_fs, lnc, partial, qperm, p.part, p.nparts, qpb, border, nunits, col0, col1, p.pl_nr, \
-                       refine ? reinterpret_cast<const double*>(ws + p.off_center) : nullptr)
+                       refine ? (const double*)A.center : nullptr)
     if (write_dist && !fuse) { if (refine) MCE_MERGE(true, false, true); else MCE_MERGE(true, false, false); }
     else if (write_dist && fuse) { if (refine) MCE_MERGE(true, true, true); else MCE_MERGE(true, true, false); }
     else { if (refine) MCE_MERGE(false, true, true); else MCE_MERGE(false, true, false); }

@@ -15,8 +15,6 @@ namespace {
 
 constexpr int kThreads = 256;
 
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 constexpr int kCoordBits = 24;    // coordinate bits in a 64-bit k-d sort key
 constexpr int kMinCoordBits32 = 18;   // ... at least so many in a 32-bit one (sign + 8 exponent + 9 mantissa bits: medians to 2e-3 of the coordinate)
 constexpr int kAlign = 64;        // units (32-row tiles) per aligned group: the list chunk of the pruned walk
@@ -561,113 +559,57 @@ hipError_t kd_sort(const double* P, int64_t n, int64_t n_pad, int d, int unit_ro
 
 }  // namespace
 
-int prune_layout(int64_t nq, int64_t nq_pad, int nqblk, int64_t nr, int64_t nr_pad, int64_t nchunk, int d, PruneLayout& L)
+size_t prune_tmp_bytes(int64_t nmax, size_t nwaves)
 {
-    const int64_t nmax = std::max(nq_pad, nr_pad);
-    const int64_t pairs = (int64_t)nqblk * nchunk;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L.perm_r = take((size_t)nr_pad * 4);
-    L.perm_q = take((size_t)nq_pad * 4);
-    L.keys_a = take((size_t)nmax * 8);
-    L.keys_b = take((size_t)nmax * 8);
-    L.vals_b = take((size_t)nmax * 4);
-    L.Ys = take((size_t)nr * d * 8);
-    L.Xs = take((size_t)nq * d * 8);
-    // float planes of the coordinates while a set is being sorted (kd_sort): they live in the Xs region where it is large enough
-    // (it is written only after the last sort), else in room of their own
-    L.cf32 = (size_t)nq * d * 8 >= (size_t)std::max(nq, nr) * d * 4 ? L.Xs : take((size_t)std::max(nq, nr) * d * 4);
-    L.tbox_r = take((size_t)(nr_pad / kPruneTileRows) * 2 * d * 4);
-    L.tbox_q = take((size_t)(nq_pad / kPruneTileRows) * 2 * d * 4);
-    L.tboxT_r = take((size_t)(nr_pad / kPruneTileRows) * 2 * d * 4);
-    L.box_r = take((size_t)nchunk * 2 * d * 4);
-    L.box_q = take((size_t)nqblk * 2 * d * 4);
-    const size_t nwaves = (size_t)nqblk * kPruneWavesPerBlock;
-    L.bkey_a = take(nwaves * 4);
-    L.bkey_b = take(nwaves * 4);
-    L.bval_a = take(nwaves * 4);
-    L.border = take(nwaves * 4);
-    L.list_d_b = take((size_t)pairs * 4);
-    L.list_c_b = take((size_t)pairs * 4);
     size_t border_tmp = 0;
     (void)rocprim::radix_sort_pairs_desc(nullptr, border_tmp, (const float*)nullptr, (float*)nullptr, (const int*)nullptr, (int*)nullptr,
                                          nwaves, 0u, 32u);
-    L.tmp_bytes = std::max(sort_tmp_bytes(nmax), border_tmp);
-    L.tmp = take(L.tmp_bytes);
-    L.total = off;
-    return 0;
+    return std::max(sort_tmp_bytes(nmax), border_tmp);
 }
 
-hipError_t prune_prepare_part(const double* dY, int64_t nr, int d, int64_t nr_pad, char* ws, const PruneLayout& L, int part, int nparts, hipStream_t st,
+hipError_t prune_prepare_part(const double* dY, int64_t nr, int d, int64_t nr_pad, const PruneArena& A, int part, int nparts, hipStream_t st,
                               int64_t& seg_lo, int64_t& seg_hi)
 {
-    int* perm_r = reinterpret_cast<int*>(ws + L.perm_r);
     const int64_t ntile_r = nr_pad / kPruneTileRows;
-    hipError_t e = kd_sort(dY, nr, nr_pad, d, kPruneTileRows, (int)ntile_r, perm_r, reinterpret_cast<unsigned long long*>(ws + L.keys_a),
-                           reinterpret_cast<unsigned long long*>(ws + L.keys_b), reinterpret_cast<int*>(ws + L.vals_b), reinterpret_cast<float*>(ws + L.cf32),
-                           ws + L.tmp, L.tmp_bytes, st, part, nparts, &seg_lo, &seg_hi);
+    hipError_t e = kd_sort(dY, nr, nr_pad, d, kPruneTileRows, (int)ntile_r, A.perm_r, A.keys_a, A.keys_b, A.vals_b, A.cf32, A.tmp, A.z.prune_tmp_bytes, st, part,
+                           nparts, &seg_lo, &seg_hi);
     if (e != hipSuccess) return e;
     // zeros outside the own range: the ranks' permutations ADD up to the whole one (padding rows are -1 inside the range that holds them)
-    if (seg_lo > 0 && (e = zero_async(perm_r, (size_t)seg_lo * sizeof(int), st)) != hipSuccess) return e;
-    if (seg_hi < nr_pad && (e = zero_async(perm_r + seg_hi, (size_t)(nr_pad - seg_hi) * sizeof(int), st)) != hipSuccess) return e;
+    if (seg_lo > 0 && (e = zero_async(A.perm_r, (size_t)seg_lo * sizeof(int), st)) != hipSuccess) return e;
+    if (seg_hi < nr_pad && (e = zero_async(A.perm_r + seg_hi, (size_t)(nr_pad - seg_hi) * sizeof(int), st)) != hipSuccess) return e;
     return hipSuccess;
 }
 
 hipError_t prune_prepare(const double* dX, int64_t nq, const double* dY, int64_t nr, int d, bool same_set, int qpb, int chunk_rows,
-                         int64_t nq_pad, int nqblk, int64_t nr_pad, int64_t nchunk, char* ws, const PruneLayout& L, hipStream_t st,
-                         PruneOut& out, bool perm_ready)
+                         int64_t nq_pad, int nqblk, int64_t nr_pad, int64_t nchunk, const PruneArena& A, hipStream_t st, bool perm_ready)
 {
-    int* perm_r = reinterpret_cast<int*>(ws + L.perm_r);
-    int* perm_q = reinterpret_cast<int*>(ws + L.perm_q);
-    unsigned long long* keys_a = reinterpret_cast<unsigned long long*>(ws + L.keys_a);
-    unsigned long long* keys_b = reinterpret_cast<unsigned long long*>(ws + L.keys_b);
-    int* vals_b = reinterpret_cast<int*>(ws + L.vals_b);
-    double* Ys = reinterpret_cast<double*>(ws + L.Ys);
-    double* Xs = reinterpret_cast<double*>(ws + L.Xs);
-    float* cf32 = reinterpret_cast<float*>(ws + L.cf32);
-    float* tbox_r = reinterpret_cast<float*>(ws + L.tbox_r);
-    float* tbox_q = reinterpret_cast<float*>(ws + L.tbox_q);
-    float* tboxT_r = reinterpret_cast<float*>(ws + L.tboxT_r);
-    float* box_r = reinterpret_cast<float*>(ws + L.box_r);
-    float* box_q = reinterpret_cast<float*>(ws + L.box_q);
-    float* list_d_b = reinterpret_cast<float*>(ws + L.list_d_b);
-    int* list_c_b = reinterpret_cast<int*>(ws + L.list_c_b);
-    void* tmp = ws + L.tmp;
     const int64_t ntile_r = nr_pad / kPruneTileRows, ntile_q = nq_pad / kPruneTileRows;
     auto blocks_for = [](int64_t n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); };
 
     // references: k-d order down to single 32-row tiles, reordered copy, tile and chunk boxes
-    // (perm_ready: the order is in perm_r already -- prune_prepare_part on every rank + the all-reduce of the permutation)
-    hipError_t e = perm_ready ? hipSuccess : kd_sort(dY, nr, nr_pad, d, kPruneTileRows, (int)ntile_r, perm_r, keys_a, keys_b, vals_b, cf32, tmp, L.tmp_bytes, st);
+    // (perm_ready: the order is in A.perm_r already -- prune_prepare_part on every rank + the all-reduce of the permutation)
+    hipError_t e = perm_ready ? hipSuccess : kd_sort(dY, nr, nr_pad, d, kPruneTileRows, (int)ntile_r, A.perm_r, A.keys_a, A.keys_b, A.vals_b, A.cf32, A.tmp, A.z.prune_tmp_bytes, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gather_rows_kernel, blocks_for(nr * d), dim3(kThreads), 0, st, dY, perm_r, nr, d, Ys);
+    hipLaunchKernelGGL(gather_rows_kernel, blocks_for(nr * d), dim3(kThreads), 0, st, dY, A.perm_r, nr, d, A.Ys);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(tile_box_kernel, blocks_for(ntile_r * d), dim3(kThreads), 0, st, Ys, nr, d, ntile_r, tbox_r);
+    hipLaunchKernelGGL(tile_box_kernel, blocks_for(ntile_r * d), dim3(kThreads), 0, st, A.Ys, nr, d, ntile_r, A.tbox_r);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(group_box_kernel, blocks_for(nchunk * d), dim3(kThreads), 0, st, tbox_r, ntile_r, d, chunk_rows / kPruneTileRows, (int)nchunk, box_r);
+    hipLaunchKernelGGL(group_box_kernel, blocks_for(nchunk * d), dim3(kThreads), 0, st, A.tbox_r, ntile_r, d, chunk_rows / kPruneTileRows, (int)nchunk, A.box_r);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (same_set) {
-        out.Xs = Ys;
-        out.qperm = perm_r;          // query tile t IS reference tile t
-        out.tbox_q = tbox_r;
-    } else {
-        e = kd_sort(dX, nq, nq_pad, d, kPruneTileRows, (int)ntile_q, perm_q, keys_a, keys_b, vals_b, cf32, tmp, L.tmp_bytes, st);
+    const float* const tbox_q = same_set ? A.tbox_r : A.tbox_q;          // (one set: query tile t IS reference tile t)
+    if (!same_set) {
+        e = kd_sort(dX, nq, nq_pad, d, kPruneTileRows, (int)ntile_q, A.perm_q, A.keys_a, A.keys_b, A.vals_b, A.cf32, A.tmp, A.z.prune_tmp_bytes, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(gather_rows_kernel, blocks_for(nq * d), dim3(kThreads), 0, st, dX, perm_q, nq, d, Xs);
+        hipLaunchKernelGGL(gather_rows_kernel, blocks_for(nq * d), dim3(kThreads), 0, st, dX, A.perm_q, nq, d, A.Xs);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(tile_box_kernel, blocks_for(ntile_q * d), dim3(kThreads), 0, st, Xs, nq, d, ntile_q, tbox_q);
+        hipLaunchKernelGGL(tile_box_kernel, blocks_for(ntile_q * d), dim3(kThreads), 0, st, A.Xs, nq, d, ntile_q, A.tbox_q);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        out.Xs = Xs;
-        out.qperm = perm_q;
-        out.tbox_q = tbox_q;
     }
-    hipLaunchKernelGGL(transpose_tile_box_kernel, blocks_for(ntile_r * 2 * d), dim3(kThreads), 0, st, tbox_r, ntile_r, d,
-                       chunk_rows / kPruneTileRows, tboxT_r);
+    hipLaunchKernelGGL(transpose_tile_box_kernel, blocks_for(ntile_r * 2 * d), dim3(kThreads), 0, st, A.tbox_r, ntile_r, d,
+                       chunk_rows / kPruneTileRows, A.tboxT_r);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    out.tbox_r = tboxT_r;
-    out.cbox_r = box_r;
-    hipLaunchKernelGGL(group_box_kernel, blocks_for((int64_t)nqblk * d), dim3(kThreads), 0, st, out.tbox_q, same_set ? ntile_r : ntile_q, d,
-                       qpb / kPruneTileRows, nqblk, box_q);
+    hipLaunchKernelGGL(group_box_kernel, blocks_for((int64_t)nqblk * d), dim3(kThreads), 0, st, tbox_q, same_set ? ntile_r : ntile_q, d,
+                       qpb / kPruneTileRows, nqblk, A.box_q);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     static_assert(kBandKeys % kThreads == 0 && kPruneMaxDim * 2 <= kThreads, "chunk_list_kernel geometry");
     if (nchunk <= kListStage) {
@@ -679,32 +621,23 @@ hipError_t prune_prepare(const double* dX, int64_t nq, const double* dY, int64_t
             if (e != hipSuccess) return e;
             if (dev < 16) attr_set[dev] = true;
         }
-        hipLaunchKernelGGL(chunk_list_kernel, dim3((unsigned)nqblk), dim3(kThreads), chunk_list_lds_bytes((int)nchunk), st, box_q, box_r, (int)nchunk, d, list_d_b, list_c_b);
+        hipLaunchKernelGGL(chunk_list_kernel, dim3((unsigned)nqblk), dim3(kThreads), chunk_list_lds_bytes((int)nchunk), st, A.box_q, A.box_r, (int)nchunk, d, A.list_d, A.list_c);
     } else {
-        hipLaunchKernelGGL(chunk_list_big_kernel, dim3((unsigned)nqblk), dim3(kThreads), 0, st, box_q, box_r, (int)nchunk, d, list_d_b, list_c_b);
+        hipLaunchKernelGGL(chunk_list_big_kernel, dim3((unsigned)nqblk), dim3(kThreads), 0, st, A.box_q, A.box_r, (int)nchunk, d, A.list_d, A.list_c);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     {
-        float* bkey_a = reinterpret_cast<float*>(ws + L.bkey_a);
-        float* bkey_b = reinterpret_cast<float*>(ws + L.bkey_b);
-        int* bval_a = reinterpret_cast<int*>(ws + L.bval_a);
-        int* border = reinterpret_cast<int*>(ws + L.border);
         const int nwaves = nqblk * kPruneWavesPerBlock;
         const int tpw = qpb / kPruneTileRows / kPruneWavesPerBlock;
-        hipLaunchKernelGGL(wave_cost_kernel, dim3((unsigned)((nwaves + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, out.tbox_q, nwaves, tpw,
-                           same_set ? ntile_r : ntile_q, d, bkey_a, bval_a);
+        hipLaunchKernelGGL(wave_cost_kernel, dim3((unsigned)((nwaves + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, tbox_q, nwaves, tpw,
+                           same_set ? ntile_r : ntile_q, d, A.bkey_a, A.bval_a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        size_t tb2 = L.tmp_bytes;
+        size_t tb2 = A.z.prune_tmp_bytes;
         // (the keys are non-negative floats or -1: as unsigned bit patterns -1 would sort FIRST in descending order -- the
         //  float comparison of rocPRIM's radix sort handles the sign)
-        e = rocprim::radix_sort_pairs_desc(tmp, tb2, (const float*)bkey_a, bkey_b, (const int*)bval_a, border, (size_t)nwaves, 0u, 32u, st);
+        e = rocprim::radix_sort_pairs_desc(A.tmp, tb2, (const float*)A.bkey_a, A.bkey_b, (const int*)A.bval_a, A.border, (size_t)nwaves, 0u, 32u, st);
         if (e != hipSuccess) return e;
-        out.border = border;
     }
-    out.Ys = Ys;
-    out.rperm = perm_r;
-    out.clist = list_c_b;
-    out.cdist = list_d_b;
     return hipSuccess;
 }
 
@@ -748,48 +681,24 @@ __global__ __launch_bounds__(kNormRows) void norm_key_kernel(const double* __res
 
 }  // namespace
 
-int sym_layout(int64_t n, int64_t n_pad, int nqblk, int d, int kcap, int qpb, int per_row, SymLayout& L)
-{
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L.perm = take((size_t)n_pad * 4);
-    L.keys_a = take((size_t)n_pad * 4);
-    L.keys_b = take((size_t)n_pad * 4);
-    L.vals_a = take((size_t)n_pad * 4);
-    L.Ys = take((size_t)n * d * 8);
-    L.thr = take((size_t)n_pad * 8);
-    L.rrow = take((size_t)n_pad * 4);
-    L.rtile = take((size_t)(n_pad / 32) * 4);
-    L.slots = take((size_t)n_pad * kcap * 8);
-    L.bucket_cnt = take((size_t)nqblk * 4 * 3);
-    L.bucket_flag = L.bucket_cnt + (size_t)nqblk * 4;
-    L.done = L.bucket_flag + (size_t)nqblk * 4;
-    L.cap = per_row * qpb;
-    L.bucket = take((size_t)nqblk * L.cap * 16);
-    L.tmp_bytes = sort_pairs_tmp_bytes<unsigned>(n_pad, 32u);
-    L.tmp = take(L.tmp_bytes);
-    L.total = off;
-    return 0;
-}
+size_t sym_tmp_bytes(int64_t n_pad) { return sort_pairs_tmp_bytes<unsigned>(n_pad, 32u); }
 
-hipError_t sym_prepare(const double* dY, int64_t n, int d, const double* center, int64_t n_pad, char* ws, const SymLayout& L, hipStream_t st)
+hipError_t sym_prepare(const double* dY, int64_t n, int d, const double* center, int64_t n_pad, const SymArena& A, hipStream_t st)
 {
-    int* perm = reinterpret_cast<int*>(ws + L.perm);
-    unsigned* keys_a = reinterpret_cast<unsigned*>(ws + L.keys_a);
-    unsigned* keys_b = reinterpret_cast<unsigned*>(ws + L.keys_b);
-    int* vals_a = reinterpret_cast<int*>(ws + L.vals_a);
-    double* Ys = reinterpret_cast<double*>(ws + L.Ys);
+    int *const perm = A.perm, *const vals_a = A.vals_a;
+    unsigned *const keys_a = A.keys_a, *const keys_b = A.keys_b;
+    double* const Ys = A.Ys;
     const unsigned blocks = (unsigned)((n_pad + kNormRows - 1) / kNormRows);
     hipLaunchKernelGGL(norm_key_kernel, dim3(blocks), dim3(kNormRows), (size_t)kNormRows * (d + 1) * sizeof(double), st, dY, n, n_pad, d, center,
                        keys_a, vals_a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     // (stable: rows at the same distance keep the caller's order -- the permutation is deterministic)
-    e = sort_pairs(ws + L.tmp, L.tmp_bytes, (const unsigned*)keys_a, keys_b, (const int*)vals_a, perm, n_pad, 32u, st);
+    e = sort_pairs(A.tmp, A.z.sym_tmp_bytes, (const unsigned*)keys_a, keys_b, (const int*)vals_a, perm, n_pad, 32u, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n * d + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, dY, perm, n, d, Ys);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    e = zero_async(ws + L.bucket_cnt, (size_t)3 * (L.bucket_flag - L.bucket_cnt), st);      // counts | flags | done
+    e = zero_async(A.counters, A.counters_bytes(), st);      // counts | flags | done
     return e;
 }
 

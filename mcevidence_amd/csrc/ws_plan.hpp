@@ -1,5 +1,6 @@
-// ws_plan.hpp -- the library's one workspace planner (host only, plain C++17: the layout headers that a CPU test compiles take it
-// from here, capi.hip through capi_common.hpp).
+// ws_plan.hpp -- the library's workspace planner (host only, plain C++17: the layout headers that a CPU test compiles -- feed_layout.hpp,
+// search_layout.hpp -- take it from here, capi.hip through capi_common.hpp).  Still counted by hand with prep_align: the rows of
+// capi_prep.hpp and capi_farm.hpp that are not WsPlan takes yet.
 #pragma once
 #include <cstddef>
 

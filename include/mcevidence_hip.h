@@ -498,6 +498,43 @@ int mce_jack_dotp_f64(const double* dist, const int64_t* idx, int64_t nq, int32_
                       int64_t nr, int32_t G, int32_t k0, int32_t kmax, int32_t d, const double* w, const double* fs, double* dotp_groups,
                       double* dotp_full, int64_t* short_rows, int64_t* nshort, int32_t device);
 
+/* The k-NN relative entropy D_KL(P || Q) of two weighted samples with a delete-a-group jackknife from ONE pair of neighbour searches
+ * (docs/design/knn_divergence.md; rule: csrc/knn_div.hpp).
+ *
+ * mce_div_whiten_dev: z[n][d] (packed: what mce_knn_f64_dev reads) = linv (x - mean) for the rows d_x[n][ld] on the device; linv[d * d]
+ * (lower triangle, row major) and mean[d] are HOST arrays and travel with the call; the products of a coordinate are added in column
+ * order.  report[MCE_DIV_REPORT] (HOST): the sum of d_w, the count of weights that are not > 0 or not finite, the lowest column with a
+ * value that is not finite (-1: none), n -- summed in an order the sizes fix.  1 <= d <= MCE_DIV_MAX_DIM.  The stream is synchronised on
+ * return.  Workspace: mce_div_whiten_workspace_bytes(n, d).
+ *
+ * mce_knn_div_terms_dev: every query row q (a row of P: d_qid[q], or q where d_qid is NULL) has two ascending lists of L entries, the
+ * AUTO list d_distP / d_idxP [nq][L] (its neighbours in P; an entry whose row is the query's own is skipped) and the CROSS list
+ * d_distQ / d_idxQ [nq][L] (its neighbours in Q); a row below 0 ends a list.  d_gq[nq], d_grP[nP], d_grQ[nQ]: groups in [0, G);
+ * d_aq[nq], d_aP[nP], d_bQ[nQ]: weights.  d_sums[(G + 1)][K][2]: slot 0 the full sample, slot 1 + b with group b deleted from both
+ * samples; per rank k the sums N and X of the rule.  The weight of P and of its groups is formed inside the call.  A row is SHORT when
+ * skipping some group other than its own (or none) leaves fewer than K entries in either list: it enters no sum; its row number is
+ * appended to d_short_rows [nq], ascending, and *d_nshort (device) counts them.  G = 0: no groups (the group pointers may be NULL), the
+ * full slot alone.  Otherwise 2 <= G <= MCE_JACK_MAX_GROUPS.  K <= L <= MCE_GENERIC_MAX_K; K > MCE_DIV_MAX_K: MCE_ERR_K_RANGE.  Lists of
+ * up to 32 entries are processed from registers, longer ones from memory.  fp64, plain stores, sums in an order the sizes fix: two runs
+ * give the same bits.  The stream is synchronised on return.  The *_f64 forms take HOST pointers (nshort too), upload to `device` and
+ * call the device forms.  Argument errors -- G out of range, a group id out of range, L < K -- : MCE_ERR_INVALID. */
+#define MCE_DIV_MAX_K 16
+#define MCE_DIV_MAX_DIM 64
+#define MCE_DIV_REPORT 4
+size_t mce_div_whiten_workspace_bytes(int64_t n, int32_t d);
+int mce_div_whiten_dev(const double* d_x, int64_t ld, int64_t n, int32_t d, const double* linv, const double* mean, const double* d_w, double* d_z,
+                       double* report, void* ws, size_t ws_bytes, void* stream);
+int mce_div_whiten_f64(const double* x, int64_t ld, int64_t n, int32_t d, const double* linv, const double* mean, const double* w, double* z,
+                       double* report, int32_t device);
+size_t mce_knn_div_workspace_bytes(int64_t nq, int64_t nP, int32_t G, int32_t K);
+int mce_knn_div_terms_dev(const double* d_distP, const int64_t* d_idxP, const double* d_distQ, const int64_t* d_idxQ, int64_t nq, int32_t L,
+                          const int64_t* d_qid, const int32_t* d_gq, const int32_t* d_grP, int64_t nP, const int32_t* d_grQ, int64_t nQ, int32_t G,
+                          int32_t K, int32_t d, const double* d_aq, const double* d_aP, const double* d_bQ, double* d_sums, int64_t* d_short_rows,
+                          int64_t* d_nshort, void* ws, size_t ws_bytes, void* stream);
+int mce_knn_div_terms_f64(const double* distP, const int64_t* idxP, const double* distQ, const int64_t* idxQ, int64_t nq, int32_t L, const int64_t* qid,
+                          const int32_t* gq, const int32_t* grP, int64_t nP, const int32_t* grQ, int64_t nQ, int32_t G, int32_t K, int32_t d,
+                          const double* aq, const double* aP, const double* bQ, double* sums, int64_t* short_rows, int64_t* nshort, int32_t device);
+
 /* The bookkeeping of the delete-a-group jackknife for chains that stay on the device (the resident route and the farm;
  * docs/design/jackknife_resident.md; rule: csrc/jack_groups.hpp), for MANY systems (the asking roots of a farm wave) in one call.
  *

@@ -168,6 +168,14 @@ SIGNATURES["mce_jack_dotp_dev"] = (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P
 SIGNATURES["mce_jack_dotp_f64"] = (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P, _P, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P,
                                               _P, _P, _P, _P, _c.c_int32])
 
+MCE_DIV_MAX_K, MCE_DIV_MAX_DIM, MCE_DIV_REPORT = 16, 64, 4
+SIGNATURES["mce_div_whiten_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int32])
+SIGNATURES["mce_div_whiten_dev"] = (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int32, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P])
+SIGNATURES["mce_div_whiten_f64"] = (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int32, _P, _P, _P, _P, _P, _c.c_int32])
+SIGNATURES["mce_knn_div_workspace_bytes"] = (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32])
+_DIV_TERMS_ARGS = [_P, _P, _P, _P, _c.c_int64, _c.c_int32, _P, _P, _P, _c.c_int64, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _P, _P, _P, _P]
+SIGNATURES["mce_knn_div_terms_dev"] = (_c.c_int, _DIV_TERMS_ARGS + [_P, _c.c_size_t, _P])
+SIGNATURES["mce_knn_div_terms_f64"] = (_c.c_int, _DIV_TERMS_ARGS + [_c.c_int32])
 
 
 class MomentsSeg(ctypes.Structure):
@@ -1507,6 +1515,92 @@ def jack_dotp(dist, idx, gq, gr, G, k0, kmax, d, w, fs, qid=None, device=0):
                                 gr.shape[0], G, int(k0), kmax, int(d), w.ctypes.data, fs.ctypes.data, groups.ctypes.data, full.ctypes.data,
                                 short.ctypes.data, _c.addressof(nshort), int(device)))
     return groups, full, short[:int(nshort.value)].copy()
+
+
+def div_whiten_workspace_bytes(n, d):
+    """scratch bytes of ``div_whiten_dev``"""
+    nb = int(load().mce_div_whiten_workspace_bytes(int(n), int(d)))
+    if nb == 0:
+        raise ValueError("knn divergence: invalid sizes n=%d d=%d" % (n, d))
+    return nb
+
+
+def _div_metric(linv, mean, d):
+    linv = np.ascontiguousarray(linv, dtype=np.float64)
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    if 1 <= int(d) <= MCE_DIV_MAX_DIM and (linv.size != int(d) * int(d) or mean.size != int(d)):
+        raise ValueError("knn divergence: linv[d * d] and mean[d] expected")
+    return linv, mean
+
+
+def div_whiten_dev(d_x, ld, n, d, linv, mean, d_w, d_z, ws, ws_bytes, stream=0):
+    """``mce_div_whiten_dev``: z = linv (x - mean) of rows that are on the device, into ``d_z`` (packed [n, d]); ``linv`` / ``mean`` are host
+    arrays.  Returns the report: (sum of w, weights that are not > 0 or not finite, lowest non-finite column or -1, rows)."""
+    linv, mean = _div_metric(linv, mean, d)
+    report = np.full(MCE_DIV_REPORT, np.nan)
+    check(load().mce_div_whiten_dev(d_x or None, int(ld), int(n), int(d), linv.ctypes.data, mean.ctypes.data, d_w or None, d_z or None, report.ctypes.data,
+                                    ws or None, int(ws_bytes), stream or None))
+    return report
+
+
+def div_whiten(x, d, linv, mean, w, device=0):
+    """``mce_div_whiten_f64``: the same from HOST arrays ``x`` [n, ld] and ``w`` [n] -> (z[n, d], report)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if x.ndim != 2 or x.shape[0] != w.size:
+        raise ValueError("knn divergence: rows and w of one length expected")
+    linv, mean = _div_metric(linv, mean, d)
+    z = np.zeros((w.size, max(int(d), 1)))
+    report = np.full(MCE_DIV_REPORT, np.nan)
+    check(load().mce_div_whiten_f64(x.ctypes.data, x.shape[1], w.size, int(d), linv.ctypes.data, mean.ctypes.data, w.ctypes.data, z.ctypes.data,
+                                    report.ctypes.data, int(device)))
+    return z, report
+
+
+def knn_div_workspace_bytes(nq, nP, G, K):
+    """scratch bytes of ``knn_div_terms_dev``"""
+    n = int(load().mce_knn_div_workspace_bytes(int(nq), int(nP), int(G), int(K)))
+    if n == 0:
+        raise ValueError("knn divergence: invalid sizes nq=%d nP=%d G=%d K=%d" % (nq, nP, G, K))
+    return n
+
+
+def knn_div_terms_dev(d_distP, d_idxP, d_distQ, d_idxQ, nq, L, d_qid, d_gq, d_grP, nP, d_grQ, nQ, G, K, d, d_aq, d_aP, d_bQ, d_sums, d_short_rows,
+                      d_nshort, ws, ws_bytes, stream=0):
+    """the sums of the k-NN relative entropy from lists that are on the device (``mce_knn_div_terms_dev``); device POINTERS, the stream
+    is synchronised on return"""
+    check(load().mce_knn_div_terms_dev(d_distP, d_idxP, d_distQ, d_idxQ, int(nq), int(L), d_qid or None, d_gq or None, d_grP or None, int(nP),
+                                       d_grQ or None, int(nQ), int(G), int(K), int(d), d_aq, d_aP, d_bQ, d_sums, d_short_rows, d_nshort, ws, int(ws_bytes),
+                                       stream or None))
+
+
+def knn_div_terms(distP, idxP, distQ, idxQ, gq, grP, grQ, G, K, d, aq, aP, bQ, qid=None, device=0):
+    """``mce_knn_div_terms_f64``: the sums from the two neighbour lists [nq, L] of every query row on the host; ``gq`` / ``grP`` / ``grQ``
+    may be None where ``G`` is 0.  Returns (sums[G + 1, K, 2], short_rows int64, ascending)."""
+    lib = load()
+    distP, distQ = _f64_allow_inf(distP), _f64_allow_inf(distQ)
+    idxP, idxQ = np.ascontiguousarray(idxP, dtype=np.int64), np.ascontiguousarray(idxQ, dtype=np.int64)
+    aq, aP, bQ = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (aq, aP, bQ))
+    if distP.ndim != 2 or idxP.shape != distP.shape or distQ.shape != distP.shape or idxQ.shape != distP.shape or aq.shape != (distP.shape[0],):
+        raise ValueError("shape mismatch: distP %r, idxP %r, distQ %r, idxQ %r, aq %r" % (distP.shape, idxP.shape, distQ.shape, idxQ.shape, aq.shape))
+    nq, L = distP.shape
+    groups = [None if g is None else np.ascontiguousarray(g, dtype=np.int32).reshape(-1) for g in (gq, grP, grQ)]
+    for g, n, what in zip(groups, (nq, aP.size, bQ.size), ("gq", "grP", "grQ")):
+        if g is not None and g.size != n:
+            raise ValueError("knn divergence: %s must have one entry per row" % what)
+    if qid is not None:
+        qid = np.ascontiguousarray(qid, dtype=np.int64)
+        if qid.shape != (nq,):
+            raise ValueError("qid must have one entry per query row")
+    G, K = int(G), int(K)
+    sums = np.zeros((max(G, 0) + 1, max(K, 1), 2), dtype=np.float64)
+    short = np.zeros(max(nq, 1), dtype=np.int64)
+    nshort = _c.c_int64(0)
+    ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
+    check(lib.mce_knn_div_terms_f64(distP.ctypes.data, idxP.ctypes.data, distQ.ctypes.data, idxQ.ctypes.data, nq, L, ptr(qid), ptr(groups[0]), ptr(groups[1]),
+                                    aP.size, ptr(groups[2]), bQ.size, G, K, int(d), aq.ctypes.data, aP.ctypes.data, bQ.ctypes.data, sums.ctypes.data,
+                                    short.ctypes.data, _c.addressof(nshort), int(device)))
+    return sums, short[:int(nshort.value)].copy()
 
 
 def prune_part_applies(nr, d, kmax, nparts):

@@ -105,6 +105,17 @@ def build_parser(prog=None):
                         "sigma, n_local, rows and the bandwidth h")
     p.add_argument("--shift-bandwidth", dest="shift_bandwidth", default=None, type=float, metavar="SCALE",
                    help="with --shift-kde: the bandwidth as a multiple of Silverman's rule (default 1; raise it where n_local is small)")
+    p.add_argument("--gain-knn", dest="gain_knn", nargs="?", const=4, default=None, type=int, metavar="K",
+                   help="with --tension: the information gain too -- the relative entropy D_KL(AB || A), D_KL(AB || B), D_KL(A || B) and "
+                        "D_KL(B || A) between the runs' posteriors from nearest-neighbour distances (mcevidence_amd.divergence), for the ranks "
+                        "k = 1 .. K (default 4, at most 16), each with a delete-a-block jackknife error bar; four more lines after the shift")
+    p.add_argument("--gain-groups", dest="gain_groups", default=None, type=int, metavar="G",
+                   help="with --gain-knn or --divergence: the jackknife blocks of each chain (default 8; 0: no error bar; at most 64)")
+    p.add_argument("--divergence", dest="divergence", nargs="+", default=None, metavar=("ROOT_Q", "K"),
+                   help="print the relative entropy D_KL(root_name || ROOT_Q)[k] = x +- sigma, k = 1 .. K (default 4), between the posteriors of the "
+                        "two roots over the parameters they share (by name where both have a .paramnames file, else the leading columns), from "
+                        "nearest-neighbour distances; composes with --burn, --thin, --thin-corr and -np (both roots take them); write it after "
+                        "root_name")
     return p
 
 
@@ -277,6 +288,44 @@ def _shift_kw(args):
     return {"shift": "both", "boost": args.shift_kde, "bandwidth_scale": 1.0 if args.shift_bandwidth is None else args.shift_bandwidth}
 
 
+def _gain_kw(args):
+    """--gain-knn / --gain-groups, where the first was given"""
+    if args.gain_knn is None:
+        return {}
+    return {"gain": "knn", "gain_k": args.gain_knn, "gain_groups": 8 if args.gain_groups is None else args.gain_groups}
+
+
+def divergence_main(args):
+    """``--divergence ROOT_Q [K]``: D_KL(root_name || ROOT_Q)[k] over the shared parameters, from the host rows of two ``MCEvidence``
+    objects; both roots take --burn, --thin, --thin-corr and -np"""
+    import copy
+    from . import divergence, tension
+    from .summary import param_names
+    roots = [args.root_name, args.divergence[0]]
+    K = int(args.divergence[1]) if len(args.divergence) > 1 else 4
+    logging.getLogger("mcevidence_amd").setLevel(
+        logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose == 1 else logging.WARNING))
+    data, names = [], []
+    for r in roots:
+        a = copy.copy(args)
+        a.root_name = r
+        pvol = prior.get_prior_volume(a, cosmo=not args.allparams)      # (sets a.ndim, as for one root)
+        m = MCEvidence(r, ndim=a.ndim, priorvolume=pvol, idchain=args.idchain, kmax=args.kmax, verbose=0, burnlen=args.burnlen, thinlen=args.thinlen,
+                       **_thin_kw(args), **_backend_kw(args))
+        data.append(tension._host_rows(m))
+        names.append(param_names(r, m.ndim))
+    shared, ip, iq = tension._pair_shared(names[0], names[1])
+    (xp, wp), (xq, wq) = data
+    out = tension.knn_divergence(xp[:, ip], wp, xq[:, iq], wq, kmax=K, groups=8 if args.gain_groups is None else args.gain_groups, names=shared)
+    print()
+    print("Relative entropy of {} against {}".format(*roots))
+    for line in divergence.lines(out, label="D_KL({} ‖ {})".format(*roots)):
+        print(line)
+    print(tension.FOOTNOTE_GAIN)
+    print("")
+    return out
+
+
 def tension_main(args):
     """``--tension ROOT_A ROOT_B``: the three roots as ``--farm`` prints roots, then the tension lines and their footnote.  ``--cross``,
     ``--converge``, ``--summary`` and ``--marginals`` go to all three roots (``--information`` is always set); ``--farm`` and ``--resident`` name another
@@ -295,7 +344,7 @@ def tension_main(args):
     ea, eb, eab, info = tension.evidence_tension(roots[0], roots[1], roots[2], kmax=args.kmax, ndim=ndims, priorvolume=pvols, burnlen=args.burnlen,
                                                  thinlen=args.thinlen, idchain=args.idchain, split=args.cross, **_thin_kw(args), **_converge_kw(args),
                                                  **_summary_kw(args), **_marginals_kw(args), **_contours_kw(args), **_jackknife_kw(args), **_backend_kw(args),
-                                                 **_shift_kw(args))
+                                                 **_shift_kw(args), **_gain_kw(args))
     note = None
     for r, mle, inf in zip(roots, (ea, eb, eab), info["roots"]):
         print()
@@ -314,6 +363,8 @@ def tension_main(args):
     print(tension.FOOTNOTE)
     if args.shift_kde is not None:
         print(tension.FOOTNOTE_KDE)
+    if args.gain_knn is not None:
+        print(tension.FOOTNOTE_GAIN)
     print("")
     return ea, eb, eab, info
 
@@ -335,6 +386,20 @@ def main(argv=None):
         build_parser(prog="MCEvidence.py").error("--shift-kde BOOST: a positive number of offsets expected")
     if args.shift_bandwidth is not None and not args.shift_bandwidth > 0.0:
         build_parser(prog="MCEvidence.py").error("--shift-bandwidth SCALE: a positive number expected")
+    if args.gain_knn is not None and args.tension is None:
+        build_parser(prog="MCEvidence.py").error("--gain-knn belongs to --tension ROOT_A ROOT_B")
+    if args.gain_groups is not None and args.gain_knn is None and args.divergence is None:
+        build_parser(prog="MCEvidence.py").error("--gain-groups belongs to --gain-knn or --divergence")
+    if args.gain_knn is not None and not 1 <= args.gain_knn <= 16:
+        build_parser(prog="MCEvidence.py").error("--gain-knn K: 1 .. 16 expected")
+    if args.gain_groups is not None and args.gain_groups != 0 and not 2 <= args.gain_groups <= 64:
+        build_parser(prog="MCEvidence.py").error("--gain-groups G: 0, or 2 .. 64 expected")
+    if args.divergence is not None:
+        if len(args.divergence) > 2 or (len(args.divergence) == 2 and not (args.divergence[1].isdigit() and 1 <= int(args.divergence[1]) <= 16)):
+            build_parser(prog="MCEvidence.py").error("--divergence ROOT_Q [K]: one root and, optionally, K in 1 .. 16 expected")
+        if args.tension is not None or args.farm or args.resident:
+            build_parser(prog="MCEvidence.py").error("--divergence compares root_name with ROOT_Q: it does not combine with --tension, --farm or --resident")
+        return divergence_main(args)
     if (args.marginals_grid is not None or args.marginals_scale is not None or args.marginals_out is not None) and args.marginals is None:
         build_parser(prog="MCEvidence.py").error("--marginals-grid, --marginals-scale and --marginals-out belong to --marginals")
     if args.bounds is not None and args.marginals is None:

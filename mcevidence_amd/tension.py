@@ -24,6 +24,12 @@ estimates the posterior mass of the parameter DIFFERENCE above the density at "n
 on the difference chain (Raveri & Doux 2021, arXiv:2105.03324) and puts its dict into ``t["shift_kde"]``; independent data sets stay
 assumed.
 
+ln I and D_KL measure a posterior against the flat prior only.  How much one run learnt beyond ANOTHER is the relative entropy between
+their posteriors: ``knn_divergence`` (``evidence_tension(gain="knn")``, divergence.py) estimates D_KL(P || Q) of two chains from
+nearest-neighbour distances, with a delete-a-block jackknife error bar from one pair of searches, and ``t["gain"]`` holds the four of
+them: "AB|A" and "AB|B" (the information gained by adding the other data set, over the parameters the pair of runs shares), "A|B" and
+"B|A" (between the two data sets, over the parameters A and B share).  It needs no likelihood column and no prior volume.
+
 ln R is only meaningful when the three runs share the prior on the shared parameters and each ln E carries its own full prior volume
 (``priorvolume``); nothing here can check that.
 
@@ -39,7 +45,8 @@ import numpy as np
 
 logger = logging.getLogger("mcevidence_amd")
 
-__all__ = ["combine", "evidence_tension", "lines", "shared_parameters", "p_value", "sigma_equivalent", "parameter_shift_kde", "FOOTNOTE", "FOOTNOTE_KDE"]
+__all__ = ["combine", "evidence_tension", "lines", "shared_parameters", "p_value", "sigma_equivalent", "parameter_shift_kde", "knn_divergence", "GAIN_KEYS", "FOOTNOTE",
+           "FOOTNOTE_KDE", "FOOTNOTE_GAIN"]
 
 OK, NO_DIMENSION, NOT_FINITE = 0, 1, 2
 SHIFT_OK, SHIFT_NOT_POSITIVE, SHIFT_NOT_FINITE = 0, 1, 2
@@ -48,6 +55,11 @@ FOOTNOTE = ("* tension: p and sigma of ln S assume Gaussian posteriors (d - 2 ln
 
 
 from .shift_kde import FOOTNOTE as FOOTNOTE_KDE  # noqa: E402  (the second footnote sentence, printed where the KDE shift was asked for)
+
+GAIN_KEYS = ("AB|A", "AB|B", "A|B", "B|A")
+FOOTNOTE_GAIN = ("  gain: k-NN relative entropy D_KL(P || Q)[k] between two chains, in nats, whitened with P's covariance; \u00b1: delete-a-block jackknife, "
+                 "conditional on that metric; the estimator's bias grows with the number of parameters and with k, and autocorrelated rows "
+                 "shrink its error bar (use --thin-corr).")
 
 
 def _gammaincc_large(a, x):
@@ -171,12 +183,23 @@ def parameter_shift_kde(rows_a, w_a, rows_b, w_b, boost=1, bandwidth_scale=1.0, 
     return shift_kde.estimate(rows_a, w_a, rows_b, w_b, boost=boost, bandwidth_scale=bandwidth_scale, max_rows=max_rows, device=device, names=names)
 
 
-def combine(a, b, ab, shared=None, shift_kde=None):
+def knn_divergence(rows_p, w_p, rows_q, w_q, kmax=4, groups=8, device=None, names=None):
+    """The relative entropy D_KL(P || Q)[k], k = 1 .. ``kmax``, between two runs from their rows in the SHARED columns (``rows_p`` [nP, d],
+    ``rows_q`` [nQ, d]) and their weights: NumPy arrays or torch tensors of one device.  Both chains are whitened with P's covariance; the
+    estimate is the k-NN one of Wang, Kulkarni & Verdu (2009) with weights, its error bar a delete-a-block jackknife over ``groups`` blocks
+    of each chain (0: none) from ONE pair of neighbour searches.  -> dict(names, D[k], sigma[k], D_bias_corrected[k], D_groups[G, k],
+    excluded[k], rows_per_level, groups, kmax, rows_p, rows_q, dof, status, column, chain); divergence.py has the rule, the statuses and
+    the assumptions (independent rows)."""
+    from . import divergence
+    return divergence.estimate(rows_p, w_p, rows_q, w_q, kmax=kmax, groups=groups, device=device, names=names)
+
+
+def combine(a, b, ab, shared=None, shift_kde=None, gain=None):
     """``a``, ``b``, ``ab``: (lnE[kmax - 1], info) of the runs on A, on B and on both, each with ``info["information"]`` and
     ``info["covariance"]`` -> dict(lnR[k], lnI[k], lnS, d, p, sigma_equiv, shift{names, delta, chi2, dof, p, sigma_equiv, status},
     status) and, with ``info["jackknife"]`` in all three, sigma{lnR[k], lnS, d}.  The module's docstring has the definitions and the
     assumptions (Gaussian posteriors; independent data sets for the shift).  ``shift_kde``: ``parameter_shift_kde``'s dict, which goes
-    into ``t["shift_kde"]`` as it is."""
+    into ``t["shift_kde"]`` as it is; ``gain``: the dict of ``knn_divergence``'s dicts, which goes into ``t["gain"]`` as it is."""
     runs = []
     for name, (lnE, info) in (("a", a), ("b", b), ("ab", ab)):
         if "information" not in info or "covariance" not in info:
@@ -208,12 +231,14 @@ def combine(a, b, ab, shared=None, shift_kde=None):
         out["sigma"] = {"lnR": _rss(*[j["sigma"] for j in jks]), "lnS": float(_rss(*[s["mean_logL"] for s in sgs])), "d": float(_rss(*[s["bmd"] for s in sgs]))}
     if shift_kde is not None:
         out["shift_kde"] = shift_kde
+    if gain is not None:
+        out["gain"] = gain
     return out
 
 
 def lines(t):
     """the lines printed after the three roots: ln R / ln I per k, ln S, d, p and its sigma, then the shift (and the KDE shift where it was
-    asked for); +- where the jackknife ran"""
+    asked for), then the four gain lines where they were asked for; +- where the jackknife ran"""
     sg = t.get("sigma")
     pm = (lambda key, k=None: " ± {}".format(sg[key] if k is None else sg[key][k])) if sg else (lambda key, k=None: "")
     out = []
@@ -227,6 +252,11 @@ def lines(t):
     if t.get("shift_kde") is not None:
         from . import shift_kde
         out.extend(shift_kde.lines(t["shift_kde"]))
+    if t.get("gain") is not None:
+        from . import divergence
+        for key in GAIN_KEYS:
+            p, q = key.split("|")
+            out.extend(divergence.lines(t["gain"][key], label="gain D_KL({} || {})".format(p, q), ranks=False))
     return out
 
 
@@ -260,7 +290,42 @@ def _farm_rows(root, ndim, kw, i):
         return _host_rows(m)
 
 
-def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", shift="gaussian", boost=1, bandwidth_scale=1.0, **kw):
+def _refuse_gain(kw):
+    """the combinations ``gain=`` refuses"""
+    from . import parallel
+    if kw.get("brange") is not None or kw.get("nbatch", 1) > 1:
+        raise ValueError("gain with batched runs (brange=%r, nbatch=%r) is not supported: one batch, every sample" % (kw.get("brange"), kw.get("nbatch", 1)))
+    if kw.get("isfunc"):
+        raise ValueError("gain with isfunc is not supported: importance sampling changes the weights and leaves the likelihood column unchanged")
+    if parallel.is_distributed():
+        raise ValueError("gain under an initialised process group is not supported: run it in one process")
+
+
+def _pair_shared(names_p, names_q):
+    """the parameters a joint run and one of its parts share: by name where both have names, else the leading columns of the shorter"""
+    if _default_names(names_p) or _default_names(names_q):
+        return shared_parameters(names_p, names_q, min(len(names_p), len(names_q)))
+    return shared_parameters(names_p, names_q, None)
+
+
+def _gain(covs, rows, shared, gain_k, gain_groups, device):
+    """``t["gain"]``: covs the three runs' info["covariance"] (A, B, AB), rows(i, nd) their rows and weights"""
+    data = [rows(i, len(covs[i]["names"])) for i in range(3)]
+    if len({type(x) for x, _ in data}) > 1:                    # (a root on the device, another on the host: all on the host)
+        data = [tuple(v.cpu().numpy() if hasattr(v, "cpu") else v for v in xw) for xw in data]
+    pairs = {"AB|A": (2, 0, _pair_shared(covs[2]["names"], covs[0]["names"])), "AB|B": (2, 1, _pair_shared(covs[2]["names"], covs[1]["names"])),
+             "A|B": (0, 1, shared_parameters(covs[0]["names"], covs[1]["names"], shared))}
+    pairs["B|A"] = (1, 0, (pairs["A|B"][2][0], pairs["A|B"][2][2], pairs["A|B"][2][1]))
+    out = {}
+    for key in GAIN_KEYS:
+        p, q, (names, ip, iq) = pairs[key]
+        (xp, wp), (xq, wq) = data[p], data[q]
+        out[key] = knn_divergence(xp[:, ip], wp, xq[:, iq], wq, kmax=gain_k, groups=gain_groups, device=device, names=names)
+    return out
+
+
+def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", shift="gaussian", boost=1, bandwidth_scale=1.0, gain=None, gain_k=4,
+                     gain_groups=8, **kw):
     """The three runs and their tension: ``route="farm"``: ``evidence_many_from_files([root_a, root_b, root_ab], information=True,
     covariance=True, info=True, **kw)`` (a root the farm does not cover takes its per-root route); ``route="host"``: three
     ``MCEvidence(root, information=True, covariance=True, **kw).evidence(info=True)``.  ``kw``: the farm's keywords (``kmax``, ``ndim``,
@@ -270,11 +335,18 @@ def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", shift="
     the lines as they are without the keyword), "kde" or "both": ``parameter_shift_kde`` with ``boost`` and ``bandwidth_scale`` on the rows
     and weights ``covariance=`` measured in A and B, in ``info["tension"]["shift_kde"]`` -- the Gaussian shift stays in either case.  The
     host route uses its three objects' rows (``mce_kde_shift_f64``); the farm route reads A and B once more after the farm pass
-    (``ResidentChains.from_files(...).rows()``, the sums by ``mce_kde_shift_dev``; a root the resident plan declines: its host rows)."""
+    (``ResidentChains.from_files(...).rows()``, the sums by ``mce_kde_shift_dev``; a root the resident plan declines: its host rows).
+    ``gain``: None (the dict and the lines as they are without the keyword) or "knn": ``knn_divergence`` with ``gain_k`` ranks and
+    ``gain_groups`` jackknife blocks for the four pairs of ``GAIN_KEYS``, in ``info["tension"]["gain"]``; it takes its rows exactly where
+    ``shift="kde"`` takes them, for AB too."""
     if route not in ("farm", "host"):
         raise ValueError("tension: route=%r: 'farm' or 'host' expected" % (route,))
     if shift not in ("gaussian", "kde", "both"):
         raise ValueError("tension: shift=%r: 'gaussian', 'kde' or 'both' expected" % (shift,))
+    if gain not in (None, "knn"):
+        raise ValueError("tension: gain=%r: None or 'knn' expected" % (gain,))
+    if gain is not None:
+        _refuse_gain(kw)
     roots = [root_a, root_b, root_ab]
     for k in ("information", "covariance", "info"):
         if k in kw:
@@ -282,7 +354,7 @@ def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", shift="
     if route == "farm":
         from .farm import evidence_many_from_files
         outs = evidence_many_from_files(roots, information=True, covariance=True, info=True, **kw)
-        rows = (lambda i, nd: _farm_rows(roots[i], nd, kw, i)) if shift != "gaussian" else None
+        rows = (lambda i, nd: _farm_rows(roots[i], nd, kw, i)) if shift != "gaussian" or gain is not None else None
     else:
         from .evidence import MCEvidence
         from .farm import _per_root
@@ -302,7 +374,7 @@ def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", shift="
         for i, r in enumerate(roots):
             m = MCEvidence(r, information=True, covariance=True, **{k: v[i] for k, v in per.items()}, **kw)
             outs.append(m.evidence(info=True, **call))
-            if shift != "gaussian" and i < 2:                   # (A and B are kept for their rows; otherwise one object at a time, as before)
+            if (shift != "gaussian" and i < 2) or gain is not None:          # (kept for their rows; otherwise one object at a time, as before)
                 ms.append(m)
             del m
         rows = lambda i, nd: _host_rows(ms[i])                                     # noqa: E731
@@ -314,5 +386,8 @@ def evidence_tension(root_a, root_b, root_ab, shared=None, route="farm", shift="
         if type(xa) is not type(xb):                            # (one root on the device, one on the host: both on the host)
             xa, wa, xb, wb = [v.cpu().numpy() if hasattr(v, "cpu") else v for v in (xa, wa, xb, wb)]
         kde = parameter_shift_kde(xa[:, ia], wa, xb[:, ib], wb, boost=boost, bandwidth_scale=bandwidth_scale, device=kw.get("device", None), names=names)
-    t = combine(outs[0], outs[1], outs[2], shared=shared, shift_kde=kde)
+    gains = None
+    if gain is not None:
+        gains = _gain([o[1]["covariance"] for o in outs], rows, shared, gain_k, gain_groups, kw.get("device", None))
+    t = combine(outs[0], outs[1], outs[2], shared=shared, shift_kde=kde, gain=gains)
     return outs[0][0], outs[1][0], outs[2][0], {"tension": t, "roots": [o[1] for o in outs], "route": route}
